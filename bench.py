@@ -5,7 +5,12 @@ GPU.  Images shard across ranks (one process per GPU); the only collective is an
 fixed-size per-image records after the timed region.
 
     python bench.py [--config main|kodak|s1080|sd1080|kodak-sweep|vbr-mixed] [--gpus N --steps K --warmup W]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is
+given, and prints the line.  --full adds the legs that take runs of their own (`roofline`, `decode`,
+`cpu_baseline` and the deltas against the CPU oracle); without it those keys are null or absent.
 
 Workloads (weights: seeded realistic-rate sets, mlic_amd/synthetic.py RATE_LAMBDAS; no checkpoints
 offline; images: seeded synthetic):
@@ -17,7 +22,7 @@ offline; images: seeded synthetic):
               lambda stand-ins = 144 jobs, LPT-sharded over the ranks (strong scaling)
   vbr-mixed   config 5: MLICPP_L_VBR, 2 x 3840x2176 + 6 x 1920x1088 per GPU, a VBR level per image
               (weak scaling)
-Rank 0 prints ONE JSON line.  `roofline` is the kernel family with the most device time in the timed
+Rank 0 prints ONE JSON line.  With --full, `roofline` is the kernel family with the most device time in the timed
 configuration, measured live with HIP events on the executor streams in an extra untimed step, plus
 `step_frac` = T_roof / T_meas over every kernel of the step; `cpu_baseline` times the
 CPU oracle (torch fp32 restatement + native rANS) on a bounded sample on this box's cores.
@@ -109,9 +114,17 @@ def parse(argv=None):
     ap.add_argument("--synth-fp16", action="store_true",
                     help="SURVEY 8(f)4: g_s subpel convs on fp16 operands with fp32 accumulation (x_hat within "
                          "the 0.01 dB gate, bitstreams unchanged); default off: the headline stays fp32-faithful")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the profiled passes")
-    ap.add_argument("--layers-out", default="", help="write the per-layer timing table here")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the profiled "
+                         "roofline passes, the decode sub-record and the CPU-oracle baseline / deltas (each can "
+                         "be dropped again with its --no-... switch).  Off: a plain run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what their last step returned (bitstreams, x_hat) as "
+                         "DIR/<name>.npy, see dump_outputs()")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the profiled passes")
+    ap.add_argument("--layers-out", default="", help="write the per-layer timing table here (needs --full)")
     ap.add_argument("--records-out", default="", help="write the gathered per-image records (JSON) here")
     ap.add_argument("--profile-lanes", type=int, default=0,
                     help="lanes of the profiled step (0 = same as --lanes, so its launches match the timed "
@@ -138,6 +151,10 @@ def parse(argv=None):
                     help="phase both: skip the decode sub-record (a second timed region of K decompress-only "
                          "steps over the streams the timed enc+dec steps produced, with its own roofline)")
     a = ap.parse_args(argv)
+    if not a.full:
+        if a.layers_out:
+            ap.error("--layers-out is written by the profiled passes: add --full")
+        a.no_cpu_baseline = a.no_roofline = a.no_decode_record = True
     wl = WORKLOADS[a.config]
     a.lanes_auto = a.lanes <= 0 and "MLIC_LANES" not in os.environ and "lanes_many" in wl
     if a.lanes <= 0:
@@ -302,6 +319,61 @@ def oracle_deltas(model: str, levels, H: int, W: int, gpu_nets, dev):
     return out
 
 
+# ------------------------------------------------------------------------------------------ inputs / outputs
+def synth_inputs(groups, threads: int):
+    """Starts drawing every group's images and returns collect(), which waits for them and returns one
+    CPU batch per group.  synthetic.synth_image is seconds of numpy per 1080p image, so the images are
+    drawn on a thread pool (numpy releases the GIL) while the caller builds its models; each image
+    depends on its own seed only, so the batches are the ones a serial loop draws."""
+    from concurrent.futures import ThreadPoolExecutor
+    from mlic_amd import synthetic
+    tp = ThreadPoolExecutor(max(1, threads))
+    futs = [[tp.submit(synthetic.synth_image, j.H, j.W, j.seed) for j in g] for _, g in groups]
+    tp.shutdown(wait=False)
+
+    def collect():
+        return [torch.cat([f.result() for f in fs]) for fs in futs]
+    return collect
+
+
+# --dump-outputs: element caps of the sampled arrays (float32: 40 + 16 + 4 MB, under 64 MB in all)
+DUMP_CAPS = {"x_hat": 10 << 20, "y_strings": 4 << 20, "z_strings": 1 << 20}
+
+
+def _dump_sample(total: int, cap: int, seed: int):
+    """None (keep every element) or `cap` sorted positions in [0, total), the same on every run."""
+    if total <= cap:
+        return None
+    return np.sort(np.random.Generator(np.random.PCG64(seed)).integers(0, total, cap))
+
+
+def dump_outputs(dirpath: str, groups, last, suffix: str = ""):
+    """What a caller of the timed path received in the last timed step, as float32 / float64 .npy files:
+      streams.npy    float64 [images, 3]: job id, y stream bytes, z stream bytes (groups in batch order)
+      y_strings.npy  float32: the y streams' bytes, concatenated in that order
+      z_strings.npy  float32: the z streams' bytes, likewise
+      x_hat.npy      float32: decompress()'s x_hat of every batch, flattened and concatenated
+    An array over its DUMP_CAPS entry is cut to a fixed seeded sample of its positions."""
+    os.makedirs(dirpath, exist_ok=True)
+    ys = [s for gi in range(len(groups)) for s in last[gi][0]["strings"][0]]
+    zs = [s for gi in range(len(groups)) for s in last[gi][0]["strings"][1]]
+    ids = [j.id for _, js in groups for j in js]
+    out = {"streams": np.array([[i, len(y), len(z)] for i, y, z in zip(ids, ys, zs)], np.float64).reshape(-1, 3)}
+    for name, strings, seed in (("y_strings", ys, 1), ("z_strings", zs, 2)):
+        flat = np.frombuffer(b"".join(bytes(s) for s in strings), np.uint8)
+        idx = _dump_sample(flat.size, DUMP_CAPS[name], seed)
+        out[name] = (flat if idx is None else flat[idx]).astype(np.float32)
+    xh = [last[gi][1]["x_hat"].reshape(-1) for gi in range(len(groups))]
+    offs = np.cumsum([0] + [int(t.numel()) for t in xh])
+    idx = _dump_sample(int(offs[-1]), DUMP_CAPS["x_hat"], 3)
+    if idx is not None:
+        cut = np.searchsorted(idx, offs)
+        xh = [t[torch.from_numpy(idx[cut[g]:cut[g + 1]] - offs[g]).to(t.device)] for g, t in enumerate(xh)]
+    out["x_hat"] = torch.cat([t.float().cpu() for t in xh]).numpy()
+    for name, arr in out.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), arr)
+
+
 # ------------------------------------------------------------------------------- timing + collectives
 def timed_steps(run_steps, steps: int, distributed: bool, dev, sync=None) -> float:
     """The timed region: barrier + device sync on both sides of exactly `steps` steps; returns the
@@ -385,12 +457,15 @@ def main(argv=None):
 
     # one model instance per group when groups run concurrently (a handle's lanes serve one call at a
     # time), one per weight set otherwise
-    nets, gnet = {}, []
+    inputs = synth_inputs(groups, min(16, len(cores)))
+    nets, gnet, sds = {}, [], {}
     for gi, ((model, rate, _, _), _js) in enumerate(groups):
         key = (model, rate, gi if conc > 1 else 0)
         if key not in nets:
+            if (model, rate) not in sds:  # one draw per weight set, shared by its instances
+                sds[(model, rate)] = synthetic.synth_state_dict(model, 0, rate=rate)
             n = get_model(model)
-            n.load_state_dict(synthetic.synth_state_dict(model, 0, rate=rate))
+            n.load_state_dict(sds[(model, rate)])
             n = n.to(dev).eval()
             n.update()
             n.set_lanes(a.lanes)
@@ -405,7 +480,7 @@ def main(argv=None):
             nets[key] = n
         gnet.append(nets[key])
     # inputs resident in HBM before the timed region
-    xs = [torch.cat([synthetic.synth_image(j.H, j.W, j.seed) for j in js]).to(dev) for _, js in groups]
+    xs = [x.to(dev) for x in inputs()]
     streams = [torch.cuda.Stream(dev) for _ in groups]
     torch.cuda.synchronize()
     is_vbr = wl["model"].endswith("_VBR")
@@ -484,6 +559,8 @@ def main(argv=None):
     wall_split = {k: round(1000 * v / a.steps, 2) for k, v in split.items()}
     if decode_only:
         wall_split.pop("compress")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, groups, last, "" if world == 1 else f"_rank{rank}")
 
     # per-image records (mlic_amd.dist.RECORD_FIELDS): the one collective, all_gather over RCCL/xGMI
     F = {k: i for i, k in enumerate(mdist.RECORD_FIELDS)}

@@ -26,7 +26,7 @@ if has model; then
   rc=$?; tail -3 "$OUT/model.log"; [ $rc -eq 0 ] || { grep -E "^FAILED|^E  " "$OUT/model.log" | head -30; exit $rc; }
 fi
 if has bench; then
-  MLIC_DWPW2=$F timeout -k 10 400 python3 -u bench.py --steps 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
+  MLIC_DWPW2=$F timeout -k 10 400 python3 -u bench.py --full --steps 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
   head -c 300 "$OUT/bench.json"; echo
 fi
 echo "dwpw2_check done"

@@ -9,7 +9,7 @@ timeout -k 10 300 python3 -u -m pytest tests/test_gpu_conv.py tests/test_gpu_par
 tail -1 "$OUT/la_tests.log"
 for r in 1 2; do
   for t in "$@"; do
-    MLIC_HIP_LIB=$PWD/mlic_amd/libmlic_hip_$t.so timeout -k 10 400 python3 -u bench.py --steps 3 --no-cpu-baseline \
+    MLIC_HIP_LIB=$PWD/mlic_amd/libmlic_hip_$t.so timeout -k 10 400 python3 -u bench.py --full --steps 3 --no-cpu-baseline \
       --layers-out "$OUT/layers_${t}_$r.tsv" > "$OUT/bench_${t}_$r.json" 2> "$OUT/bench_${t}_$r.err" ||
       { echo "bench $t failed"; tail -5 "$OUT/bench_${t}_$r.err"; exit 1; }
     python3 -c "
