@@ -183,6 +183,18 @@ int mlic_local_attn_packed_run(void* stream, const float* qkv, const float* rel_
 int mlic_local_attn_packed_half_run(void* stream, const float* qkv, const float* rel_table, const int32_t* rel_index,
                                     uint16_t* out, int H, int W, int B, float scale, int ckbd);
 int mlic_image_sq_err_u8(void* stream, const float* a, const float* b, int B, int64_t n_per, double* out);
+/* bytes of device scratch mlic_image_ms_ssim_u8 needs (pooled planes + partial sums); host logic only,
+ * no GPU touched; nonzero rc with a message when C < 1, B < 1 or min(H, W) <= 160 */
+int mlic_ms_ssim_scratch_bytes(int B, int C, int H, int W, size_t* bytes);
+/* per-image MS-SSIM (pytorch_msssim defaults, data_range 255: DESIGN.md §3) of two [B][C][H][W] fp32 images
+ * in [0,1], made uint8-valued as mlic_image_sq_err_u8 does; element strides {image, channel, row} per
+ * operand (column stride 1), so a crop of a padded x_hat is scored in place; out: B doubles (device);
+ * terms: optional B*5*C doubles (device), the relu'd per-level per-channel cs / ssim means, level-major
+ * within an image; asynchronous on `stream`.  Arguments are checked before any GPU call; nothing outside
+ * scratch[0, bytes), out and terms is written.  Bit-reproducible, and independent of B. */
+int mlic_image_ms_ssim_u8(void* stream, const float* a, const int64_t* a_strides, const float* b,
+                          const int64_t* b_strides, int B, int C, int H, int W, void* scratch,
+                          size_t scratch_bytes, double* out, double* terms);
 /* per-image sum of -log2(lik) over n_per elements (fixed reduction order); synchronous */
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out);
 /* GaussianConditional likelihood (compressai, eval; mlicpp.py:132,168) element-wise: lik = max(Phi((0.5-|v|)/s')

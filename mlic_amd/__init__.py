@@ -4,6 +4,8 @@
     net = get_model("MLICPP_L").cuda().eval()
 """
 from .models import MLICPlusPlus, MLICPlusPlusSD, MLICPlusPlusSDVbr, MLICPlusPlusVbr, get_model, model_config  # noqa: F401
+from .metrics import ms_ssim_db, ms_ssim_u8  # noqa: F401
 from .spec import CONFIGS  # noqa: F401
 
-__all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusVbr", "get_model", "model_config", "CONFIGS"]
+__all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusVbr", "get_model", "model_config", "CONFIGS",
+           "ms_ssim_u8", "ms_ssim_db"]

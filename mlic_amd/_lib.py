@@ -66,6 +66,8 @@ def _sig(lib):
         "mlic_local_attn_packed_run": [p, p, p, p, p, i, i, i, f],
         "mlic_local_attn_packed_half_run": [p, p, p, p, p, i, i, i, f, i],
         "mlic_image_sq_err_u8": [p, p, p, i, i64, p],
+        "mlic_ms_ssim_scratch_bytes": [i, i, i, i, P(sz)],
+        "mlic_image_ms_ssim_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, sz, p, p],
         "mlic_neglog2_sum": [p, p, i, i64, p],
         "mlic_gaussian_likelihood": [p, p, p, p, i64, f, p],
         "mlic_scale_indexes": [p, p, i64, p, i, p],

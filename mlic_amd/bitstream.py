@@ -82,8 +82,10 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def code_image(net, img: torch.Tensor, **kw) -> Dict:
-    """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop."""
+def code_image(net, img: torch.Tensor, ms_ssim: bool = False, **kw) -> Dict:
+    """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
+    ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
+    None when the image is too small for the five levels)."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
     x = pad64(img)
@@ -99,5 +101,9 @@ def code_image(net, img: torch.Tensor, **kw) -> Dict:
     dec = net.decompress(strings, shape, **kw)
     dect = time.time() - t0
     x_hat = dec["x_hat"][:, :, :H, :W]
-    return {"H": H, "W": W, "bytes": nbytes, "bpp": 8.0 * nbytes / (H * W), "psnr": psnr_u8(img, x_hat),
-            "enc_s": enc, "dec_s": dect, "x_hat": x_hat}
+    r = {"H": H, "W": W, "bytes": nbytes, "bpp": 8.0 * nbytes / (H * W), "psnr": psnr_u8(img, x_hat),
+         "enc_s": enc, "dec_s": dect, "x_hat": x_hat}
+    if ms_ssim:
+        from . import metrics
+        r["ms_ssim"] = metrics.ms_ssim_u8(img, x_hat).item() if min(H, W) > metrics.MIN_SIDE else None
+    return r

@@ -601,6 +601,25 @@ int mlic_image_sq_err_u8(void* stream, const float* a, const float* b, int B, in
   return guard([&] { sq_err_u8(a, n_per, b, n_per, out, n_per, B, (hipStream_t)stream); });
 }
 
+int mlic_ms_ssim_scratch_bytes(int B, int C, int H, int W, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr, "ms_ssim_scratch_bytes: null bytes");
+    *bytes = ms_ssim_scratch_bytes(B, C, H, W);
+  });
+}
+
+int mlic_image_ms_ssim_u8(void* stream, const float* a, const int64_t* a_strides, const float* b,
+                          const int64_t* b_strides, int B, int C, int H, int W, void* scratch,
+                          size_t scratch_bytes, double* out, double* terms) {
+  return guard([&] {
+    const size_t need = ms_ssim_scratch_bytes(B, C, H, W);  // checks B, C, H, W
+    MLIC_CHECK(a && b && a_strides && b_strides && out, "ms_ssim: null argument");
+    MLIC_CHECK(scratch != nullptr && scratch_bytes >= need, "ms_ssim: scratch too small (mlic_ms_ssim_scratch_bytes)");
+    MLIC_CHECK(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, "ms_ssim: scratch must be 8-byte aligned");
+    ms_ssim_u8(a, a_strides, b, b_strides, B, C, H, W, scratch, out, terms, (hipStream_t)stream);
+  });
+}
+
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out) {
   return guard([&] {
     double* part = nullptr;

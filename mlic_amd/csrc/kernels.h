@@ -250,6 +250,12 @@ void sq_err_u8(const float* a, int64_t a_bs, const float* b, int64_t b_bs, doubl
 // per-image sum of -log2(lik) (fixed order); part = neglog2_partial_doubles(B) doubles of scratch
 int64_t neglog2_partial_doubles(int B);
 void neglog2_sum(const float* lik, int64_t n_per, int B, double* out, double* part, hipStream_t st);
+// per-image MS-SSIM of uint8-valued images (metrics.hip): a, b [B][C][H][W] fp32 in [0,1] with element
+// strides {image, channel, row}; scratch = ms_ssim_scratch_bytes() bytes; out B doubles; terms (optional)
+// [B][5][C] doubles.  ms_ssim_scratch_bytes is host logic only and throws on B < 1, C < 1, min(H, W) <= 160.
+size_t ms_ssim_scratch_bytes(int B, int C, int H, int W);
+void ms_ssim_u8(const float* a, const int64_t* a_strides, const float* b, const int64_t* b_strides, int B, int C,
+                int H, int W, void* scratch, double* out, double* terms, hipStream_t st);
 // GaussianConditional likelihood (vbr_scale != 1: of y*sc, s*sc, m*sc) and build_indexes, element-wise
 void gauss_likelihood(const float* y, const float* s, const float* m, int64_t n, float vbr_scale, float* lik,
                       hipStream_t st);
