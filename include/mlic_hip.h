@@ -119,7 +119,10 @@ int mlic_set_poison(mlic_model* m, int on);
  * per wave of the fused 1x1 chain (-1 default = $MLIC_CHAIN_NJ or 1; 2 = four waves of 32 pixels, the same
  * bits); "ep_half" = the slice loop's EntropyParameters chains (and its LocalContext, read by the non-anchor
  * EntropyParameters only) over their own phase's checkerboard half
- * (-1 default = $MLIC_EP_HALF or on; 0 = the whole grid: the same bits at every pixel that is read) */
+ * (-1 default = $MLIC_EP_HALF or on; 0 = the whole grid: the same bits at every pixel that is read);
+ * "image_io_path" = the form of the uint8 ingest / egress kernels (-1 default = by the byte image's strides;
+ * 0 = the general-stride form, 1 = the interleaved HWC form, 2 = the planar CHW form; a forced form that the
+ * strides do not fit is refused) -- every form gives the same bits */
 int mlic_set_kernel_option(const char* name, int value);
 /* 1 when this library holds the A/B-only kernel families (v1 split-fp16 tiles = precision 1, the halo
  * tiles = conv impl 6, the VALU local attention = local-attention impl 0; `make AB=1`), else 0: the
@@ -195,6 +198,71 @@ int mlic_ms_ssim_scratch_bytes(int B, int C, int H, int W, size_t* bytes);
 int mlic_image_ms_ssim_u8(void* stream, const float* a, const int64_t* a_strides, const float* b,
                           const int64_t* b_strides, int B, int C, int H, int W, void* scratch,
                           size_t scratch_bytes, double* out, double* terms);
+
+/* ---- uint8 images in, file bytes out, uint8 images back (utils/testing.py:338-424, submit/decode.py) ----
+ *
+ * ingest: B images of H x W x 3 bytes (device), read in place through element strides {image, row, column,
+ * channel} (interleaved HWC = {H*W*3, W*3, 3, 1}, planar CHW = {3*H*W, W, 1, H*W}; a crop view, a row-padded
+ * buffer or RGBA = {.., .., 4, 1} work as well; no alignment is assumed) -> dst: contiguous fp32
+ * [B][3][Hp][Wp], Hp >= H and Wp >= W multiples of 64.  Every element of dst is written: v / 255 (true IEEE
+ * division, torch's CPU `u8.float().div(255)` bit for bit) inside the image, +0.0 in the right / bottom padding.
+ * Asynchronous on `stream`; arguments are checked before any GPU call. */
+int mlic_image_ingest_u8(void* stream, const uint8_t* src, const int64_t* src_strides, int B, int H, int W, float* dst,
+                         int Hp, int Wp);
+/* egress: the H x W crop of fp32 src (element strides {image, channel, row}, column stride 1: a padded x_hat
+ * is cropped in place, the convention of mlic_image_ms_ssim_u8) -> uint8 floor(clamp(v, 0, 1) * 255) (the
+ * expression of mlic_image_sq_err_u8; NaN -> 0) written through dst_strides {image, row, column, channel}.
+ * Only the crop's bytes are written.  ref (optional, device, its own {image, row, column, channel} strides,
+ * the same H x W) together with sq_err (B uint64, device): sq_err[b] = the exact sum over image b of the squared
+ * uint8 differences, accumulated in integers (deterministic), so PSNR = 10 log10(255^2 * 3 H W / sq_err) comes
+ * with the decode.  ref and sq_err are both given or both NULL.  Asynchronous on `stream`; arguments are checked
+ * before any GPU call. */
+int mlic_image_egress_u8(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W, uint8_t* dst,
+                         const int64_t* dst_strides, const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err);
+
+/* The bitstream file of one image (utils/utils.py:28-83), big-endian:
+ *     H, W [, level]  |  h_z, w_z, n_strings = 2  |  y length, y bytes  |  z length, z bytes
+ * The format has no magic number: whether the level word is there is the caller's knowledge (a *_VBR model).
+ * Host only, no GPU touched. */
+typedef struct mlic_container_info {
+  uint32_t H, W;       /* the unpadded image */
+  uint32_t hz, wz;     /* ceil(H / 64), ceil(W / 64): the shape mlic_decompress takes */
+  int32_t level;       /* -1 when the file has no level word */
+  int32_t reserved;
+  uint64_t y_off, y_len; /* the y string is data[y_off, y_off + y_len) */
+  uint64_t z_off, z_len;
+} mlic_container_info;
+int mlic_container_bytes(size_t y_len, size_t z_len, int vbr, size_t* bytes);
+/* level < 0: no level word.  *len = the file's size; out == NULL only queries it. */
+int mlic_container_write(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_t wz, const uint8_t* y, size_t y_len,
+                         const uint8_t* z, size_t z_len, uint8_t* out, size_t cap, size_t* len);
+/* Validating parser: never reads outside data[0, n) and makes no copies (info holds offsets into data).
+ * Refused, each with its own message: input truncated anywhere; n_strings != 2; a length running past the
+ * end; bytes left over after the z string; H == 0 or W == 0; h_z != ceil(H / 64) or w_z != ceil(W / 64);
+ * (64 h_z) * (64 w_z) > max_pixels; with vbr, level >= n_levels. */
+int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, uint64_t max_pixels,
+                         mlic_container_info* info);
+
+/* One image, pixels to file bytes: ingest into a staging buffer the handle owns (it grows on demand and is
+ * freed by mlic_destroy), mlic_compress with B = 1, the container.  rgb_dev: H x W x 3 bytes on the device
+ * with strides {row, column, channel}; level >= 0 is written into the header (vbr_scale is that level's gain),
+ * -1 writes none.  *len = the file's size.  out == NULL: the image is encoded and only the size reported;
+ * rgb_dev == NULL: nothing is encoded, the file of the handle's last encode is written again (so: one call
+ * with out == NULL, allocate, one call with rgb_dev == NULL).  Returns with the file complete.
+ * These two B = 1 conveniences run on one lane: they do not overlap one image's entropy coding with another's
+ * kernels as a batched mlic_compress / mlic_decompress does.  Batch users compose mlic_image_ingest_u8,
+ * mlic_compress, mlic_container_write themselves (mlic_amd/codec.py does). */
+int mlic_encode_image_u8(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H, int W,
+                         float vbr_scale, int level, uint8_t* out, size_t cap, size_t* len);
+/* File bytes to pixels: mlic_container_parse (n_levels > 0 says the file has a level word; max_pixels bounds
+ * the padded size before anything is allocated), mlic_decompress into the staging buffer, egress of the crop to
+ * rgb_dev through strides {row, column, channel} (non-negative).  cap_bytes = bytes addressable from rgb_dev:
+ * a file whose H x W needs more is refused before any GPU call.  vbr_gains: n_levels floats, the gain of each
+ * level (NULL = 1).  H, W, level (-1 = none) are reported; rgb_dev == NULL only parses and reports them (m may
+ * be NULL then).  Asynchronous on `stream` once the entropy decoding is done. */
+int mlic_decode_image_u8(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels, uint64_t max_pixels,
+                         const float* vbr_gains, uint8_t* rgb_dev, const int64_t* strides, size_t cap_bytes, int* H,
+                         int* W, int* level);
 /* per-image sum of -log2(lik) over n_per elements (fixed reduction order); synchronous */
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out);
 /* GaussianConditional likelihood (compressai, eval; mlicpp.py:132,168) element-wise: lik = max(Phi((0.5-|v|)/s')

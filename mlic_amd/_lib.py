@@ -20,6 +20,13 @@ class MlicError(RuntimeError):
     pass
 
 
+class ContainerInfo(C.Structure):
+    """mlic_container_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("hz", C.c_uint32), ("wz", C.c_uint32), ("level", C.c_int32),
+                ("reserved", C.c_int32), ("y_off", C.c_uint64), ("y_len", C.c_uint64), ("z_off", C.c_uint64),
+                ("z_len", C.c_uint64)]
+
+
 def _sig(lib):
     p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
     P = C.POINTER
@@ -68,6 +75,13 @@ def _sig(lib):
         "mlic_image_sq_err_u8": [p, p, p, i, i64, p],
         "mlic_ms_ssim_scratch_bytes": [i, i, i, i, P(sz)],
         "mlic_image_ms_ssim_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, sz, p, p],
+        "mlic_image_ingest_u8": [p, p, P(i64), i, i, i, p, i, i],
+        "mlic_image_egress_u8": [p, p, P(i64), i, i, i, p, P(i64), p, P(i64), p],
+        "mlic_container_bytes": [sz, sz, i, P(sz)],
+        "mlic_container_write": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, p, sz, p, sz, P(sz)],
+        "mlic_container_parse": [p, sz, i, i, C.c_uint64, P(ContainerInfo)],
+        "mlic_encode_image_u8": [p, p, p, P(i64), i, i, f, i, p, sz, P(sz)],
+        "mlic_decode_image_u8": [p, p, p, sz, i, C.c_uint64, p, p, P(i64), sz, P(i), P(i), P(i)],
         "mlic_neglog2_sum": [p, p, i, i64, p],
         "mlic_gaussian_likelihood": [p, p, p, p, i64, f, p],
         "mlic_scale_indexes": [p, p, i64, p, i, p],

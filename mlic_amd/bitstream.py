@@ -55,6 +55,19 @@ def read_stream(fd, vbr: bool = False):
     return hdr, strings, (hz, wz)
 
 
+def read_stream_checked(fd, vbr: bool = False, n_levels=None, max_pixels: int = 1 << 28):
+    """read_stream through the library's validating parser (csrc/container.cpp): the same return value for a
+    well-formed file, _lib.MlicError for a truncated or inconsistent one (a length past the end, h_z / w_z that
+    do not belong to H / W, a padded size above max_pixels, a level >= n_levels, trailing bytes).  fd: a binary
+    file object (read to its end) or the file's bytes."""
+    from . import codec
+    data = fd if isinstance(fd, (bytes, bytearray, memoryview)) else fd.read()
+    data = bytes(data)
+    c = codec.parse_container(data, vbr, n_levels, max_pixels)
+    hdr = (c.H, c.W, c.level) if vbr else (c.H, c.W)
+    return hdr, [[data[c.y_off:c.y_off + c.y_len]], [data[c.z_off:c.z_off + c.z_len]]], (c.hz, c.wz)
+
+
 def write_file(path: str, H: int, W: int, out: Dict, level=None) -> int:
     with open(path, "wb") as f:
         return write_stream(f, H, W, out["shape"], out["strings"], level)

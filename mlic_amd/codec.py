@@ -1,0 +1,280 @@
+"""uint8 images in, bitstream files out, uint8 images back (utils/testing.py:338-424, submit/decode.py):
+
+    PIL image -> ToTensor -> pad to 64 -> compress -> file  |  file -> decompress -> crop -> uint8 image
+
+`ingest_u8` is ToTensor + pad in one kernel launch (uint8 of any layout / strides -> fp32 [B,3,Hp,Wp], v / 255
+exactly as torch's CPU `u8.float().div(255)`, zeros in the padding), `egress_u8` is crop + clamp * 255 + cast in
+one launch (optionally with the exact per-image sum of squared uint8 differences against a reference, so PSNR
+comes with the decode).  The file is the layout documented in bitstream.py, written and parsed by the library
+(csrc/container.cpp); the parser validates every field before anything is sized from it.
+
+CUDA tensors run the HIP kernels (csrc/image_io.hip) on the current stream; CPU tensors run a torch
+restatement, so everything but the model also works without a GPU (as metrics.py does).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, bitstream
+
+MAX_PIXELS = 1 << 28  # default bound on a file's padded Hp * Wp (a 16384 x 16384 image)
+_NO_LEVEL_LIMIT = 0x7FFFFFFF
+
+
+# ------------------------------------------------------------------------------------------ layouts
+def _layout(t: torch.Tensor, layout: Optional[str]) -> str:
+    if layout is None:
+        if t.shape[-1] == 3:
+            return "hwc"
+        if t.shape[-3] == 3:
+            return "chw"
+        raise ValueError(f"cannot tell the layout of an image tensor of shape {tuple(t.shape)}: pass layout=")
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    return layout
+
+
+def _u8_batch(img, layout: Optional[str], what: str):
+    """-> (4-dim uint8 tensor, layout): a single image gains the batch dimension."""
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img))
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() not in (3, 4):
+        raise ValueError(f"{what}: a uint8 tensor or array [B,H,W,3] / [B,3,H,W] (or one image) expected")
+    if img.dim() == 3:
+        img = img.unsqueeze(0)
+    layout = _layout(img, layout)
+    if img.size(3 if layout == "hwc" else 1) != 3:
+        raise ValueError(f"{what}: {layout} image with 3 channels expected, got shape {tuple(img.shape)}")
+    if 0 in img.shape:
+        raise ValueError(f"{what}: empty image {tuple(img.shape)}")
+    return img, layout
+
+
+def _hw(t: torch.Tensor, layout: str):
+    return (t.size(1), t.size(2)) if layout == "hwc" else (t.size(2), t.size(3))
+
+
+def _strides(t: torch.Tensor, layout: str):
+    """Element strides {image, row, column, channel} of a 4-dim image tensor."""
+    s = t.stride()
+    return (s[0], s[1], s[2], s[3]) if layout == "hwc" else (s[0], s[2], s[3], s[1])
+
+
+def _in_place(t: torch.Tensor, layout: str) -> torch.Tensor:
+    """The kernels read any strides but zero column / channel strides (an expanded tensor)."""
+    _, _, col, ch = _strides(t, layout)
+    return t.contiguous() if col == 0 or ch == 0 else t
+
+
+def _nchw(t: torch.Tensor, layout: str) -> torch.Tensor:
+    return t.permute(0, 3, 1, 2) if layout == "hwc" else t
+
+
+def _pad64(n: int) -> int:
+    return (n + 63) // 64 * 64
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ------------------------------------------------------------------------------------------ kernels
+def ingest_u8(img, layout: Optional[str] = "hwc") -> torch.Tensor:
+    """uint8 images [B,H,W,3] (layout "hwc") or [B,3,H,W] ("chw"), or one image, with any strides (a crop, a
+    row-padded buffer, the RGB of an RGBA array are read in place) -> the model's input: contiguous fp32
+    [B,3,Hp,Wp], Hp / Wp the next multiples of 64; v / 255 inside the image (true division: the value
+    torchvision's ToTensor produces) and exactly 0 in the right / bottom padding."""
+    img, layout = _u8_batch(img, layout, "ingest_u8")
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    if not img.is_cuda:
+        return bitstream.pad64(_nchw(img, layout).float().div(255)).contiguous()
+    img = _in_place(img, layout)
+    Hp, Wp = _pad64(H), _pad64(W)
+    with torch.cuda.device(img.device):
+        x = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=img.device)
+        if _lib.poison():
+            x.fill_(float("nan"))
+        _lib.call("mlic_image_ingest_u8", _stream(), C.c_void_p(img.data_ptr()), (C.c_int64 * 4)(*_strides(img, layout)),
+                  B, H, W, C.c_void_p(x.data_ptr()), Hp, Wp)
+    return x
+
+
+def egress_u8(x_hat: torch.Tensor, H: int, W: int, layout: str = "hwc", ref=None, out: Optional[torch.Tensor] = None):
+    """The top-left H x W crop of fp32 [B,3,>=H,>=W] (a padded x_hat, read in place) as uint8
+    floor(clamp(v, 0, 1) * 255) -- bitstream.to_u8; a NaN gives 0 on the device -- in `layout`: [B,H,W,3] or
+    [B,3,H,W].  out: an optional uint8 tensor of that shape with any strides (a window of a larger canvas); only
+    the crop's bytes are written.  ref: a uint8 image batch of that shape (any strides): returns (image, sq_err)
+    with sq_err int64 [B], the exact per-image sum of squared uint8 differences."""
+    layout = _layout(x_hat, layout)
+    if x_hat.dim() != 4 or x_hat.size(1) != 3 or x_hat.dtype != torch.float32:
+        raise ValueError(f"egress_u8: fp32 [B,3,h,w] expected, got {x_hat.dtype} {tuple(x_hat.shape)}")
+    B = x_hat.size(0)
+    if not (1 <= H <= x_hat.size(2) and 1 <= W <= x_hat.size(3)) or B < 1:
+        raise ValueError(f"egress_u8: crop {H} x {W} of {tuple(x_hat.shape)}")
+    shape = (B, H, W, 3) if layout == "hwc" else (B, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x_hat.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x_hat.device:
+        raise ValueError(f"egress_u8: out must be uint8 {shape} on {x_hat.device}")
+    if ref is not None:
+        ref, _ = _u8_batch(ref, layout, "egress_u8 ref")
+        if tuple(ref.shape) != shape:
+            raise ValueError(f"egress_u8: ref must have shape {shape}, got {tuple(ref.shape)}")
+        ref = ref.to(x_hat.device)
+    if not x_hat.is_cuda:
+        u = bitstream.to_u8(x_hat[:, :, :H, :W])
+        out.copy_(u.permute(0, 2, 3, 1) if layout == "hwc" else u)
+        if ref is None:
+            return out
+        d = out.to(torch.int64) - ref.to(torch.int64)
+        return out, (d * d).flatten(1).sum(1)
+    if x_hat.stride(3) != 1:
+        x_hat = x_hat.contiguous()
+    if 0 in _strides(out, layout)[2:]:
+        raise ValueError("egress_u8: out has a zero column or channel stride")
+    with torch.cuda.device(x_hat.device):
+        sq = None
+        if ref is not None:
+            ref = _in_place(ref, layout)
+            sq = torch.full((B,), -1, dtype=torch.int64, device=x_hat.device)
+        _lib.call("mlic_image_egress_u8", _stream(), C.c_void_p(x_hat.data_ptr()), (C.c_int64 * 3)(*x_hat.stride()[:3]),
+                  B, H, W, C.c_void_p(out.data_ptr()), (C.c_int64 * 4)(*_strides(out, layout)),
+                  None if ref is None else C.c_void_p(ref.data_ptr()),
+                  None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)),
+                  None if sq is None else C.c_void_p(sq.data_ptr()))
+    return out if ref is None else (out, sq)
+
+
+# ---------------------------------------------------------------------------------------- container
+def container_bytes(y_len: int, z_len: int, vbr: bool = False) -> int:
+    n = C.c_size_t()
+    _lib.call("mlic_container_bytes", y_len, z_len, int(vbr), C.byref(n))
+    return n.value
+
+
+def write_container(H: int, W: int, shape, y: bytes, z: bytes, level: Optional[int] = None) -> bytes:
+    """One image's file (byte-identical to bitstream.write_stream(fd, H, W, shape, [[y], [z]], level))."""
+    n = C.c_size_t()
+    lv = -1 if level is None else int(level)
+    if level is not None and lv < 0:
+        raise ValueError("write_container: negative level")
+    buf = C.create_string_buffer(max(1, container_bytes(len(y), len(z), level is not None)))
+    _lib.call("mlic_container_write", H, W, lv, int(shape[0]), int(shape[1]), y, len(y), z, len(z), buf, len(buf),
+              C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container(data: bytes, vbr: bool = False, n_levels: Optional[int] = None,
+                    max_pixels: int = MAX_PIXELS) -> _lib.ContainerInfo:
+    """The validating parser (mlic_container_parse): raises _lib.MlicError on any malformed input.  vbr says
+    whether the file has a level word (the format cannot tell); n_levels bounds it (None: any level)."""
+    data = bytes(data)
+    info = _lib.ContainerInfo()
+    nl = (_NO_LEVEL_LIMIT if n_levels is None else int(n_levels)) if vbr else 0
+    _lib.call("mlic_container_parse", data, len(data), int(vbr), nl, int(max_pixels), C.byref(info))
+    return info
+
+
+def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> Dict:
+    """What a file says about itself, validated: H, W, level (None without one), the z grid `shape`, the
+    padded size, the string lengths and the bpp of the whole file."""
+    c = parse_container(data, vbr, n_levels, max_pixels)
+    return {"H": c.H, "W": c.W, "level": c.level if vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz,
+            "Wp": 64 * c.wz, "y_len": c.y_len, "z_len": c.z_len, "bytes": len(data),
+            "bpp": 8.0 * len(data) / (c.H * c.W)}
+
+
+def _strings(data: bytes, c: _lib.ContainerInfo):
+    return data[c.y_off:c.y_off + c.y_len], data[c.z_off:c.z_off + c.z_len]
+
+
+# -------------------------------------------------------------------------------------------- codec
+def _levels(net, level, B: int):
+    """-> (per-image level list or None, kwargs of net.compress / net.decompress)."""
+    vbr = hasattr(net, "levels")
+    if level is None:
+        if vbr:
+            raise ValueError("a variable-rate model needs level= (it is written into the file's header)")
+        return None, {}
+    if not vbr:
+        raise ValueError("level= given for a fixed-rate model")
+    lv = [int(v) for v in (level if isinstance(level, (list, tuple)) else np.asarray(level).reshape(-1).tolist())]
+    if len(lv) == 1:
+        lv = lv * B
+    if len(lv) != B or any(not 0 <= v < net.levels for v in lv):
+        raise ValueError(f"level: one value or {B}, each in [0, {net.levels})")
+    return lv, {"s": lv}
+
+
+@torch.no_grad()
+def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None) -> List[bytes]:
+    """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
+    the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
+    ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
+    one per image), required for *_VBR models."""
+    img, layout = _u8_batch(imgs_u8, layout, "encode_images")
+    img = img.to(net.device)
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    lv, kw = _levels(net, level, B)
+    out = net.compress(ingest_u8(img, layout), **kw)
+    ys, zs = out["strings"]
+    return [write_container(H, W, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
+
+
+@torch.no_grad()
+def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS):
+    """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
+    (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
+    image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
+    [B,max H,max W,3] tensor.  Every file goes through the validating parser first."""
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("decode_images: no files")
+    vbr = hasattr(net, "levels")
+    cs = [parse_container(f, vbr, net.levels if vbr else None, max_pixels) for f in files]
+    if len({(c.hz, c.wz) for c in cs}) != 1:
+        raise ValueError(f"decode_images: the files must share one padded size, got z grids "
+                         f"{sorted({(c.hz, c.wz) for c in cs})}")
+    B = len(files)
+    pairs = [_strings(f, c) for f, c in zip(files, cs)]
+    kw = {"s": [c.level for c in cs]} if vbr else {}
+    x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
+    H, W = max(c.H for c in cs), max(c.W for c in cs)
+    if ref is not None:
+        ref, _ = _u8_batch(ref, "hwc", "decode_images ref")
+        if tuple(ref.shape) != (B, H, W, 3):
+            raise ValueError(f"decode_images: ref must be uint8 {(B, H, W, 3)}, got {tuple(ref.shape)}")
+        ref = ref.to(x_hat.device)
+    if all((c.H, c.W) == (H, W) for c in cs):
+        r = egress_u8(x_hat, H, W, "hwc", ref=ref)
+        img, sq = r if ref is not None else (r, None)
+    else:
+        img = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=x_hat.device)
+        sq = None if ref is None else torch.zeros(B, dtype=torch.int64, device=x_hat.device)
+        for b, c in enumerate(cs):
+            r = egress_u8(x_hat[b:b + 1], c.H, c.W, "hwc", out=img[b:b + 1, :c.H, :c.W],
+                          ref=None if ref is None else ref[b:b + 1, :c.H, :c.W])
+            if ref is not None:
+                sq[b] = r[1][0]
+    sq = None if sq is None else sq.cpu().tolist()
+    info = []
+    for b, c in enumerate(cs):
+        d = {"H": c.H, "W": c.W, "level": c.level if vbr else None, "bytes": len(files[b]),
+             "bpp": 8.0 * len(files[b]) / (c.H * c.W)}
+        if sq is not None:
+            d["sq_err"] = int(sq[b])
+            d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W)
+        info.append(d)
+    return img, info
+
+
+def psnr_from_sq_err(sq_err: int, n: int) -> float:
+    """PSNR (max 255, utils/metrics.py:32-33) from a sum of squared uint8 differences over n values."""
+    return 10.0 * math.log10(255.0 ** 2 * n / sq_err) if sq_err > 0 else float("inf")

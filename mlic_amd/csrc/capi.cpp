@@ -7,12 +7,18 @@
 #include <string>
 #include <vector>
 
+#include "container.h"
 #include "model.h"
 
 using namespace mlic;
 
 struct mlic_model {
   Model* impl;
+  // mlic_encode_image_u8 / mlic_decode_image_u8: the padded fp32 image [3][Hp][Wp] between the uint8 kernels and
+  // the model (grows on demand), and the header fields of the last encode
+  float* stage = nullptr;
+  size_t stage_bytes = 0;
+  int enc_H = 0, enc_W = 0, enc_level = -1;  // enc_H == 0: nothing encoded yet
 };
 
 static thread_local std::string g_err;
@@ -58,7 +64,8 @@ int mlic_create(const char* model_name, int n, const char* const* names, const f
                 const int64_t* shapes, const int* ndims, void* stream, mlic_model** out) {
   return guard([&] {
     MLIC_CHECK(out != nullptr, "null out");
-    auto* m = new mlic_model{nullptr};
+    auto* m = new mlic_model();
+    m->impl = nullptr;
     try {
       m->impl = new Model(model_name, n, names, ptrs, shapes, ndims, (hipStream_t)stream);
       if (const char* e = std::getenv("MLIC_LANES")) m->impl->set_lanes(std::atoi(e));
@@ -77,6 +84,7 @@ int mlic_destroy(mlic_model* m) {
   return guard([&] {
     if (!m) return;
     delete m->impl;
+    if (m->stage) (void)hipFree(m->stage);
     delete m;
   });
 }
@@ -236,6 +244,7 @@ int mlic_set_kernel_option(const char* name, int value) {
     else if (n == "narrow_limit") set_narrow_limit(value);
     else if (n == "chain_nj") chain_set_nj(value);
     else if (n == "ep_half") chain_set_ep_half(value);
+    else if (n == "image_io_path") image_io_set_path(value);
     else throw Error("mlic: unknown kernel option " + n);
   });
 }
@@ -617,6 +626,130 @@ int mlic_image_ms_ssim_u8(void* stream, const float* a, const int64_t* a_strides
     MLIC_CHECK(scratch != nullptr && scratch_bytes >= need, "ms_ssim: scratch too small (mlic_ms_ssim_scratch_bytes)");
     MLIC_CHECK(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, "ms_ssim: scratch must be 8-byte aligned");
     ms_ssim_u8(a, a_strides, b, b_strides, B, C, H, W, scratch, out, terms, (hipStream_t)stream);
+  });
+}
+
+int mlic_image_ingest_u8(void* stream, const uint8_t* src, const int64_t* src_strides, int B, int H, int W, float* dst,
+                         int Hp, int Wp) {
+  return guard([&] { image_ingest_u8(src, src_strides, B, H, W, dst, Hp, Wp, (hipStream_t)stream); });
+}
+
+int mlic_image_egress_u8(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W, uint8_t* dst,
+                         const int64_t* dst_strides, const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err) {
+  return guard([&] {
+    image_egress_u8(src, src_strides, B, H, W, dst, dst_strides, ref, ref_strides, sq_err, (hipStream_t)stream);
+  });
+}
+
+static void container_ok(const char* err) {
+  if (err) throw Error(std::string("mlic: ") + err);
+}
+
+int mlic_container_bytes(size_t y_len, size_t z_len, int vbr, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr, "container_bytes: null bytes");
+    *bytes = container_bytes(y_len, z_len, vbr != 0);
+  });
+}
+
+int mlic_container_write(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_t wz, const uint8_t* y, size_t y_len,
+                         const uint8_t* z, size_t z_len, uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] { container_ok(container_write(H, W, level, hz, wz, y, y_len, z, z_len, out, cap, len)); });
+}
+
+static void to_abi(const ContainerInfo& c, mlic_container_info* o) {
+  o->H = c.H;
+  o->W = c.W;
+  o->hz = c.hz;
+  o->wz = c.wz;
+  o->level = c.level;
+  o->reserved = 0;
+  o->y_off = c.y_off;
+  o->y_len = c.y_len;
+  o->z_off = c.z_off;
+  o->z_len = c.z_len;
+}
+
+int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, uint64_t max_pixels,
+                         mlic_container_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse: null info");
+    MLIC_CHECK(!vbr || n_levels >= 1, "container_parse: a VBR file needs n_levels >= 1");
+    ContainerInfo c;
+    container_ok(container_parse(data, n, vbr != 0, (uint32_t)std::max(n_levels, 0), max_pixels, &c));
+    to_abi(c, info);
+  });
+}
+
+// the handle's staging image: at least `bytes`, grown by reallocation (hipFree waits for the device)
+static float* stage(mlic_model* m, size_t bytes) {
+  if (m->stage_bytes < bytes) {
+    if (m->stage) HIP_OK(hipFree(m->stage));
+    m->stage = nullptr;
+    m->stage_bytes = 0;
+    HIP_OK(hipMalloc((void**)&m->stage, bytes));
+    m->stage_bytes = bytes;
+  }
+  return m->stage;
+}
+
+int mlic_encode_image_u8(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H, int W,
+                         float vbr_scale, int level, uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    Model& mod = impl(m);
+    MLIC_CHECK(len != nullptr, "encode_image_u8: null len");
+    if (rgb_dev != nullptr) {
+      MLIC_CHECK(strides != nullptr && H >= 1 && W >= 1, "encode_image_u8: strides, H >= 1 and W >= 1 expected");
+      MLIC_CHECK(H <= (1 << 24) && W <= (1 << 24), "encode_image_u8: image side above 2^24");
+      const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64;
+      const int64_t s4[4] = {0, strides[0], strides[1], strides[2]};
+      m->enc_H = 0;
+      float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
+      image_ingest_u8(rgb_dev, s4, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
+      const float sc[1] = {vbr_scale};
+      mod.compress(x, 1, Hp, Wp, sc, (hipStream_t)stream);
+      m->enc_H = H;
+      m->enc_W = W;
+      m->enc_level = level < 0 ? -1 : level;
+    }
+    MLIC_CHECK(m->enc_H > 0, "encode_image_u8: rgb_dev is NULL and the handle has no encoded image");
+    const EncodedImage& e = mod.encoded(0);
+    container_ok(container_write((uint32_t)m->enc_H, (uint32_t)m->enc_W, m->enc_level, (uint32_t)((m->enc_H + 63) / 64),
+                                 (uint32_t)((m->enc_W + 63) / 64), reinterpret_cast<const uint8_t*>(e.y.data()),
+                                 e.y.size(), reinterpret_cast<const uint8_t*>(e.z.data()), e.z.size(), out, cap, len));
+  });
+}
+
+int mlic_decode_image_u8(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels, uint64_t max_pixels,
+                         const float* vbr_gains, uint8_t* rgb_dev, const int64_t* strides, size_t cap_bytes, int* H,
+                         int* W, int* level) {
+  return guard([&] {
+    MLIC_CHECK(file != nullptr || n == 0, "decode_image_u8: null file");
+    const bool vbr = n_levels > 0;
+    ContainerInfo c;
+    // 2^24 pixels a side at most (the int sizes of this ABI), whatever max_pixels allows
+    container_ok(container_parse(file, n, vbr, (uint32_t)std::max(n_levels, 0), max_pixels, &c));
+    MLIC_CHECK(c.H <= (1u << 24) && c.W <= (1u << 24), "decode_image_u8: image side above 2^24");
+    if (H) *H = (int)c.H;
+    if (W) *W = (int)c.W;
+    if (level) *level = c.level;
+    if (rgb_dev == nullptr) return;
+    Model& mod = impl(m);
+    MLIC_CHECK(strides != nullptr && strides[0] >= 0 && strides[1] > 0 && strides[2] > 0,
+               "decode_image_u8: strides {row, column, channel} must be non-negative, column and channel nonzero");
+    const uint64_t extent = 1 + (uint64_t)(c.H - 1) * (uint64_t)strides[0] + (uint64_t)(c.W - 1) * (uint64_t)strides[1] +
+                            2 * (uint64_t)strides[2];
+    MLIC_CHECK(extent <= cap_bytes, "decode_image_u8: the file's image does not fit cap_bytes");
+    const int Hp = (int)c.hz * 64, Wp = (int)c.wz * 64;
+    float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
+    const uint8_t* ys[1] = {file + c.y_off};
+    const uint8_t* zs[1] = {file + c.z_off};
+    const size_t yl[1] = {c.y_len}, zl[1] = {c.z_len};
+    const float sc[1] = {vbr && vbr_gains ? vbr_gains[c.level] : 1.0f};
+    mod.decompress(ys, yl, zs, zl, 1, (int)c.hz, (int)c.wz, x, sc, (hipStream_t)stream);
+    const int64_t s3[3] = {0, (int64_t)Hp * Wp, Wp};
+    const int64_t d4[4] = {0, strides[0], strides[1], strides[2]};
+    image_egress_u8(x, s3, 1, (int)c.H, (int)c.W, rgb_dev, d4, nullptr, nullptr, nullptr, (hipStream_t)stream);
   });
 }
 

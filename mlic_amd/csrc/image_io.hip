@@ -1,0 +1,284 @@
+// uint8 image ingest / egress (utils/testing.py:338-424: ToTensor -> pad ... crop -> uint8), one launch each.
+//
+// ingest: uint8 H x W x 3 images, read through element strides {image, row, column, channel}, become the
+// model's input: fp32 [B][3][Hp][Wp], v / 255 inside the image (a true IEEE division: torch's CPU
+// `u8.float().div(255)` bit for bit; v * (1 / 255.f) differs for 126 of the 256 values) and +0 in the
+// right / bottom padding.  Every destination element is written.
+// egress: the H x W crop of fp32 planes (element strides {image, channel, row}) becomes uint8,
+// floor(clamp(v, 0, 1) * 255) as sq_err_u8_kernel and metrics.hip have it (fmaxf drops a NaN: NaN -> 0), written
+// through {image, row, column, channel} strides; nothing outside the crop's bytes is written.  With a
+// reference image the per-image sum of squared uint8 differences is accumulated in integers (exact,
+// order-independent: one 64-bit integer atomic per block).
+//
+// A block is four waves; a wave owns one image row of the tile and 256 pixels of it.  Byte rows start at
+// any address (W * 3 is odd for odd W), so the two canonical layouts go through LDS: the row segment sits
+// in LDS at its global address mod 4, whole aligned dwords move as dwords, and the up to three bytes at
+// either end move as bytes -- nothing outside the segment is read or written.  The fp32 side is one
+// 256-byte row piece per wave instruction.  Any other stride set takes the general kernels (byte accesses
+// straight from / to global memory); all forms give the same bits.
+#include "kernels.h"
+
+#include <atomic>
+
+namespace mlic {
+
+namespace {
+
+constexpr int IO_TW = 256, IO_ROWS = 4;        // tile: one row per wave, 4 pixels per lane
+constexpr int IO_SEG = IO_TW / 4 + 1;          // dwords of a 256-byte segment at any alignment
+constexpr int IO_LDS = 3 * IO_SEG;             // per wave: one 768-byte segment (HWC) or three of 256 (CHW)
+// With a reference image a block walks this many row groups and issues one atomic for all of them: 69 120
+// blocks' atomics onto 32 addresses (32 x 1080 x 1920, one group per block) cost 0.40 ms of that launch's 0.65
+constexpr int IO_REF_GROUPS = 16;
+enum { IO_GENERAL = 0, IO_HWC = 1, IO_CHW = 2 };
+
+struct IoStride3 {
+  int64_t img, ch, row;
+};
+struct IoStride4 {
+  int64_t img, row, col, ch;
+};
+
+__device__ inline int addr_mod4(const void* p) { return (int)(reinterpret_cast<uintptr_t>(p) & 3); }
+
+// global bytes p[0, n) -> LDS bytes r[sh, sh + n), sh = p mod 4 (r is dword-aligned): one wave
+__device__ inline void stage_in(const uint8_t* __restrict__ p, int n, uint32_t* r, int lane) {
+  const int sh = addr_mod4(p);
+  uint8_t* r8 = reinterpret_cast<uint8_t*>(r);
+  const int end = sh + n, nd = (end + 3) >> 2;
+  for (int k = lane; k < nd; k += 64) {
+    const int lo = 4 * k, hi = lo + 4;
+    if (lo >= sh && hi <= end) {
+      r[k] = *reinterpret_cast<const uint32_t*>(p + (lo - sh));
+    } else {
+      for (int i = max(lo, sh); i < min(hi, end); ++i) r8[i] = p[i - sh];
+    }
+  }
+}
+
+// LDS bytes r[sh, sh + n) -> global bytes p[0, n), sh = p mod 4: one wave
+__device__ inline void stage_out(uint8_t* __restrict__ p, int n, const uint32_t* r, int lane) {
+  const int sh = addr_mod4(p);
+  const uint8_t* r8 = reinterpret_cast<const uint8_t*>(r);
+  const int end = sh + n, nd = (end + 3) >> 2;
+  for (int k = lane; k < nd; k += 64) {
+    const int lo = 4 * k, hi = lo + 4;
+    if (lo >= sh && hi <= end) {
+      *reinterpret_cast<uint32_t*>(p + (lo - sh)) = r[k];
+    } else {
+      for (int i = max(lo, sh); i < min(hi, end); ++i) p[i - sh] = r8[i];
+    }
+  }
+}
+
+// blockIdx.x = (image, row block, column tile), column tile fastest; y = this wave's row in the block's first
+// row group (a row block is `rows` rows)
+struct IoTile {
+  int64_t img;
+  int y, x0;
+};
+__device__ inline IoTile io_tile(int tiles_x, int tiles_y, int rows = IO_ROWS) {
+  const int64_t t = blockIdx.x;
+  const int64_t ry = t / tiles_x;
+  IoTile o;
+  o.x0 = (int)(t - ry * tiles_x) * IO_TW;
+  o.img = ry / tiles_y;
+  o.y = (int)(ry - o.img * tiles_y) * rows + (int)(threadIdx.x >> 6);
+  return o;
+}
+
+template <int PATH>
+__global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ src, IoStride4 s, int H, int W,
+                                                        float* __restrict__ dst, int Hp, int Wp, int tiles_x,
+                                                        int tiles_y) {
+  __shared__ uint32_t S[IO_ROWS][IO_LDS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const IoTile t = io_tile(tiles_x, tiles_y);
+  // pixels of this wave's row segment that lie inside the image (the rest is padding)
+  const int nx = t.y < H ? min(IO_TW, max(W - t.x0, 0)) : 0;
+  const uint8_t* row = src + t.img * s.img + (int64_t)t.y * s.row + (int64_t)t.x0 * s.col;  // used when nx > 0
+  int sh[3] = {0, 0, 0};
+  if (PATH == IO_HWC && nx > 0) {
+    sh[0] = addr_mod4(row);
+    stage_in(row, 3 * nx, S[wave], lane);
+  }
+  if (PATH == IO_CHW && nx > 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      sh[c] = addr_mod4(row + c * s.ch);
+      stage_in(row + c * s.ch, nx, S[wave] + c * IO_SEG, lane);
+    }
+  }
+  if (PATH != IO_GENERAL) __syncthreads();
+  const uint8_t* S8 = reinterpret_cast<const uint8_t*>(S[wave]);
+  const int64_t plane = (int64_t)Hp * Wp;
+  float* out = dst + t.img * 3 * plane + (int64_t)t.y * Wp + t.x0;
+#pragma unroll
+  for (int j = 0; j < IO_TW / 64; ++j) {
+    const int px = lane + 64 * j;
+    if (t.x0 + px >= Wp) break;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float v = 0.0f;
+      if (px < nx) {
+        uint8_t u;
+        if (PATH == IO_HWC) u = S8[sh[0] + 3 * px + c];
+        else if (PATH == IO_CHW) u = S8[c * IO_SEG * 4 + sh[c] + px];
+        else u = row[(int64_t)px * s.col + c * s.ch];
+        v = (float)u / 255.0f;  // correctly rounded (hipcc's default for fp32 division)
+      }
+      out[c * plane + px] = v;
+    }
+  }
+}
+
+template <int PATH, bool REF>
+__global__ __launch_bounds__(256) void egress_u8_kernel(const float* __restrict__ src, IoStride3 ss, int H, int W,
+                                                        uint8_t* __restrict__ dst, IoStride4 ds,
+                                                        const uint8_t* __restrict__ ref, IoStride4 rs,
+                                                        unsigned long long* __restrict__ sq_err, int tiles_x,
+                                                        int tiles_y) {
+  __shared__ uint32_t S[IO_ROWS][IO_LDS];
+  __shared__ unsigned int red[IO_ROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int G = REF ? IO_REF_GROUPS : 1;  // row groups this block walks
+  const IoTile t = io_tile(tiles_x, tiles_y, G * IO_ROWS);
+  uint8_t* S8 = reinterpret_cast<uint8_t*>(S[wave]);
+  unsigned int acc = 0;  // <= G * 4 * 3 * 255^2 per lane
+  for (int g = 0; g < G; ++g) {
+    const int y = t.y + g * IO_ROWS;
+    const int nx = y < H ? min(IO_TW, W - t.x0) : 0;  // x0 < W: the tiles cover the crop only
+    const float* in = src + t.img * ss.img + (int64_t)y * ss.row + t.x0;
+    uint8_t* row = dst + t.img * ds.img + (int64_t)y * ds.row + (int64_t)t.x0 * ds.col;
+    const uint8_t* rrow = REF ? ref + t.img * rs.img + (int64_t)y * rs.row + (int64_t)t.x0 * rs.col : nullptr;
+    int sh[3] = {0, 0, 0};
+    if (PATH == IO_HWC) sh[0] = addr_mod4(row);
+    if (PATH == IO_CHW) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sh[c] = addr_mod4(row + c * ds.ch);
+    }
+#pragma unroll
+    for (int j = 0; j < IO_TW / 64; ++j) {
+      const int px = lane + 64 * j;
+      if (px >= nx) break;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v = in[c * ss.ch + px];
+        const uint8_t u = (uint8_t)floorf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f);
+        if (PATH == IO_HWC) S8[sh[0] + 3 * px + c] = u;
+        else if (PATH == IO_CHW) S8[c * IO_SEG * 4 + sh[c] + px] = u;
+        else row[(int64_t)px * ds.col + c * ds.ch] = u;
+        if (REF) {
+          const int d = (int)u - (int)rrow[(int64_t)px * rs.col + c * rs.ch];
+          acc += (unsigned int)(d * d);
+        }
+      }
+    }
+    if (PATH != IO_GENERAL) {
+      __syncthreads();
+      if (PATH == IO_HWC && nx > 0) stage_out(row, 3 * nx, S[wave], lane);
+      if (PATH == IO_CHW && nx > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) stage_out(row + c * ds.ch, nx, S[wave] + c * IO_SEG, lane);
+      }
+      if (G > 1) __syncthreads();  // the next group's bytes go into the same LDS
+    }
+  }
+  if (REF) {
+    // a wave's sum is at most 64 * G * 4 * 3 * 255^2 < 2^30
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned long long s =
+          (unsigned long long)red[0] + (unsigned long long)red[1] + (unsigned long long)red[2] + (unsigned long long)red[3];
+      if (s) atomicAdd(sq_err + t.img, s);
+    }
+  }
+}
+
+std::atomic<int> g_path{-1};
+
+// the kernel form for a byte image with these strides; throws when a forced form does not fit
+int io_path(const int64_t* s) {
+  const bool hwc = s[2] == 3 && s[3] == 1, chw = s[2] == 1;
+  const int forced = g_path.load();
+  if (forced < 0) return hwc ? IO_HWC : chw ? IO_CHW : IO_GENERAL;
+  MLIC_CHECK(forced != IO_HWC || hwc, "image_io_path 1 (HWC) needs column stride 3 and channel stride 1");
+  MLIC_CHECK(forced != IO_CHW || chw, "image_io_path 2 (CHW) needs column stride 1");
+  return forced;
+}
+
+unsigned io_blocks(int B, int rows, int cols, int* tiles_x, int* tiles_y, int block_rows = IO_ROWS) {
+  *tiles_x = (cols + IO_TW - 1) / IO_TW;
+  *tiles_y = (rows + block_rows - 1) / block_rows;
+  const int64_t blocks = (int64_t)B * *tiles_x * *tiles_y;
+  MLIC_CHECK(blocks <= 0x7fffffffLL, "image_io: batch too large for one launch");
+  return (unsigned)blocks;
+}
+
+}  // namespace
+
+void image_io_set_path(int path) {
+  MLIC_CHECK(path >= -1 && path <= IO_CHW, "image_io_path must be -1 (by layout), 0, 1 or 2");
+  g_path = path;
+}
+
+void image_ingest_u8(const uint8_t* src, const int64_t* s, int B, int H, int W, float* dst, int Hp, int Wp,
+                     hipStream_t st) {
+  MLIC_CHECK(src != nullptr && s != nullptr && dst != nullptr, "image_ingest_u8: null argument");
+  MLIC_CHECK(B >= 1 && H >= 1 && W >= 1, "image_ingest_u8: B, H and W must be positive");
+  MLIC_CHECK(Hp >= H && Wp >= W && Hp % 64 == 0 && Wp % 64 == 0,
+             "image_ingest_u8: Hp, Wp must be multiples of 64 that cover H, W");
+  MLIC_CHECK(s[2] != 0 && s[3] != 0, "image_ingest_u8: zero column or channel stride");
+  MLIC_CHECK(reinterpret_cast<uintptr_t>(dst) % 4 == 0, "image_ingest_u8: dst must be 4-byte aligned");
+  const int path = io_path(s);
+  int tx, ty;
+  const unsigned blocks = io_blocks(B, Hp, Wp, &tx, &ty);
+  const IoStride4 ss{s[0], s[1], s[2], s[3]};
+  if (path == IO_HWC)
+    hipLaunchKernelGGL(ingest_u8_kernel<IO_HWC>, dim3(blocks), dim3(256), 0, st, src, ss, H, W, dst, Hp, Wp, tx, ty);
+  else if (path == IO_CHW)
+    hipLaunchKernelGGL(ingest_u8_kernel<IO_CHW>, dim3(blocks), dim3(256), 0, st, src, ss, H, W, dst, Hp, Wp, tx, ty);
+  else
+    hipLaunchKernelGGL(ingest_u8_kernel<IO_GENERAL>, dim3(blocks), dim3(256), 0, st, src, ss, H, W, dst, Hp, Wp, tx, ty);
+  HIP_OK(hipGetLastError());
+}
+
+template <int PATH>
+static void egress_launch(unsigned blocks, hipStream_t st, const float* src, IoStride3 ss, int H, int W, uint8_t* dst,
+                          IoStride4 ds, const uint8_t* ref, IoStride4 rs, uint64_t* sq, int tx, int ty) {
+  auto* sq64 = reinterpret_cast<unsigned long long*>(sq);
+  if (ref)
+    hipLaunchKernelGGL((egress_u8_kernel<PATH, true>), dim3(blocks), dim3(256), 0, st, src, ss, H, W, dst, ds, ref, rs,
+                       sq64, tx, ty);
+  else
+    hipLaunchKernelGGL((egress_u8_kernel<PATH, false>), dim3(blocks), dim3(256), 0, st, src, ss, H, W, dst, ds, ref, rs,
+                       sq64, tx, ty);
+}
+
+void image_egress_u8(const float* src, const int64_t* s, int B, int H, int W, uint8_t* dst, const int64_t* d,
+                     const uint8_t* ref, const int64_t* r, uint64_t* sq_err, hipStream_t st) {
+  MLIC_CHECK(src != nullptr && s != nullptr && dst != nullptr && d != nullptr, "image_egress_u8: null argument");
+  MLIC_CHECK(B >= 1 && H >= 1 && W >= 1, "image_egress_u8: B, H and W must be positive");
+  MLIC_CHECK(d[2] != 0 && d[3] != 0, "image_egress_u8: zero column or channel stride (dst)");
+  MLIC_CHECK((ref != nullptr) == (sq_err != nullptr), "image_egress_u8: ref and sq_err go together");
+  MLIC_CHECK(ref == nullptr || (r != nullptr && r[2] != 0 && r[3] != 0),
+             "image_egress_u8: ref needs strides with nonzero column and channel stride");
+  MLIC_CHECK(reinterpret_cast<uintptr_t>(src) % 4 == 0 && reinterpret_cast<uintptr_t>(sq_err) % 8 == 0,
+             "image_egress_u8: src must be 4-byte and sq_err 8-byte aligned");
+  const int path = io_path(d);
+  int tx, ty;
+  const unsigned blocks = io_blocks(B, H, W, &tx, &ty, (ref ? IO_REF_GROUPS : 1) * IO_ROWS);
+  const IoStride3 ss{s[0], s[1], s[2]};
+  const IoStride4 ds{d[0], d[1], d[2], d[3]};
+  const IoStride4 rs = ref ? IoStride4{r[0], r[1], r[2], r[3]} : IoStride4{0, 0, 0, 0};
+  if (sq_err) HIP_OK(hipMemsetAsync(sq_err, 0, sizeof(uint64_t) * (size_t)B, st));
+  if (path == IO_HWC) egress_launch<IO_HWC>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
+  else if (path == IO_CHW) egress_launch<IO_CHW>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
+  else egress_launch<IO_GENERAL>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
+  HIP_OK(hipGetLastError());
+}
+
+}  // namespace mlic

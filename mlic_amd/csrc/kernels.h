@@ -256,6 +256,20 @@ void neglog2_sum(const float* lik, int64_t n_per, int B, double* out, double* pa
 size_t ms_ssim_scratch_bytes(int B, int C, int H, int W);
 void ms_ssim_u8(const float* a, const int64_t* a_strides, const float* b, const int64_t* b_strides, int B, int C,
                 int H, int W, void* scratch, double* out, double* terms, hipStream_t st);
+// uint8 image I/O (image_io.hip).  Both check their arguments before any HIP call and throw.
+// ingest: B images of H x W x 3 bytes read through element strides {image, row, column, channel} -> dst fp32
+// [B][3][Hp][Wp] contiguous (Hp, Wp multiples of 64), v / 255 inside the image and +0 in the padding.
+void image_ingest_u8(const uint8_t* src, const int64_t* src_strides, int B, int H, int W, float* dst, int Hp, int Wp,
+                     hipStream_t st);
+// egress: the H x W crop of src fp32 (element strides {image, channel, row}, column stride 1) as
+// floor(clamp(v, 0, 1) * 255) (NaN -> 0) through dst's {image, row, column, channel} strides; with ref (its own
+// strides), sq_err[b] = the exact sum of squared uint8 differences of image b
+void image_egress_u8(const float* src, const int64_t* src_strides, int B, int H, int W, uint8_t* dst,
+                     const int64_t* dst_strides, const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err,
+                     hipStream_t st);
+// mlic_set_kernel_option("image_io_path"): -1 = by layout (default), 0 = the general-stride kernels, 1 = the
+// interleaved (HWC) form, 2 = the planar (CHW) form; a forced form the layout does not fit is an error
+void image_io_set_path(int path);
 // GaussianConditional likelihood (vbr_scale != 1: of y*sc, s*sc, m*sc) and build_indexes, element-wise
 void gauss_likelihood(const float* y, const float* s, const float* m, int64_t n, float vbr_scale, float* lik,
                       hipStream_t st);

@@ -1,0 +1,141 @@
+"""Image file -> bitstream file -> image file with the uint8 codec path (mlic_amd/codec.py).
+
+    python tools/mlic_codec.py encode IMAGE OUT.bit --model MLICPP_L --checkpoint ckpt.pth.tar
+    python tools/mlic_codec.py decode IN.bit IMAGE  --model MLICPP_L --checkpoint ckpt.pth.tar
+    ... --synthetic SEED instead of --checkpoint: the seeded synthetic weights (mlic_amd/synthetic.py)
+    ... --level N: the level of a *_VBR model (encode; a decode reads it from the file)
+
+Binary PPM (P6, maxval 255) is read and written here; any other format goes through PIL when it imports.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+# ---------------------------------------------------------------------------------------------- PPM
+def _ppm_tokens(data: bytes, count: int):
+    """The first `count` whitespace-separated header tokens ('#' comments skipped) and the offset of the byte
+    after the single whitespace that ends the last one."""
+    toks, pos, n = [], 0, len(data)
+    while len(toks) < count:
+        while pos < n and data[pos:pos + 1].isspace():
+            pos += 1
+        if pos < n and data[pos:pos + 1] == b"#":
+            while pos < n and data[pos:pos + 1] not in (b"\n", b"\r"):
+                pos += 1
+            continue
+        start = pos
+        while pos < n and not data[pos:pos + 1].isspace():
+            pos += 1
+        if start == pos:
+            raise ValueError("PPM: truncated header")
+        toks.append(data[start:pos])
+    if pos >= n or not data[pos:pos + 1].isspace():
+        raise ValueError("PPM: no whitespace after the header")
+    return toks, pos + 1
+
+
+def read_ppm(data: bytes) -> np.ndarray:
+    """Binary PPM (P6, maxval 255) bytes -> uint8 [H, W, 3]."""
+    toks, off = _ppm_tokens(data, 4)
+    if toks[0] != b"P6":
+        raise ValueError("PPM: not a binary P6 file")
+    try:
+        W, H, maxval = (int(t) for t in toks[1:])
+    except ValueError:
+        raise ValueError("PPM: header fields are not numbers") from None
+    if W < 1 or H < 1 or maxval != 255:
+        raise ValueError(f"PPM: {W} x {H}, maxval {maxval}: a non-empty 8-bit image expected")
+    if len(data) - off < H * W * 3:
+        raise ValueError("PPM: pixel data truncated")
+    return np.frombuffer(data, np.uint8, H * W * 3, off).reshape(H, W, 3).copy()
+
+
+def write_ppm(img: np.ndarray) -> bytes:
+    """uint8 [H, W, 3] -> binary PPM bytes."""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"PPM: uint8 [H, W, 3] expected, got {img.dtype} {img.shape}")
+    return b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes()
+
+
+def _is_ppm(path: str) -> bool:
+    return os.path.splitext(path)[1].lower() in (".ppm", ".pnm")
+
+
+def load_image(path: str) -> np.ndarray:
+    if _is_ppm(path):
+        with open(path, "rb") as f:
+            return read_ppm(f.read())
+    try:
+        from PIL import Image
+    except ImportError:
+        raise SystemExit(f"{path}: only binary PPM is read without PIL") from None
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+
+
+def save_image(path: str, img: np.ndarray):
+    if _is_ppm(path):
+        with open(path, "wb") as f:
+            f.write(write_ppm(img))
+        return
+    try:
+        from PIL import Image
+    except ImportError:
+        raise SystemExit(f"{path}: only binary PPM is written without PIL") from None
+    Image.fromarray(img, "RGB").save(path)
+
+
+# -------------------------------------------------------------------------------------------- model
+def load_model(args):
+    import torch
+    from mlic_amd import get_model, synthetic
+    if not torch.cuda.is_available():
+        raise SystemExit("mlic_codec needs a HIP device")
+    net = get_model(args.model)
+    if args.checkpoint:
+        sd = torch.load(args.checkpoint, map_location="cpu")
+        sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+    else:
+        sd = synthetic.synth_state_dict(args.model, args.synthetic)
+    net.load_state_dict(sd)
+    net = net.to(torch.device("cuda:0")).eval()
+    net.update()
+    return net
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("mode", choices=["encode", "decode"])
+    ap.add_argument("src")
+    ap.add_argument("dst")
+    ap.add_argument("--model", default="MLICPP_L")
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("--checkpoint")
+    g.add_argument("--synthetic", type=int, metavar="SEED")
+    ap.add_argument("--level", type=int, default=None)
+    args = ap.parse_args(argv)
+    from mlic_amd import codec
+    if args.mode == "encode":
+        img = load_image(args.src)
+        net = load_model(args)
+        data = codec.encode_images(net, img, level=args.level, layout="hwc")[0]
+        with open(args.dst, "wb") as f:
+            f.write(data)
+        print(f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {len(data)} bytes, "
+              f"{8.0 * len(data) / (img.shape[0] * img.shape[1]):.4f} bpp")
+    else:
+        with open(args.src, "rb") as f:
+            data = f.read()
+        net = load_model(args)
+        img, info = codec.decode_images(net, [data])
+        save_image(args.dst, img[0].cpu().numpy())
+        print(f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp")
+
+
+if __name__ == "__main__":
+    main()
