@@ -219,6 +219,22 @@ int mlic_image_ingest_u8(void* stream, const uint8_t* src, const int64_t* src_st
  * before any GPU call. */
 int mlic_image_egress_u8(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W, uint8_t* dst,
                          const int64_t* dst_strides, const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err);
+/* The rate loop's prefilter (utils/testing.py:363-390: crop, 3x3 depthwise conv with padding 1, pad to 64 again)
+ * in one launch, with the gather that compacts the images still over budget.  src: contiguous fp32
+ * [Bsrc][3][Hp][Wp] as mlic_image_ingest_u8 writes it; dst: contiguous fp32 [n][3][Hp][Wp]; src_index: n image
+ * indices into src on the device (each in [0, Bsrc): the kernel cannot check them; duplicates allowed), NULL =
+ * the identity.  Output image i is the filter of input image src_index[i]: inside the H x W image
+ * dst = sum_t w[t] * v[t] over the 3x3 neighbourhood with v = 0 outside the H x W image (not outside the padded
+ * buffer), +0.0 in the right / bottom padding; every element of dst is written.  fp32, taps row-major (dy = -1..1,
+ * then dx = -1..1), acc = 0; acc = acc + w[t] * v[t] with every product and sum rounded once (no FMA): what a
+ * torch CPU loop `acc = acc + w[t] * view_t` computes, bit for bit.  w9: 9 host floats, NULL = the reference's
+ * sigma 0.5 Gaussian (corner 0x1.73b62cp-7, edge 0x1.575320p-4, centre 0x1.3d1b0ep-1).
+ * Refused before any GPU call, each with its own message: n < 1; H < 1 or W < 1; Hp / Wp not multiples of 64
+ * that cover H / W; NULL src or dst; dst overlapping src (the stencil cannot run in place).  Bsrc is not known
+ * here, so the overlap test covers the n images starting at src and at dst; with src_index the caller keeps dst
+ * disjoint from every image it names.  Asynchronous on `stream`. */
+int mlic_image_blur3_pad(void* stream, const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp,
+                         const float* w9, float* dst);
 
 /* The bitstream file of one image (utils/utils.py:28-83), big-endian:
  *     H, W [, level]  |  h_z, w_z, n_strings = 2  |  y length, y bytes  |  z length, z bytes
@@ -254,6 +270,17 @@ int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, u
  * mlic_compress, mlic_container_write themselves (mlic_amd/codec.py does). */
 int mlic_encode_image_u8(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H, int W,
                          float vbr_scale, int level, uint8_t* out, size_t cap, size_t* len);
+/* mlic_encode_image_u8 under a rate budget (utils/testing.py:363-390): encode; while the whole file, header
+ * included, is above max_bpp bits per pixel of the H x W image and fewer than max_passes filter passes were
+ * made, filter the float image with mlic_image_blur3_pad (default weights) and encode again.  The float image
+ * is filtered again on the next pass, never re-quantised; it ping-pongs between the staging buffer and a second
+ * one the handle owns likewise.  *passes = filter passes made (0: the first file fit); the file may still be
+ * above the budget when *passes == max_passes.  max_bpp must be positive and finite, max_passes >= 0.  The
+ * out == NULL / rgb_dev == NULL protocol is that of mlic_encode_image_u8 (*passes is reported on both calls).
+ * The level of a *_VBR model is the caller's choice (mlic_amd/codec.py picks it from the budget). */
+int mlic_encode_image_u8_budget(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H,
+                                int W, float vbr_scale, int level, double max_bpp, int max_passes, uint8_t* out,
+                                size_t cap, size_t* len, int* passes);
 /* File bytes to pixels: mlic_container_parse (n_levels > 0 says the file has a level word; max_pixels bounds
  * the padded size before anything is allocated), mlic_decompress into the staging buffer, egress of the crop to
  * rgb_dev through strides {row, column, channel} (non-negative).  cap_bytes = bytes addressable from rgb_dev:

@@ -77,10 +77,12 @@ def _sig(lib):
         "mlic_image_ms_ssim_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, sz, p, p],
         "mlic_image_ingest_u8": [p, p, P(i64), i, i, i, p, i, i],
         "mlic_image_egress_u8": [p, p, P(i64), i, i, i, p, P(i64), p, P(i64), p],
+        "mlic_image_blur3_pad": [p, p, p, i, i, i, i, i, p, p],
         "mlic_container_bytes": [sz, sz, i, P(sz)],
         "mlic_container_write": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, p, sz, p, sz, P(sz)],
         "mlic_container_parse": [p, sz, i, i, C.c_uint64, P(ContainerInfo)],
         "mlic_encode_image_u8": [p, p, p, P(i64), i, i, f, i, p, sz, P(sz)],
+        "mlic_encode_image_u8_budget": [p, p, p, P(i64), i, i, f, i, C.c_double, i, p, sz, P(sz), P(i)],
         "mlic_decode_image_u8": [p, p, p, sz, i, C.c_uint64, p, p, P(i64), sz, P(i), P(i), P(i)],
         "mlic_neglog2_sum": [p, p, i, i64, p],
         "mlic_gaussian_likelihood": [p, p, p, p, i64, f, p],

@@ -4,7 +4,8 @@ File layout (utils/utils.py:28-83, utils/testing.py:203-262):
     >II   H, W of the unpadded image            (VBR: >III H, W, level)
     >III  h_z, w_z, n_strings (= 2)
     n_strings x ( >I length, bytes )            y stream, then z stream (image 0 only: B = 1)
-Harness semantics (utils/testing.py:338-424) minus the NAIC "bpp > 0.1 => blur and retry" loop:
+Harness semantics (utils/testing.py:338-424; the NAIC "bpp > 0.1 => blur and retry" loop is code_image's
+max_bpp=, off by default):
 pad right/bottom with zeros to a multiple of 64, compress, write, read, decompress, crop;
 bpp = 8 * filesize / (H * W) of the unpadded image; PSNR on uint8 images made by clamp(0,1)*255 and
 truncation (torchvision ToPILImage), max 255 (utils/metrics.py:32-33).
@@ -95,19 +96,33 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 
 @torch.no_grad()
-def code_image(net, img: torch.Tensor, ms_ssim: bool = False, **kw) -> Dict:
+def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
-    None when the image is too small for the five levels)."""
+    None when the image is too small for the five levels).
+    max_bpp: the reference's rate constraint (utils/testing.py:363-390) through codec.rate_loop on the float
+    image: while the file is above max_bpp and fewer than max_passes filter passes were made, filter and code
+    again.  The record then also holds "passes" and "met" (bpp <= max_bpp); psnr stays against the unfiltered
+    img, and enc_s covers the whole loop."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
     x = pad64(img)
-    t0 = time.time()
-    out = net.compress(x, **kw)
-    enc = time.time() - t0
-    buf = io.BytesIO()
     level = kw.get("s") if kw else None
-    nbytes = write_stream(buf, H, W, out["shape"], out["strings"], level)
+    buf = io.BytesIO()
+    passes = None
+    if max_bpp is None:
+        t0 = time.time()
+        out = net.compress(x, **kw)
+        enc = time.time() - t0
+        nbytes = write_stream(buf, H, W, out["shape"], out["strings"], level)
+    else:
+        from . import codec
+        if set(kw) - {"s"}:
+            raise ValueError(f"code_image: max_bpp goes with the level s= only, got {sorted(kw)}")
+        t0 = time.time()
+        files, ps, _ = codec.rate_loop(net, x.contiguous().float(), H, W, level, max_bpp, max_passes)
+        enc = time.time() - t0
+        nbytes, passes = buf.write(files[0]), ps[0]
     buf.seek(0)
     hdr, strings, shape = read_stream(buf, vbr=level is not None)
     t0 = time.time()
@@ -116,6 +131,8 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, **kw) -> Dict:
     x_hat = dec["x_hat"][:, :, :H, :W]
     r = {"H": H, "W": W, "bytes": nbytes, "bpp": 8.0 * nbytes / (H * W), "psnr": psnr_u8(img, x_hat),
          "enc_s": enc, "dec_s": dect, "x_hat": x_hat}
+    if passes is not None:
+        r["passes"], r["met"] = passes, r["bpp"] <= max_bpp
     if ms_ssim:
         from . import metrics
         r["ms_ssim"] = metrics.ms_ssim_u8(img, x_hat).item() if min(H, W) > metrics.MIN_SIDE else None

@@ -8,6 +8,11 @@ one launch (optionally with the exact per-image sum of squared uint8 differences
 comes with the decode).  The file is the layout documented in bitstream.py, written and parsed by the library
 (csrc/container.cpp); the parser validates every field before anything is sized from it.
 
+`encode_images(max_bpp=...)` adds the reference's rate constraint (utils/testing.py:363-390): while a file is
+above the budget, the float image goes through the 3x3 Gaussian prefilter `blur3_pad` (one launch that also
+compacts the images of a batch still over budget) and is coded again; `level="auto"` picks a *_VBR model's level
+from the budget.  Off by default.
+
 CUDA tensors run the HIP kernels (csrc/image_io.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
 """
@@ -151,6 +156,70 @@ def egress_u8(x_hat: torch.Tensor, H: int, W: int, layout: str = "hwc", ref=None
     return out if ref is None else (out, sq)
 
 
+def _f32(hexfloat: str) -> float:
+    v = float.fromhex(hexfloat)
+    assert float(np.float32(v)) == v
+    return v
+
+
+# The rate loop's 3x3 Gaussian, sigma = 0.5 (utils/testing.py:264-284): exp(-d2 / (2 sigma^2)) over the grid's
+# squared distances from the centre, scaled by 1 / (2 pi sigma^2) and divided by its sum, as torch evaluates it
+# in fp32.  Row-major, dy = -1..1 then dx = -1..1; the same constants are the kernel's default.
+_CORNER, _EDGE, _CENTRE = _f32("0x1.73b62cp-7"), _f32("0x1.575320p-4"), _f32("0x1.3d1b0ep-1")
+BLUR3_WEIGHTS = (_CORNER, _EDGE, _CORNER, _EDGE, _CENTRE, _EDGE, _CORNER, _EDGE, _CORNER)
+
+
+def blur3_pad(x: torch.Tensor, H: int, W: int, index=None, weights=None) -> torch.Tensor:
+    """The rate loop's prefilter on the model's padded input (utils/testing.py:363-390: crop to H x W, 3x3
+    depthwise conv with padding 1, pad to 64 again) in one launch.  x: contiguous fp32 [B,3,Hp,Wp] (Hp, Wp
+    multiples of 64, as ingest_u8 returns it).  index: n image indices into x (a sequence or an integer tensor;
+    duplicates allowed; None = every image in order): output image i is the filter of x[index[i]], so the images
+    still over a budget are filtered and compacted together.  Returns a new fp32 [n,3,Hp,Wp]: inside the image
+    acc = 0; acc = acc + w[t] * v[t] over the 3x3 taps in row-major order, v = 0 outside the H x W image, each
+    product and sum rounded once; +0 in the padding.  weights: nine floats, row-major (None = BLUR3_WEIGHTS).
+    CUDA tensors run the kernel on the current stream, CPU tensors the torch loop with the same arithmetic."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.size(1) != 3 or x.dtype != torch.float32 or x.size(0) < 1:
+        raise ValueError("blur3_pad: fp32 [B,3,Hp,Wp] expected")
+    B, _, Hp, Wp = x.shape
+    H, W = int(H), int(W)
+    if Hp % 64 or Wp % 64 or not (1 <= H <= Hp and 1 <= W <= Wp):
+        raise ValueError(f"blur3_pad: {H} x {W} image in a {Hp} x {Wp} buffer: multiples of 64 that cover it expected")
+    w = [float(v) for v in (BLUR3_WEIGHTS if weights is None else
+                            weights.reshape(-1).tolist() if torch.is_tensor(weights) else
+                            np.asarray(weights, dtype=np.float64).reshape(-1).tolist())]
+    if len(w) != 9:
+        raise ValueError("blur3_pad: nine weights expected")
+    idx = None
+    if index is not None:
+        idx = [int(v) for v in (index.reshape(-1).tolist() if torch.is_tensor(index) else list(index))]
+        if not idx or any(not 0 <= v < B for v in idx):
+            raise ValueError(f"blur3_pad: index must name at least one image, each in [0, {B})")
+    n = B if idx is None else len(idx)
+    x = x.contiguous()
+    if not x.is_cuda:
+        w32 = torch.tensor(w, dtype=torch.float32)
+        src = x if idx is None else x.index_select(0, torch.tensor(idx, dtype=torch.int64))
+        xp = torch.nn.functional.pad(src[:, :, :H, :W], (1, 1, 1, 1))
+        acc = torch.zeros(n, 3, H, W, dtype=torch.float32)
+        for t in range(9):
+            dy, dx = divmod(t, 3)
+            acc = acc + w32[t] * xp[:, :, dy:dy + H, dx:dx + W]
+        out = torch.zeros(n, 3, Hp, Wp, dtype=torch.float32)
+        out[:, :, :H, :W] = acc
+        return out
+    with torch.cuda.device(x.device):
+        out = torch.empty(n, 3, Hp, Wp, dtype=torch.float32, device=x.device)
+        if _lib.poison():
+            out.fill_(float("nan"))
+        ix = None if idx is None else torch.tensor(idx, dtype=torch.int32).to(x.device)
+        _lib.call("mlic_image_blur3_pad", _stream(), C.c_void_p(x.data_ptr()),
+                  None if ix is None else C.c_void_p(ix.data_ptr()), n, H, W, Hp, Wp,
+                  None if weights is None else (C.c_float * 9)(*w), C.c_void_p(out.data_ptr()))
+        if ix is not None:
+            ix.record_stream(torch.cuda.current_stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------- container
 def container_bytes(y_len: int, z_len: int, vbr: bool = False) -> int:
     n = C.c_size_t()
@@ -212,20 +281,117 @@ def _levels(net, level, B: int):
     return lv, {"s": lv}
 
 
+def _check_budget(max_bpp, max_passes):
+    if max_bpp is not None:
+        if isinstance(max_bpp, bool) or not isinstance(max_bpp, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(max_bpp) or not max_bpp > 0:
+            raise ValueError(f"max_bpp must be a positive finite number, got {max_bpp!r}")
+    if isinstance(max_passes, bool) or not isinstance(max_passes, (int, np.integer)) or max_passes < 0:
+        raise ValueError(f"max_passes must be a non-negative integer, got {max_passes!r}")
+
+
 @torch.no_grad()
-def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None) -> List[bytes]:
+def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_passes: int = 8):
+    """The reference's rate constraint (utils/testing.py:363-390, VBR :467-527) on the padded float images x
+    [B,3,Hp,Wp] of H x W images: code the batch; the images whose whole file is above max_bpp bits per pixel
+    (8 * len(file) / (H * W), header included) and that had fewer than max_passes filter passes are filtered and
+    compacted by one blur3_pad launch and coded again as a smaller batch, until none is left.  The float image is
+    what is filtered again; it is never re-quantised.  Per image the result is the file of the first pass count
+    k <= max_passes that fits, else the file after max_passes passes (the reference loops forever there).
+    level: None (fixed rate), one level or one per image, or "auto" (VBR): per image the highest level whose
+    unfiltered file fits, found by scanning down from net.levels - 1 with the images that fit leaving the batch
+    (no monotonicity assumed: the first fit from the top is the definition); an image over the budget at level
+    0 goes on into the filter loop at level 0.  -> (files, passes, levels) in input order; levels is None for
+    a fixed-rate model."""
+    _check_budget(max_bpp, max_passes)
+    if max_bpp is None:
+        raise ValueError("rate_loop: max_bpp expected")
+    B = x.size(0)
+    auto = isinstance(level, str)
+    if auto:
+        if level != "auto":
+            raise ValueError(f"level: an integer, one per image or 'auto' expected, got {level!r}")
+        if not hasattr(net, "levels"):
+            raise ValueError("level='auto' given for a fixed-rate model")
+        lv = [net.levels - 1] * B
+    else:
+        lv, _ = _levels(net, level, B)
+    files: List[Optional[bytes]] = [None] * B
+    passes = [0] * B
+
+    def code(cur, ids):
+        kw = {} if lv is None else {"s": [lv[b] for b in ids]}
+        out = net.compress(cur, **kw)
+        ys, zs = out["strings"]
+        for j, b in enumerate(ids):
+            files[b] = write_container(H, W, out["shape"], ys[j], zs[j], None if lv is None else lv[b])
+
+    def over(b):
+        return 8.0 * len(files[b]) / (H * W) > max_bpp
+
+    def keep(cur, ids, sub):
+        """The images `sub` of the batch `cur` (which holds `ids`), compacted."""
+        if len(sub) == len(ids):
+            return cur
+        return cur.index_select(0, torch.tensor([ids.index(b) for b in sub], dtype=torch.int64, device=cur.device))
+
+    cur, ids = x, list(range(B))
+    code(cur, ids)
+    if auto:
+        for l in range(net.levels - 2, -1, -1):
+            sub = [b for b in ids if over(b)]
+            if not sub:
+                break
+            cur, ids = keep(cur, ids, sub), sub
+            for b in ids:
+                lv[b] = l
+            code(cur, ids)
+    while True:
+        sub = [b for b in ids if over(b) and passes[b] < max_passes]
+        if not sub:
+            break
+        cur, ids = blur3_pad(cur, H, W, index=None if len(sub) == len(ids) else [ids.index(b) for b in sub]), sub
+        for b in ids:
+            passes[b] += 1
+        code(cur, ids)
+    return files, passes, lv
+
+
+@torch.no_grad()
+def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
+                  max_passes: int = 8, return_info: bool = False):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
-    one per image), required for *_VBR models."""
+    one per image), required for *_VBR models.
+    max_bpp: a budget in bits per pixel of the whole file; the images above it go through rate_loop (filter and
+    code again, at most max_passes times each), and level="auto" (VBR, needs max_bpp) picks per image the highest
+    level whose unfiltered file fits.  An image gets the file it gets when coded alone; files come back in input
+    order.  return_info=True: (files, info) with info[b] = {"bytes", "bpp", "passes", "level", "met"}; met says
+    whether the file is within the budget (True without one)."""
     img, layout = _u8_batch(imgs_u8, layout, "encode_images")
+    _check_budget(max_bpp, max_passes)
+    if isinstance(level, str) and max_bpp is None:
+        raise ValueError("level='auto' needs max_bpp (the level is chosen from the budget)")
     img = img.to(net.device)
     B = img.size(0)
     H, W = _hw(img, layout)
-    lv, kw = _levels(net, level, B)
-    out = net.compress(ingest_u8(img, layout), **kw)
-    ys, zs = out["strings"]
-    return [write_container(H, W, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
+    if max_bpp is None:
+        lv, kw = _levels(net, level, B)
+        out = net.compress(ingest_u8(img, layout), **kw)
+        ys, zs = out["strings"]
+        files = [write_container(H, W, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
+        passes = [0] * B
+    else:
+        files, passes, lv = rate_loop(net, ingest_u8(img, layout), H, W, level, max_bpp, max_passes)
+    if not return_info:
+        return files
+    info = []
+    for b, f in enumerate(files):
+        bpp = 8.0 * len(f) / (H * W)
+        info.append({"bytes": len(f), "bpp": bpp, "passes": passes[b], "level": None if lv is None else lv[b],
+                     "met": max_bpp is None or bpp <= max_bpp})
+    return files, info
 
 
 @torch.no_grad()

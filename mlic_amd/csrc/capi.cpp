@@ -3,6 +3,7 @@
 
 #include <cstdlib>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -18,7 +19,11 @@ struct mlic_model {
   // the model (grows on demand), and the header fields of the last encode
   float* stage = nullptr;
   size_t stage_bytes = 0;
+  // mlic_encode_image_u8_budget: the other half of the filter's ping-pong (grows likewise)
+  float* stage2 = nullptr;
+  size_t stage2_bytes = 0;
   int enc_H = 0, enc_W = 0, enc_level = -1;  // enc_H == 0: nothing encoded yet
+  int enc_passes = 0;                        // filter passes of the last encode
 };
 
 static thread_local std::string g_err;
@@ -85,6 +90,7 @@ int mlic_destroy(mlic_model* m) {
     if (!m) return;
     delete m->impl;
     if (m->stage) (void)hipFree(m->stage);
+    if (m->stage2) (void)hipFree(m->stage2);
     delete m;
   });
 }
@@ -634,6 +640,11 @@ int mlic_image_ingest_u8(void* stream, const uint8_t* src, const int64_t* src_st
   return guard([&] { image_ingest_u8(src, src_strides, B, H, W, dst, Hp, Wp, (hipStream_t)stream); });
 }
 
+int mlic_image_blur3_pad(void* stream, const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp,
+                         const float* w9, float* dst) {
+  return guard([&] { image_blur3_pad(src, src_index, n, H, W, Hp, Wp, w9, dst, (hipStream_t)stream); });
+}
+
 int mlic_image_egress_u8(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W, uint8_t* dst,
                          const int64_t* dst_strides, const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err) {
   return guard([&] {
@@ -682,15 +693,25 @@ int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, u
 }
 
 // the handle's staging image: at least `bytes`, grown by reallocation (hipFree waits for the device)
-static float* stage(mlic_model* m, size_t bytes) {
-  if (m->stage_bytes < bytes) {
-    if (m->stage) HIP_OK(hipFree(m->stage));
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    HIP_OK(hipMalloc((void**)&m->stage, bytes));
-    m->stage_bytes = bytes;
+static float* grow(float*& buf, size_t& have, size_t bytes) {
+  if (have < bytes) {
+    if (buf) HIP_OK(hipFree(buf));
+    buf = nullptr;
+    have = 0;
+    HIP_OK(hipMalloc((void**)&buf, bytes));
+    have = bytes;
   }
-  return m->stage;
+  return buf;
+}
+static float* stage(mlic_model* m, size_t bytes) { return grow(m->stage, m->stage_bytes, bytes); }
+static float* stage2(mlic_model* m, size_t bytes) { return grow(m->stage2, m->stage2_bytes, bytes); }
+
+// the file of the handle's last one-image encode
+static void write_encoded(mlic_model* m, Model& mod, uint8_t* out, size_t cap, size_t* len) {
+  const EncodedImage& e = mod.encoded(0);
+  container_ok(container_write((uint32_t)m->enc_H, (uint32_t)m->enc_W, m->enc_level, (uint32_t)((m->enc_H + 63) / 64),
+                               (uint32_t)((m->enc_W + 63) / 64), reinterpret_cast<const uint8_t*>(e.y.data()),
+                               e.y.size(), reinterpret_cast<const uint8_t*>(e.z.data()), e.z.size(), out, cap, len));
 }
 
 int mlic_encode_image_u8(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H, int W,
@@ -711,12 +732,50 @@ int mlic_encode_image_u8(mlic_model* m, void* stream, const uint8_t* rgb_dev, co
       m->enc_H = H;
       m->enc_W = W;
       m->enc_level = level < 0 ? -1 : level;
+      m->enc_passes = 0;
     }
     MLIC_CHECK(m->enc_H > 0, "encode_image_u8: rgb_dev is NULL and the handle has no encoded image");
-    const EncodedImage& e = mod.encoded(0);
-    container_ok(container_write((uint32_t)m->enc_H, (uint32_t)m->enc_W, m->enc_level, (uint32_t)((m->enc_H + 63) / 64),
-                                 (uint32_t)((m->enc_W + 63) / 64), reinterpret_cast<const uint8_t*>(e.y.data()),
-                                 e.y.size(), reinterpret_cast<const uint8_t*>(e.z.data()), e.z.size(), out, cap, len));
+    write_encoded(m, mod, out, cap, len);
+  });
+}
+
+int mlic_encode_image_u8_budget(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H,
+                                int W, float vbr_scale, int level, double max_bpp, int max_passes, uint8_t* out,
+                                size_t cap, size_t* len, int* passes) {
+  return guard([&] {
+    Model& mod = impl(m);
+    MLIC_CHECK(len != nullptr, "encode_image_u8_budget: null len");
+    if (rgb_dev != nullptr) {
+      MLIC_CHECK(strides != nullptr && H >= 1 && W >= 1, "encode_image_u8_budget: strides, H >= 1 and W >= 1 expected");
+      MLIC_CHECK(H <= (1 << 24) && W <= (1 << 24), "encode_image_u8_budget: image side above 2^24");
+      MLIC_CHECK(max_bpp > 0 && std::isfinite(max_bpp), "encode_image_u8_budget: max_bpp must be positive and finite");
+      MLIC_CHECK(max_passes >= 0, "encode_image_u8_budget: max_passes must not be negative");
+      const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64;
+      const size_t bytes = sizeof(float) * 3 * (size_t)Hp * (size_t)Wp;
+      const int64_t s4[4] = {0, strides[0], strides[1], strides[2]};
+      const float sc[1] = {vbr_scale};
+      m->enc_H = 0;
+      float* x = stage(m, bytes);
+      image_ingest_u8(rgb_dev, s4, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
+      int k = 0;
+      for (;;) {
+        mod.compress(x, 1, Hp, Wp, sc, (hipStream_t)stream);  // returns with the strings complete
+        const EncodedImage& e = mod.encoded(0);
+        const double bpp = 8.0 * (double)container_bytes(e.y.size(), e.z.size(), level >= 0) / ((double)H * (double)W);
+        if (!(bpp > max_bpp) || k >= max_passes) break;
+        float* y = x == m->stage ? stage2(m, bytes) : m->stage;
+        image_blur3_pad(x, nullptr, 1, H, W, Hp, Wp, nullptr, y, (hipStream_t)stream);
+        x = y;
+        ++k;
+      }
+      m->enc_H = H;
+      m->enc_W = W;
+      m->enc_level = level < 0 ? -1 : level;
+      m->enc_passes = k;
+    }
+    MLIC_CHECK(m->enc_H > 0, "encode_image_u8_budget: rgb_dev is NULL and the handle has no encoded image");
+    if (passes) *passes = m->enc_passes;
+    write_encoded(m, mod, out, cap, len);
   });
 }
 

@@ -9,6 +9,8 @@
 // through {image, row, column, channel} strides; nothing outside the crop's bytes is written.  With a
 // reference image the per-image sum of squared uint8 differences is accumulated in integers (exact,
 // order-independent: one 64-bit integer atomic per block).
+// blur3_pad: the rate loop's 3x3 prefilter on the padded fp32 planes, with the gather that compacts the images
+// still over budget (its own comment below).
 //
 // A block is four waves; a wave owns one image row of the tile and 256 pixels of it.  Byte rows start at
 // any address (W * 3 is odd for odd W), so the two canonical layouts go through LDS: the row segment sits
@@ -198,6 +200,97 @@ __global__ __launch_bounds__(256) void egress_u8_kernel(const float* __restrict_
   }
 }
 
+// The rate loop's prefilter (utils/testing.py:363-390: crop, 3x3 depthwise conv with padding 1, pad to 64
+// again) on the padded fp32 planes, one read and one write of the plane.  A thread owns BL_RUN consecutive
+// columns of BL_ROWS consecutive rows: 256 threads are whole row groups (Wp / BL_RUN is a multiple of 16), a
+// block never leaves its plane (Hp * Wp / (BL_RUN * BL_ROWS) is a multiple of 256) and a wave's loads and
+// stores are contiguous 16-byte pieces (one float4 per lane when both buffers are 16-byte aligned).  The
+// BL_ROWS + 2 input rows are read once each and feed up to three output rows from registers; the columns left
+// and right of a run come from the neighbouring lanes (a wave shuffle), and from memory only at the two ends of
+// a wave.  A tap outside the H x W image is 0 whatever the padded buffer holds there, and every element is
+// written (0 from column W / row H).  Per element: acc = 0; acc = acc + w[t] * v[t], t row-major (dy, then
+// dx), each product and each sum rounded once.
+constexpr int BL_RUN = 4, BL_ROWS = 4;
+
+struct Blur9 {
+  float w[9];
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void blur3_pad_kernel(const float* __restrict__ src,
+                                                        const int32_t* __restrict__ src_index, int H, int W, int Hp,
+                                                        int Wp, Blur9 k, float* __restrict__ dst,
+                                                        unsigned plane_blocks) {
+  const unsigned pc = blockIdx.x / plane_blocks;  // output plane: image * 3 + channel
+  const int q = (int)(blockIdx.x - pc * plane_blocks) * 256 + (int)threadIdx.x;  // run group within the plane
+  const int rw = Wp / BL_RUN;
+  const int yb = q / rw, x0 = (q - yb * rw) * BL_RUN, y0 = yb * BL_ROWS;
+  const int lane = threadIdx.x & 63;
+  const unsigned img = pc / 3, c = pc - 3 * img;
+  const int64_t from = src_index ? (int64_t)src_index[img] : (int64_t)img;
+  const int64_t plane = (int64_t)Hp * Wp;
+  const float* sp = src + (from * 3 + c) * plane + x0;
+  // rows start at multiples of 16 lanes, so lane - 1 (lane + 1) holds the run to the left (right) in the same
+  // rows unless this run is the first (last) of its row or this lane the first (last) of its wave
+  const bool left_lane = lane > 0 && x0 > 0, right_lane = lane < 63 && x0 + BL_RUN < Wp;
+  float acc[BL_ROWS][BL_RUN];
+#pragma unroll
+  for (int r = 0; r < BL_ROWS; ++r)
+#pragma unroll
+    for (int e = 0; e < BL_RUN; ++e) acc[r][e] = 0.0f;
+  // every lane takes every step (the shuffles need the whole wave); a lane outside the image holds zeros
+#pragma unroll
+  for (int j = 0; j < BL_ROWS + 2; ++j) {
+    const int yy = y0 - 1 + j;
+    const bool row = yy >= 0 && yy < H;
+    const float* rp = sp + (int64_t)yy * Wp;  // dereferenced only inside the image
+    float v[BL_RUN + 2];                      // columns x0 - 1 .. x0 + BL_RUN, 0 outside the image
+#pragma unroll
+    for (int e = 0; e < BL_RUN + 2; ++e) v[e] = 0.0f;
+    if (row && x0 < W) {
+      float m[BL_RUN];
+      if (VEC) {
+        const float4 f = *reinterpret_cast<const float4*>(rp);  // x0 + BL_RUN <= Wp: inside the row
+        m[0] = f.x, m[1] = f.y, m[2] = f.z, m[3] = f.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < BL_RUN; ++e) m[e] = rp[e];
+      }
+#pragma unroll
+      for (int e = 0; e < BL_RUN; ++e) v[e + 1] = x0 + e < W ? m[e] : 0.0f;
+    }
+    const float lf = __shfl_up(v[BL_RUN], 1, 64), rt = __shfl_down(v[1], 1, 64);
+    if (left_lane) v[0] = lf;
+    else if (row && x0 > 0 && x0 < W) v[0] = rp[-1];
+    if (right_lane) v[BL_RUN + 1] = rt;
+    else if (row && x0 + BL_RUN < W) v[BL_RUN + 1] = rp[BL_RUN];
+#pragma unroll
+    for (int r = 0; r < BL_ROWS; ++r) {
+      const int dy = j - r - 1;  // input row j is tap row dy of output row r
+      if (dy < -1 || dy > 1) continue;
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const float w = k.w[(dy + 1) * 3 + dx];
+#pragma unroll
+        for (int e = 0; e < BL_RUN; ++e) acc[r][e] = __fadd_rn(acc[r][e], __fmul_rn(w, v[e + dx]));
+      }
+    }
+  }
+  float* dp = dst + (int64_t)pc * plane + (int64_t)y0 * Wp + x0;
+#pragma unroll
+  for (int r = 0; r < BL_ROWS; ++r) {
+    float o[BL_RUN];
+#pragma unroll
+    for (int e = 0; e < BL_RUN; ++e) o[e] = y0 + r < H && x0 + e < W ? acc[r][e] : 0.0f;
+    if (VEC) {
+      *reinterpret_cast<float4*>(dp + (int64_t)r * Wp) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < BL_RUN; ++e) dp[(int64_t)r * Wp + e] = o[e];
+    }
+  }
+}
+
 std::atomic<int> g_path{-1};
 
 // the kernel form for a byte image with these strides; throws when a forced form does not fit
@@ -278,6 +371,39 @@ void image_egress_u8(const float* src, const int64_t* s, int B, int H, int W, ui
   if (path == IO_HWC) egress_launch<IO_HWC>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
   else if (path == IO_CHW) egress_launch<IO_CHW>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
   else egress_launch<IO_GENERAL>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
+  HIP_OK(hipGetLastError());
+}
+
+void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp, const float* w9,
+                     float* dst, hipStream_t st) {
+  MLIC_CHECK(n >= 1, "image_blur3_pad: n must be positive");
+  MLIC_CHECK(H >= 1 && W >= 1, "image_blur3_pad: H and W must be positive");
+  MLIC_CHECK(Hp >= H && Wp >= W && Hp % 64 == 0 && Wp % 64 == 0,
+             "image_blur3_pad: Hp, Wp must be multiples of 64 that cover H, W");
+  MLIC_CHECK(src != nullptr && dst != nullptr, "image_blur3_pad: null src or dst");
+  MLIC_CHECK(reinterpret_cast<uintptr_t>(src) % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 4 == 0,
+             "image_blur3_pad: src and dst must be 4-byte aligned");
+  const uint64_t plane = (uint64_t)Hp * (uint64_t)Wp;
+  MLIC_CHECK(plane <= (1ull << 31), "image_blur3_pad: padded plane above 2^31 elements");
+  const uint64_t plane_blocks = plane / (BL_RUN * BL_ROWS * 256);  // exact: 64 * 64 divides the plane
+  const uint64_t blocks = (uint64_t)n * 3 * plane_blocks;
+  MLIC_CHECK(blocks <= 0x7fffffffull, "image_blur3_pad: batch too large for one launch");
+  // the n images on either side, with the source batch's size unknown: the stencil cannot run in place
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+  const uint64_t bytes = (uint64_t)n * 3 * plane * sizeof(float);
+  MLIC_CHECK(!(d0 >= s0 && d0 - s0 < bytes) && !(s0 >= d0 && s0 - d0 < bytes),
+             "image_blur3_pad: dst overlaps src (the filter cannot run in place)");
+  Blur9 k = {{0x1.73b62cp-7f, 0x1.575320p-4f, 0x1.73b62cp-7f, 0x1.575320p-4f, 0x1.3d1b0ep-1f, 0x1.575320p-4f,
+              0x1.73b62cp-7f, 0x1.575320p-4f, 0x1.73b62cp-7f}};  // sigma 0.5, normalised (utils/testing.py:264-284)
+  if (w9)
+    for (int t = 0; t < 9; ++t) k.w[t] = w9[t];
+  const bool vec = s0 % 16 == 0 && d0 % 16 == 0;  // planes and rows are multiples of 16 bytes
+  if (vec)
+    hipLaunchKernelGGL(blur3_pad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, src, src_index, H, W, Hp, Wp, k,
+                       dst, (unsigned)plane_blocks);
+  else
+    hipLaunchKernelGGL(blur3_pad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, src, src_index, H, W, Hp, Wp,
+                       k, dst, (unsigned)plane_blocks);
   HIP_OK(hipGetLastError());
 }
 

@@ -267,6 +267,12 @@ void image_ingest_u8(const uint8_t* src, const int64_t* src_strides, int B, int 
 void image_egress_u8(const float* src, const int64_t* src_strides, int B, int H, int W, uint8_t* dst,
                      const int64_t* dst_strides, const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err,
                      hipStream_t st);
+// the rate loop's prefilter: dst image i [3][Hp][Wp] = the 3x3 filter (w9: 9 host floats, row-major; null = the
+// reference's sigma 0.5 Gaussian) of src image src_index[i] (device indices; null = i), taps outside the H x W
+// image 0, +0 in the padding, every element written; acc = acc + w[t] * v[t] in tap order, no FMA.  dst must not
+// overlap the n images at src, nor any image src_index names.  Checks its arguments before any HIP call.
+void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp, const float* w9,
+                     float* dst, hipStream_t st);
 // mlic_set_kernel_option("image_io_path"): -1 = by layout (default), 0 = the general-stride kernels, 1 = the
 // interleaved (HWC) form, 2 = the planar (CHW) form; a forced form the layout does not fit is an error
 void image_io_set_path(int path);

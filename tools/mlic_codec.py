@@ -4,6 +4,9 @@
     python tools/mlic_codec.py decode IN.bit IMAGE  --model MLICPP_L --checkpoint ckpt.pth.tar
     ... --synthetic SEED instead of --checkpoint: the seeded synthetic weights (mlic_amd/synthetic.py)
     ... --level N: the level of a *_VBR model (encode; a decode reads it from the file)
+    ... --max-bpp X [--max-passes N]: encode under a budget of X bits per pixel (the whole file): while the file
+        is above it, the 3x3 Gaussian prefilter and another encode, at most N times (default 8)
+    ... --level auto (with --max-bpp): the highest level of a *_VBR model whose unfiltered file fits
 
 Binary PPM (P6, maxval 255) is read and written here; any other format goes through PIL when it imports.
 """
@@ -108,7 +111,29 @@ def load_model(args):
     return net
 
 
-def main(argv=None):
+def _level(v: str):
+    if v == "auto":
+        return v
+    try:
+        n = int(v)
+    except ValueError:
+        n = -1
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"a level number or 'auto' expected, got {v!r}")
+    return n
+
+
+def _budget(v: str) -> float:
+    try:
+        x = float(v)
+    except ValueError:
+        x = 0.0
+    if not (x > 0 and x != float("inf")):
+        raise argparse.ArgumentTypeError(f"a positive finite number of bits per pixel expected, got {v!r}")
+    return x
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("mode", choices=["encode", "decode"])
     ap.add_argument("src")
@@ -117,17 +142,36 @@ def main(argv=None):
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("--checkpoint")
     g.add_argument("--synthetic", type=int, metavar="SEED")
-    ap.add_argument("--level", type=int, default=None)
+    ap.add_argument("--level", type=_level, default=None, metavar="N|auto")
+    ap.add_argument("--max-bpp", type=_budget, default=None, metavar="X")
+    ap.add_argument("--max-passes", type=int, default=8, metavar="N")
     args = ap.parse_args(argv)
+    if args.level == "auto" and args.max_bpp is None:
+        ap.error("--level auto needs --max-bpp")
+    if args.max_passes < 0:
+        ap.error("--max-passes must not be negative")
+    if args.mode == "decode" and args.max_bpp is not None:
+        ap.error("--max-bpp goes with encode")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     from mlic_amd import codec
     if args.mode == "encode":
         img = load_image(args.src)
         net = load_model(args)
-        data = codec.encode_images(net, img, level=args.level, layout="hwc")[0]
+        files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
+                                          max_passes=args.max_passes, return_info=True)
+        data = files[0]
         with open(args.dst, "wb") as f:
             f.write(data)
-        print(f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {len(data)} bytes, "
-              f"{8.0 * len(data) / (img.shape[0] * img.shape[1]):.4f} bpp")
+        line = (f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {len(data)} bytes, "
+                f"{8.0 * len(data) / (img.shape[0] * img.shape[1]):.4f} bpp")
+        if args.max_bpp is not None:
+            line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
+                     f"{'met' if info[0]['met'] else 'not met'}")
+        print(line)
     else:
         with open(args.src, "rb") as f:
             data = f.read()
