@@ -102,13 +102,19 @@ int mlic_set_synthesis_precision(mlic_model* m, int mode);
 /* test switch: fill every workspace block with NaN (0xFF bytes) when it is handed out, so a kernel
  * reading memory its producer never wrote fails visibly (also $MLIC_POISON=1).  Off by default. */
 int mlic_set_poison(mlic_model* m, int on);
-/* process-wide kernel A/B switches (tests, micro-benchmarks): "x4_halo" = the conv_x4 kernel's
+/* process-wide kernel A/B switches (tests, micro-benchmarks).  One table holds every switch, its
+ * environment fallback and its rule (csrc/options.cpp).  Every entry point of this ABI takes one
+ * snapshot of all of them when it is entered and reads nothing else until it returns -- its sizing pass
+ * and its real pass, every lane thread it starts and every model pass of a budget encode see the same
+ * values -- so a set from any thread is safe at any time and takes effect at the next call, never inside
+ * one.  The environment is read once per process, at the library's first use.  A value of -1 (and for
+ * "chain_nj" 0 too) returns an option to its environment variable or default; an unknown name, or an
+ * "image_io_path" outside [-1, 2], is an error and changes nothing.  "x4_halo" = the conv_x4 kernel's
  * halo-staged B operand for K x K stride-1 convs (1 on, 0 off, -1 default = $MLIC_X4_HALO or on);
  * "linatt_fused" = the linear attention's output written straight into the
  * reprojection conv's packed operand ($MLIC_LINATT_FUSED); "dw_strip" = the register-strip depthwise
  * 3x3 for stride-1 planes up to 64 columns ($MLIC_DW_STRIP); "x4_splitk" = split-K for few-tile
- * 3x3 / 5x5 convs (default off, $MLIC_X4_SPLITK=1) -- set it before a handle's first call (the
- * workspace is sized for the setting in force then); "dwpw2" = the form of the fused depthwise +
+ * 3x3 / 5x5 convs (default off, $MLIC_X4_SPLITK=1); "dwpw2" = the form of the fused depthwise +
  * pointwise for Cin = Cout in {96, 128, 160, 192} (-1 default = $MLIC_DWPW2 or 2: the register-row
  * dwpw3_kernel; 1 the row-pipelined LDS form, A/B-only library since round 6; 0 the round-4 dwpw_kernel) --
  * every form gives the same bits; "pw3" = the full-resolution 1x1 convs with Cin = Cout (GDN / IGDN at
@@ -124,6 +130,10 @@ int mlic_set_poison(mlic_model* m, int on);
  * 0 = the general-stride form, 1 = the interleaved HWC form, 2 = the planar CHW form; a forced form that the
  * strides do not fit is refused) -- every form gives the same bits */
 int mlic_set_kernel_option(const char* name, int value);
+/* the effective value of a mlic_set_kernel_option name as the next call would see it, after the
+ * option's own rule: what was set, else the environment, else the default ("x4_halo": 0 off, 1 = 5 x 5
+ * only, 2 = 3 x 3 too; "chain_nj": 1 or 2; "narrow_limit": 1 .. 32767; the on / off switches: 0 or 1) */
+int mlic_get_kernel_option(const char* name, int* value);
 /* 1 when this library holds the A/B-only kernel families (v1 split-fp16 tiles = precision 1, the halo
  * tiles = conv impl 6, the VALU local attention = local-attention impl 0; `make AB=1`), else 0: the
  * product build fails those requests loudly */

@@ -55,6 +55,7 @@ def _sig(lib):
         "mlic_set_synthesis_precision": [p, i],
         "mlic_set_poison": [p, i],
         "mlic_set_kernel_option": [C.c_char_p, i],
+        "mlic_get_kernel_option": [C.c_char_p, P(i)],
         "mlic_ab_families": [P(i)],
         "mlic_batch_stream": [p, i, i, p, sz, P(sz)],
         "mlic_decompress_batch_stream": [p, p, p, sz, P(p), P(sz), i, i, i, p, p],

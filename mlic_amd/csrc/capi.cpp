@@ -1,7 +1,6 @@
 // C ABI of libmlic_hip.so (include/mlic_hip.h): status codes, thread-local error text.
 #include "../../include/mlic_hip.h"
 
-#include <cstdlib>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,6 +9,7 @@
 
 #include "container.h"
 #include "model.h"
+#include "options.h"
 
 using namespace mlic;
 
@@ -31,6 +31,7 @@ static thread_local std::string g_err;
 template <class F>
 static int guard(F&& f) {
   try {
+    OptionScope scope;  // the whole entry runs under one snapshot of the kernel options
     f();
     return 0;
   } catch (const std::exception& e) {
@@ -73,10 +74,10 @@ int mlic_create(const char* model_name, int n, const char* const* names, const f
     m->impl = nullptr;
     try {
       m->impl = new Model(model_name, n, names, ptrs, shapes, ndims, (hipStream_t)stream);
-      if (const char* e = std::getenv("MLIC_LANES")) m->impl->set_lanes(std::atoi(e));
-      if (const char* e = std::getenv("MLIC_PRECISION")) m->impl->set_precision(std::atoi(e));
-      if (const char* e = std::getenv("MLIC_SYNTH_FP16")) m->impl->set_synthesis_precision(std::atoi(e) == 1 ? 1 : 0);
-      if (const char* e = std::getenv("MLIC_POISON")) m->impl->set_poison(std::atoi(e) != 0);
+      if (opt_str(OPT_LANES)) m->impl->set_lanes(opt(OPT_LANES));
+      if (opt_str(OPT_PRECISION)) m->impl->set_precision(opt(OPT_PRECISION));
+      if (opt_str(OPT_SYNTH_FP16)) m->impl->set_synthesis_precision(opt(OPT_SYNTH_FP16));
+      if (opt_str(OPT_POISON)) m->impl->set_poison(opt(OPT_POISON) != 0);
     } catch (...) {
       delete m;
       throw;
@@ -240,18 +241,14 @@ int mlic_ab_families(int* built) {
 int mlic_set_kernel_option(const char* name, int value) {
   return guard([&] {
     MLIC_CHECK(name, "null option name");
-    const std::string n = name;
-    if (n == "x4_halo") x4_set_halo(value);
-    else if (n == "linatt_fused") linatt_set_fused(value);
-    else if (n == "dw_strip") dw_set_strip(value);
-    else if (n == "x4_splitk") x4_set_splitk(value);
-    else if (n == "dwpw2") dwpw2_set(value);
-    else if (n == "pw3") pw3_set(value);
-    else if (n == "narrow_limit") set_narrow_limit(value);
-    else if (n == "chain_nj") chain_set_nj(value);
-    else if (n == "ep_half") chain_set_ep_half(value);
-    else if (n == "image_io_path") image_io_set_path(value);
-    else throw Error("mlic: unknown kernel option " + n);
+    opt_set(name, value);
+  });
+}
+
+int mlic_get_kernel_option(const char* name, int* value) {
+  return guard([&] {
+    MLIC_CHECK(name && value, "null option name or value");
+    *value = opt_get(name);
   });
 }
 
@@ -886,7 +883,7 @@ int mlic_rans_decode_narrow(const uint8_t* data, size_t nbytes, const uint8_t* i
     std::vector<int16_t> s16(np);
     *widened = 0;
     for (int k = 0; k < nparts; ++k) {
-      if (rans_decode_piece(d, indexes + k * np, np, t, s16.data(), out + k * np))
+      if (rans_decode_piece(d, indexes + k * np, np, t, s16.data(), out + k * np, opt(OPT_NARROW_LIMIT)))
         for (int64_t i = 0; i < np; ++i) out[k * np + i] = s16[i];
       else
         ++*widened;

@@ -26,7 +26,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 #ifndef MLIC_CH_PK  // chain layer transitions: 1 = packed-fp32 bias + GELU of value pairs, 0 = scalar
@@ -411,31 +410,7 @@ bool chain_supported(int nl, const int* cout) {
 
 // $MLIC_CHAIN_NJ / mlic_set_kernel_option("chain_nj"): 16-pixel column blocks per wave (1: eight waves
 // of 16 pixels, 2: four waves of 32); the same MFMA order per accumulator and the same K order, so both
-// give the same bits
-static int g_chain_nj = -1;
-void chain_set_nj(int nj) { g_chain_nj = nj; }
-static int chain_nj() {
-  static const int env = [] {
-    const char* e = std::getenv("MLIC_CHAIN_NJ");
-    return e ? std::atoi(e) : 1;
-  }();
-  const int v = g_chain_nj > 0 ? g_chain_nj : env;
-  return v == 2 ? 2 : 1;
-}
-
-// $MLIC_EP_HALF / mlic_set_kernel_option("ep_half"): EntropyParameters' chains run on their own
-// phase's checkerboard half only (ChainParams::ckbd); 0 = the whole grid (A/B, the same bits at every
-// pixel a consumer reads)
-static int g_ep_half = -1;
-void chain_set_ep_half(int on) { g_ep_half = on; }
-bool chain_ep_half() {
-  static const int env = [] {
-    const char* e = std::getenv("MLIC_EP_HALF");
-    return e ? std::atoi(e) : 1;
-  }();
-  return (g_ep_half >= 0 ? g_ep_half : env) != 0;
-}
-
+// give the same bits (chosen in chain_forward)
 template <int NJ>
 static void launch_chain(const ChainParams& P, int nl, const int* cout, hipStream_t st) {
   dim3 grid(((P.ckbd ? P.HW / 2 : P.HW) + CH_BN - 1) / CH_BN, P.B);
@@ -455,7 +430,7 @@ void chain_forward(const ChainParams& P, int nl, const int* cout, hipStream_t st
              "chain: Cin multiple of 64 (or 0 with aux), HW of 4");
   MLIC_CHECK(P.ckbd == 0 || (P.ckbd <= 2 && P.W > 0 && P.W % 2 == 0 && P.HW % P.W == 0), "chain: checkerboard half needs W even");
   MLIC_CHECK(!P.sq_in || P.ckbd, "chain: squeezed inputs need a checkerboard half");
-  if (chain_nj() == 2) launch_chain<2>(P, nl, cout, st);
+  if (opt(OPT_CHAIN_NJ) == 2) launch_chain<2>(P, nl, cout, st);
   else launch_chain<1>(P, nl, cout, st);
 }
 

@@ -2,24 +2,13 @@
 // the per-kernel C-ABI test entry (mlic_conv_run) and the micro-benchmark all run the same choice.
 #include "kernels.h"
 
-#include <cstdlib>
-
 namespace mlic {
-
-// $MLIC_X4=0 disables the LDS-DMA x4 kernel (A/B switch)
-static bool x4_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_X4");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
 
 // kernel sizes x4 takes (digits of $MLIC_X4_K, default "135"): the A/B switch for 1x1 / 5x5 layers
 // (5x5: the context reprojections, 8 x 68 x 120, 64..320 channels: x4 1.1-1.9x the halo kernel)
 static bool x4_k_on(int K) {
   static const int mask = [] {
-    const char* e = std::getenv("MLIC_X4_K");
+    const char* e = opt_str(OPT_X4_K);
     int m = 0;
     for (const char* c = e ? e : "135"; *c; ++c)
       if (*c >= '0' && *c <= '9') m |= 1 << (*c - '0');
@@ -51,7 +40,8 @@ int conv_select(const ConvParams& P, const ConvWeights& w, int precision) {
   // 96..288 -> 96 / 128 at the latent grid: 1.26-1.75x x3v2)
   const bool big1 = (int64_t)P.Cin * P.Cout >= (1 << 18), mid1 = P.Cin >= 192 && P.Cout >= 192;
   const bool x4_shape = P.K == 1 ? (big1 || mid1) : P.Cout >= 64;
-  if (w.wx4 && x4_on() && x4_k_on(P.K) && x4_shape && conv_x4_ok(P, w.cin_pad)) return CONV_X4;
+  // $MLIC_X4=0 disables the LDS-DMA x4 kernel (A/B switch)
+  if (w.wx4 && opt(OPT_X4) && x4_k_on(P.K) && x4_shape && conv_x4_ok(P, w.cin_pad)) return CONV_X4;
   // halo: the 5x5 reprojection (145 vs 126 TF/s); for 3x3 the 8-wave 256x256 x3v2 tile is faster
   // (243 vs 232 TF/s on the g_s subpel conv), for 1x1 the halo staging does not pay
   if (P.K == 5 && conv_halo_ok(P, w.cin_pad) &&

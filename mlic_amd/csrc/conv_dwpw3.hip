@@ -31,7 +31,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#include <cstdlib>
 
 namespace mlic {
 
@@ -681,24 +680,15 @@ void dwpw3_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, 
 //   0 dwpw_kernel (conv_dwpw.hip, rounds 3-4: one wave per SIMD, the same bits);
 //   1 the row-pipelined LDS form dwpw2_kernel -- an A/B-only family since round 6 (ab/conv_dwpw2.hip,
 //     linked by make AB=1 only: its masked-residual builds gave intermittent wrong rows).
-static int g_dwpw2 = -1;
-void dwpw2_set(int on) { g_dwpw2 = on; }
-static int d2_form() {
-  static const int env = [] {
-    const char* e = std::getenv("MLIC_DWPW2");
-    return e ? std::atoi(e) : 2;
-  }();
-  return g_dwpw2 < 0 ? env : g_dwpw2;
-}
 bool dwpw2_ok(const ConvParams& P, int cin_pad) {
-  const int f = d2_form();
+  const int f = opt(OPT_DWPW2);
   if (f == 2) return dwpw3_shape_ok(P, cin_pad);
   if (f == 1) return dwpw2_lds_ok(P, cin_pad);
   return false;
 }
 void dwpw2_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, const float* dww,
                    const float* dwb, hipStream_t st) {
-  if (d2_form() == 2) return dwpw3_forward(P, wh, wl, cin_pad, dww, dwb, st);
+  if (opt(OPT_DWPW2) == 2) return dwpw3_forward(P, wh, wl, cin_pad, dww, dwb, st);
   dwpw2_lds_forward(P, wh, wl, cin_pad, dww, dwb, st);
 }
 
@@ -706,15 +696,6 @@ void dwpw2_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, 
 // GELU, GDN, IGDN, with or without residual).  $MLIC_PW3 / mlic_set_kernel_option("pw3"): 0 off, 1 (default)
 // from 256 K px per image (at 272 x 480 pw_resident measured faster: 0.45 vs 0.48 ms GELU, 0.64 vs 0.66 GDN;
 // at 544 x 960 pw3's GDN / IGDN 2.07 vs 2.30), 2 at every grid (tests)
-static int g_pw3 = -1;
-void pw3_set(int on) { g_pw3 = on; }
-static int pw3_setting() {
-  static const int env = [] {
-    const char* e = std::getenv("MLIC_PW3");
-    return e ? std::atoi(e) : 1;
-  }();
-  return g_pw3 < 0 ? env : g_pw3;
-}
 static int pw3_mode(const ConvParams& P) {
   const int e = P.epi & ~EPI_RES;
   if (e == EPI_NONE) return 0;
@@ -724,7 +705,7 @@ static int pw3_mode(const ConvParams& P) {
   return -1;
 }
 bool pw3_ok(const ConvParams& P, int cin_pad) {
-  const int mode = pw3_mode(P), setting = pw3_setting();
+  const int mode = pw3_mode(P), setting = opt(OPT_PW3);
   if (setting == 0 || mode < 0 || (mode >= 2 && !P.aux)) return false;
   if (setting == 1 && (int64_t)P.H * P.W < 262144) return false;
   if (P.K != 1 || P.stride != 1 || P.pad != 0 || P.nseg != 1 || P.seg[0].C != P.Cin || cin_pad < P.Cin) return false;

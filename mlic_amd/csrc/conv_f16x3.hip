@@ -24,7 +24,6 @@
 #include "kernels.h"
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 
@@ -37,13 +36,7 @@ constexpr int XB_K = 32;         // k per tile
 constexpr int XB_PITCH = 40;     // halves per LDS row (32 + 8 pad) = 80 bytes
 
 // $MLIC_V2_WIDE=0 disables the 8-wave 256x256 tile (A/B switch)
-static bool v2_wide() {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_V2_WIDE");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
+static bool v2_wide() { return opt(OPT_V2_WIDE) != 0; }
 
 // ---------------------------------------------------------------------------------------------
 // v2: B (activations) staged in its natural [k][n] orientation — float4 loads along pixels for

@@ -22,7 +22,6 @@
 #include "kernels.h"
 
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -812,8 +811,7 @@ int x4_bm(int Cout) {
   // A/B: $MLIC_X4_BM_FOR="Cout:BM,Cout:BM" forces the tile height of the listed Cout values
   static const std::vector<std::pair<int, int>> force = [] {
     std::vector<std::pair<int, int>> v;
-    const char* e = std::getenv("MLIC_X4_BM_FOR");
-    for (const char* q = e; q && *q;) {
+    for (const char* q = opt_str(OPT_X4_BM_FOR); q && *q;) {
       int c = 0, m = 0, n = 0;
       if (std::sscanf(q, "%d:%d%n", &c, &m, &n) != 2) break;
       if (m == 64 || m == 96 || m == 128 || m == 192 || m == 224 || m == 256) v.emplace_back(c, m);
@@ -829,17 +827,10 @@ int x4_bm(int Cout) {
   // per 8 images): 256-row tiles leave half the CUs idle (120 workgroups), 128-row tiles fill them --
   // 252 -> 157 us (8 x 17 x 30, profiles/r06/ab/x4_tile_height_ab.log); 480 -> 1920 (1/32) is equal either way
   if (Cout == 1280) return 128;
-  static const bool t96 = [] {  // A/B: MLIC_X4_BM96=0 keeps 128-row tiles for Cout 65..96
-    const char* e = std::getenv("MLIC_X4_BM96");
-    return !(e && e[0] == '0');
-  }();
-  if (t96 && Cout > 64 && Cout <= 96) return 96;
+  // A/B: MLIC_X4_BM96=0 keeps 128-row tiles for Cout 65..96, MLIC_X4_BM224=0 256-row tiles for Cout 193..224
+  if (opt(OPT_X4_BM96) && Cout > 64 && Cout <= 96) return 96;
   if (Cout > 128 && Cout <= 192) return 192;
-  static const bool t224 = [] {  // A/B: MLIC_X4_BM224=0 keeps 256-row tiles for Cout 193..224
-    const char* e = std::getenv("MLIC_X4_BM224");
-    return !(e && e[0] == '0');
-  }();
-  if (t224 && Cout > 192 && Cout <= 224) return 224;
+  if (opt(OPT_X4_BM224) && Cout > 192 && Cout <= 224) return 224;
   const int w256 = (Cout + 255) / 256 * 256 - Cout, w128 = (Cout + 127) / 128 * 128 - Cout;
   return (Cout >= 192 && 8 * (w256 - w128) <= Cout) ? 256 : 128;
 }
@@ -921,28 +912,11 @@ __global__ __launch_bounds__(256) void x4_split_reduce_kernel(ConvParams P, cons
 }
 
 // $MLIC_X4_RS=0: the LDS-DMA operand path (A/B switch); default the register-staged one
-static bool x4_rs() {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_X4_RS");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
+static bool x4_rs() { return opt(OPT_X4_RS) != 0; }
 
 // the halo-staged B operand (conv_x4_kernel HALO) for a packed K x K stride-1 conv whose LDS images fit;
-// $MLIC_X4_HALO=0: B staged per tap (A/B switch)
-static int g_x4_halo = -1;  // mlic_set_kernel_option("x4_halo"): -1 = $MLIC_X4_HALO / default (5 x 5 only)
-void x4_set_halo(int on) { g_x4_halo = on; }
-// 0 = off, 1 = 5 x 5 only (the default), 2 = 3 x 3 too ($MLIC_X4_HALO=2; the option's 1 means 3 x 3 too)
-static int x4_halo_setting() {
-  static const int env = [] {
-    const char* e = std::getenv("MLIC_X4_HALO");
-    return e ? std::atoi(e) : 1;
-  }();
-  if (g_x4_halo >= 0) return g_x4_halo == 0 ? 0 : 2;
-  return env;
-}
-static bool x4_halo_on() { return x4_halo_setting() != 0; }
+// $MLIC_X4_HALO=0: B staged per tap (A/B switch).  OPT_X4_HALO: 0 = off, 1 = 5 x 5 only (the default),
+// 2 = 3 x 3 too ($MLIC_X4_HALO=2; the option's 1 means 3 x 3 too)
 template <int K, int BM>
 constexpr bool x4_halo_fits() {
   constexpr int a = 2 * BM * ROWB, h = 2 * (TR + K - 1) * (TC + K - 1) * ROWB;
@@ -954,19 +928,16 @@ constexpr bool x4_halo_fits() {
 // recomputed per read, which eats the saved B loads).  Default: 5x5 only; "x4_halo" = 1 forces it for
 // 3x3 too (A/B), 0 turns it off.
 static bool x4_halo(const ConvParams& P, bool hi) {
-  if (!x4_halo_on() || P.K == 1 || P.stride != 1) return false;
-  if (P.K == 3 && x4_halo_setting() != 2) return false;
+  const int setting = opt(OPT_X4_HALO);
+  if (setting == 0 || P.K == 1 || P.stride != 1) return false;
+  if (P.K == 3 && setting != 2) return false;
   const int bm = x4_bm(P.Cout);
   return 2 * bm * ROWB + 2 * (TR + P.K - 1) * (TC + P.K - 1) * ROWB <= 160 * 1024;
 }
 
 // $MLIC_X4_DIRECT=0: 1x1 layers read the packed copy too (A/B switch)
 bool x4_direct_ok(const ConvParams& P, bool hi) {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_X4_DIRECT");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on && P.K == 1 && !hi && !(P.epi & EPI_SQUARE_IN) && x4_rs();
+  return opt(OPT_X4_DIRECT) && P.K == 1 && !hi && !(P.epi & EPI_SQUARE_IN) && x4_rs();
 }
 
 template <int K, int BM>
@@ -976,10 +947,7 @@ static void launch_x4(const ConvParams& P, const _Float16* act, const _Float16* 
   x4_tgrid(P, H, W);
   const int ntx = (W + TC - 1) / TC, nty = (H + TR - 1) / TR;
   dim3 grid((P.Cout + BM - 1) / BM, ntx * nty, P.B * nsplit);
-  static const int abl = [] {
-    const char* e = std::getenv("MLIC_X4_ABL");  // diagnostics: 1 = no DMA in the loop, 2 = no MFMA
-    return e ? std::atoi(e) : 0;
-  }();
+  const int abl = opt(OPT_X4_ABL);  // diagnostics: 1 = no DMA in the loop, 2 = no MFMA
   if (K == 1 && !act)
     hipLaunchKernelGGL((conv_x4_kernel<K, BM, true, false, K == 1>), grid, dim3(X4T), 0, st, P, act, wx, nchunk, H, W,
                        abl, nsplit);
@@ -1014,15 +982,8 @@ static void launch_x4(const ConvParams& P, const _Float16* act, const _Float16* 
 // split adds a partial-sum pass and a combine launch: main config 91.1 / 91.6 img/s without against
 // 90.2 / 90.3 with (alternating, one box); Kodak-size and MLICPP_M_SMALL_DEC within noise.
 // $MLIC_X4_SPLITK=1 or mlic_set_kernel_option("x4_splitk", 1) turns it on (tests, A/B).
-static int g_x4_splitk = -1;
-void x4_set_splitk(int v) { g_x4_splitk = v; }
 int x4_splitk(const ConvParams& P, int cin_pad, bool hi) {
-  static const bool env_on = [] {
-    const char* e = std::getenv("MLIC_X4_SPLITK");
-    return e && std::atoi(e) != 0;
-  }();
-  const bool on = g_x4_splitk >= 0 ? g_x4_splitk != 0 : env_on;
-  if (!on || !x4_rs() || P.K == 1) return 1;
+  if (!opt(OPT_X4_SPLITK) || !x4_rs() || P.K == 1) return 1;
   int H, W;
   x4_tgrid(P, H, W);
   const int tiles = ((P.Cout + x4_bm(P.Cout) - 1) / x4_bm(P.Cout)) * ((W + TC - 1) / TC) * ((H + TR - 1) / TR);

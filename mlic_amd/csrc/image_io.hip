@@ -20,8 +20,6 @@
 // straight from / to global memory); all forms give the same bits.
 #include "kernels.h"
 
-#include <atomic>
-
 namespace mlic {
 
 namespace {
@@ -291,12 +289,10 @@ __global__ __launch_bounds__(256) void blur3_pad_kernel(const float* __restrict_
   }
 }
 
-std::atomic<int> g_path{-1};
-
 // the kernel form for a byte image with these strides; throws when a forced form does not fit
 int io_path(const int64_t* s) {
   const bool hwc = s[2] == 3 && s[3] == 1, chw = s[2] == 1;
-  const int forced = g_path.load();
+  const int forced = opt(OPT_IMAGE_IO_PATH);
   if (forced < 0) return hwc ? IO_HWC : chw ? IO_CHW : IO_GENERAL;
   MLIC_CHECK(forced != IO_HWC || hwc, "image_io_path 1 (HWC) needs column stride 3 and channel stride 1");
   MLIC_CHECK(forced != IO_CHW || chw, "image_io_path 2 (CHW) needs column stride 1");
@@ -312,11 +308,6 @@ unsigned io_blocks(int B, int rows, int cols, int* tiles_x, int* tiles_y, int bl
 }
 
 }  // namespace
-
-void image_io_set_path(int path) {
-  MLIC_CHECK(path >= -1 && path <= IO_CHW, "image_io_path must be -1 (by layout), 0, 1 or 2");
-  g_path = path;
-}
 
 void image_ingest_u8(const uint8_t* src, const int64_t* s, int B, int H, int W, float* dst, int Hp, int Wp,
                      hipStream_t st) {

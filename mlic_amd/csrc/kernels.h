@@ -1,6 +1,7 @@
 // Host-side launchers of the MLIC++ HIP kernels (see conv_mfma.hip, kernels.hip).
 #pragma once
 #include "common.h"
+#include "options.h"
 
 #include <algorithm>
 
@@ -45,11 +46,10 @@ bool dwpw_ok(const ConvParams& P, int cin_pad);
 // the model's choice on top of dwpw_ok: grids where the fused kernel measured faster (per image only)
 bool dwpw_grid_ok(const ConvParams& P);
 // producer / consumer forms for Cin = Cout in {96, 128, 160, 192}, bias / GELU (+ residual): dwpw_forward
-// takes the chosen one (dwpw2_set) where it applies
+// takes the chosen one where it applies: mlic_set_kernel_option("dwpw2"): -1 = $MLIC_DWPW2 (default 2),
+// 0 = dwpw_kernel, 1 = the row-pipelined LDS form (ab/conv_dwpw2.hip: A/B-only family, make AB=1), 2 = the
+// register-row form (conv_dwpw3.hip)
 bool dwpw2_ok(const ConvParams& P, int cin_pad);
-// mlic_set_kernel_option("dwpw2"): -1 = $MLIC_DWPW2 (default 2), 0 = dwpw_kernel, 1 = the row-pipelined
-// LDS form (ab/conv_dwpw2.hip: A/B-only family, make AB=1), 2 = the register-row form (conv_dwpw3.hip)
-void dwpw2_set(int on);
 // the A/B-only row-pipelined LDS form (ab/conv_dwpw2.hip; the product build's stub reports false / throws)
 bool dwpw2_lds_ok(const ConvParams& P, int cin_pad);
 void dwpw2_lds_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, const float* dww,
@@ -60,7 +60,6 @@ bool dwpw3_shape_ok(const ConvParams& P, int cin_pad);
 // -1 = $MLIC_PW3 (default 1), 0 off, 1 from 256 K px per image, 2 every grid
 bool pw3_ok(const ConvParams& P, int cin_pad);
 void pw3_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, hipStream_t st);
-void pw3_set(int on);
 void dwpw3_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, const float* dww,
                    const float* dwb, hipStream_t st);
 void dwpw2_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, const float* dww,
@@ -81,10 +80,6 @@ bool conv_x4_ok(const ConvParams& P, int cin_pad);
 void x4_pack_act(const ConvParams& P, int cin_pad, _Float16* dst, hipStream_t st, bool hi = false);
 // 1x1 layers: x4 builds its B rows from the fp32 input itself (no packed copy; act = nullptr)
 bool x4_direct_ok(const ConvParams& P, bool hi);
-// A/B switch of the halo-staged B operand (tests): 1 on, 0 off, -1 the default ($MLIC_X4_HALO)
-void x4_set_halo(int on);
-// A/B switch of the fused linear attention (model.cpp linatt_reproject): 1 on, 0 off, -1 default
-void linatt_set_fused(int on);
 // part: the split-K partial planes (x4_part_bytes bytes; nullptr = no split)
 int x4_splitk(const ConvParams& P, int cin_pad, bool hi = false);
 int64_t x4_part_bytes(const ConvParams& P, int cin_pad, bool hi = false);
@@ -145,8 +140,6 @@ struct DwParams {
   int B;
 };
 void dw3x3(const DwParams& P, hipStream_t st);
-void dw_set_strip(int v);
-void x4_set_splitk(int v);  // -1 default ($MLIC_X4_SPLITK, off), 0 off, 1 on  // A/B: 0 = the LDS-tile kernel for narrow stride-1 planes too
 
 void ln_channels(const float* x, int64_t x_bs, float* y, int64_t y_bs, const float* g, const float* b, int C,
                  int HW, int B, hipStream_t st);
@@ -275,7 +268,6 @@ void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, i
                      float* dst, hipStream_t st);
 // mlic_set_kernel_option("image_io_path"): -1 = by layout (default), 0 = the general-stride kernels, 1 = the
 // interleaved (HWC) form, 2 = the planar (CHW) form; a forced form the layout does not fit is an error
-void image_io_set_path(int path);
 // GaussianConditional likelihood (vbr_scale != 1: of y*sc, s*sc, m*sc) and build_indexes, element-wise
 void gauss_likelihood(const float* y, const float* s, const float* m, int64_t n, float vbr_scale, float* lik,
                       hipStream_t st);
@@ -312,10 +304,5 @@ void chain_pack(const _Float16* wh, const _Float16* wl, int Cout, int Cin, int c
 void chain_forward(const ChainParams& P, int nl, const int* cout, hipStream_t st);
 // mlic_set_kernel_option("chain_nj"): 16-pixel column blocks per wave (-1 = $MLIC_CHAIN_NJ or 1; 2 = the
 // rounds 2-5 four-wave form); the same bits either way
-void chain_set_nj(int nj);
-// mlic_set_kernel_option("ep_half"): EntropyParameters on its phase's half of the grid (-1 = $MLIC_EP_HALF
-// or on; 0 = the whole grid)
-void chain_set_ep_half(int on);
-bool chain_ep_half();
 
 }  // namespace mlic

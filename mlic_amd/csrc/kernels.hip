@@ -14,7 +14,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#include <cstdlib>
 
 namespace mlic {
 
@@ -306,17 +305,6 @@ __global__ __launch_bounds__(64 * DWS_WAVES) void dw3x3_s1_strip_kernel(DwParams
   }
 }
 
-static int g_dw_strip = -1;  // -1: $MLIC_DW_STRIP (default on), else the kernel option
-void dw_set_strip(int v) { g_dw_strip = v; }
-static bool dw_strip_on() {
-  if (g_dw_strip >= 0) return g_dw_strip != 0;
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_DW_STRIP");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
-
 void dw3x3(const DwParams& P, hipStream_t st) {
   MLIC_CHECK(P.stride == 1 || P.stride == 2, "dw stride");
   MLIC_CHECK(P.Ho == (P.H - 1) / P.stride + 1 && P.Wo == (P.W - 1) / P.stride + 1, "dw output size");
@@ -329,8 +317,9 @@ void dw3x3(const DwParams& P, hipStream_t st) {
   MLIC_CHECK(tot == P.C, "dw segments");
   // narrow planes (<= 64 columns: the Kodak-size latent, 32 x 48) take the strip form: 10.4 vs 14.1 us
   // for 16 x 224 x 32 x 48 (rocprof); at the 1080p latent (120 columns) both forms are within 2 %
-  // (21.2 / 21.6 us for 8 x 224 x 68 x 120, against 17.0 us for a plain copy of the same bytes)
-  if (P.stride == 1 && aligned && P.W / 4 <= 16 && dw_strip_on()) {
+  // (21.2 / 21.6 us for 8 x 224 x 68 x 120, against 17.0 us for a plain copy of the same bytes);
+  // $MLIC_DW_STRIP=0 / the "dw_strip" option: the LDS-tile kernel for narrow planes too (A/B)
+  if (P.stride == 1 && aligned && P.W / 4 <= 16 && opt(OPT_DW_STRIP)) {
     // strip height: the fewest loaded rows per plane (R + 2 per strip of R) among 8 / 12 / 17
     const int cand[3] = {8, 12, 17};
     int best = 0;
@@ -410,11 +399,7 @@ void ln_channels(const float* x, int64_t x_bs, float* y, int64_t y_bs, const flo
 // LocalContext windowed attention: the MFMA kernels (attn_local.hip); the round-1 VALU kernel is an
 // A/B baseline in ab/attn_local_valu.hip (make AB=1, $MLIC_LOCAL_ATTN_VALU=1).
 void local_attn(const LocalAttnParams& P, hipStream_t st) {
-  static const bool valu = [] {
-    const char* e = std::getenv("MLIC_LOCAL_ATTN_VALU");
-    return e && std::atoi(e) != 0;
-  }();
-  if (valu) local_attn_valu(P, st);
+  if (opt(OPT_LOCAL_ATTN_VALU)) local_attn_valu(P, st);
   else local_attn_mfma(P, st);
 }
 

@@ -2,7 +2,6 @@
 // the HIP kernels (conv_mfma.hip, kernels.hip), this file only wires views, weights and phases.
 #include "model.h"
 
-#include <cstdlib>
 
 #include <algorithm>
 #include <cmath>
@@ -301,11 +300,7 @@ void Model::add_taps(const std::string& base, const float* w_dev, int Cin, hipSt
 
 // $MLIC_TAPS=0: g_s's output conv on the narrow VALU kernel (A/B switch)
 bool Model::taps_on() const {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_TAPS");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on && prec() == PREC_F16X3_V2;
+  return opt(OPT_TAPS) && prec() == PREC_F16X3_V2;
 }
 
 // LDS weight images of the fused chains: EntropyParameters (entropy.py:10-18, layers .0 .2 .4 .6) and
@@ -441,10 +436,7 @@ void Model::add_hoist(const std::map<std::string, std::pair<const float*, int>>&
 // ≈ 2 ms per 8 images on each side (measured, main config, alternating pairs on one box: 91.4 vs 89.9
 // img/s).  $MLIC_HOIST=1 / 0 forces it on / off (A/B).
 bool Model::hoist_on() const {
-  static const int env = [] {
-    const char* e = std::getenv("MLIC_HOIST");
-    return e ? std::atoi(e) : -1;
-  }();
+  const int env = opt(OPT_HOIST);
   bool want = env >= 0 ? env != 0 : false;
   if (env < 0)
     for (int i = 0; i < cfg_.S && !want; ++i)
@@ -457,20 +449,12 @@ bool Model::hoist_on() const {
 // dwsep convs with an even width (default; $MLIC_DWPW=0 is the A/B switch; the results are
 // bit-identical either way)
 bool Model::dwpw_on() const {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_DWPW");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on && prec() == PREC_F16X3_V2;
+  return opt(OPT_DWPW) && prec() == PREC_F16X3_V2;
 }
 
 // $MLIC_CHAIN=0: the per-layer path for EntropyParameters / LocalContext MLP (A/B switch)
 bool Model::chain_on() const {
-  static const bool on = [] {
-    const char* e = std::getenv("MLIC_CHAIN");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on && prec() == PREC_F16X3_V2;
+  return opt(OPT_CHAIN) && prec() == PREC_F16X3_V2;
 }
 
 Model::~Model() {
@@ -496,9 +480,7 @@ Lane& Model::lane(int i) {
     // staggered priorities (lane 0 highest): symmetric lanes would reach their host entropy-coding
     // phases together and leave the GPU idle; with priorities they drift apart and each lane's host
     // coding overlaps the lower-priority lanes' kernels.  MLIC_LANE_PRIORITY=0 disables.
-    const char* e = std::getenv("MLIC_LANE_PRIORITY");
-    const bool stagger = !(e && std::atoi(e) == 0);
-    if (stagger) {
+    if (opt(OPT_LANE_PRIORITY)) {
       int least = 0, greatest = 0;
       HIP_OK(hipDeviceGetStreamPriorityRange(&least, &greatest));
       const int prio = std::min(least, greatest + prio_base_ + (int)lanes_.size());
@@ -926,11 +908,8 @@ View Model::local_context(const View& x, int i, bool half) {
   const int C = x.C, H = x.H, W = x.W;
   View out = alloc(2 * C, H, W);
   const size_t m = L().arena.mark();
-  static const bool packed_on = [] {  // $MLIC_LA_PACKED=0: the unfolded fp32 path (A/B switch)
-    const char* e = std::getenv("MLIC_LA_PACKED");
-    return !(e && std::atoi(e) == 0);
-  }();
-  const bool packed = packed_on && prec() == PREC_F16X3_V2 && C == 32 && convs_.count(p + ".fusion.__x4perm");
+  // $MLIC_LA_PACKED=0: the unfolded fp32 path (A/B switch)
+  const bool packed = opt(OPT_LA_PACKED) && prec() == PREC_F16X3_V2 && C == 32 && convs_.count(p + ".fusion.__x4perm");
   // non-anchor half only: every stage after the qkv projection is per query pixel, so it runs on the
   // squeezed half (planes of H x W / 2, pixel y W / 2 + x / 2) and the MLP chain writes the full-grid
   // output at the non-anchor pixels (the reference computes the whole grid; its only consumer, the
@@ -1056,17 +1035,8 @@ View Model::inter_context(const View& x, int i) {
   return out;
 }
 
-// $MLIC_LINATT_FUSED=0: the three-launch linear attention + fp32 att + the reprojection's own pack (A/B)
-static int g_linatt_fused = -1;  // mlic_set_kernel_option("linatt_fused"): -1 = the environment / on
-void linatt_set_fused(int on) { g_linatt_fused = on; }
-static bool linatt_fused_on() {
-  static const bool env = [] {
-    const char* e = std::getenv("MLIC_LINATT_FUSED");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return g_linatt_fused < 0 ? env : g_linatt_fused != 0;
-}
-
+// $MLIC_LINATT_FUSED=0 / mlic_set_kernel_option("linatt_fused", 0): the three-launch linear attention + fp32
+// att + the reprojection's own pack (A/B)
 // the linear attention and the 5x5 reprojection conv that consumes it (context.py:180-190, 235-241).
 // Fused (default, when the reprojection runs on conv_x4): ctx (partials + the fixed-order combine),
 // then ctx^T . softmax_c(q) written straight into the conv's packed split operand -- the fp32
@@ -1084,7 +1054,7 @@ void Model::linatt_reproject(const View& k, const View& v, const View& q, int he
   const View geo{nullptr, D, H, W, (int64_t)D * HW};  // geometry only: the fused conv reads its packed operand
   const ConvParams P = conv_params({geo}, rp, 1, 2, a, EPI_NONE, nullptr, nullptr);
   const ConvWeights cwt{rp.w, rp.wh, rp.wl, rp.cin_pad, rp.wx4, rp.wexp};
-  if (linatt_fused_on() && rp.cin_pad == D && D % 32 == 0 && conv_select(P, cwt, prec()) == CONV_X4) {
+  if (opt(OPT_LINATT_FUSED) && rp.cin_pad == D && D % 32 == 0 && conv_select(P, cwt, prec()) == CONV_X4) {
     timed(PCAT_LINATT, fl * 0.5, 4.0 * B * HW * D * 2.0, [&] {
       linear_attention_ctx(k.p, k.bs, v.p, v.bs, part, ctx, heads, hd, H, W, B, nsplit, kmask, L().st);
     }, tag);
@@ -1133,9 +1103,11 @@ View Model::intra_context(const View& x1, const View& x2, int i) {
 }
 
 // entropy.py:7-29
+// $MLIC_EP_HALF / mlic_set_kernel_option("ep_half"): EntropyParameters' chains run on their own phase's
+// checkerboard half only (ChainParams::ckbd); 0 = the whole grid (A/B, the same bits at every pixel a consumer reads)
 bool Model::ep_half_chain(const std::string& kind, int i, int H, int W, bool hoisted) const {
   const std::string p = "entropy_parameters_" + kind + "." + std::to_string(i) + ".fusion";
-  if (!chain_ep_half() || W % 2 != 0 || (H * W) % 4 != 0) return false;
+  if (!opt(OPT_EP_HALF) || W % 2 != 0 || (H * W) % 4 != 0) return false;
   return hoisted ? chains_ctx_.count(p) > 0 : (chain_on() && chains_.count(p) > 0);
 }
 
@@ -1146,7 +1118,7 @@ View Model::entropy_parameters(const std::vector<View>& ctx, const View* hyper, 
   const int H = geo.H, W = geo.W;
   // the phase's checkerboard half only: the reference computes the whole grid and masks the other half
   // to zero (ckbd_anchor / ckbd_nonanchor, mlicpp.py:226-228, 239-241) before any use
-  const int ckbd = phase_only && chain_ep_half() && W % 2 == 0 ? (kind == "nonanchor" ? 2 : 1) : 0;
+  const int ckbd = phase_only && opt(OPT_EP_HALF) && W % 2 == 0 ? (kind == "nonanchor" ? 2 : 1) : 0;
   const ConvW& l3 = cw(p + ".6");
   View out = alloc(l3.Cout, H, W);
   auto hc = chains_ctx_.find(p);
@@ -1201,7 +1173,8 @@ class PhaseDecoder {
   // stream); one decoder then walks the images of each phase in order
   PhaseDecoder(int B, const uint8_t* const* y, const size_t* ylen, const CdfTables* t, int32_t* h_sym,
                int16_t* h_sym16, uint8_t* h_idx8, HostStats* hs, HostPool* pool, bool single = false)
-      : t_(t), h_sym_(h_sym), h_sym16_(h_sym16), h_idx8_(h_idx8), hs_(hs), pool_(pool), B_(B) {
+      : t_(t), h_sym_(h_sym), h_sym16_(h_sym16), h_idx8_(h_idx8), hs_(hs), pool_(pool), B_(B),
+        nlim_(opt(OPT_NARROW_LIMIT)) {  // read here, in the lane thread: the pool's workers run under no snapshot
     dec_.resize(single ? 1 : B);
     for (size_t b = 0; b < dec_.size(); ++b) dec_[b].set_stream(y[b], ylen[b]);
   }
@@ -1219,7 +1192,8 @@ class PhaseDecoder {
     std::vector<char> wide(parts, 0);
     auto work = [&](int b) {
       HostStats::Scope d{hs_->dec_ns};
-      if (!rans_decode_piece(dec_[b], h_idx8_ + b * n, n, *t_, h_sym16_ + b * n, h_sym_ + b * n)) wide[b] = 1;
+      if (!rans_decode_piece(dec_[b], h_idx8_ + b * n, n, *t_, h_sym16_ + b * n, h_sym_ + b * n, nlim_))
+        wide[b] = 1;
     };
     if (parts == 1) work(0);
     else pool_->run(B, work, HostPool::DECODE);
@@ -1244,7 +1218,7 @@ class PhaseDecoder {
   uint8_t* h_idx8_;
   HostStats* hs_;
   HostPool* pool_;
-  int B_;
+  int B_, nlim_;
 };
 
 // mlicpp.py:107-176 (forward), 220-277 (compress), 309-366 (decompress)
@@ -1331,7 +1305,7 @@ void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& 
           Q.sym16 = cb->sym16 + off;
           Q.idx8 = cb->idx8 + off;
           Q.ovf = cb->ovf;
-          Q.nlim = narrow_limit();
+          Q.nlim = opt(OPT_NARROW_LIMIT);
         }
         timed(PCAT_ELEM, 0.0, 4.0 * L().B * C * HW * 5, [&] { quant_phase(Q, L().st); }, "quant_phase");
         Lane& l = L();
@@ -1420,13 +1394,7 @@ void Model::ensure_host(size_t n) {
 // mode 0 against 84.5 with mode 1, Kodak-size 391 against 381 -- the copies run as blit kernels
 // (__amd_rocclr_copyBuffer) on the CUs, and 20 of them per call beside the network cost more than the
 // one copy they save at the end; an extra stream per lane also shares the box's 4 hardware queues
-int Model::phase_d2h_mode() {
-  static const int m = [] {
-    const char* e = std::getenv("MLIC_PHASE_D2H");
-    return e ? std::atoi(e) : 0;
-  }();
-  return m;
-}
+int Model::phase_d2h_mode() { return opt(OPT_PHASE_D2H); }
 
 void Model::ensure_chost(size_t n) {
   Lane& l = L();
@@ -1565,7 +1533,8 @@ void Model::over_lanes(int B, hipStream_t caller, F&& fn, int max_lanes) {
     const int cnt = B / nl + (i < B % nl ? 1 : 0);
     Lane& l = lane(i);
     HIP_OK(hipStreamWaitEvent(l.st, ready, 0));
-    th.emplace_back([&, i, first, cnt, &l = l] {
+    th.emplace_back([&, i, first, cnt, &l = l, snap = OptionScope::current()] {
+      OptionScope scope(snap);  // the lane thread reads the caller's snapshot of the kernel options
       tl_lane_ = &l;
       try {
         fn(l, first, cnt);
@@ -1787,7 +1756,7 @@ HostPool& Model::host_pool() {
   static std::unique_ptr<HostPool> pool;
   std::call_once(once, [] {
     int n = (int)std::thread::hardware_concurrency();
-    if (const char* e = std::getenv("MLIC_HOST_THREADS")) n = std::atoi(e);
+    if (opt_str(OPT_HOST_THREADS)) n = opt(OPT_HOST_THREADS);
     n = std::max(1, std::min(n, 16));
     pool = std::make_unique<HostPool>(n);
   });

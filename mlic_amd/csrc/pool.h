@@ -8,13 +8,14 @@
 // against FIFO 87.8).  $MLIC_POOL_PRIO: 2 (default) encodes first, 1 decodes first, 0 one FIFO.
 #pragma once
 #include <condition_variable>
-#include <cstdlib>
 #include <deque>
 #include <exception>
 #include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
+
+#include "options.h"
 
 namespace mlic {
 
@@ -47,7 +48,7 @@ class HostPool {
     batch.left = n - 1;
     {
       std::lock_guard<std::mutex> g(m_);
-      const int pr = prio();
+      const int pr = opt(OPT_POOL_PRIO);
       const bool urgent = (pr == 1 && kind == DECODE) || (pr == 2 && kind == ENCODE);
       auto& q = urgent ? uq_ : q_;
       for (int i = 1; i < n; ++i)
@@ -77,13 +78,6 @@ class HostPool {
   }
 
  private:
-  static int prio() {
-    static const int p = [] {
-      const char* e = std::getenv("MLIC_POOL_PRIO");
-      return e ? std::atoi(e) : 2;
-    }();
-    return p;
-  }
   void loop() {
     for (;;) {
       std::function<void()> job;

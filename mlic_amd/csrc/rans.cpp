@@ -7,7 +7,6 @@
 #include "rans.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -159,12 +158,8 @@ uint32_t RansDecoderState::get_word() {
   return pos_ < words_.size() ? words_[pos_++] : 0u;
 }
 
-static std::atomic<int> g_narrow_limit{32767};
-void set_narrow_limit(int lim) { g_narrow_limit.store(lim <= 0 || lim > 32767 ? 32767 : lim); }
-int narrow_limit() { return g_narrow_limit.load(std::memory_order_relaxed); }
-
 template <class I, class S>
-bool RansDecoderState::decode(const I* indexes, int64_t n, const CdfTables& t, S* out) {
+bool RansDecoderState::decode(const I* indexes, int64_t n, const CdfTables& t, S* out, int nlim) {
   constexpr uint64_t mask = (1ull << PRECISION) - 1;
   constexpr int SHIFT = PRECISION - CdfTables::LUT_BITS;
   const int32_t* len = t.length.data();
@@ -173,7 +168,7 @@ bool RansDecoderState::decode(const I* indexes, int64_t n, const CdfTables& t, S
   const int32_t* cdfs = t.cdf.data();
   const CdfTables::Dom* dom = t.dom.data();
   const int stride = t.stride;
-  const int32_t nhi = sizeof(S) < sizeof(int32_t) ? (int32_t)narrow_limit() : 0;  // the narrow range
+  const int32_t nhi = sizeof(S) < sizeof(int32_t) ? (int32_t)nlim : 0;  // the narrow range
   uint64_t state = state_;
   for (int64_t i = 0; i < n; ++i) {
     const int32_t ci = (int32_t)indexes[i];
@@ -238,18 +233,18 @@ bool RansDecoderState::decode(const I* indexes, int64_t n, const CdfTables& t, S
   state_ = state;
   return true;
 }
-template bool RansDecoderState::decode<int32_t, int32_t>(const int32_t*, int64_t, const CdfTables&, int32_t*);
+template bool RansDecoderState::decode<int32_t, int32_t>(const int32_t*, int64_t, const CdfTables&, int32_t*, int);
 
 bool rans_decode_piece(RansDecoderState& d, const uint8_t* indexes, int64_t n, const CdfTables& t, int16_t* s16,
-                       int32_t* s32) {
+                       int32_t* s32, int nlim) {
   const RansDecoderState::Mark m = d.mark();
-  if (d.decode(indexes, n, t, s16)) return true;
+  if (d.decode(indexes, n, t, s16, nlim)) return true;
   d.reset(m);
   d.decode(indexes, n, t, s32);
   return false;
 }
-template bool RansDecoderState::decode<uint8_t, int32_t>(const uint8_t*, int64_t, const CdfTables&, int32_t*);
-template bool RansDecoderState::decode<uint8_t, int16_t>(const uint8_t*, int64_t, const CdfTables&, int16_t*);
+template bool RansDecoderState::decode<uint8_t, int32_t>(const uint8_t*, int64_t, const CdfTables&, int32_t*, int);
+template bool RansDecoderState::decode<uint8_t, int16_t>(const uint8_t*, int64_t, const CdfTables&, int16_t*, int);
 
 void CdfTables::prepare() {
   enc.assign((size_t)n * stride, EncSym{~0ull, 1, 0, 0, 0});

@@ -186,6 +186,122 @@ def test_rans_narrow_decode_fallback(golden, limit):
     assert np.array_equal(entropy.rans_decode(data, idx8.astype(np.int32), cdf, length, offset), sym)
 
 
+# The kernel options (csrc/options.cpp): name -> (environment variable, default).  _effective restates each
+# option's rule: `o` is the value last given to mlic_set_kernel_option (-1: never set), the result is what
+# mlic_get_kernel_option must report.
+OPTIONS = {"x4_halo": ("MLIC_X4_HALO", 1), "x4_splitk": ("MLIC_X4_SPLITK", 0), "linatt_fused": ("MLIC_LINATT_FUSED", 1),
+           "dw_strip": ("MLIC_DW_STRIP", 1), "ep_half": ("MLIC_EP_HALF", 1), "chain_nj": ("MLIC_CHAIN_NJ", 1),
+           "dwpw2": ("MLIC_DWPW2", 2), "pw3": ("MLIC_PW3", 1), "narrow_limit": (None, 32767),
+           "image_io_path": (None, -1)}
+
+
+def _effective(name, o, environ):
+    var, default = OPTIONS[name]
+    env = default
+    if var is not None and var in environ:  # atoi
+        m = re.match(r"\s*[+-]?\d+", environ[var])
+        env = int(m.group()) if m else 0
+    if name == "x4_halo":
+        return (0 if o == 0 else 2) if o >= 0 else env
+    if name in ("x4_splitk", "linatt_fused", "dw_strip", "ep_half"):
+        return int(o != 0) if o >= 0 else int(env != 0)
+    if name == "chain_nj":
+        return 2 if (o if o > 0 else env) == 2 else 1
+    if name == "narrow_limit":
+        return 32767 if o <= 0 or o > 32767 else o
+    return o if o >= 0 else env  # dwpw2, pw3, image_io_path
+
+
+def _get_option(name):
+    v = C.c_int(-99)
+    _lib.call("mlic_get_kernel_option", name.encode(), C.byref(v))
+    return v.value
+
+
+@pytest.mark.parametrize("name", sorted(OPTIONS))
+def test_kernel_option_default_set_and_revert(name):
+    revert = 0 if name == "narrow_limit" else -1
+    default = _effective(name, -1, os.environ)
+    if OPTIONS[name][0] is None or OPTIONS[name][0] not in os.environ:
+        assert default == OPTIONS[name][1]
+    assert _get_option(name) == default
+    try:
+        for v in (-1, 0, 1, 2, 3) + ((40, 40000) if name == "narrow_limit" else ()):
+            if name == "image_io_path" and v == 3:  # out of range: refused, the 2 stays
+                with pytest.raises(_lib.MlicError):
+                    _lib.call("mlic_set_kernel_option", name.encode(), v)
+                assert _get_option(name) == 2
+                continue
+            _lib.call("mlic_set_kernel_option", name.encode(), v)
+            assert _get_option(name) == _effective(name, v, os.environ), v
+    finally:
+        _lib.call("mlic_set_kernel_option", name.encode(), revert)
+    assert _get_option(name) == default
+
+
+def test_kernel_option_errors_change_nothing():
+    try:
+        _lib.call("mlic_set_kernel_option", b"image_io_path", 1)
+        for bad in (3, -2):
+            with pytest.raises(_lib.MlicError, match=r"mlic: image_io_path must be -1 \(by layout\), 0, 1 or 2"):
+                _lib.call("mlic_set_kernel_option", b"image_io_path", bad)
+            assert _get_option("image_io_path") == 1
+    finally:
+        _lib.call("mlic_set_kernel_option", b"image_io_path", -1)
+    before = {n: _get_option(n) for n in OPTIONS}
+    with pytest.raises(_lib.MlicError, match="mlic: unknown kernel option x4_hallo"):
+        _lib.call("mlic_set_kernel_option", b"x4_hallo", 1)
+    with pytest.raises(_lib.MlicError, match="mlic: unknown kernel option x4_hallo"):
+        _get_option("x4_hallo")
+    assert {n: _get_option(n) for n in OPTIONS} == before
+
+
+# a fresh process per case (this one has read its environment already), on ctypes alone: the getter's values
+# as the process starts, then after each (name, value) set
+_OPTION_CHILD = """
+import ctypes as C, json, sys
+lib = C.CDLL(sys.argv[1])
+def get(n):
+    v = C.c_int(-99)
+    assert lib.mlic_get_kernel_option(n.encode(), C.byref(v)) == 0
+    return v.value
+out = {"start": {n: get(n) for n in json.loads(sys.argv[2])}, "steps": []}
+for n, v in json.loads(sys.argv[3]):
+    assert lib.mlic_set_kernel_option(n.encode(), C.c_int(v)) == 0
+    out["steps"].append(get(n))
+print(json.dumps(out))
+"""
+
+
+@pytest.mark.parametrize("var,value,name,sets", [
+    ("MLIC_CHAIN_NJ", "2", "chain_nj", (1, -1, 1, 0, 3, -1)),
+    ("MLIC_X4_HALO", "0", "x4_halo", (1, -1, 0, -1)),
+    ("MLIC_X4_HALO", "2", "x4_halo", (0, -1, 1, -1)),
+    ("MLIC_EP_HALF", "0", "ep_half", (1, -1, 0, -1)),
+    ("MLIC_DWPW2", "0", "dwpw2", (2, -1, 1, -1)),
+    ("MLIC_X4_SPLITK", "1", "x4_splitk", (0, -1, 1, -1)),
+    ("MLIC_LINATT_FUSED", "0", "linatt_fused", (1, -1)),
+    ("MLIC_DW_STRIP", "0", "dw_strip", (1, -1)),
+    ("MLIC_PW3", "2", "pw3", (0, -1)),
+])
+def test_kernel_option_environment_fallback(var, value, name, sets):
+    """An option starts at its environment variable, a set overrides the variable, and -1 (for chain_nj 0 as
+    well) returns to the variable, not to the built-in default; the other options keep their defaults."""
+    import json
+    import subprocess
+    import sys
+    environ = {k: v for k, v in os.environ.items() if k not in {e for e, _ in OPTIONS.values()}}
+    environ[var] = value
+    r = subprocess.run([sys.executable, "-c", _OPTION_CHILD, _lib.LIB_PATH, json.dumps(sorted(OPTIONS)),
+                        json.dumps([(name, v) for v in sets])], env=environ, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    out = json.loads(r.stdout)
+    assert out["start"] == {n: _effective(n, -1, environ) for n in OPTIONS}
+    assert out["start"][name] != OPTIONS[name][1]  # the case's variable moves its option off the default
+    assert out["steps"] == [_effective(name, v, environ) for v in sets]
+    assert out["steps"][-1] == out["start"][name]
+
+
 def test_rans_empty_stream(golden):
     cdf, length, offset = _gc_tables(golden)
     data = entropy.rans_encode(np.zeros(0, np.int32), np.zeros(0, np.int32), cdf, length, offset)
