@@ -209,6 +209,48 @@ int mlic_image_ms_ssim_u8(void* stream, const float* a, const int64_t* a_strides
                           const int64_t* b_strides, int B, int C, int H, int W, void* scratch,
                           size_t scratch_bytes, double* out, double* terms);
 
+/* ---- LPIPS-VGG: lpips.LPIPS(net="vgg", version="0.1")(a/255, b/255, normalize=True) in eval mode, restated in
+ * DESIGN.md §3, of two [B][3][H][W] fp32 images in [0,1] made uint8-valued as mlic_image_sq_err_u8 does ----
+ *
+ * create: the weights as device fp32 tensors in the table form of mlic_create.  13 conv weights [Cout][Cin][3][3]
+ * and 13 biases, matched by the vgg16().features index that ends their name ("net.slice1.0.weight" and
+ * "0.weight" are the same tensor; indices 0 2 5 7 10 12 14 17 19 21 24 26 28); five "lin{k}.model.1.weight"
+ * [1][C][1][1] ("lins.*" duplicates are ignored); optionally "scaling_layer.shift" and "scaling_layer.scale"
+ * [1][3][1][1] (default: the package's constants).  A missing tensor, an extra conv tensor or any other
+ * unexpected name, and a mis-shaped tensor are refused, each with a message naming the tensor.  The weights are
+ * packed once; the caller's tensors are not referenced after the call returns.  A handle serves one call at a
+ * time. */
+typedef struct mlic_lpips mlic_lpips;
+int mlic_lpips_create(int n, const char* const* names, const float* const* ptrs, const int64_t* shapes,
+                      const int* ndims, void* stream, mlic_lpips** out);
+int mlic_lpips_destroy(mlic_lpips* h);
+/* the dense convs' kernel family: 2 = split-fp16 conv_x4 (default), 0 = the fp32 MFMA conv */
+int mlic_lpips_set_precision(mlic_lpips* h, int precision);
+/* bytes of device scratch mlic_image_lpips_u8 needs; host logic only, no GPU touched; nonzero rc with a message
+ * when B < 1, H or W < 16, or H * W > 2^23.  The B pairs are processed in chunks sized so that the scratch stays
+ * under 4 GiB (one 1920x1088 pair needs about 3.5 GiB; a single pair above 4 GiB is its own chunk), so the
+ * need grows with B only up to that cap.  It depends on the kernel options in force (x4_splitk). */
+int mlic_lpips_scratch_bytes(int B, int H, int W, size_t* bytes);
+/* per-pair LPIPS; element strides {image, channel, row} per operand (column stride 1), so a crop of a padded
+ * x_hat is scored in place; out: B doubles (device); terms: optional B*5 doubles (device), the five taps'
+ * terms whose sum (in tap order) is the value.  Checked before any GPU call, each with its own message: null
+ * handle; B < 1; H or W < 16; null images; scratch too small or not 256-byte aligned; null out.  Nothing outside
+ * scratch[0, bytes), out and terms is written, and no scratch element is read that this call did not write.
+ * Identical operands give exactly 0.  Bit-reproducible, and independent of B and of the chunking.
+ * fp16 range guard: at precision 2 the call waits for `stream` once to read the guard's flag; when an operand of
+ * a dense conv left fp16's range (|v| >= 65520) the WHOLE call runs again with the fp32 MFMA convs and is
+ * counted, so in such a call the images that did not overflow also carry the fp32 family's bits (which may
+ * differ from their split-fp16 result within the accuracy gate).  At precision 0 the call is asynchronous. */
+int mlic_image_lpips_u8(mlic_lpips* h, void* stream, const float* a, const int64_t* a_strides, const float* b,
+                        const int64_t* b_strides, int B, int H, int W, void* scratch, size_t scratch_bytes,
+                        double* out, double* terms);
+/* stage timing (tools/lpips_bench.py): ms3 (optional, 3 doubles) = device-event milliseconds of {the stem, the
+ * twelve dense convs with their operand packs, the tap launches with the reduce} summed over the calls since the
+ * last read, then cleared; `on` switches the timing for the calls that follow (a timed call waits for `stream`) */
+int mlic_lpips_profile(mlic_lpips* h, int on, double* ms3);
+/* calls that were re-run in fp32 by the range guard since the last reset */
+int mlic_lpips_range_fallbacks(mlic_lpips* h, int64_t* count, int reset);
+
 /* ---- uint8 images in, file bytes out, uint8 images back (utils/testing.py:338-424, submit/decode.py) ----
  *
  * ingest: B images of H x W x 3 bytes (device), read in place through element strides {image, row, column,

@@ -76,6 +76,13 @@ def _sig(lib):
         "mlic_image_sq_err_u8": [p, p, p, i, i64, p],
         "mlic_ms_ssim_scratch_bytes": [i, i, i, i, P(sz)],
         "mlic_image_ms_ssim_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, sz, p, p],
+        "mlic_lpips_create": [i, P(C.c_char_p), P(p), P(i64), P(i), p, P(p)],
+        "mlic_lpips_destroy": [p],
+        "mlic_lpips_set_precision": [p, i],
+        "mlic_lpips_scratch_bytes": [i, i, i, P(sz)],
+        "mlic_image_lpips_u8": [p, p, p, P(i64), p, P(i64), i, i, i, p, sz, p, p],
+        "mlic_lpips_range_fallbacks": [p, P(i64), i],
+        "mlic_lpips_profile": [p, i, P(C.c_double)],
         "mlic_image_ingest_u8": [p, p, P(i64), i, i, i, p, i, i],
         "mlic_image_egress_u8": [p, p, P(i64), i, i, i, p, P(i64), p, P(i64), p],
         "mlic_image_blur3_pad": [p, p, p, i, i, i, i, i, p, p],

@@ -26,6 +26,10 @@ struct mlic_model {
   int enc_passes = 0;                        // filter passes of the last encode
 };
 
+struct mlic_lpips {
+  Lpips* impl = nullptr;
+};
+
 static thread_local std::string g_err;
 
 template <class F>
@@ -629,6 +633,73 @@ int mlic_image_ms_ssim_u8(void* stream, const float* a, const int64_t* a_strides
     MLIC_CHECK(scratch != nullptr && scratch_bytes >= need, "ms_ssim: scratch too small (mlic_ms_ssim_scratch_bytes)");
     MLIC_CHECK(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, "ms_ssim: scratch must be 8-byte aligned");
     ms_ssim_u8(a, a_strides, b, b_strides, B, C, H, W, scratch, out, terms, (hipStream_t)stream);
+  });
+}
+
+int mlic_lpips_create(int n, const char* const* names, const float* const* ptrs, const int64_t* shapes,
+                      const int* ndims, void* stream, mlic_lpips** out) {
+  return guard([&] {
+    MLIC_CHECK(out != nullptr, "lpips_create: null out");
+    *out = nullptr;
+    auto* h = new mlic_lpips();
+    try {
+      h->impl = lpips_create(n, names, ptrs, shapes, ndims, (hipStream_t)stream);
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+  });
+}
+
+int mlic_lpips_destroy(mlic_lpips* h) {
+  return guard([&] {
+    if (!h) return;
+    lpips_destroy(h->impl);
+    delete h;
+  });
+}
+
+int mlic_lpips_set_precision(mlic_lpips* h, int precision) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_lpips handle");
+    lpips_set_precision(h->impl, precision);
+  });
+}
+
+int mlic_lpips_scratch_bytes(int B, int H, int W, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr, "lpips_scratch_bytes: null bytes");
+    *bytes = lpips_scratch_bytes(B, H, W);
+  });
+}
+
+int mlic_image_lpips_u8(mlic_lpips* h, void* stream, const float* a, const int64_t* a_strides, const float* b,
+                        const int64_t* b_strides, int B, int H, int W, void* scratch, size_t scratch_bytes,
+                        double* out, double* terms) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_lpips handle");
+    const size_t need = lpips_scratch_bytes(B, H, W);  // checks B, H, W
+    MLIC_CHECK(a && b && a_strides && b_strides, "lpips: null image or strides");
+    MLIC_CHECK(scratch != nullptr && scratch_bytes >= need, "lpips: scratch too small (mlic_lpips_scratch_bytes)");
+    MLIC_CHECK(reinterpret_cast<uintptr_t>(scratch) % 256 == 0, "lpips: scratch must be 256-byte aligned");
+    MLIC_CHECK(out != nullptr, "lpips: null out");
+    lpips_u8(h->impl, a, a_strides, b, b_strides, B, H, W, scratch, out, terms, (hipStream_t)stream);
+  });
+}
+
+int mlic_lpips_profile(mlic_lpips* h, int on, double* ms3) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_lpips handle");
+    lpips_profile(h->impl, on != 0, ms3);
+  });
+}
+
+int mlic_lpips_range_fallbacks(mlic_lpips* h, int64_t* count, int reset) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_lpips handle");
+    const int64_t v = lpips_range_fallbacks(h->impl, reset != 0);
+    if (count) *count = v;
   });
 }
 

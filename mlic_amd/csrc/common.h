@@ -59,6 +59,7 @@ enum Epi : int {
   EPI_RES = 64,        // v = v + res[c,p]          (residual add, last)
   EPI_SHUFFLE = 128,   // store through PixelShuffle(2): out[c/4, 2h+(c%4)/2, 2w+c%2]
   EPI_SQUARE_IN = 256, // B operand is x*x (GDN's conv2d(x**2, gamma, beta))
+  EPI_RELU_IN = 512,   // B operand is max(x, 0): the producing layer's ReLU rides on x4's operand pack (x4 only)
 };
 
 constexpr int MAXSEG = 6;

@@ -82,6 +82,8 @@ void conv_run(int impl, const ConvParams& P0, const ConvWeights& w, hipStream_t 
   const bool split = impl == CONV_X3 || impl == CONV_X3V2 || impl == CONV_PW || impl == CONV_HALO || impl == CONV_X4 ||
                      impl == CONV_X4H;
   P.wexp = split ? w.wexp : 0;
+  MLIC_CHECK(!(P.epi & EPI_RELU_IN) || impl == CONV_X4 || impl == CONV_X4H,
+             "EPI_RELU_IN: only x4's operand pack applies it");
   switch (impl) {
     case CONV_F32: conv_forward(P, st); break;
     case CONV_X3: conv_f16x3_forward(P, w.wh, w.wl, w.cin_pad, st); break;

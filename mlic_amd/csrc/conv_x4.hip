@@ -610,6 +610,7 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
 struct X4Pack {
   Seg seg[MAXSEG];
   int nseg, Cin, H, W, pad, nchunk, square, npix;  // npix: real pixels (K = 1 folds H*W into rows of 32)
+  int relu;  // EPI_RELU_IN: the operand is max(x, 0) of the stored pre-activation (NaN kept)
   int hi;  // reduced-precision layout: [hi of channels 0-31 | hi of channels 32-63] per 64-channel chunk
   _Float16* dst;
   int* rflag;
@@ -637,6 +638,7 @@ __global__ __launch_bounds__(256) void x4_pack_act_kernel(X4Pack Q) {
       const bool ok = inb && ch0 + j < Q.Cin && ch0 - c0 + j < sg.C;
       v[j] = ok ? src[(int64_t)j * HW] : 0.0f;
       if (Q.square) v[j] *= v[j];
+      if (Q.relu) v[j] = v[j] < 0.0f ? 0.0f : v[j];
       bad |= f16_unsafe(v[j]);
     }
   };
@@ -889,6 +891,7 @@ void x4_pack_act(const ConvParams& P, int cin_pad, _Float16* dst, hipStream_t st
   Q.nchunk = x4_nchunk(cin_pad, hi);
   Q.hi = hi ? 1 : 0;
   Q.square = (P.epi & EPI_SQUARE_IN) ? 1 : 0;
+  Q.relu = (P.epi & EPI_RELU_IN) ? 1 : 0;
   Q.dst = dst;
   Q.rflag = P.rflag;
   const int npos = (Q.H + 2 * Q.pad) * (Q.W + 2 * Q.pad);
@@ -937,7 +940,7 @@ static bool x4_halo(const ConvParams& P, bool hi) {
 
 // $MLIC_X4_DIRECT=0: 1x1 layers read the packed copy too (A/B switch)
 bool x4_direct_ok(const ConvParams& P, bool hi) {
-  return opt(OPT_X4_DIRECT) && P.K == 1 && !hi && !(P.epi & EPI_SQUARE_IN) && x4_rs();
+  return opt(OPT_X4_DIRECT) && P.K == 1 && !hi && !(P.epi & (EPI_SQUARE_IN | EPI_RELU_IN)) && x4_rs();
 }
 
 template <int K, int BM>
@@ -1005,7 +1008,7 @@ void conv_x4_forward(const ConvParams& P, const _Float16* act, const _Float16* w
   // otherwise they are not read: the packed copy (x4_pack_act) is
   MLIC_CHECK(conv_x4_ok(P, cin_pad) && wx && (act || x4_direct_ok(P, hi)), "conv_x4: unsupported shape");
   ConvParams Q = P;
-  if (act) Q.epi &= ~EPI_SQUARE_IN;
+  if (act) Q.epi &= ~(EPI_SQUARE_IN | EPI_RELU_IN);
   const int nchunk = x4_nchunk(cin_pad, hi);
   const int bm = x4_bm(P.Cout);
   const int nsplit = part ? x4_splitk(P, cin_pad, hi) : 1;

@@ -249,6 +249,24 @@ void neglog2_sum(const float* lik, int64_t n_per, int B, double* out, double* pa
 size_t ms_ssim_scratch_bytes(int B, int C, int H, int W);
 void ms_ssim_u8(const float* a, const int64_t* a_strides, const float* b, const int64_t* b_strides, int B, int C,
                 int H, int W, void* scratch, double* out, double* terms, hipStream_t st);
+// LPIPS-VGG of uint8-valued images (lpips.hip; the definition in DESIGN.md §3).  The handle owns the packed
+// weights (13 convs, 5 lin layers, the scaling layer), the fp16 range flag and its fallback counter; it serves
+// one call at a time.  a, b [B][3][H][W] fp32 with element strides {image, channel, row}; out B doubles, terms
+// (optional) [B][5] doubles.  lpips_scratch_bytes is host logic only and throws on B < 1, H or W < 16.  At
+// precision 2 lpips_u8 waits for the stream once (it reads the range flag) and, when an operand of a dense conv
+// left fp16's range, runs the whole call again with the fp32 MFMA convs and counts it.
+class Lpips;
+Lpips* lpips_create(int n, const char* const* names, const float* const* ptrs, const int64_t* shapes,
+                    const int* ndims, hipStream_t st);
+void lpips_destroy(Lpips* h);
+void lpips_set_precision(Lpips* h, int precision);
+size_t lpips_scratch_bytes(int B, int H, int W);
+void lpips_u8(Lpips* h, const float* a, const int64_t* a_strides, const float* b, const int64_t* b_strides, int B,
+              int H, int W, void* scratch, double* out, double* terms, hipStream_t st);
+int64_t lpips_range_fallbacks(Lpips* h, bool reset);
+// stage timing with device events: ms3 (optional) = {stem, dense convs, taps + reduce} summed over the calls since
+// the last read, then cleared; `on` switches it for the calls that follow (a timed call waits for its stream)
+void lpips_profile(Lpips* h, bool on, double* ms3);
 // uint8 image I/O (image_io.hip).  Both check their arguments before any HIP call and throw.
 // ingest: B images of H x W x 3 bytes read through element strides {image, row, column, channel} -> dst fp32
 // [B][3][Hp][Wp] contiguous (Hp, Wp multiples of 64), v / 255 inside the image and +0 in the padding.
