@@ -86,7 +86,7 @@ int mlic_decompress_v(mlic_model* m, void* stream, const uint8_t* const* y, cons
                       const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz, float* x_hat,
                       const float* vbr_scales);
 
-/* module-level entry points (tests / profiling): which = local|chan|inter|intra|epa|epn|lrpn|g_a|h_a|h_s|g_s|rbu|rbws */
+/* module-level entry points (tests / profiling): which = local|chan|inter|intra|epa|epn|lrpa|lrpn|g_a|h_a|h_s|g_s|rbu|rbws */
 int mlic_run_module(mlic_model* m, void* stream, const char* which, int idx, const float* in0, const float* in1,
                     int B, int Cin, int H, int W, float* out);
 int mlic_workspace_bytes(mlic_model* m, size_t* arena, size_t* weights);
@@ -128,7 +128,17 @@ int mlic_set_poison(mlic_model* m, int on);
  * (-1 default = $MLIC_EP_HALF or on; 0 = the whole grid: the same bits at every pixel that is read);
  * "image_io_path" = the form of the uint8 ingest / egress kernels (-1 default = by the byte image's strides;
  * 0 = the general-stride form, 1 = the interleaved HWC form, 2 = the planar CHW form; a forced form that the
- * strides do not fit is refused) -- every form gives the same bits */
+ * strides do not fit is refused) -- every form gives the same bits.  Three switches for work whose result
+ * nobody reads (the first two off by default: they did not move the benchmark beyond its spread): "lrp_half" = the LRP head (last
+ * depthwise + point conv with 0.5 tanh, checkerboard mask and the residual into y_hat) on its phase's
+ * checkerboard half only (-1 default = $MLIC_LRP_HALF or 0 = the whole grid; the same bits, except that under
+ * 1 a residual of -0.0 at a masked pixel stays -0.0 instead of becoming +0.0); "intra_half" = the intra context
+ * reads its masked inputs through the resident 1x1's input mask instead of two masked copies and, where its
+ * consumer runs on the non-anchor half ("ep_half"), runs its last depthwise + 1x1 on that half (-1 default =
+ * $MLIC_INTRA_HALF or 0 = the copies and the whole grid; 2 = as 1, and mlic_run_module("intra") takes the half
+ * tail too: only its non-anchor pixels are then defined); "gdn_skip" = g_a's first 1x1 stride-2 skip conv
+ * (3 -> N) computed inside the GDN launch that adds it, where "pw3" serves that launch (-1 default =
+ * $MLIC_GDN_SKIP or on; 0 = its own launch; the same bits) */
 int mlic_set_kernel_option(const char* name, int value);
 /* the effective value of a mlic_set_kernel_option name as the next call would see it, after the
  * option's own rule: what was set, else the environment, else the default ("x4_halo": 0 off, 1 = 5 x 5

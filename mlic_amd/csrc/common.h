@@ -89,6 +89,19 @@ struct ConvParams {
   int64_t res_bs;
   int B;
   int* rflag;             // fp16 range guard of the split-fp16 paths (range_check), or null
+  // pw_resident_kernel only (pw_resident_ok), checkerboard parity 1 = anchor ((y + x) odd), 2 = non-anchor:
+  int in_mask;            // the input is read as 0.0f at the pixels of the other parity (a ckbd_mask copy, not made)
+  int scatter;            // the input planes hold that parity's pixels squeezed (H x W = the squeezed grid, pixel
+                          // (y, q)); out / res (channel stride out_cs = the full plane) are addressed at the
+                          // full-grid pixel of (y, q), the other half is neither read nor written
+  // dwpw3_kernel's pointwise GDN only (pw3_ok): the residual is not loaded but computed, ResidualBlockWithStride's
+  // 1x1 stride-2 skip conv of the block input: res[co](y, x) = sum over c in order of fma(skx[c](2y, 2x), skw[c][co])
+  // from 0, + skb[co] (conv1x1_smallcin_kernel's sequence); skx = null: no such residual
+  const float* skx;       // [B][sk_cin][sk_H][sk_W], batch stride skx_bs
+  int64_t skx_bs;
+  int sk_cin, sk_H, sk_W; // sk_cin = 3 (pw3_ok); Ho = (sk_H - 1) / 2 + 1, Wo likewise
+  const float* skw;       // packed [sk_cin][Cout]
+  const float* skb;       // [Cout]
 };
 
 // device helpers -----------------------------------------------------------------------------

@@ -22,6 +22,9 @@ static bool x4_k_on(int K) {
 // whatever batch either side runs (a stream coded in a batch of 8 decodes alone).  The grid-fill
 // thresholds are per image, sized for the bench's batches (8 per lane).
 int conv_select(const ConvParams& P, const ConvWeights& w, int precision) {
+  // the masked-input / scattering forms exist on the resident kernel only; the model builds them where this
+  // function chose CONV_PW for the layer's plain whole-grid form (the same family, so the same bits)
+  if (P.in_mask || P.scatter) return CONV_PW;
   if (conv_smallcin_ok(P)) return CONV_SMALLCIN;  // exact fp32 VALU, all precisions
   if (conv_narrow_ok(P)) return CONV_NARROW;      // exact fp32 VALU, all precisions
   if (precision == 0 || !w.wh) return CONV_F32;

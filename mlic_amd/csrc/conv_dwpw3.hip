@@ -131,7 +131,13 @@ __device__ __forceinline__ void d3_neighbours_k(int k, float e, float v, float& 
 // MODE: 0 = bias only, 1 = GELU (dwpw_kernel's modes), 2 = GDN, 3 = IGDN (pw_resident's: x * rsqrt(v),
 // x * sqrt(v), the aux operand x = the conv input); RES: residual add last.  PW: the pointwise conv
 // alone (no depthwise; MODE 2 / 3 convolve x * x) -- the full-resolution GDN / IGDN of g_a / g_s
-template <int N, int MODE, bool RES, bool PW = false>
+// SKIP (PW, MODE 2, RES): the residual is ResidualBlockWithStride's 1x1 stride-2 skip conv of the block input,
+// computed here (ConvParams::skx ..) instead of loaded: the lane reads the input image's 3 channels at (2y, 2x)
+// -- three dword loads in place of sixteen -- and forms each of its 16 channels by conv1x1_smallcin_kernel's
+// sequence (v = 0, fma per input channel in order, + bias) from weights and bias held in LDS beside the
+// pointwise bias.  The skip conv's launch, its full-resolution write and this kernel's read of it are gone.
+// SKIP = the skip conv's Cin (3: the image; 0 = no computed residual).
+template <int N, int MODE, bool RES, bool PW = false, int SKIP = 0>
 __global__ __launch_bounds__(N / 16 * 64) void dwpw3_kernel(ConvParams P, int R, const _Float16* __restrict__ wh,
                                                            const _Float16* __restrict__ wl, int cin_pad,
                                                            const float* __restrict__ dww,
@@ -141,8 +147,10 @@ __global__ __launch_bounds__(N / 16 * 64) void dwpw3_kernel(ConvParams P, int R,
   constexpr int AB = KS * 4096;   // one A image: [ks][block][hi / lo][1 KB]
   constexpr int NBUF = MLIC_D3_NBUF;
   constexpr int AIMG0 = 0, CTR0 = NBUF * AB, BIAS0 = CTR0 + 2 * NBUF * 4;
-  constexpr int LDS = BIAS0 + N * 4;
+  constexpr int SKW0 = BIAS0 + N * 4;  // SKIP: skip weights [SKIP][N], then the skip bias [N]
+  constexpr int LDS = SKW0 + (SKIP ? (SKIP + 1) * N * 4 : 0);
   static_assert(LDS <= 160 * 1024, "dwpw3: LDS");
+  static_assert(!SKIP || (PW && MODE == 2 && RES), "dwpw3: the computed residual is the pointwise GDN's");
   static_assert(MLIC_D3_ASYNC || NBUF == 2, "dwpw3: the barrier form alternates two A images");
   __shared__ __attribute__((aligned(16))) char sm[LDS];
   float* sbias = reinterpret_cast<float*>(sm + BIAS0);
@@ -156,6 +164,11 @@ __global__ __launch_bounds__(N / 16 * 64) void dwpw3_kernel(ConvParams P, int R,
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   for (int r = tid; r < N; r += blockDim.x) sbias[r] = P.bias ? P.bias[r] : 0.0f;
+  float* sskw = reinterpret_cast<float*>(sm + SKW0);
+  if constexpr (SKIP) {
+    for (int r = tid; r < SKIP * N; r += blockDim.x) sskw[r] = P.skw[r];
+    for (int r = tid; r < N; r += blockDim.x) sskw[SKIP * N + r] = P.skb[r];
+  }
 
   const int H = P.H, W = P.W, HW = H * W;
   const int nseg = (W + D3_TC - 1) / D3_TC;
@@ -480,7 +493,11 @@ __global__ __launch_bounds__(N / 16 * 64) void dwpw3_kernel(ConvParams P, int R,
     // stores / loads at an offset past the end (dropped / 0) -- no exec-masked memory operations beside
     // the MFMAs (dwpw2's masked residual loads there gave wrong results in some rows)
     const auto rs_o = d3_rsrc(P.out + (int64_t)b * P.out_bs + (int64_t)(32 * cw) * HW, 32u * hw4);
-    const auto rs_r = RES ? d3_rsrc(P.res + (int64_t)b * P.res_bs + (int64_t)(32 * cw) * HW, 32u * hw4) : rs_o;
+    const auto rs_r =
+        RES && SKIP == 0 ? d3_rsrc(P.res + (int64_t)b * P.res_bs + (int64_t)(32 * cw) * HW, 32u * hw4) : rs_o;
+    // SKIP: image b of the block input, its SKIP planes
+    const uint32_t shw4 = SKIP ? (uint32_t)(P.sk_H * P.sk_W) * 4u : 0u;
+    const auto rs_s = SKIP ? d3_rsrc(P.skx + (int64_t)b * P.skx_bs, (uint32_t)SKIP * shw4) : rs_o;
     constexpr bool GDN = MODE == 2 || MODE == 3;
     const auto rs_x = GDN ? d3_rsrc(P.aux + (int64_t)b * P.aux_bs + (int64_t)(32 * cw) * HW, 32u * hw4) : rs_o;
 #if !MLIC_D3_ASYNC
@@ -510,7 +527,17 @@ __global__ __launch_bounds__(N / 16 * 64) void dwpw3_kernel(ConvParams P, int R,
             so += (q & 3) == 3 ? 5u * hw4 : hw4;
           }
         }
-        if constexpr (RES) {
+        float xs[SKIP ? SKIP : 1];  // SKIP: the block input's channels at (2 y, 2 px)
+        if constexpr (SKIP != 0) {
+          const uint32_t vs = ok ? (uint32_t)(2 * y * P.sk_W + 2 * px) * 4u : 0x80000000u;
+          uint32_t so = 0;
+#pragma unroll
+          for (int c = 0; c < SKIP; ++c) {
+            asm volatile("" : "+s"(so));
+            xs[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_s, vs, so, 0));
+            so += shw4;
+          }
+        } else if constexpr (RES) {
           uint32_t so = 0;
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
@@ -552,6 +579,27 @@ __global__ __launch_bounds__(N / 16 * 64) void dwpw3_kernel(ConvParams P, int R,
           const float4 b4 = *reinterpret_cast<const float4*>(sb + 8 * g);
           const float bq[4] = {b4.x, b4.y, b4.z, b4.w};
           if constexpr (GDN) {
+            if constexpr (SKIP != 0) {
+              // the skip conv's outputs of channels 32 cw + 8 g + 4 h .. + 3: v = 0, fma per input channel in
+              // order, then + bias (conv1x1_smallcin_kernel + conv_store with no prescale, no epilogue), on
+              // channel pairs as packed-fp32 VALU (element for element the scalar sequence)
+              const float* sw = sskw + 32 * cw + 4 * h + 8 * g;
+              const float4 kb = *reinterpret_cast<const float4*>(sw + SKIP * N);
+              mlic_float2 s01 = {0.0f, 0.0f}, s23 = {0.0f, 0.0f};
+#pragma unroll
+              for (int c = 0; c < SKIP; ++c) {
+                const float4 w4 = *reinterpret_cast<const float4*>(sw + c * N);
+                const mlic_float2 x2 = {xs[c], xs[c]};
+                s01 = __builtin_elementwise_fma(x2, mlic_float2{w4.x, w4.y}, s01);
+                s23 = __builtin_elementwise_fma(x2, mlic_float2{w4.z, w4.w}, s23);
+              }
+              s01 = s01 + mlic_float2{kb.x, kb.y};
+              s23 = s23 + mlic_float2{kb.z, kb.w};
+              xr[4 * g] = s01[0];
+              xr[4 * g + 1] = s01[1];
+              xr[4 * g + 2] = s23[0];
+              xr[4 * g + 3] = s23[1];
+            }
             // pw_resident's GDN epilogue: the range check on the pre-activation, x * rsqrt(v) / x * sqrt(v)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -712,15 +760,21 @@ bool pw3_ok(const ConvParams& P, int cin_pad) {
   if (P.Cin != P.Cout || (P.Cin != 96 && P.Cin != 128 && P.Cin != 160 && P.Cin != 192)) return false;
   if (P.Ho != P.H || P.Wo != P.W || P.out_cs != (int64_t)P.H * P.W) return false;
   if ((int64_t)P.Cin * P.H * P.W * 4 >= (1ll << 31)) return false;
+  if (P.skx) {  // the computed skip residual: the plain GDN of a stride-2 block, the image within a buffer's range
+    // (the instantiated input width is the image's 3 channels; another Cin <= 4 keeps the two launches)
+    if (mode != 2 || (P.epi & EPI_RES) || P.sk_cin != 3 || !P.skw || !P.skb) return false;
+    if (P.H != (P.sk_H - 1) / 2 + 1 || P.W != (P.sk_W - 1) / 2 + 1) return false;
+    if ((int64_t)P.sk_cin * P.sk_H * P.sk_W * 4 >= (1ll << 31)) return false;
+  }
   return true;
 }
-template <int N, int M, bool RS>
+template <int N, int M, bool RS, int SK = 0>
 static void launch_pw3(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, hipStream_t st) {
   const int R = d3_rows(P.B, P.H, P.W);
   const int64_t want = (int64_t)((P.W + D3_TC - 1) / D3_TC) * ((P.H + R - 1) / R) * P.B;
   const int64_t g = std::min<int64_t>(want, (int64_t)d3_num_cus());
   const dim3 grid((unsigned)((g + 7) / 8 * 8));
-  hipLaunchKernelGGL((dwpw3_kernel<N, M, RS, true>), grid, dim3(N / 16 * 64), 0, st, P, R, wh, wl, cin_pad,
+  hipLaunchKernelGGL((dwpw3_kernel<N, M, RS, true, SK>), grid, dim3(N / 16 * 64), 0, st, P, R, wh, wl, cin_pad,
                      (const float*)nullptr, (const float*)nullptr);
   HIP_OK(hipGetLastError());
 }
@@ -729,6 +783,7 @@ void pw3_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, in
   const int mode = pw3_mode(P), res = (P.epi & EPI_RES) ? 1 : 0;
 #define P3_RUN(NN)                                                                \
   if (P.Cin == NN) {                                                              \
+    if (P.skx) return launch_pw3<NN, 2, true, 3>(P, wh, wl, cin_pad, st);           \
     if (mode == 0 && !res) return launch_pw3<NN, 0, false>(P, wh, wl, cin_pad, st); \
     if (mode == 0 && res) return launch_pw3<NN, 0, true>(P, wh, wl, cin_pad, st);   \
     if (mode == 1 && !res) return launch_pw3<NN, 1, false>(P, wh, wl, cin_pad, st); \

@@ -54,7 +54,10 @@ constexpr int pw_apitch() { return CIN + 8; }  // halves; +16 B per row spreads 
 
 // MODE: 0 = bias only, 1 = GELU, 2 = GDN (x * rsqrt), 3 = IGDN (x * sqrt), 4 = 0.5 tanh + the
 // checkerboard mask of P.epi (the LRP head); residual add (RES) last
-template <int CIN, int CT, int MODE, bool RES>
+// XF (PW_XCOMBOS only): bit 0 = P.in_mask (the ring value is consumed as keep ? v : 0.0f, the bits a
+// ckbd_mask copy of the input gives), bit 1 = P.scatter (squeezed checkerboard-half input, output and
+// residual at that half's full-grid pixels); the k-loop and the epilogue's op order are the plain form's
+template <int CIN, int CT, int MODE, bool RES, int XF = 0>
 __global__ __launch_bounds__(PW_THREADS) void pw_resident_kernel(ConvParams P, const _Float16* __restrict__ wh,
                                                                   const _Float16* __restrict__ wl, int cin_pad) {
   constexpr int KS = CIN / 16;
@@ -149,6 +152,13 @@ __global__ __launch_bounds__(PW_THREADS) void pw_resident_kernel(ConvParams P, c
     const uint32_t voc = voff_of(tile);
     const auto rsn = rsrc_of(nt);
     const uint32_t von = voff_of(nt);
+    bool kin = true;  // XF & 1: this lane's pixel is of the parity P.in_mask keeps (stride 1)
+    if (XF & 1) {
+      const int bt = tile / tpi;
+      const int pt = min(((tile - bt * tpi) << 5) + l32, HW - 1);
+      const int yt = pt / P.Wo;
+      kin = is_anchor(yt, pt - yt * P.Wo) == (P.in_mask == 1);
+    }
 
     floatx16 acc[CT];
 #pragma unroll
@@ -164,6 +174,7 @@ __global__ __launch_bounds__(PW_THREADS) void pw_resident_kernel(ConvParams P, c
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         float v = ring[j % D][i];
+        if (XF & 1) v = kin ? v : 0.0f;
         if (square) v *= v;
         const _Float16 hv = (_Float16)v;
         bh[i] = hv;
@@ -212,7 +223,12 @@ __global__ __launch_bounds__(PW_THREADS) void pw_resident_kernel(ConvParams P, c
     const int b = tile / tpi;
     const int p = ((tile - b * tpi) << 5) + l32;
     const uint32_t cs4 = (uint32_t)P.out_cs * 4u;
-    const uint32_t vo_out = (uint32_t)p * 4u + (uint32_t)(4 * h) * cs4;
+    int pf = p;  // the output / residual pixel: under XF & 2 the full-grid pixel of squeezed pixel (y, q)
+    if (XF & 2) {
+      const int y = p / P.Wo, q = p - y * P.Wo;
+      pf = y * 2 * P.Wo + 2 * q + ((y + (P.scatter == 1 ? 1 : 0)) & 1);
+    }
+    const uint32_t vo_out = (uint32_t)pf * 4u + (uint32_t)(4 * h) * cs4;
     const auto rs_out = make_rsrc(P.out + (int64_t)b * P.out_bs, (uint32_t)P.Cout * cs4);
     constexpr bool gdn = MODE == 2 || MODE == 3, igdn = MODE == 3, gelu = MODE == 1, tanh_mask = MODE == 4;
     // checkerboard mask: keep v where this pixel's anchor-ness matches the flag (MODE 4 only)
@@ -336,6 +352,11 @@ static int pw_mode(const ConvParams& P) {
   X(32, 1, 0, 0) X(64, 2, 0, 0) X(32, 3, 0, 0)                                                    \
   /* global contexts: mlp.0 GELU (96 -> 128, 64 -> 128), mlp.4 + residual 128 -> 64, skip */      \
   X(96, 4, 1, 0) X(64, 4, 1, 0) X(128, 2, 0, 1) X(96, 2, 0, 0)
+// (CIN, CT, MODE, RES, XF): the intra context's queries.0 / keys.0 with the input parity mask; the LRP head
+// and the intra context's mlp.4 + residual from a squeezed half (slice_ch 32)
+#define PW_XCOMBOS(X) X(32, 1, 0, 0, 1) X(128, 1, 4, 1, 2) X(128, 2, 0, 1, 2)
+
+static int pw_xf(const ConvParams& P) { return (P.in_mask ? 1 : 0) | (P.scatter ? 2 : 0); }
 
 bool pw_resident_ok(const ConvParams& P, int cin_pad) {
   if (P.K != 1 || (P.stride != 1 && P.stride != 2) || P.pad != 0 || P.nseg != 1) return false;
@@ -349,6 +370,18 @@ bool pw_resident_ok(const ConvParams& P, int cin_pad) {
   if ((int64_t)P.Cin * HW * 4 >= (1ll << 31) || (int64_t)P.Cout * HW * 4 >= (1ll << 31)) return false;
   const int ct = (P.Cout + 31) / 32;
   const int res = (P.epi & EPI_RES) ? 1 : 0;
+  if (const int xf = pw_xf(P)) {
+    if (P.stride != 1 || (unsigned)P.in_mask > 2u || (unsigned)P.scatter > 2u) return false;
+    // scatter: every computed value is kept (no epilogue mask); out / res planes are the full grid
+    if (P.scatter && ((P.epi & (EPI_MASK_ANCHOR | EPI_MASK_NONANCHOR)) || P.out_cs != 2 * HW ||
+                      (int64_t)P.Cout * P.out_cs * 4 >= (1ll << 31)))
+      return false;
+#define MLIC_PW_XOK(CIN, CT, M, R, X) \
+  if (P.Cin == CIN && ct == CT && mode == M && res == R && xf == X) return true;
+    PW_XCOMBOS(MLIC_PW_XOK)
+#undef MLIC_PW_XOK
+    return false;
+  }
 #define MLIC_PW_OK(CIN, CT, M, R) \
   if (P.Cin == CIN && ct == CT && mode == M && res == R) return true;
   PW_COMBOS(MLIC_PW_OK)
@@ -356,21 +389,31 @@ bool pw_resident_ok(const ConvParams& P, int cin_pad) {
   return false;
 }
 
-template <int CIN, int CT, int M, bool R>
+template <int CIN, int CT, int M, bool R, int XF = 0>
 static void launch_pw(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, hipStream_t st) {
   const int64_t ntiles = (int64_t)((P.Ho * P.Wo + 31) / 32) * P.B;
   const int64_t want = (ntiles + PW_WAVES - 1) / PW_WAVES;
   const dim3 grid((unsigned)std::min<int64_t>(want, (int64_t)num_cus()));
-  hipLaunchKernelGGL((pw_resident_kernel<CIN, CT, M, R>), grid, dim3(PW_THREADS), 0, st, P, wh, wl, cin_pad);
+  hipLaunchKernelGGL((pw_resident_kernel<CIN, CT, M, R, XF>), grid, dim3(PW_THREADS), 0, st, P, wh, wl, cin_pad);
   HIP_OK(hipGetLastError());
 }
 
 void pw_resident_forward(const ConvParams& P, const _Float16* wh, const _Float16* wl, int cin_pad, hipStream_t st) {
   MLIC_CHECK(pw_resident_ok(P, cin_pad), "pw_resident: unsupported shape");
-  if (pw3_ok(P, cin_pad)) return pw3_forward(P, wh, wl, cin_pad, st);  // full-resolution GDN / IGDN
   const int mode = pw_mode(P);
   const int ct = (P.Cout + 31) / 32;
   const int res = (P.epi & EPI_RES) ? 1 : 0;
+  if (const int xf = pw_xf(P)) {
+#define MLIC_PW_XRUN(CIN, CT, M, R, X)                                 \
+  if (P.Cin == CIN && ct == CT && mode == M && res == R && xf == X) {  \
+    launch_pw<CIN, CT, M, R != 0, X>(P, wh, wl, cin_pad, st);          \
+    return;                                                            \
+  }
+    PW_XCOMBOS(MLIC_PW_XRUN)
+#undef MLIC_PW_XRUN
+  }
+  if (pw3_ok(P, cin_pad)) return pw3_forward(P, wh, wl, cin_pad, st);  // full-resolution GDN / IGDN
+  MLIC_CHECK(!P.skx, "pw_resident: the computed skip residual is pw3's");
 #define MLIC_PW_RUN(CIN, CT, M, R)                                  \
   if (P.Cin == CIN && ct == CT && mode == M && res == R) {          \
     launch_pw<CIN, CT, M, R != 0>(P, wh, wl, cin_pad, st);          \

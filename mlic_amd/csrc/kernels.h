@@ -138,8 +138,15 @@ struct DwParams {
   int64_t out_bs;
   int gelu;
   int B;
+  // checkerboard half (dw_half_ok): 0 = every pixel; 1 = the anchor pixels only ((y + x) odd), 2 = the
+  // non-anchor pixels only, written squeezed: planes of H x W / 2, pixel (y, x) at y * W / 2 + x / 2
+  // (LocalAttnParams::ckbd's layout); each value is the whole-grid form's, bit for bit
+  int ckbd;
 };
 void dw3x3(const DwParams& P, hipStream_t st);
+// shapes the half form serves (stride 1, W a multiple of 4 up to 256, 16-byte batch strides); base pointers
+// must be 16-byte aligned (checked at the launch, so the answer is the same in an arena's planning pass)
+bool dw_half_ok(const DwParams& P);
 
 void ln_channels(const float* x, int64_t x_bs, float* y, int64_t y_bs, const float* g, const float* b, int C,
                  int HW, int B, hipStream_t st);

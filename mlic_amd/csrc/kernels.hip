@@ -305,9 +305,105 @@ __global__ __launch_bounds__(64 * DWS_WAVES) void dw3x3_s1_strip_kernel(DwParams
   }
 }
 
+// checkerboard half of the stride-1 depthwise (DwParams::ckbd), in the strip form for planes of up to 64
+// float4 columns (the 1080p latent's 120-column rows: two strips per wave): a lane holds columns 4q .. 4q + 3 of
+// its strip's rows as above and computes, of each row y, the two columns of the wanted parity, 4q + e0 and
+// 4q + e0 + 2 with e0 = (y + [anchor]) & 1 -- the window columns are picked by a per-row select, so each output is
+// the whole-grid kernel's sum (acc = 0, taps row-major by fma, + bias [, GELU]) -- and stores them as one float2
+// at the squeezed position y * W / 2 + 2q.
+template <int R>
+__global__ __launch_bounds__(64 * DWS_WAVES) void dw3x3_s1_half_kernel(DwParams P, int nstrip) {
+  const int lane = threadIdx.x & 63;
+  const int W4 = P.W >> 2, spw = 64 / W4, Wq = P.W >> 1;
+  const int k = lane / W4, q = lane - k * W4;
+  const int64_t strip = ((int64_t)blockIdx.x * DWS_WAVES + (threadIdx.x >> 6)) * spw + k;
+  const int64_t nall = (int64_t)P.B * P.C * nstrip;
+  const bool live = k < spw && strip < nall;  // dead lanes still run (their DPP sources), never store
+  const int64_t st = live ? strip : 0;
+  const int plane = (int)(st / nstrip), si = (int)(st - (int64_t)plane * nstrip);
+  const int b = plane / P.C, c = plane - b * P.C;
+  int sg = 0, c0 = 0;
+  while (sg + 1 < P.nseg && c >= c0 + P.seg[sg].C) { c0 += P.seg[sg].C; ++sg; }
+  const float4* src = reinterpret_cast<const float4*>(P.seg[sg].p + (int64_t)b * P.seg[sg].bs +
+                                                      (int64_t)(c - c0) * P.H * P.W) + q;
+  const int y0 = si * R;
+  auto ld = [&](int y) {
+    return (live && y >= 0 && y < P.H) ? src[(int64_t)y * W4] : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  float w[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) w[t] = P.w[c * 9 + t];
+  const float bias = P.bias ? P.bias[c] : 0.0f;
+  float* dst = P.out + (int64_t)b * P.out_bs + (int64_t)c * P.H * Wq + 2 * q;
+  float4 rows[R + 2];
+#pragma unroll
+  for (int i = 0; i < R + 2; ++i) rows[i] = ld(y0 - 1 + i);
+  float win[3][6];
+  auto unpack = [&](const float4& v, float* d) {
+    const float l = dws_shr(v.w), r = dws_shl(v.x);
+    d[0] = q > 0 ? l : 0.0f;
+    d[1] = v.x; d[2] = v.y; d[3] = v.z; d[4] = v.w;
+    d[5] = q < W4 - 1 ? r : 0.0f;
+  };
+  unpack(rows[0], win[0]);
+  unpack(rows[1], win[1]);
+  const int par0 = (y0 + (P.ckbd == 1 ? 1 : 0)) & 1;  // e0 of the strip's first row
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    unpack(rows[r + 2], win[(r + 2) % 3]);
+    const bool odd = ((par0 + r) & 1) != 0;  // e0 = 1: columns 4q + 1, 4q + 3
+    float o[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      float acc = 0.0f;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const float* wr = win[(r + ky) % 3];
+          acc = fmaf(w[ky * 3 + kx], odd ? wr[2 * e + 1 + kx] : wr[2 * e + kx], acc);
+        }
+      float v = acc + bias;
+      if (P.gelu) v = gelu_epi(v);
+      o[e] = v;
+    }
+    const int oy = y0 + r;
+    if (live && oy < P.H) *reinterpret_cast<float2*>(dst + (int64_t)oy * Wq) = make_float2(o[0], o[1]);
+  }
+}
+
+bool dw_half_ok(const DwParams& P) {
+  bool ok = P.stride == 1 && P.Ho == P.H && P.Wo == P.W && (P.W % 4) == 0 && P.W / 4 <= 64 && (P.out_bs % 4) == 0;
+  for (int i = 0; i < P.nseg; ++i) ok = ok && (P.seg[i].bs % 4) == 0;
+  return ok;
+}
+
+static void dw3x3_half(const DwParams& P, hipStream_t st) {
+  bool aligned = (reinterpret_cast<uintptr_t>(P.out) % 16) == 0;
+  for (int i = 0; i < P.nseg; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(P.seg[i].p) % 16) == 0;
+  MLIC_CHECK((P.ckbd == 1 || P.ckbd == 2) && dw_half_ok(P) && aligned, "dw half: unsupported shape");
+  // strip height as in the whole-grid strip form: the fewest loaded rows per plane among 8 / 12 / 17
+  const int cand[3] = {8, 12, 17};
+  int best = 0;
+  int64_t cost = INT64_MAX;
+  for (int i = 0; i < 3; ++i) {
+    const int n = (P.H + cand[i] - 1) / cand[i];
+    const int64_t c = (int64_t)n * (cand[i] + 2);
+    if (c < cost) { cost = c; best = i; }
+  }
+  const int R = cand[best], nstrip = (P.H + R - 1) / R, spw = 64 / (P.W / 4);
+  const int64_t strips = (int64_t)P.B * P.C * nstrip, waves = (strips + spw - 1) / spw;
+  const dim3 grid((unsigned)((waves + DWS_WAVES - 1) / DWS_WAVES));
+  if (R == 8) hipLaunchKernelGGL(dw3x3_s1_half_kernel<8>, grid, dim3(64 * DWS_WAVES), 0, st, P, nstrip);
+  else if (R == 12) hipLaunchKernelGGL(dw3x3_s1_half_kernel<12>, grid, dim3(64 * DWS_WAVES), 0, st, P, nstrip);
+  else hipLaunchKernelGGL(dw3x3_s1_half_kernel<17>, grid, dim3(64 * DWS_WAVES), 0, st, P, nstrip);
+  HIP_OK(hipGetLastError());
+}
+
 void dw3x3(const DwParams& P, hipStream_t st) {
   MLIC_CHECK(P.stride == 1 || P.stride == 2, "dw stride");
   MLIC_CHECK(P.Ho == (P.H - 1) / P.stride + 1 && P.Wo == (P.W - 1) / P.stride + 1, "dw output size");
+  if (P.ckbd) return dw3x3_half(P, st);
   int tot = 0;
   bool aligned = (P.W % 4) == 0 && (reinterpret_cast<uintptr_t>(P.out) % 16) == 0 && (P.out_bs % 4) == 0;
   for (int i = 0; i < P.nseg; ++i) {

@@ -651,7 +651,8 @@ ConvParams Model::conv_params(const std::vector<View>& ins, const ConvW& w, int 
   return P;
 }
 
-void Model::dw(const std::vector<View>& ins, const DwW& w, int stride, const View& out, bool gelu) {
+DwParams Model::dw_params(const std::vector<View>& ins, const DwW& w, int stride, const View& out, bool gelu,
+                          int ckbd) {
   DwParams P{};
   P.nseg = (int)ins.size();
   int c = 0;
@@ -666,15 +667,54 @@ void Model::dw(const std::vector<View>& ins, const DwW& w, int stride, const Vie
   P.stride = stride;
   P.Ho = (P.H - 1) / stride + 1;
   P.Wo = (P.W - 1) / stride + 1;
-  MLIC_CHECK(out.H == P.Ho && out.W == P.Wo, "depthwise output shape");
+  MLIC_CHECK(out.H == P.Ho && out.W * (ckbd ? 2 : 1) == P.Wo, "depthwise output shape");
   P.w = w.w;
   P.bias = w.b;
   P.out = out.p;
   P.out_bs = out.bs;
   P.gelu = gelu ? 1 : 0;
   P.B = L().B;
-  const double outn = (double)L().B * c * P.Ho * P.Wo;
-  timed(PCAT_DW, 18.0 * outn, 4.0 * ((double)L().B * c * P.H * P.W + outn), [&] { dw3x3(P, L().st); }, w.name);
+  P.ckbd = ckbd;  // a checkerboard half: `out` holds the squeezed planes (H x W / 2)
+  return P;
+}
+
+void Model::dw(const std::vector<View>& ins, const DwW& w, int stride, const View& out, bool gelu, int ckbd) {
+  const DwParams P = dw_params(ins, w, stride, out, gelu, ckbd);
+  const double outn = (double)L().B * P.C * out.H * out.W;
+  timed(PCAT_DW, 18.0 * outn, 4.0 * ((double)L().B * P.C * P.H * P.W + outn), [&] { dw3x3(P, L().st); }, w.name);
+}
+
+// The checkerboard half `ckbd` (1 anchor, 2 non-anchor) of pw(dw(ins)) [+ res], written into `out` at that half's
+// pixels only: the half depthwise into squeezed planes (DwParams::ckbd), then the scattering resident 1x1
+// (ConvParams::scatter), which reads `res` at the same pixels.  `epi` is the pointwise epilogue without the
+// whole-grid form's checkerboard mask `mask_epi` (every value the half form computes is kept).  Returns false,
+// with nothing launched, unless the whole-grid form would run as dw3x3 + pw_resident_kernel (`fusable`: conv3x3
+// would take the fused dwpw kernel first where it applies) and both half kernels serve the shape: every value
+// written is then the whole-grid form's, bit for bit.
+bool Model::dw_pw_half(const std::vector<View>& ins, const DwW& d, bool gelu, const ConvW& w, int epi, int mask_epi,
+                       const View& out, const View* res, int ckbd, bool fusable) {
+  const int H = ins[0].H, W = ins[0].W;
+  if (W % 2 != 0 || !w.wh) return false;
+  const View geo{nullptr, d.C, H, W, (int64_t)d.C * H * W};  // geometry only
+  const ConvParams PF = conv_params({geo}, w, 1, 0, out, epi | mask_epi, nullptr, res);
+  const ConvWeights cwt{w.w, w.wh, w.wl, w.cin_pad, w.wx4, w.wexp};
+  if (fusable && dwpw_on() && ins.size() == 1 && dwpw_ok(PF, w.cin_pad) && dwpw_grid_ok(PF)) return false;
+  if (conv_select(PF, cwt, prec()) != CONV_PW || pw3_ok(PF, w.cin_pad)) return false;
+  const size_t m = L().arena.mark();
+  const View sq = alloc(d.C, H, W / 2);
+  const View og{out.p, out.C, H, W / 2, out.bs};
+  View rg;
+  if (res) rg = View{res->p, res->C, H, W / 2, res->bs};
+  ConvParams PX = conv_params({sq}, w, 1, 0, og, epi, nullptr, res ? &rg : nullptr);
+  PX.out_cs = out.hw();
+  PX.scatter = ckbd;
+  const bool ok = dw_half_ok(dw_params(ins, d, 1, sq, gelu, ckbd)) && pw_resident_ok(PX, w.cin_pad);
+  if (ok) {
+    dw(ins, d, 1, sq, gelu, ckbd);
+    run_conv(PX, w, nullptr);
+  }
+  L().arena.release(m);
+  return ok;
 }
 
 // a fused chain over a (multi-segment) input; GELU between the layers (entropy.py:10-18, MLP fc1 -> fc2)
@@ -782,9 +822,27 @@ View Model::rbws(const View& x, const std::string& p, bool dwsep) {
   const size_t m = L().arena.mark();
   View t1 = conv3x3({x}, p + ".conv1", 2, dwsep, EPI_GELU);
   View t2 = conv3x3({t1}, p + ".conv2", 1, dwsep, EPI_NONE);
-  View s = alloc(sk.Cout, Ho, Wo);
-  conv({x}, sk, 2, 0, s, EPI_NONE);
-  gdn(t2, p + ".gdn", false, out, &s);
+  // $MLIC_GDN_SKIP / mlic_set_kernel_option("gdn_skip") (0 = the two launches, A/B): the skip conv of the image
+  // (g_a's first block, 3 -> N) is computed inside the GDN launch's epilogue where that launch is dwpw3's
+  // pointwise form (pw3_ok): no skip launch, no full-resolution plane written and read back; the same bits
+  const ConvW& gw = cw(p + ".gdn.__gdn");
+  ConvParams PG = conv_params({t2}, gw, 1, 0, out, EPI_SQUARE_IN | EPI_GDN, &t2, nullptr);
+  PG.skx = x.p;
+  PG.skx_bs = x.bs;
+  PG.sk_cin = sk.Cin;
+  PG.sk_H = x.H;
+  PG.sk_W = x.W;
+  PG.skw = sk.w;
+  PG.skb = sk.b;
+  const ConvWeights gwt{gw.w, gw.wh, gw.wl, gw.cin_pad, gw.wx4, gw.wexp};
+  if (opt(OPT_GDN_SKIP) && sk.K == 1 && sk.Cin <= 4 && x.C == sk.Cin && sk.Cout == gw.Cout && gw.wh &&
+      conv_select(PG, gwt, prec()) == CONV_PW && pw3_ok(PG, gw.cin_pad)) {
+    run_conv(PG, gw, nullptr);
+  } else {
+    View s = alloc(sk.Cout, Ho, Wo);
+    conv({x}, sk, 2, 0, s, EPI_NONE);
+    gdn(t2, p + ".gdn", false, out, &s);
+  }
   L().arena.release(m);
   return out;
 }
@@ -1076,28 +1134,67 @@ void Model::linatt_reproject(const View& k, const View& v, const View& q, int he
 
 // context.py:140-193 LinearGlobalIntraContext: q from non-anchor cells of x1, k from anchor cells of
 // x1, v from x2; the squeezed-half softmaxes are computed on the full grid with parity masks.
-View Model::intra_context(const View& x1, const View& x2, int i) {
+// $MLIC_INTRA_HALF / mlic_set_kernel_option("intra_half") (default 0 = two masked copies, whole-grid tail; 2 = 1, and
+// run_module("intra") takes the half form as well): queries.0 / keys.0
+// read x1 through the resident 1x1's input parity mask (ConvParams::in_mask) in place of two masked copies, and
+// with `half` -- the only consumer is the non-anchor EntropyParameters chain on its half (ep_half_chain) -- the
+// tail mlp.2 / mlp.4 + residual runs on the non-anchor pixels only (dw_pw_half): the output's anchor pixels are
+// then not written.  Every value that is written is the whole-grid form's.
+View Model::intra_context(const View& x1, const View& x2, int i, bool half) {
   const std::string p = "global_intra_context." + std::to_string(i);
   const int D = x1.C, H = x1.H, W = x1.W, HW = H * W;
   const int heads = 2, hd = D / 2;
+  const bool on = opt(OPT_INTRA_HALF) != 0;
   View out = alloc(2 * D, H, W);
   const size_t m = L().arena.mark();
-  View x1n = alloc(D, H, W);
-  View x1a = alloc(D, H, W);
-  timed(PCAT_ELEM, 0.0, 16.0 * L().B * D * HW, [&] {
-    ckbd_mask(x1.p, x1.bs, x1n.p, x1n.bs, D, H, W, L().B, 0, L().st);
-    ckbd_mask(x1.p, x1.bs, x1a.p, x1a.bs, D, H, W, L().B, 1, L().st);
-  }, p + ".ckbd");
-  View q = qkv_branch(x1n, p + ".queries");
-  View k = qkv_branch(x1a, p + ".keys");
+  // the masked 1x1 of x1 (parity 1 = anchor kept, 2 = non-anchor kept) + the branch's depthwise
+  auto masked_branch = [&](const std::string& bp, int parity, View& o) {
+    const ConvW& w = cw(bp + ".0");
+    const DwW& d = dww(bp + ".1");
+    const View geo{nullptr, w.Cout, H, W, (int64_t)w.Cout * HW};  // geometry only
+    const ConvParams P0 = conv_params({x1}, w, 1, 0, geo, EPI_NONE, nullptr, nullptr);
+    const ConvWeights cwt{w.w, w.wh, w.wl, w.cin_pad, w.wx4, w.wexp};
+    ConvParams PX = P0;
+    PX.in_mask = parity;
+    // only where the copy's consumer would be pw_resident_kernel: the same kernel, so the same bits
+    if (!on || !w.wh || conv_select(P0, cwt, prec()) != CONV_PW || pw3_ok(P0, w.cin_pad) ||
+        !pw_resident_ok(PX, w.cin_pad))
+      return false;
+    o = alloc(d.C, H, W);
+    const size_t m3 = L().arena.mark();
+    const View t = alloc(w.Cout, H, W);
+    PX.out = t.p;
+    PX.out_bs = t.bs;
+    run_conv(PX, w, nullptr);
+    dw({t}, d, 1, o, false);
+    L().arena.release(m3);
+    return true;
+  };
+  View q, k;
+  {
+    const size_t m2 = L().arena.mark();
+    if (!masked_branch(p + ".queries", 2, q) || !masked_branch(p + ".keys", 1, k)) {
+      L().arena.release(m2);  // (both branches have one shape: the first refusal launches nothing)
+      View x1n = alloc(D, H, W);
+      View x1a = alloc(D, H, W);
+      timed(PCAT_ELEM, 0.0, 16.0 * L().B * D * HW, [&] {
+        ckbd_mask(x1.p, x1.bs, x1n.p, x1n.bs, D, H, W, L().B, 0, L().st);
+        ckbd_mask(x1.p, x1.bs, x1a.p, x1a.bs, D, H, W, L().B, 1, L().st);
+      }, p + ".ckbd");
+      q = qkv_branch(x1n, p + ".queries");
+      k = qkv_branch(x1a, p + ".keys");
+    }
+  }
   View v = qkv_branch(x2, p + ".values");
   const ConvW& rp = cw(p + ".reprojection");
   View a = alloc(rp.Cout, H, W);
   linatt_reproject(k, v, q, heads, hd, 1, 2, rp, a, p + ".attn");
   View m1 = conv1x1(a, p + ".mlp.0", 1, EPI_GELU);
-  View m2 = alloc(m1.C, H, W);
-  dw({m1}, dww(p + ".mlp.2"), 1, m2, true);
-  conv({m2}, cw(p + ".mlp.4"), 1, 0, out, EPI_NONE, nullptr, &a);
+  if (!(on && half && dw_pw_half({m1}, dww(p + ".mlp.2"), true, cw(p + ".mlp.4"), EPI_NONE, 0, out, &a, 2, false))) {
+    View m2 = alloc(m1.C, H, W);
+    dw({m1}, dww(p + ".mlp.2"), 1, m2, true);
+    conv({m2}, cw(p + ".mlp.4"), 1, 0, out, EPI_NONE, nullptr, &a);
+  }
   L().arena.release(m);
   return out;
 }
@@ -1159,8 +1256,14 @@ void Model::lrp(const std::vector<View>& ins, const std::string& kind, int i, co
       View o = conv3x3(cur, q, 1, true, EPI_GELU);
       cur = {o};
     } else {
-      const int epi = EPI_TANH_HALF | (anchor ? EPI_MASK_ANCHOR : EPI_MASK_NONANCHOR);
-      conv3x3(cur, q, 1, true, epi, &yh, &yh);
+      // $MLIC_LRP_HALF / mlic_set_kernel_option("lrp_half") (default 0: the whole grid): the head on its
+      // phase's checkerboard half only.  The whole-grid form stores res + 0.0f at the other half, this one
+      // leaves res as it is (the same bits unless res is -0.0)
+      const int mask = anchor ? EPI_MASK_ANCHOR : EPI_MASK_NONANCHOR;
+      if (opt(OPT_LRP_HALF) && dw_pw_half(cur, dww(q + ".depth_conv"), false, cw(q + ".point_conv"), EPI_TANH_HALF,
+                                          mask, yh, &yh, anchor ? 1 : 2, true))
+        continue;
+      conv3x3(cur, q, 1, true, EPI_TANH_HALF | mask, &yh, &yh);
     }
   }
   L().arena.release(m);
@@ -1270,11 +1373,12 @@ void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& 
       Q.phase = ph;
       View pn;
       if (ph == 1) {
-        View local = local_context(ysl, idx, ep_half_chain("nonanchor", idx, H, W, hp != nullptr));
+        const bool half = ep_half_chain("nonanchor", idx, H, W, hp != nullptr);
+        View local = local_context(ysl, idx, half);
         if (idx == 0) {
           pn = entropy_parameters({local}, &hyper, "nonanchor", 0, hp, true);
         } else {
-          View intra = intra_context(yhat.ch((idx - 1) * C, C), ysl, idx);
+          View intra = intra_context(yhat.ch((idx - 1) * C, C), ysl, idx, half);
           pn = entropy_parameters({local, intra, inter, chan}, &hyper, "nonanchor", idx, hp, true);
         }
       }
@@ -1861,7 +1965,8 @@ void Model::run_module(const std::string& which, int i, const float* in0, const 
     else if (which == "inter") r = inter_context(a, i);
     else if (which == "intra") {
       View b{const_cast<float*>(in1), Cin, H, W, (int64_t)Cin * H * W};
-      r = intra_context(a, b, i);
+      // "intra_half" = 2 (tests): the slice loop's half form, only the non-anchor pixels of out are defined
+      r = intra_context(a, b, i, opt(OPT_INTRA_HALF) == 2);
     } else if (which == "epa") r = entropy_parameters({a}, nullptr, "anchor", i);
     else if (which == "epn") r = entropy_parameters({a}, nullptr, "nonanchor", i);
     else if (which == "g_a") r = g_a(a);
@@ -1878,6 +1983,11 @@ void Model::run_module(const std::string& which, int i, const float* in0, const 
       View o{out, cfg_.C, H, W, (int64_t)cfg_.C * H * W};
       if (!L().dry) HIP_OK(hipMemcpyAsync(out, in1, sizeof(float) * B * o.bs, hipMemcpyDeviceToDevice, L().st));
       lrp({a}, "nonanchor", i, o, false);
+      return;
+    } else if (which == "lrpa") {
+      View o{out, cfg_.C, H, W, (int64_t)cfg_.C * H * W};
+      if (!L().dry) HIP_OK(hipMemcpyAsync(out, in1, sizeof(float) * B * o.bs, hipMemcpyDeviceToDevice, L().st));
+      lrp({a}, "anchor", i, o, true);
       return;
     } else throw Error("mlic: unknown module " + which);
     if (!L().dry) HIP_OK(hipMemcpyAsync(out, r.p, sizeof(float) * B * r.bs, hipMemcpyDeviceToDevice, L().st));

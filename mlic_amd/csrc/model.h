@@ -319,7 +319,10 @@ class Model {
   bool taps_on() const;
   void conv_pair(const std::vector<View>& ins, const ConvW& w1, const View& out1, int epi1, const ConvW& w2,
                  const View& out2, int epi2);
-  void dw(const std::vector<View>& ins, const DwW& w, int stride, const View& out, bool gelu);
+  DwParams dw_params(const std::vector<View>& ins, const DwW& w, int stride, const View& out, bool gelu, int ckbd);
+  void dw(const std::vector<View>& ins, const DwW& w, int stride, const View& out, bool gelu, int ckbd = 0);
+  bool dw_pw_half(const std::vector<View>& ins, const DwW& d, bool gelu, const ConvW& w, int epi, int mask_epi,
+                  const View& out, const View* res, int ckbd, bool fusable);
   View conv3x3(const std::vector<View>& ins, const std::string& p, int stride, bool dwsep, int epi,
                const View* res = nullptr, const View* out = nullptr);
   View conv1x1(const View& in, const std::string& p, int stride, int epi, const View* res = nullptr);
@@ -338,7 +341,7 @@ class Model {
   bool ep_half_chain(const std::string& kind, int i, int H, int W, bool hoisted) const;
   View channel_context(const View& x, int i);
   View inter_context(const View& x, int i);
-  View intra_context(const View& x1, const View& x2, int i);
+  View intra_context(const View& x1, const View& x2, int i, bool half = false);
   // ctx: the context segments of the layer-0 concat (entropy.py), hyper appended last; hoisted: the
   // slice loop's precomputed W_hyp . hyper rows of all EPs (or null); phase_only: the output is read at the
   // kind's own checkerboard pixels only (the slice loop), so the chain may skip the other half

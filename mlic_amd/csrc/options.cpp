@@ -40,6 +40,10 @@ const Row kRows[] = {
     {"pw3", "MLIC_PW3", 1, raw},
     {"narrow_limit", nullptr, 32767, narrow},
     {"image_io_path", nullptr, -1, raw},  // -1 = by layout; opt_set refuses values outside [-1, 2]
+    // round 7; the two half forms are off by default: they did not move the main line beyond its spread
+    {"lrp_half", "MLIC_LRP_HALF", 0, flag},
+    {"intra_half", "MLIC_INTRA_HALF", 0, raw},  // 2 = on, and the module-level test entry takes the half form too
+    {"gdn_skip", "MLIC_GDN_SKIP", 1, flag},
     // frozen, in the enum's order.  MLIC_HOIST: -1 = auto (Model::hoist_on); MLIC_HOST_THREADS and mlic_create's
     // MLIC_LANES, MLIC_PRECISION, MLIC_SYNTH_FP16, MLIC_POISON apply only when set (opt_str)
     {nullptr, "MLIC_X4", 1, flag},           {nullptr, "MLIC_X4_K", 0, str},
