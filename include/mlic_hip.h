@@ -261,6 +261,42 @@ int mlic_lpips_profile(mlic_lpips* h, int on, double* ms3);
 /* calls that were re-run in fp32 by the range guard since the last reset */
 int mlic_lpips_range_fallbacks(mlic_lpips* h, int64_t* count, int reset);
 
+/* ---- DISTS: DISTS_pytorch 0.1's DISTS()(a/255, b/255) in eval mode, restated in DESIGN.md §3, of two
+ * [B][3][H][W] fp32 images in [0,1] made uint8-valued as mlic_image_sq_err_u8 does.  The same VGG16 trunk as
+ * LPIPS with L2 pooling (3x3 Hanning, stride 2, ceil grids) and a head of per-channel means, variances and
+ * covariances over six feature sets (the image and five taps, 1475 channels) ----
+ *
+ * create: the table form of mlic_lpips_create.  The 13 conv weights and biases by their trailing features index
+ * ("stage2.5.weight" and "5.weight" are the same tensor); "alpha" and "beta" [1][1475][1][1]; optionally "mean"
+ * and "std" [1][3][1][1] (default 0.485 0.456 0.406 / 0.229 0.224 0.225); names ending in ".filter" (the
+ * package's pooling buffers) are ignored.  Missing, extra and mis-shaped tensors are refused by name, and so is
+ * a sum(alpha) + sum(beta) that is zero or not finite.  A handle serves one call at a time. */
+typedef struct mlic_dists mlic_dists;
+int mlic_dists_create(int n, const char* const* names, const float* const* ptrs, const int64_t* shapes,
+                      const int* ndims, void* stream, mlic_dists** out);
+int mlic_dists_destroy(mlic_dists* h);
+/* the dense convs' kernel family: 2 = split-fp16 conv_x4 (default), 0 = the fp32 MFMA conv */
+int mlic_dists_set_precision(mlic_dists* h, int precision);
+/* bytes of device scratch mlic_image_dists_u8 needs; host logic only, no GPU touched; nonzero rc with a message
+ * when B < 1, H or W < 16, or H * W > 2^23.  Chunked under the same 4 GiB cap as LPIPS. */
+int mlic_dists_scratch_bytes(int B, int H, int W, size_t* bytes);
+/* per-pair DISTS; element strides {image, channel, row} per operand (column stride 1); out: B doubles (device);
+ * terms: optional B*12 doubles (device) [T1_0, T2_0, .., T1_5, T2_5], the structure and texture terms of the six
+ * sets, whose sum in that order is the value.  Checked before any GPU call, each with its own message: null
+ * handle; B < 1; H or W < 16; null images or strides; a row stride below W or a negative stride; scratch too
+ * small or not 256-byte aligned; null out.  Nothing outside scratch[0, bytes), out and terms is written, and no
+ * scratch element is read that this call did not write.  Identical operands give exactly 0 (value and terms).
+ * Bit-reproducible, and independent of B, of the chunking and of the strides.  The fp16 range guard and its
+ * whole-call fp32 re-run are those of mlic_image_lpips_u8. */
+int mlic_image_dists_u8(mlic_dists* h, void* stream, const float* a, const int64_t* a_strides, const float* b,
+                        const int64_t* b_strides, int B, int H, int W, void* scratch, size_t scratch_bytes,
+                        double* out, double* terms);
+/* stage timing (tools/dists_bench.py), as mlic_lpips_profile: {the stem, the dense convs, the set-0, tap, stats
+ * and reduce launches} */
+int mlic_dists_profile(mlic_dists* h, int on, double* ms3);
+/* calls that were re-run in fp32 by the range guard since the last reset */
+int mlic_dists_range_fallbacks(mlic_dists* h, int64_t* count, int reset);
+
 /* ---- uint8 images in, file bytes out, uint8 images back (utils/testing.py:338-424, submit/decode.py) ----
  *
  * ingest: B images of H x W x 3 bytes (device), read in place through element strides {image, row, column,

@@ -83,6 +83,13 @@ def _sig(lib):
         "mlic_image_lpips_u8": [p, p, p, P(i64), p, P(i64), i, i, i, p, sz, p, p],
         "mlic_lpips_range_fallbacks": [p, P(i64), i],
         "mlic_lpips_profile": [p, i, P(C.c_double)],
+        "mlic_dists_create": [i, P(C.c_char_p), P(p), P(i64), P(i), p, P(p)],
+        "mlic_dists_destroy": [p],
+        "mlic_dists_set_precision": [p, i],
+        "mlic_dists_scratch_bytes": [i, i, i, P(sz)],
+        "mlic_image_dists_u8": [p, p, p, P(i64), p, P(i64), i, i, i, p, sz, p, p],
+        "mlic_dists_range_fallbacks": [p, P(i64), i],
+        "mlic_dists_profile": [p, i, P(C.c_double)],
         "mlic_image_ingest_u8": [p, p, P(i64), i, i, i, p, i, i],
         "mlic_image_egress_u8": [p, p, P(i64), i, i, i, p, P(i64), p, P(i64), p],
         "mlic_image_blur3_pad": [p, p, p, i, i, i, i, i, p, p],

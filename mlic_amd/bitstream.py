@@ -97,12 +97,13 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
-               **kw) -> Dict:
+               dists=None, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
     lpips=metric (a metrics.LPIPS, or any callable (a, b) -> [B] tensor) adds "lpips": metric(img, cropped x_hat)
     as a float, None when min(H, W) < 16; off by default.
+    dists=metric (a metrics.DISTS, or any such callable) adds "dists" in the same way.
     max_bpp: the reference's rate constraint (utils/testing.py:363-390) through codec.rate_loop on the float
     image: while the file is above max_bpp and fewer than max_passes filter passes were made, filter and code
     again.  The record then also holds "passes" and "met" (bpp <= max_bpp); psnr stays against the unfiltered
@@ -142,4 +143,7 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     if lpips is not None:
         from . import metrics
         r["lpips"] = lpips(img, x_hat).item() if min(H, W) >= metrics.LPIPS_MIN_SIDE else None
+    if dists is not None:
+        from . import metrics
+        r["dists"] = dists(img, x_hat).item() if min(H, W) >= metrics.DISTS_MIN_SIDE else None
     return r

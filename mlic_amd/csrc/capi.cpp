@@ -30,6 +30,10 @@ struct mlic_lpips {
   Lpips* impl = nullptr;
 };
 
+struct mlic_dists {
+  Dists* impl = nullptr;
+};
+
 static thread_local std::string g_err;
 
 template <class F>
@@ -699,6 +703,77 @@ int mlic_lpips_range_fallbacks(mlic_lpips* h, int64_t* count, int reset) {
   return guard([&] {
     MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_lpips handle");
     const int64_t v = lpips_range_fallbacks(h->impl, reset != 0);
+    if (count) *count = v;
+  });
+}
+
+int mlic_dists_create(int n, const char* const* names, const float* const* ptrs, const int64_t* shapes,
+                      const int* ndims, void* stream, mlic_dists** out) {
+  return guard([&] {
+    MLIC_CHECK(out != nullptr, "dists_create: null out");
+    *out = nullptr;
+    auto* h = new mlic_dists();
+    try {
+      h->impl = dists_create(n, names, ptrs, shapes, ndims, (hipStream_t)stream);
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+  });
+}
+
+int mlic_dists_destroy(mlic_dists* h) {
+  return guard([&] {
+    if (!h) return;
+    dists_destroy(h->impl);
+    delete h;
+  });
+}
+
+int mlic_dists_set_precision(mlic_dists* h, int precision) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_dists handle");
+    dists_set_precision(h->impl, precision);
+  });
+}
+
+int mlic_dists_scratch_bytes(int B, int H, int W, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr, "dists_scratch_bytes: null bytes");
+    *bytes = dists_scratch_bytes(B, H, W);
+  });
+}
+
+int mlic_image_dists_u8(mlic_dists* h, void* stream, const float* a, const int64_t* a_strides, const float* b,
+                        const int64_t* b_strides, int B, int H, int W, void* scratch, size_t scratch_bytes,
+                        double* out, double* terms) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_dists handle");
+    const size_t need = dists_scratch_bytes(B, H, W);  // checks B, H, W
+    MLIC_CHECK(a && b && a_strides && b_strides, "dists: null image or strides");
+    // the images are read in place with int64 element offsets: rows must not overlap and the column stride is 1
+    MLIC_CHECK(a_strides[2] >= W && b_strides[2] >= W && a_strides[1] >= 0 && b_strides[1] >= 0 &&
+                   a_strides[0] >= 0 && b_strides[0] >= 0,
+               "dists: bad strides (row stride below W, or a negative stride)");
+    MLIC_CHECK(scratch != nullptr && scratch_bytes >= need, "dists: scratch too small (mlic_dists_scratch_bytes)");
+    MLIC_CHECK(reinterpret_cast<uintptr_t>(scratch) % 256 == 0, "dists: scratch must be 256-byte aligned");
+    MLIC_CHECK(out != nullptr, "dists: null out");
+    dists_u8(h->impl, a, a_strides, b, b_strides, B, H, W, scratch, out, terms, (hipStream_t)stream);
+  });
+}
+
+int mlic_dists_profile(mlic_dists* h, int on, double* ms3) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_dists handle");
+    dists_profile(h->impl, on != 0, ms3);
+  });
+}
+
+int mlic_dists_range_fallbacks(mlic_dists* h, int64_t* count, int reset) {
+  return guard([&] {
+    MLIC_CHECK(h != nullptr && h->impl != nullptr, "null mlic_dists handle");
+    const int64_t v = dists_range_fallbacks(h->impl, reset != 0);
     if (count) *count = v;
   });
 }

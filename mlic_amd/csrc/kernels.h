@@ -274,6 +274,20 @@ int64_t lpips_range_fallbacks(Lpips* h, bool reset);
 // stage timing with device events: ms3 (optional) = {stem, dense convs, taps + reduce} summed over the calls since
 // the last read, then cleared; `on` switches it for the calls that follow (a timed call waits for its stream)
 void lpips_profile(Lpips* h, bool on, double* ms3);
+// DISTS of uint8-valued images (dists.hip; the definition in DESIGN.md §3) on the same trunk (vgg_trunk.h), with
+// LPIPS's handle rules, chunking, range guard and stage timing.  The table holds the 13 convs, "alpha" and
+// "beta" [1][1475][1][1], optionally "mean" and "std" [1][3][1][1]; "*.filter" buffers are ignored.  out B
+// doubles, terms (optional) [B][12] doubles [T1_0, T2_0, .., T1_5, T2_5].
+class Dists;
+Dists* dists_create(int n, const char* const* names, const float* const* ptrs, const int64_t* shapes,
+                    const int* ndims, hipStream_t st);
+void dists_destroy(Dists* h);
+void dists_set_precision(Dists* h, int precision);
+size_t dists_scratch_bytes(int B, int H, int W);
+void dists_u8(Dists* h, const float* a, const int64_t* a_strides, const float* b, const int64_t* b_strides, int B,
+              int H, int W, void* scratch, double* out, double* terms, hipStream_t st);
+int64_t dists_range_fallbacks(Dists* h, bool reset);
+void dists_profile(Dists* h, bool on, double* ms3);
 // uint8 image I/O (image_io.hip).  Both check their arguments before any HIP call and throw.
 // ingest: B images of H x W x 3 bytes read through element strides {image, row, column, channel} -> dst fp32
 // [B][3][Hp][Wp] contiguous (Hp, Wp multiples of 64), v / 255 inside the image and +0 in the padding.
