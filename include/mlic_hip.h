@@ -86,6 +86,48 @@ int mlic_decompress_v(mlic_model* m, void* stream, const uint8_t* const* y, cons
                       const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz, float* x_hat,
                       const float* vbr_scales);
 
+/* ---- ROI coding on *_VBR models (DESIGN.md §5 "ROI coding") ----
+ * The VBR gain is a quantisation step: y_hat = round((y - mu) * g) / g + mu, the table index from sigma * g, the
+ * likelihood at (y, sigma, mu) * g.  The _g forms of forward / compress / decompress take it per latent pixel:
+ * gain_plane = device fp32 [B][H/16][W/16] (decompress: [B][4 hz][4 wz]) in place of vbr_scales, produced on
+ * `stream`.  The library derives the reciprocal plane itself (one small kernel per call, the correctly rounded
+ * fp32 1 / g), so a constant plane gives exactly the bits and bytes of the scalar call with that gain.  z, the
+ * hyperprior, the contexts, LRP and g_s do not see the plane.  Every value must be finite and positive: that
+ * is the caller's contract and is not checked on the device (mlic_roi_gain_plane keeps it).  Encoder and
+ * decoder must use bit-identical planes.  Per-image strings only: mlic_batch_stream refuses the images of a
+ * mlic_compress_g, and mlic_decompress_g wants one y string per image.  Refused before any GPU call, each with
+ * its own message: a model that is not *_VBR; a null plane; a missing y string. */
+int mlic_forward_g(mlic_model* m, void* stream, const float* x, int B, int H, int W, float* x_hat, float* y_lik,
+                   float* z_lik, const float* gain_plane);
+int mlic_compress_g(mlic_model* m, void* stream, const float* x, int B, int H, int W, const float* gain_plane);
+int mlic_decompress_g(mlic_model* m, void* stream, const uint8_t* const* y, const size_t* y_len,
+                      const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz, float* x_hat,
+                      const float* gain_plane);
+/* mask -> level map.  mask: uint8 on the device, nonzero = inside the ROI, read in place through element strides
+ * {image, row, column}; levels: uint8 [B][hz][wz] (device) on the z grid, hz = ceil(H / 64), wz = ceil(W / 64),
+ * one cell per 64 x 64 pixel block clipped to H x W.  In integers:
+ *     level = lo + ceil((hi - lo) * count / area)
+ * with count the cell's nonzero mask pixels and area its pixels inside the image (>= 1): lo where the cell holds
+ * no ROI pixel, hi where it is all ROI, and any ROI pixel lifts the cell above lo.  One launch, deterministic,
+ * asynchronous on `stream`.  Refused before any GPU call: null arguments; B, H or W < 1; lo > hi; lo < 0 or
+ * hi > 255. */
+int mlic_image_roi_levels_u8(void* stream, const uint8_t* mask, const int64_t* mask_strides, int B, int H, int W, int lo,
+                             int hi, uint8_t* levels);
+/* level map -> gain plane, nearest expansion: g[b][i][j] = gains_host[levels[b][i >> 2][j >> 2]] over the latent
+ * grid [B][4 hz][4 wz] (device fp32).  gains_host: n_levels <= 16 host floats (|Gain| of the model), each finite
+ * and positive; a level >= n_levels (excluded by mlic_container_parse_roi) reads the last entry.  Encoder and
+ * decoder both build their plane with this one kernel from the same bytes.  Asynchronous on `stream`. */
+int mlic_roi_gain_plane(void* stream, const uint8_t* levels, int B, int hz, int wz, const float* gains_host,
+                        int n_levels, float* g);
+/* Squared error inside and outside the ROI: a, b uint8 images (device) with {image, row, column, channel}
+ * strides, mask as above; out: [B][4] uint64 (device) = {squared error inside, pixels inside, squared error
+ * outside, pixels outside}, the squared error summed over the three channels.  Exact integer sums (integer
+ * atomics: independent of scheduling), so PSNR_roi = 10 log10(255^2 * 3 * pixels / sq_err) comes with it;
+ * inside + outside is mlic_image_egress_u8's sq_err.  Asynchronous on `stream`. */
+int mlic_image_sq_err_roi_u8(void* stream, const uint8_t* a, const int64_t* a_strides, const uint8_t* b,
+                             const int64_t* b_strides, const uint8_t* mask, const int64_t* mask_strides, int B, int H,
+                             int W, uint64_t* out);
+
 /* module-level entry points (tests / profiling): which = local|chan|inter|intra|epa|epn|lrpa|lrpn|g_a|h_a|h_s|g_s|rbu|rbws */
 int mlic_run_module(mlic_model* m, void* stream, const char* which, int idx, const float* in0, const float* in1,
                     int B, int Cin, int H, int W, float* out);
@@ -356,6 +398,27 @@ int mlic_container_write(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_
  * (64 h_z) * (64 w_z) > max_pixels; with vbr, level >= n_levels. */
 int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, uint64_t max_pixels,
                          mlic_container_info* info);
+
+/* The ROI file: the file of mlic_container_write with the level word always present (ROI files are VBR files;
+ * it holds the map's upper level) and n_strings = 3.  The third string is the level map on the z grid: one
+ * version byte 0, then h_z * w_z levels of 4 bits each, row-major, high nibble first; 1 + ceil(h_z * w_z / 2)
+ * bytes, after a length word of 4: 260 B more per file at 1920 x 1080 (17 x 30 cells), 53 B at 768 x 512.
+ * write: levels = h_z * w_z host bytes, one per cell, each <= 15; the *len / out / cap protocol of
+ * mlic_container_write.
+ * parse: accepts 2 strings (map_len = 0: a plain VBR file) or 3; levels (optional, levels_cap >= h_z * w_z
+ * bytes) receives the unpacked map.  Refused, each with its own message: everything mlic_container_parse
+ * refuses; n_levels > 16; n_strings not 2 or 3; a map length that is not 1 + ceil(h_z * w_z / 2); a nonzero
+ * version byte; a level >= n_levels; a nonzero padding nibble.  Never reads outside data[0, n).
+ * mlic_container_parse itself keeps refusing n_strings = 3. */
+typedef struct mlic_container_roi_info {
+  mlic_container_info file;
+  uint64_t map_off, map_len; /* the packed map is data[map_off, map_off + map_len); map_len 0 = no map */
+} mlic_container_roi_info;
+int mlic_container_write_roi(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_t wz, const uint8_t* y,
+                             size_t y_len, const uint8_t* z, size_t z_len, const uint8_t* levels, uint8_t* out,
+                             size_t cap, size_t* len);
+int mlic_container_parse_roi(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                             mlic_container_roi_info* info, uint8_t* levels, size_t levels_cap);
 
 /* One image, pixels to file bytes: ingest into a staging buffer the handle owns (it grows on demand and is
  * freed by mlic_destroy), mlic_compress with B = 1, the container.  rgb_dev: H x W x 3 bytes on the device

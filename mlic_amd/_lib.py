@@ -27,6 +27,11 @@ class ContainerInfo(C.Structure):
                 ("z_len", C.c_uint64)]
 
 
+class ContainerRoiInfo(C.Structure):
+    """mlic_container_roi_info (include/mlic_hip.h)."""
+    _fields_ = [("file", ContainerInfo), ("map_off", C.c_uint64), ("map_len", C.c_uint64)]
+
+
 def _sig(lib):
     p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
     P = C.POINTER
@@ -96,6 +101,14 @@ def _sig(lib):
         "mlic_container_bytes": [sz, sz, i, P(sz)],
         "mlic_container_write": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, p, sz, p, sz, P(sz)],
         "mlic_container_parse": [p, sz, i, i, C.c_uint64, P(ContainerInfo)],
+        "mlic_forward_g": [p, p, p, i, i, i, p, p, p, p],
+        "mlic_compress_g": [p, p, p, i, i, i, p],
+        "mlic_decompress_g": [p, p, P(p), P(sz), P(p), P(sz), i, i, i, p, p],
+        "mlic_image_roi_levels_u8": [p, p, P(i64), i, i, i, i, i, p],
+        "mlic_roi_gain_plane": [p, p, i, i, i, P(f), i, p],
+        "mlic_image_sq_err_roi_u8": [p, p, P(i64), p, P(i64), p, P(i64), i, i, i, p],
+        "mlic_container_write_roi": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, p, sz, p, p, sz, P(sz)],
+        "mlic_container_parse_roi": [p, sz, i, C.c_uint64, P(ContainerRoiInfo), p, sz],
         "mlic_encode_image_u8": [p, p, p, P(i64), i, i, f, i, p, sz, P(sz)],
         "mlic_encode_image_u8_budget": [p, p, p, P(i64), i, i, f, i, C.c_double, i, p, sz, P(sz), P(i)],
         "mlic_decode_image_u8": [p, p, p, sz, i, C.c_uint64, p, p, P(i64), sz, P(i), P(i), P(i)],

@@ -4,6 +4,8 @@ File layout (utils/utils.py:28-83, utils/testing.py:203-262):
     >II   H, W of the unpadded image            (VBR: >III H, W, level)
     >III  h_z, w_z, n_strings (= 2)
     n_strings x ( >I length, bytes )            y stream, then z stream (image 0 only: B = 1)
+An ROI file (codec.encode_images(roi=...), *_VBR models) has n_strings = 3: the third string is the level map on
+the z grid, one version byte 0 and h_z * w_z levels of 4 bits each (codec.write_container_roi).
 Harness semantics (utils/testing.py:338-424; the NAIC "bpp > 0.1 => blur and retry" loop is code_image's
 max_bpp=, off by default):
 pad right/bottom with zeros to a multiple of 64, compress, write, read, decompress, crop;
@@ -97,7 +99,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
-               dists=None, **kw) -> Dict:
+               dists=None, roi=None, roi_levels=None, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -107,14 +109,41 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     max_bpp: the reference's rate constraint (utils/testing.py:363-390) through codec.rate_loop on the float
     image: while the file is above max_bpp and fewer than max_passes filter passes were made, filter and code
     again.  The record then also holds "passes" and "met" (bpp <= max_bpp); psnr stays against the unfiltered
-    img, and enc_s covers the whole loop."""
+    img, and enc_s covers the whole loop.
+    roi=mask (uint8 / bool [H,W] or [1,H,W], nonzero = inside) with roi_levels=(lo, hi), a *_VBR model: ROI coding
+    (codec.roi_levels -> codec.gain_plane -> compress(gain_map=)); the file is the ROI file with its level map,
+    the decoder rebuilds the plane from the file alone, and the record also holds "psnr_roi" and "psnr_bg" (PSNR
+    inside and outside the mask; None for a side without pixels) and "roi_levels", the map.  Not together with
+    max_bpp or s=; off by default."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
     x = pad64(img)
     level = kw.get("s") if kw else None
     buf = io.BytesIO()
     passes = None
-    if max_bpp is None:
+    if (roi is None) != (roi_levels is None):
+        raise ValueError("code_image: roi= and roi_levels=(lo, hi) go together")
+    if roi is not None:
+        from . import codec
+        if max_bpp is not None or kw:
+            raise ValueError("code_image: roi= goes with roi_levels=(lo, hi) alone, not with max_bpp or s=")
+        lo, hi = roi_levels
+        mask = codec._mask_batch(roi, "code_image roi")
+        if tuple(mask.shape) != (1, H, W):
+            raise ValueError(f"code_image: roi must be a mask of shape {(H, W)}, got {tuple(mask.shape)}")
+        mask = mask.to(img.device)
+        t0 = time.time()
+        lmap = codec.roi_levels(mask, lo, hi)
+        out = net.compress(x, gain_map=codec.gain_plane(net, lmap))
+        enc = time.time() - t0
+        data = codec.write_container_roi(H, W, out["shape"], out["strings"][0][0], out["strings"][1][0], hi, lmap[0])
+        nbytes = len(data)
+        c, fmap = codec.parse_container_roi(data, min(int(net.levels), 16))
+        t0 = time.time()
+        dec = net.decompress([[data[c.y_off:c.y_off + c.y_len]], [data[c.z_off:c.z_off + c.z_len]]], (c.hz, c.wz),
+                             gain_map=codec.gain_plane(net, torch.from_numpy(fmap)))
+        dect = time.time() - t0
+    elif max_bpp is None:
         t0 = time.time()
         out = net.compress(x, **kw)
         enc = time.time() - t0
@@ -127,16 +156,20 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
         files, ps, _ = codec.rate_loop(net, x.contiguous().float(), H, W, level, max_bpp, max_passes)
         enc = time.time() - t0
         nbytes, passes = buf.write(files[0]), ps[0]
-    buf.seek(0)
-    hdr, strings, shape = read_stream(buf, vbr=level is not None)
-    t0 = time.time()
-    dec = net.decompress(strings, shape, **kw)
-    dect = time.time() - t0
+    if roi is None:
+        buf.seek(0)
+        hdr, strings, shape = read_stream(buf, vbr=level is not None)
+        t0 = time.time()
+        dec = net.decompress(strings, shape, **kw)
+        dect = time.time() - t0
     x_hat = dec["x_hat"][:, :, :H, :W]
     r = {"H": H, "W": W, "bytes": nbytes, "bpp": 8.0 * nbytes / (H * W), "psnr": psnr_u8(img, x_hat),
          "enc_s": enc, "dec_s": dect, "x_hat": x_hat}
     if passes is not None:
         r["passes"], r["met"] = passes, r["bpp"] <= max_bpp
+    if roi is not None:
+        p = codec.psnr_roi(to_u8(img), to_u8(x_hat), mask, layout="chw")[0]
+        r["psnr_roi"], r["psnr_bg"], r["roi_levels"] = p["psnr_roi"], p["psnr_bg"], fmap
     if ms_ssim:
         from . import metrics
         r["ms_ssim"] = metrics.ms_ssim_u8(img, x_hat).item() if min(H, W) > metrics.MIN_SIDE else None

@@ -13,7 +13,13 @@ above the budget, the float image goes through the 3x3 Gaussian prefilter `blur3
 compacts the images of a batch still over budget) and is coded again; `level="auto"` picks a *_VBR model's level
 from the budget.  Off by default.
 
-CUDA tensors run the HIP kernels (csrc/image_io.hip) on the current stream; CPU tensors run a torch
+`encode_images(roi=masks, roi_levels=(lo, hi))` codes a *_VBR model with a gain per latent pixel (DESIGN.md §5
+"ROI coding"): `roi_levels` turns the mask into a level map on the z grid (one cell per 64 x 64 pixels, lo outside
+the ROI, hi inside), `gain_plane` expands it to the latent grid, and the map travels in the file as a third
+string, so `decode_images` needs nothing but the file.  `sq_err_roi` / `psnr_roi` score a decode inside and
+outside the mask.
+
+CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
 """
 from __future__ import annotations
@@ -252,15 +258,183 @@ def parse_container(data: bytes, vbr: bool = False, n_levels: Optional[int] = No
 
 def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> Dict:
     """What a file says about itself, validated: H, W, level (None without one), the z grid `shape`, the
-    padded size, the string lengths and the bpp of the whole file."""
-    c = parse_container(data, vbr, n_levels, max_pixels)
-    return {"H": c.H, "W": c.W, "level": c.level if vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz,
-            "Wp": 64 * c.wz, "y_len": c.y_len, "z_len": c.z_len, "bytes": len(data),
-            "bpp": 8.0 * len(data) / (c.H * c.W)}
+    padded size, the string lengths and the bpp of the whole file; for an ROI file also "roi_levels", its level
+    map (uint8 numpy [hz, wz])."""
+    data = bytes(data)
+    lv = None
+    if vbr and is_roi_file(data):
+        c, lv = parse_container_roi(data, 16 if n_levels is None else n_levels, max_pixels)
+    else:
+        c = parse_container(data, vbr, n_levels, max_pixels)
+    d = {"H": c.H, "W": c.W, "level": c.level if vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz,
+         "Wp": 64 * c.wz, "y_len": c.y_len, "z_len": c.z_len, "bytes": len(data),
+         "bpp": 8.0 * len(data) / (c.H * c.W)}
+    if lv is not None:
+        d["roi_levels"] = lv  # uint8 [hz, wz]: the file's level map (ROI files only)
+    return d
+
+
+def is_roi_file(data: bytes) -> bool:
+    """Whether a VBR file's n_strings word says 3 (H, W, level, h_z, w_z come before it)."""
+    return len(data) >= 24 and int.from_bytes(data[20:24], "big") == 3
+
+
+def write_container_roi(H: int, W: int, shape, y: bytes, z: bytes, level: int, levels) -> bytes:
+    """One image's ROI file (mlic_container_write_roi): the VBR file with the level map as a third string.
+    level: the header's level word (the map's upper level); levels: [hz, wz] integers, each <= 15."""
+    hz, wz = int(shape[0]), int(shape[1])
+    lv = np.ascontiguousarray(np.asarray(levels.cpu() if torch.is_tensor(levels) else levels).reshape(-1))
+    if lv.size != hz * wz or lv.min() < 0 or lv.max() > 15:
+        raise ValueError(f"write_container_roi: {hz} x {wz} levels in [0, 15] expected")
+    lv = lv.astype(np.uint8)
+    n = C.c_size_t()
+    _lib.call("mlic_container_write_roi", H, W, int(level), hz, wz, y, len(y), z, len(z), None, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_roi", H, W, int(level), hz, wz, y, len(y), z, len(z), C.c_void_p(lv.ctypes.data),
+              buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_roi(data: bytes, n_levels: int = 16, max_pixels: int = MAX_PIXELS):
+    """The validating parser of a VBR file with or without a level map (mlic_container_parse_roi) ->
+    (ContainerInfo, levels): levels is a uint8 numpy array [hz, wz], or None for a 2-string file.  Raises
+    _lib.MlicError on any malformed input; n_levels (<= 16) bounds the level word and every level of the map."""
+    data = bytes(data)
+    info = _lib.ContainerRoiInfo()
+    _lib.call("mlic_container_parse_roi", data, len(data), int(n_levels), int(max_pixels), C.byref(info), None, 0)
+    c = info.file
+    if info.map_len == 0:
+        return c, None
+    lv = np.zeros(c.hz * c.wz, np.uint8)
+    _lib.call("mlic_container_parse_roi", data, len(data), int(n_levels), int(max_pixels), C.byref(info),
+              C.c_void_p(lv.ctypes.data), lv.size)
+    return info.file, lv.reshape(c.hz, c.wz)
 
 
 def _strings(data: bytes, c: _lib.ContainerInfo):
     return data[c.y_off:c.y_off + c.y_len], data[c.z_off:c.z_off + c.z_len]
+
+
+# ---------------------------------------------------------------------------------------------- ROI
+def _mask_batch(mask, what: str) -> torch.Tensor:
+    """-> 3-dim uint8 tensor [B,H,W] (a bool mask is viewed as bytes; one mask gains the batch dimension)."""
+    if isinstance(mask, np.ndarray):
+        mask = torch.from_numpy(np.ascontiguousarray(mask))
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() not in (2, 3):
+        raise ValueError(f"{what}: a uint8 or bool mask [B,H,W] (or one [H,W]) expected")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dim() == 2:
+        mask = mask.unsqueeze(0)
+    if 0 in mask.shape:
+        raise ValueError(f"{what}: empty mask {tuple(mask.shape)}")
+    return mask
+
+
+def _check_roi_levels(lo, hi, what: str):
+    ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (lo, hi))
+    if not ok or not 0 <= lo <= hi <= 255:
+        raise ValueError(f"{what}: integer levels 0 <= lo <= hi expected, got ({lo!r}, {hi!r})")
+
+
+def roi_levels(mask, lo: int, hi: int) -> torch.Tensor:
+    """mask (uint8 / bool [B,H,W] or [H,W], nonzero = inside the ROI, any strides: read in place) -> the level map
+    uint8 [B,hz,wz] on the z grid (hz = ceil(H / 64), wz = ceil(W / 64)), one cell per 64 x 64 pixel block
+    clipped to the image: level = lo + ceil((hi - lo) * count / area) in integers, count the cell's nonzero mask
+    pixels and area its pixels inside the image.  One launch on the mask's device (CPU: the same rule in torch)."""
+    mask = _mask_batch(mask, "roi_levels")
+    _check_roi_levels(lo, hi, "roi_levels")
+    B, H, W = mask.shape
+    hz, wz = (H + 63) // 64, (W + 63) // 64
+    if not mask.is_cuda:
+        m = torch.zeros(B, 64 * hz, 64 * wz, dtype=torch.int64)
+        m[:, :H, :W] = (mask != 0)
+        cnt = m.reshape(B, hz, 64, wz, 64).sum((2, 4))
+        ys = torch.clamp(H - 64 * torch.arange(hz), max=64)
+        xs = torch.clamp(W - 64 * torch.arange(wz), max=64)
+        area = ys[:, None] * xs[None, :]
+        return (lo + ((hi - lo) * cnt + area - 1) // area).to(torch.uint8)
+    with torch.cuda.device(mask.device):
+        out = torch.full((B, hz, wz), 255, dtype=torch.uint8, device=mask.device)
+        _lib.call("mlic_image_roi_levels_u8", _stream(), C.c_void_p(mask.data_ptr()), (C.c_int64 * 3)(*mask.stride()),
+                  B, H, W, int(lo), int(hi), C.c_void_p(out.data_ptr()))
+    return out
+
+
+_roi_level_map = roi_levels  # encode_images has a parameter of that name
+
+
+def gain_plane(net, levels) -> torch.Tensor:
+    """Level map (integer [B,hz,wz] or [hz,wz], each level below net.levels) -> the gain plane fp32
+    [B,1,4 hz,4 wz] on the model's device that `gain_map=` takes: latent pixel (i, j) gets
+    |net.Gain|[levels[b][i >> 2][j >> 2]] (the coder paths' gain).  Encoder and decoder both come through here."""
+    if not hasattr(net, "levels"):
+        raise ValueError("gain_plane: a *_VBR model expected (ROI coding needs the Gain table)")
+    if isinstance(levels, np.ndarray):
+        levels = torch.from_numpy(np.ascontiguousarray(levels))
+    if not torch.is_tensor(levels) or levels.is_floating_point() or levels.dim() not in (2, 3) or 0 in levels.shape:
+        raise ValueError("gain_plane: an integer level map [B,hz,wz] (or one [hz,wz]) expected")
+    if levels.dim() == 2:
+        levels = levels.unsqueeze(0)
+    n = int(net.levels)
+    if n > 16:
+        raise ValueError(f"gain_plane: at most 16 levels fit the file's map, the model has {n}")
+    if int(levels.min()) < 0 or int(levels.max()) >= n:
+        raise ValueError(f"gain_plane: levels in [0, {n}) expected")
+    gains = net.Gain.detach().float().abs().cpu().reshape(-1)[:n].contiguous()
+    B, hz, wz = levels.shape
+    dev = net.device
+    levels = levels.to(torch.uint8).to(dev).contiguous()
+    if dev.type != "cuda":
+        return gains[levels.long()].repeat_interleave(4, 1).repeat_interleave(4, 2).unsqueeze(1).contiguous()
+    with torch.cuda.device(dev):
+        g = torch.empty(B, 1, 4 * hz, 4 * wz, dtype=torch.float32, device=dev)
+        if _lib.poison():
+            g.fill_(float("nan"))
+        _lib.call("mlic_roi_gain_plane", _stream(), C.c_void_p(levels.data_ptr()), B, hz, wz,
+                  (C.c_float * n)(*gains.tolist()), n, C.c_void_p(g.data_ptr()))
+        levels.record_stream(torch.cuda.current_stream())
+    return g
+
+
+def sq_err_roi(a, b, mask, layout: Optional[str] = None) -> torch.Tensor:
+    """Two uint8 image batches (any strides, read in place) and a mask [B,H,W] -> int64 [B,4] on their device:
+    {squared error inside the ROI, pixels inside, squared error outside, pixels outside}; the squared error is
+    summed over the three channels, in integers (exact).  Inside + outside is egress_u8's sq_err."""
+    a, layout = _u8_batch(a, layout, "sq_err_roi")
+    b, _ = _u8_batch(b, layout, "sq_err_roi")
+    mask = _mask_batch(mask, "sq_err_roi")
+    B = a.size(0)
+    H, W = _hw(a, layout)
+    if tuple(b.shape) != tuple(a.shape) or tuple(mask.shape) != (B, H, W):
+        raise ValueError(f"sq_err_roi: images of one shape and a mask {(B, H, W)} expected, got {tuple(a.shape)}, "
+                         f"{tuple(b.shape)}, {tuple(mask.shape)}")
+    b, mask = b.to(a.device), mask.to(a.device)
+    if not a.is_cuda:
+        d = _nchw(a, layout).to(torch.int64) - _nchw(b, layout).to(torch.int64)
+        sq = (d * d).sum(1)
+        inside = mask != 0
+        return torch.stack([(sq * inside).flatten(1).sum(1), inside.flatten(1).sum(1),
+                            (sq * ~inside).flatten(1).sum(1), (~inside).flatten(1).sum(1)], 1)
+    with torch.cuda.device(a.device):
+        out = torch.full((B, 4), -1, dtype=torch.int64, device=a.device)
+        _lib.call("mlic_image_sq_err_roi_u8", _stream(), C.c_void_p(a.data_ptr()), (C.c_int64 * 4)(*_strides(a, layout)),
+                  C.c_void_p(b.data_ptr()), (C.c_int64 * 4)(*_strides(b, layout)), C.c_void_p(mask.data_ptr()),
+                  (C.c_int64 * 3)(*mask.stride()), B, H, W, C.c_void_p(out.data_ptr()))
+        for t in (b, mask):
+            t.record_stream(torch.cuda.current_stream())
+    return out
+
+
+def psnr_roi(a, b, mask, layout: Optional[str] = None) -> List[Dict]:
+    """Per image {"psnr_roi", "psnr_bg", "sq_err_roi", "n_roi", "sq_err_bg", "n_bg"}: PSNR (max 255) inside and
+    outside the mask from sq_err_roi's exact sums; None for a side that holds no pixel."""
+    out = []
+    for si, ni, so, no in sq_err_roi(a, b, mask, layout).cpu().tolist():
+        out.append({"psnr_roi": psnr_from_sq_err(si, 3 * ni) if ni else None,
+                    "psnr_bg": psnr_from_sq_err(so, 3 * no) if no else None,
+                    "sq_err_roi": si, "n_roi": ni, "sq_err_bg": so, "n_bg": no})
+    return out
 
 
 # -------------------------------------------------------------------------------------------- codec
@@ -359,7 +533,7 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
 
 @torch.no_grad()
 def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
-                  max_passes: int = 8, return_info: bool = False):
+                  max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
@@ -368,14 +542,46 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     code again, at most max_passes times each), and level="auto" (VBR, needs max_bpp) picks per image the highest
     level whose unfiltered file fits.  An image gets the file it gets when coded alone; files come back in input
     order.  return_info=True: (files, info) with info[b] = {"bytes", "bpp", "passes", "level", "met"}; met says
-    whether the file is within the budget (True without one)."""
+    whether the file is within the budget (True without one).
+    roi=masks with roi_levels=(lo, hi) (a *_VBR model; not together with max_bpp or level): ROI coding.  masks:
+    uint8 / bool [B,H,W] (or one [H,W]), nonzero = inside the ROI.  Each 64 x 64 block of the image is coded at
+    level lo where it holds no ROI pixel and up to hi where it is all ROI (codec.roi_levels), and the file carries
+    the level map as a third string (its header level is hi); info[b] gains "roi_levels", the map."""
     img, layout = _u8_batch(imgs_u8, layout, "encode_images")
     _check_budget(max_bpp, max_passes)
     if isinstance(level, str) and max_bpp is None:
         raise ValueError("level='auto' needs max_bpp (the level is chosen from the budget)")
-    img = img.to(net.device)
     B = img.size(0)
     H, W = _hw(img, layout)
+    if (roi is None) != (roi_levels is None):
+        raise ValueError("roi= and roi_levels=(lo, hi) go together")
+    if roi is not None:
+        if max_bpp is not None:
+            raise ValueError("roi= together with max_bpp is not supported (ROI coding inside the rate loop)")
+        if level is not None:
+            raise ValueError("roi= together with level=: the levels of an ROI encode are roi_levels=(lo, hi)")
+        if not hasattr(net, "levels"):
+            raise ValueError("roi= given for a fixed-rate model: ROI coding needs a *_VBR model")
+        try:
+            lo, hi = roi_levels
+        except (TypeError, ValueError):
+            raise ValueError(f"roi_levels: a pair (lo, hi) expected, got {roi_levels!r}") from None
+        _check_roi_levels(lo, hi, "roi_levels")
+        if hi >= min(int(net.levels), 16):
+            raise ValueError(f"roi_levels: levels in [0, {min(int(net.levels), 16)}) expected, got ({lo}, {hi})")
+        mask = _mask_batch(roi, "encode_images roi")
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError(f"encode_images: roi must be a mask of shape {(B, H, W)}, got {tuple(mask.shape)}")
+        lmap = _roi_level_map(mask.to(net.device), int(lo), int(hi))
+        out = net.compress(ingest_u8(img.to(net.device), layout), gain_map=gain_plane(net, lmap))
+        ys, zs = out["strings"]
+        lmap = lmap.cpu().numpy()
+        files = [write_container_roi(H, W, out["shape"], ys[b], zs[b], int(hi), lmap[b]) for b in range(B)]
+        if not return_info:
+            return files
+        return files, [{"bytes": len(f), "bpp": 8.0 * len(f) / (H * W), "passes": 0, "level": int(hi), "met": True,
+                        "roi_levels": lmap[b]} for b, f in enumerate(files)]
+    img = img.to(net.device)
     if max_bpp is None:
         lv, kw = _levels(net, level, B)
         out = net.compress(ingest_u8(img, layout), **kw)
@@ -399,18 +605,31 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
     (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
     image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
-    [B,max H,max W,3] tensor.  Every file goes through the validating parser first."""
+    [B,max H,max W,3] tensor.  Every file goes through the validating parser first.  An ROI file (a *_VBR file
+    with a level map, encode_images(roi=...)) is decoded through the gain plane of its own map, and info[b] then
+    holds the map as "roi_levels"."""
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
     vbr = hasattr(net, "levels")
-    cs = [parse_container(f, vbr, net.levels if vbr else None, max_pixels) for f in files]
+    maps = [None] * len(files)
+    if vbr and any(is_roi_file(f) for f in files):
+        # ROI files carry a level map; a plain VBR file beside them decodes through a constant map of its level
+        cs = []
+        for b, f in enumerate(files):
+            c, maps[b] = parse_container_roi(f, min(int(net.levels), 16), max_pixels)
+            cs.append(c)
+    else:
+        cs = [parse_container(f, vbr, net.levels if vbr else None, max_pixels) for f in files]
     if len({(c.hz, c.wz) for c in cs}) != 1:
         raise ValueError(f"decode_images: the files must share one padded size, got z grids "
                          f"{sorted({(c.hz, c.wz) for c in cs})}")
     B = len(files)
     pairs = [_strings(f, c) for f, c in zip(files, cs)]
     kw = {"s": [c.level for c in cs]} if vbr else {}
+    if any(m is not None for m in maps):
+        lmap = np.stack([np.full((c.hz, c.wz), c.level, np.uint8) if m is None else m for c, m in zip(cs, maps)])
+        kw = {"gain_map": gain_plane(net, torch.from_numpy(lmap))}
     x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
     H, W = max(c.H for c in cs), max(c.W for c in cs)
     if ref is not None:
@@ -434,6 +653,8 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     for b, c in enumerate(cs):
         d = {"H": c.H, "W": c.W, "level": c.level if vbr else None, "bytes": len(files[b]),
              "bpp": 8.0 * len(files[b]) / (c.H * c.W)}
+        if maps[b] is not None:
+            d["roi_levels"] = maps[b]
         if sq is not None:
             d["sq_err"] = int(sq[b])
             d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W)

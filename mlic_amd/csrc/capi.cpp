@@ -220,6 +220,63 @@ int mlic_decompress(mlic_model* m, void* stream, const uint8_t* const* y, const 
   return mlic_decompress_v(m, stream, y, y_len, z, z_len, B, hz, wz, x_hat, sc.data());
 }
 
+// ROI coding: what the three _g entries refuse before any GPU call
+static Model& roi_model(mlic_model* m, const float* gain_plane, const char* who) {
+  Model& mod = impl(m);
+  if (!mod.cfg().vbr) throw Error(std::string("mlic: ") + who + ": a gain plane needs a *_VBR model, got " + mod.cfg().name);
+  if (gain_plane == nullptr) throw Error(std::string("mlic: ") + who + ": null gain plane");
+  return mod;
+}
+
+int mlic_forward_g(mlic_model* m, void* stream, const float* x, int B, int H, int W, float* x_hat, float* y_lik,
+                   float* z_lik, const float* gain_plane) {
+  return guard([&] {
+    Model& mod = roi_model(m, gain_plane, "forward_g");
+    MLIC_CHECK(x && B > 0, "bad arguments");
+    mod.forward(x, B, H, W, x_hat, y_lik, z_lik, nullptr, (hipStream_t)stream, gain_plane);
+  });
+}
+
+int mlic_compress_g(mlic_model* m, void* stream, const float* x, int B, int H, int W, const float* gain_plane) {
+  return guard([&] {
+    Model& mod = roi_model(m, gain_plane, "compress_g");
+    MLIC_CHECK(x && B > 0, "bad arguments");
+    mod.compress(x, B, H, W, nullptr, (hipStream_t)stream, gain_plane);
+  });
+}
+
+int mlic_decompress_g(mlic_model* m, void* stream, const uint8_t* const* y, const size_t* y_len,
+                      const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz, float* x_hat,
+                      const float* gain_plane) {
+  return guard([&] {
+    Model& mod = roi_model(m, gain_plane, "decompress_g");
+    MLIC_CHECK(y && y_len && z && z_len && x_hat && B > 0 && hz > 0 && wz > 0, "bad arguments");
+    for (int b = 0; b < B; ++b)
+      if (y[b] == nullptr)
+        throw Error("mlic: decompress_g: one y string per image expected (the batch-stream layout is not supported "
+                    "with a gain plane)");
+    mod.decompress(y, y_len, z, z_len, B, hz, wz, x_hat, nullptr, (hipStream_t)stream, false, gain_plane);
+  });
+}
+
+int mlic_image_roi_levels_u8(void* stream, const uint8_t* mask, const int64_t* mask_strides, int B, int H, int W, int lo,
+                             int hi, uint8_t* levels) {
+  return guard([&] { roi_levels_u8(mask, mask_strides, B, H, W, lo, hi, levels, (hipStream_t)stream); });
+}
+
+int mlic_roi_gain_plane(void* stream, const uint8_t* levels, int B, int hz, int wz, const float* gains_host,
+                        int n_levels, float* g) {
+  return guard([&] { roi_gain_plane(levels, B, hz, wz, gains_host, n_levels, g, (hipStream_t)stream); });
+}
+
+int mlic_image_sq_err_roi_u8(void* stream, const uint8_t* a, const int64_t* a_strides, const uint8_t* b,
+                             const int64_t* b_strides, const uint8_t* mask, const int64_t* mask_strides, int B, int H,
+                             int W, uint64_t* out) {
+  return guard([&] {
+    sq_err_roi_u8(a, a_strides, b, b_strides, mask, mask_strides, B, H, W, out, (hipStream_t)stream);
+  });
+}
+
 int mlic_run_module(mlic_model* m, void* stream, const char* which, int idx, const float* in0, const float* in1,
                     int B, int Cin, int H, int W, float* out) {
   return guard([&] { impl(m).run_module(which, idx, in0, in1, B, Cin, H, W, out, (hipStream_t)stream); });
@@ -832,6 +889,31 @@ int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, u
     ContainerInfo c;
     container_ok(container_parse(data, n, vbr != 0, (uint32_t)std::max(n_levels, 0), max_pixels, &c));
     to_abi(c, info);
+  });
+}
+
+int mlic_container_write_roi(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_t wz, const uint8_t* y,
+                             size_t y_len, const uint8_t* z, size_t z_len, const uint8_t* levels, uint8_t* out,
+                             size_t cap, size_t* len) {
+  return guard(
+      [&] { container_ok(container_write_roi(H, W, level, hz, wz, y, y_len, z, z_len, levels, out, cap, len)); });
+}
+
+int mlic_container_parse_roi(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                             mlic_container_roi_info* info, uint8_t* levels, size_t levels_cap) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_roi: null info");
+    ContainerInfo c;
+    size_t off = 0, len = 0;
+    container_ok(container_parse_roi(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &c, &off, &len));
+    to_abi(c, &info->file);
+    info->map_off = off;
+    info->map_len = len;
+    if (levels != nullptr && len != 0) {
+      const uint64_t cells = (uint64_t)c.hz * c.wz;
+      MLIC_CHECK(cells <= levels_cap, "container_parse_roi: levels buffer too small (h_z * w_z bytes)");
+      container_roi_unpack(data + off, cells, levels);
+    }
   });
 }
 

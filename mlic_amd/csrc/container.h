@@ -37,5 +37,25 @@ const char* container_write(uint32_t H, uint32_t W, int32_t level, uint32_t hz, 
 const char* container_parse(const uint8_t* data, size_t n, bool vbr, uint32_t n_levels, uint64_t max_pixels,
                             ContainerInfo* info);
 
+// The ROI file: the VBR file above with n_strings = 3.  The third string is the level map on the z grid:
+//     one version byte 0, then h_z * w_z levels of 4 bits each, row-major, high nibble first
+// (1 + ceil(h_z * w_z / 2) bytes; the low nibble of the last byte is 0 when the cell count is odd).  The level
+// word is always present (ROI files are VBR files) and holds the map's upper level.
+size_t container_roi_map_bytes(uint32_t hz, uint32_t wz);
+
+// levels: h_z * w_z bytes, one level per cell, each <= 15.  The *len / out / cap protocol of container_write.
+const char* container_write_roi(uint32_t H, uint32_t W, int32_t level, uint32_t hz, uint32_t wz, const uint8_t* y,
+                                size_t y_len, const uint8_t* z, size_t z_len, const uint8_t* levels, uint8_t* out,
+                                size_t cap, size_t* len);
+
+// Accepts 2 strings (*map_len = 0: a plain VBR file) or 3.  Refused beyond what container_parse refuses:
+// n_levels > 16, n_strings not 2 or 3, a map length that is not 1 + ceil(h_z * w_z / 2), a nonzero version byte,
+// a level >= n_levels, a nonzero padding nibble.  The map is data[*map_off, *map_off + *map_len), still packed.
+const char* container_parse_roi(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                ContainerInfo* info, size_t* map_off, size_t* map_len);
+
+// the packed map (version byte included) of a parsed file -> one byte per cell
+void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels);
+
 }  // namespace mlic
 #endif

@@ -214,7 +214,13 @@ struct QuantParams {
   const float* sc;  // [B] per-image VBR gain (mlicpp_vbr.py:137, Gain[s] or inputscale), when vbr
   const float* rs;  // [B] 1 / sc, computed once on the host in fp32 (the reference's 1 / scale)
   int C, H, W, B;
+  // ROI coding: the gain per latent pixel, [B][H][W], and its reciprocal plane (recip_plane); both or neither.
+  // When set (with vbr) the three kernels read sc / rs at their own pixel instead of at [b].
+  const float* scp;
+  const float* rsp;
 };
+// r[i] = 1.0f / g[i], correctly rounded (the host's fp32 1 / scale bit for bit)
+void recip_plane(const float* g, float* r, int64_t n, hipStream_t st);
 void quant_phase(const QuantParams& P, hipStream_t st);
 void phase_indexes(const QuantParams& P, hipStream_t st);
 void phase_dequant(const QuantParams& P, hipStream_t st);
@@ -305,6 +311,20 @@ void image_egress_u8(const float* src, const int64_t* src_strides, int B, int H,
 // overlap the n images at src, nor any image src_index names.  Checks its arguments before any HIP call.
 void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp, const float* w9,
                      float* dst, hipStream_t st);
+// ROI coding (roi.hip).  All three check their arguments before any HIP call and throw.
+// levels [B][hz][wz] (hz, wz = ceil(H / 64), ceil(W / 64)) of a uint8 mask read through element strides {image,
+// row, column}: level = lo + ceil((hi - lo) * count / area) per 64 x 64 cell clipped to the image, in integers
+constexpr int ROI_MAX_LEVELS = 16;  // a level is four bits in the file
+void roi_levels_u8(const uint8_t* mask, const int64_t* mask_strides, int B, int H, int W, int lo, int hi,
+                   uint8_t* levels, hipStream_t st);
+// g [B][4 hz][4 wz] = gains[levels[b][i >> 2][j >> 2]] (gains: n_levels <= 16 host floats, finite and positive)
+void roi_gain_plane(const uint8_t* levels, int B, int hz, int wz, const float* gains, int n_levels, float* g,
+                    hipStream_t st);
+// out [B][4] = {sq_err inside, pixels inside, sq_err outside, pixels outside} of two uint8 images ({image, row,
+// column, channel} strides each) split by a uint8 mask ({image, row, column}); exact integer sums
+void sq_err_roi_u8(const uint8_t* a, const int64_t* a_strides, const uint8_t* b, const int64_t* b_strides,
+                   const uint8_t* mask, const int64_t* mask_strides, int B, int H, int W, uint64_t* out,
+                   hipStream_t st);
 // mlic_set_kernel_option("image_io_path"): -1 = by layout (default), 0 = the general-stride kernels, 1 = the
 // interleaved (HWC) form, 2 = the planar (CHW) form; a forced form the layout does not fit is an error
 // GaussianConditional likelihood (vbr_scale != 1: of y*sc, s*sc, m*sc) and build_indexes, element-wise

@@ -767,6 +767,9 @@ __device__ __forceinline__ int scale_index(float s, const float* __restrict__ ta
   return idx;
 }
 
+// PLANE: the gain and its reciprocal are read at the element's own latent pixel (P.scp / P.rsp, ROI coding);
+// the expressions they enter are those of the per-image form, whose instruction stream does not change
+template <bool PLANE>
 __global__ void quant_phase_kernel(QuantParams P) {
   const int HW = P.H * P.W;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -778,7 +781,14 @@ __global__ void quant_phase_kernel(QuantParams P) {
   const bool mine = (P.phase == 0) == anc;
   const float y = P.y[(int64_t)b * P.y_bs + i];
   const float* pp = P.params + (int64_t)b * P.params_bs;
-  const float sc = P.vbr ? P.sc[b] : 1.0f, rs = P.vbr ? P.rs[b] : 1.0f;
+  float sc, rs;
+  if (PLANE) {
+    sc = P.scp[(int64_t)b * HW + p];
+    rs = P.rsp[(int64_t)b * HW + p];
+  } else {
+    sc = P.vbr ? P.sc[b] : 1.0f;
+    rs = P.vbr ? P.rs[b] : 1.0f;
+  }
   float* yh = P.yh + (int64_t)b * P.yh_bs + i;
   if (P.lik) {
     const float* pa = P.params_a + (int64_t)b * P.params_a_bs;
@@ -817,11 +827,16 @@ __global__ void quant_phase_kernel(QuantParams P) {
 void quant_phase(const QuantParams& P, hipStream_t st) {
   MLIC_CHECK(P.W % 2 == 0, "even latent width");
   const int64_t n = (int64_t)P.C * P.H * P.W;
-  hipLaunchKernelGGL(quant_phase_kernel, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  MLIC_CHECK((P.scp != nullptr) == (P.rsp != nullptr) && (P.scp == nullptr || P.vbr), "gain planes");
+  if (P.scp)
+    hipLaunchKernelGGL(quant_phase_kernel<true>, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  else
+    hipLaunchKernelGGL(quant_phase_kernel<false>, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
   HIP_OK(hipGetLastError());
 }
 
 // decoder: indexes of one phase (squeezed order), from the EP scales
+template <bool PLANE>
 __global__ void phase_indexes_kernel(QuantParams P) {
   const int HW = P.H * P.W, W2 = P.W / 2;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // squeezed index within image
@@ -832,7 +847,10 @@ __global__ void phase_indexes_kernel(QuantParams P) {
   const int h = r / W2, j = r % W2;
   const int w = 2 * j + ((P.phase == 0) ? (1 - (h & 1)) : (h & 1));
   const float s = P.params[(int64_t)b * P.params_bs + (int64_t)c * HW + h * P.W + w];
-  const int ix = scale_index(P.vbr ? s * P.sc[b] : s, P.table, P.ntable);
+  float se;
+  if (PLANE) se = s * P.scp[(int64_t)b * HW + h * P.W + w];
+  else se = P.vbr ? s * P.sc[b] : s;
+  const int ix = scale_index(se, P.table, P.ntable);
   const int64_t o = (int64_t)b * P.C * P.H * W2 + i;
   if (P.idx8) P.idx8[o] = (uint8_t)ix;
   else P.idx[o] = ix;
@@ -840,11 +858,16 @@ __global__ void phase_indexes_kernel(QuantParams P) {
 
 void phase_indexes(const QuantParams& P, hipStream_t st) {
   const int64_t n = (int64_t)P.C * P.H * (P.W / 2);
-  hipLaunchKernelGGL(phase_indexes_kernel, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  MLIC_CHECK(P.scp == nullptr || P.vbr, "gain planes");
+  if (P.scp)
+    hipLaunchKernelGGL(phase_indexes_kernel<true>, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  else
+    hipLaunchKernelGGL(phase_indexes_kernel<false>, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
   HIP_OK(hipGetLastError());
 }
 
 // decoder: yh at the phase's pixels = sym * rs + m (anchor phase also zeroes the others)
+template <bool PLANE>
 __global__ void phase_dequant_kernel(QuantParams P) {
   const int HW = P.H * P.W;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -861,12 +884,30 @@ __global__ void phase_dequant_kernel(QuantParams P) {
   const int64_t sq = (int64_t)b * P.C * HW / 2 + ((int64_t)c * P.H + h) * (P.W / 2) + (w >> 1);
   const float q = P.sym16 ? (float)P.sym16[sq] : (float)P.sym[sq];
   const float m = P.params[(int64_t)b * P.params_bs + (int64_t)(c + P.C) * HW + p];
-  *yh = P.vbr ? q * P.rs[b] + m : q + m;
+  if (PLANE) *yh = q * P.rsp[(int64_t)b * HW + p] + m;
+  else *yh = P.vbr ? q * P.rs[b] + m : q + m;
 }
 
 void phase_dequant(const QuantParams& P, hipStream_t st) {
   const int64_t n = (int64_t)P.C * P.H * P.W;
-  hipLaunchKernelGGL(phase_dequant_kernel, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  MLIC_CHECK(P.rsp == nullptr || P.vbr, "gain planes");
+  if (P.rsp)
+    hipLaunchKernelGGL(phase_dequant_kernel<true>, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  else
+    hipLaunchKernelGGL(phase_dequant_kernel<false>, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  HIP_OK(hipGetLastError());
+}
+
+// the reciprocal plane of a gain plane, once per call: the correctly rounded fp32 1 / g (hipcc's default for
+// fp32 division, as the ingest kernel's / 255), the host's `1.0f / scale` bit for bit
+__global__ void recip_plane_kernel(const float* __restrict__ g, float* __restrict__ r, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) r[i] = 1.0f / g[i];
+}
+
+void recip_plane(const float* g, float* r, int64_t n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(recip_plane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, r, n);
   HIP_OK(hipGetLastError());
 }
 

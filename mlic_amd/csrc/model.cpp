@@ -1339,7 +1339,13 @@ void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& 
     hp = &hoisted;
   }
   float* vbr_dev = nullptr;  // per-image VBR gains [2][B] (gain, 1 / gain)
-  if (L().vbr_on) {
+  const float* gplane = L().gplane;  // ROI coding: a gain per latent pixel instead, and its reciprocal plane
+  float* rplane = nullptr;
+  if (gplane) {
+    MLIC_CHECK(L().vbr_on, "gain plane without a VBR model");
+    rplane = L().arena.alloc((int64_t)L().B * HW);
+    if (!L().dry) recip_plane(gplane, rplane, (int64_t)L().B * HW, L().st);
+  } else if (L().vbr_on) {
     MLIC_CHECK((int)L().vbr_host.size() == 2 * L().B, "vbr scales");
     vbr_dev = L().arena.alloc(2 * L().B);
     if (!L().dry)
@@ -1369,7 +1375,9 @@ void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& 
       Q.ntable = 64;
       Q.vbr = L().vbr_on ? 1 : 0;
       Q.sc = vbr_dev;
-      Q.rs = vbr_dev + L().B;
+      Q.rs = vbr_dev ? vbr_dev + L().B : nullptr;
+      Q.scp = gplane;
+      Q.rsp = rplane;
       Q.phase = ph;
       View pn;
       if (ph == 1) {
@@ -1518,11 +1526,13 @@ void Model::ensure_chost(size_t n) {
   l.hc_cap = n;
 }
 
-void Model::set_vbr(const float* scales, int B) {
+void Model::set_vbr(const float* scales, int B, const float* gain_plane) {
   Lane& l = L();
   l.vbr_on = cfg_.vbr;
   l.vbr_host.assign(2 * B, 1.0f);
-  if (!l.vbr_on) return;
+  l.gplane = gain_plane;
+  MLIC_CHECK(gain_plane == nullptr || l.vbr_on, "a gain plane needs a *_VBR model");
+  if (!l.vbr_on || gain_plane) return;
   for (int b = 0; b < B; ++b) {
     const float s = scales ? scales[b] : 1.0f;
     // forward uses Gain[s] as stored (mlicpp_vbr.py:122-135); compress/decompress receive |Gain[s]|
@@ -1664,7 +1674,7 @@ void Model::over_lanes(int B, hipStream_t caller, F&& fn, int max_lanes) {
 
 // ------------------------------------------------------------------------------------- entry points
 void Model::forward(const float* x, int B, int H, int W, float* x_hat, float* y_lik, float* z_lik, const float* vbr_scales,
-                    hipStream_t st) {
+                    hipStream_t st, const float* gain_plane) {
   MLIC_CHECK(H % 64 == 0 && W % 64 == 0, "H and W must be multiples of 64 (pad like utils/testing.py:130-137)");
   // forward() runs on the caller's stream in lane 0 (torch-ordered)
   Lane& l = lane(0);
@@ -1676,7 +1686,7 @@ void Model::forward(const float* x, int B, int H, int W, float* x_hat, float* y_
     ~Restore() { l.st = s; l.prec_force = -1; tl_lane_ = nullptr; }
   } restore{l, own};
   l.st = st;  // caller's stream, including the legacy NULL stream torch uses by default
-  set_vbr(vbr_scales, B);
+  set_vbr(vbr_scales, B, gain_plane);
   range_clear(l);
   // The fp16 range guard needs a device-to-host read, i.e. a synchronisation of `st`; under stream
   // capture (hipGraph) there is none, and a captured forward cannot fall back: its flag stays set
@@ -1751,13 +1761,15 @@ static const char* kRangeMsg =
     "mlic: an activation of the entropy model exceeded the fp16 range of the split-fp16 kernels (|v| >= 65504); "
     "encode and decode this input with set_precision(0) (exact fp32 MFMA)";
 
-void Model::compress(const float* x, int B, int H, int W, const float* vbr_scales, hipStream_t st) {
+void Model::compress(const float* x, int B, int H, int W, const float* vbr_scales, hipStream_t st,
+                     const float* gain_plane) {
   MLIC_CHECK(H % 64 == 0 && W % 64 == 0, "H and W must be multiples of 64");
   MLIC_CHECK(!gc_.empty() && !eb_.empty(), "entropy tables not set: call update() first");
   enc_all_.assign(B, EncodedImage{});
-  const int64_t img = (int64_t)3 * H * W;
+  enc_plane_ = gain_plane != nullptr;
+  const int64_t img = (int64_t)3 * H * W, gp = (int64_t)(H / 16) * (W / 16);
   over_lanes(B, st, [&](Lane& l, int first, int cnt) {
-    set_vbr(vbr_scales ? vbr_scales + first : nullptr, cnt);
+    set_vbr(vbr_scales ? vbr_scales + first : nullptr, cnt, gain_plane ? gain_plane + first * gp : nullptr);
     compress_lane(x + first * img, cnt, H, W);
     for (int b = 0; b < cnt; ++b) enc_all_[first + b] = std::move(l.enc[b]);
   });
@@ -1868,11 +1880,13 @@ HostPool& Model::host_pool() {
 }
 
 void Model::decompress(const uint8_t* const* y, const size_t* ylen, const uint8_t* const* z, const size_t* zlen,
-                       int B, int hz, int wz, float* x_hat, const float* vbr_scales, hipStream_t st, bool batch_stream) {
+                       int B, int hz, int wz, float* x_hat, const float* vbr_scales, hipStream_t st, bool batch_stream,
+                       const float* gain_plane) {
   MLIC_CHECK(!gc_.empty() && !eb_.empty(), "entropy tables not set: call update() first");
-  const int64_t img = (int64_t)3 * 64 * hz * 64 * wz;
+  MLIC_CHECK(!(batch_stream && gain_plane), "a gain plane goes with per-image strings only");
+  const int64_t img = (int64_t)3 * 64 * hz * 64 * wz, gp = (int64_t)16 * hz * wz;
   over_lanes(B, st, [&](Lane& l, int first, int cnt) {
-    set_vbr(vbr_scales ? vbr_scales + first : nullptr, cnt);
+    set_vbr(vbr_scales ? vbr_scales + first : nullptr, cnt, gain_plane ? gain_plane + first * gp : nullptr);
     decompress_lane(batch_stream ? y : y + first, batch_stream ? ylen : ylen + first, z + first, zlen + first, cnt, hz,
                     wz, x_hat + first * img, batch_stream);
   }, batch_stream ? 1 : 16);
@@ -1880,6 +1894,7 @@ void Model::decompress(const uint8_t* const* y, const size_t* ylen, const uint8_
 
 std::string Model::batch_stream(int first, int count) const {
   MLIC_CHECK(first >= 0 && count >= 1 && first + count <= (int)enc_all_.size(), "batch_stream: image range");
+  MLIC_CHECK(!enc_plane_, "batch_stream: the last compress coded with a gain plane (per-image strings only)");
   const CoderView& v0 = enc_all_[first].y_in;
   const int64_t n_per = v0.n_per;
   for (int b = first; b < first + count; ++b)

@@ -156,6 +156,7 @@ struct Lane {
   bool dry = false;
   std::vector<float> vbr_host;  // [2][B]: per-image gain, then 1 / gain (uploaded by slice_loop)
   bool vbr_on = false;
+  const float* gplane = nullptr;  // ROI coding: this lane's images' gain plane [B][H/16][W/16] (device), or null
   std::vector<EncodedImage> enc;
   int32_t* h_sym = nullptr;    // decoder: z symbols; a phase's symbols when one does not fit int16
   int16_t* h_sym16 = nullptr;  // decoder: a phase's symbols (H2D)
@@ -197,16 +198,20 @@ class Model {
 
   // forward(): x [B,3,H,W] -> x_hat, y_lik [B,M,H/16,W/16], z_lik [B,N,H/64,W/64] (any may be null)
   // vbr_scales: per-image Gain (host array of B; null = 1 for all); only *_VBR models use it
+  // gain_plane (ROI coding, *_VBR models only): device fp32 [B][H/16][W/16], finite and positive, produced on
+  // `st`; when given it replaces vbr_scales in forward / compress / decompress (per-image strings only)
   void forward(const float* x, int B, int H, int W, float* x_hat, float* y_lik, float* z_lik, const float* vbr_scales,
-               hipStream_t st);
+               hipStream_t st, const float* gain_plane = nullptr);
   // compress(): network + rANS; results readable with encoded(b)
-  void compress(const float* x, int B, int H, int W, const float* vbr_scales, hipStream_t st);
+  void compress(const float* x, int B, int H, int W, const float* vbr_scales, hipStream_t st,
+                const float* gain_plane = nullptr);
   const EncodedImage& encoded(int b) const { return enc_all_.at(b); }
   // decompress(): y/z byte streams per image -> x_hat [B,3,4*16*hz,4*16*wz]
   // batch_stream: y[0] is ONE stream holding the whole batch in the reference's order (mlicpp.py:215,
   // 279-281: phase-major, image-minor); decoded on one lane (the stream is sequential)
   void decompress(const uint8_t* const* y, const size_t* ylen, const uint8_t* const* z, const size_t* zlen, int B,
-                  int hz, int wz, float* x_hat, const float* vbr_scales, hipStream_t st, bool batch_stream = false);
+                  int hz, int wz, float* x_hat, const float* vbr_scales, hipStream_t st, bool batch_stream = false,
+                  const float* gain_plane = nullptr);
   // the last compress()'s images [first, first + count) coded into ONE y stream in the reference's
   // batched order (mlicpp.py:215, 279-281): byte-identical to what the reference's compress() emits for
   // that batch when it codes the same symbols
@@ -358,7 +363,8 @@ class Model {
   void ensure_host(size_t n);
   void ensure_chost(size_t n);
   static int phase_d2h_mode();
-  void set_vbr(const float* scales, int B);
+  void set_vbr(const float* scales, int B, const float* gain_plane = nullptr);
+  bool enc_plane_ = false;  // the last compress() coded with a gain plane (batch_stream() refuses it)
 };
 
 }  // namespace mlic

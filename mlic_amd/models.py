@@ -159,6 +159,23 @@ class MLICPlusPlus(nn.Module):
         """Per-image VBR gain (float32 [B]); 1 for fixed-rate models."""
         return np.ones(B, np.float32)
 
+    def _gain_plane(self, gain_map, B: int, hy: int, wy: int, dev: torch.device):
+        """ROI coding: the checked gain plane (contiguous fp32 [B,hy,wy] on dev) or None.  Every refusal is a
+        ValueError raised before anything touches the GPU."""
+        if gain_map is None:
+            return None
+        if not self.cfg.vbr:
+            raise ValueError(f"gain_map given for a fixed-rate model ({self.model_name}): ROI coding needs a *_VBR model")
+        if not torch.is_tensor(gain_map) or gain_map.dtype != torch.float32:
+            raise ValueError(f"gain_map: a float32 tensor expected, got "
+                             f"{gain_map.dtype if torch.is_tensor(gain_map) else type(gain_map).__name__}")
+        if tuple(gain_map.shape) not in ((B, 1, hy, wy), (B, hy, wy)):
+            raise ValueError(f"gain_map: shape {(B, 1, hy, wy)} or {(B, hy, wy)} expected (the latent grid, H/16 x W/16), "
+                             f"got {tuple(gain_map.shape)}")
+        if not gain_map.is_cuda or gain_map.device != dev:
+            raise ValueError(f"gain_map is on {gain_map.device}: a CUDA tensor on {dev} expected")
+        return gain_map.reshape(B, hy, wy).contiguous()
+
     def set_precision(self, mode: int):
         """Dense-conv arithmetic: 2 = split-fp16 MFMA "f16x3" (default), 0 = fp32 MFMA."""
         self._precision = int(mode)
@@ -219,14 +236,19 @@ class MLICPlusPlus(nn.Module):
         B, _, H, W = x.shape
         if H % 64 or W % 64:
             raise ValueError("H and W must be multiples of 64 (pad as utils/testing.py:130-137)")
+        g = self._gain_plane(kw.pop("gain_map", None), B, H // 16, W // 16, x.device)
         h = self._ensure_handle(x.device)
         x = x.contiguous().float()
         x_hat = self._out(x.shape, x.device)
         y_lik = self._out((B, self.M, H // 16, W // 16), x.device)
         z_lik = self._out((B, self.N, H // 64, W // 64), x.device)
         sc = self._vbr_scales(B, **kw)
-        _lib.call("mlic_forward_v", h, self._stream(), x.data_ptr(), B, H, W, x_hat.data_ptr(), y_lik.data_ptr(),
-                  z_lik.data_ptr(), sc.ctypes.data)
+        if g is not None:
+            _lib.call("mlic_forward_g", h, self._stream(), x.data_ptr(), B, H, W, x_hat.data_ptr(), y_lik.data_ptr(),
+                      z_lik.data_ptr(), g.data_ptr())
+        else:
+            _lib.call("mlic_forward_v", h, self._stream(), x.data_ptr(), B, H, W, x_hat.data_ptr(), y_lik.data_ptr(),
+                      z_lik.data_ptr(), sc.ctypes.data)
         return {"x_hat": x_hat, "likelihoods": {"y_likelihoods": y_lik, "z_likelihoods": z_lik}}
 
     def update(self, scale_table=None, force: bool = False) -> bool:
@@ -282,16 +304,22 @@ class MLICPlusPlus(nn.Module):
         (mlicpp.py:215, 279-281; phase-major, image-minor).  decompress() accepts both.
         cost_time brackets the call with the caller's stream synchronised (the reference synchronises the
         whole device, mlicpp.py:200, 282; a stream keeps concurrent callers on other streams apart)."""
+        B, _, H, W = x.shape
+        g = self._gain_plane(kw.pop("gain_map", None), B, H // 16, W // 16, x.device)
+        if g is not None and batch_stream:
+            raise ValueError("batch_stream=True is not supported with gain_map (ROI coding writes per-image strings)")
         torch.cuda.current_stream(x.device).synchronize()
         t0 = time.time()
-        B, _, H, W = x.shape
         if H % 64 or W % 64:
             raise ValueError("H and W must be multiples of 64")
         h = self._ensure_handle(x.device)
         self._push_tables(h)
         x = x.contiguous().float()
         sc = self._vbr_scales(B, **kw)
-        _lib.call("mlic_compress_v", h, self._stream(), x.data_ptr(), B, H, W, sc.ctypes.data)
+        if g is not None:
+            _lib.call("mlic_compress_g", h, self._stream(), x.data_ptr(), B, H, W, g.data_ptr())
+        else:
+            _lib.call("mlic_compress_v", h, self._stream(), x.data_ptr(), B, H, W, sc.ctypes.data)
         ys, zs = [], []
         for b in range(B):
             yl, zl = C.c_size_t(), C.c_size_t()
@@ -314,14 +342,17 @@ class MLICPlusPlus(nn.Module):
     def decompress(self, strings, shape, **kw):
         """mlicpp.py:292-378."""
         dev = self.device
-        torch.cuda.current_stream(dev).synchronize()
-        t0 = time.time()
         ys, zs = list(strings[0]), list(strings[1])
         B = len(zs)
         single = len(ys) == 1 and B > 1  # the reference's batched layout (mlicpp.py:306-307)
         if len(ys) != B and not single:
             raise ValueError("expected one y stream per image, or one stream for the whole batch")
         hz, wz = int(shape[0]), int(shape[1])
+        g = self._gain_plane(kw.pop("gain_map", None), B, 4 * hz, 4 * wz, dev)
+        if g is not None and single:
+            raise ValueError("the batch-stream layout (one y stream for the batch) is not supported with gain_map")
+        torch.cuda.current_stream(dev).synchronize()
+        t0 = time.time()
         h = self._ensure_handle(dev)
         self._push_tables(h)
         x_hat = self._out((B, 3, hz * 64, wz * 64), dev)
@@ -332,7 +363,9 @@ class MLICPlusPlus(nn.Module):
         yl = (C.c_size_t * B)(*[len(s) for s in ys])
         zl = (C.c_size_t * B)(*[len(s) for s in zs])
         sc = self._vbr_scales(B, **kw)
-        if single:
+        if g is not None:
+            _lib.call("mlic_decompress_g", h, self._stream(), yp, yl, zp, zl, B, hz, wz, x_hat.data_ptr(), g.data_ptr())
+        elif single:
             _lib.call("mlic_decompress_batch_stream", h, self._stream(), C.cast(ybufs[0], C.c_void_p), len(ys[0]), zp,
                       zl, B, hz, wz, x_hat.data_ptr(), sc.ctypes.data)
         else:
@@ -415,14 +448,18 @@ class MLICPlusPlusVbr(MLICPlusPlus):
         out = np.where(ins != 0, ins, g[lv]).astype(np.float32)
         return np.ascontiguousarray(out)
 
-    def forward(self, x, stage: int = 2, s=1, inputscale=0):
-        return super().forward(x, stage=stage, s=s, inputscale=inputscale)
+    # gain_map (ROI coding): a CUDA fp32 tensor [B,1,H/16,W/16] or [B,H/16,W/16] of finite positive gains, one
+    # per latent pixel; when given it overrides s / inputscale (codec.gain_plane builds it from a level map)
+    def forward(self, x, stage: int = 2, s=1, inputscale=0, gain_map=None):
+        return super().forward(x, stage=stage, s=s, inputscale=inputscale, gain_map=gain_map)
 
-    def compress(self, x, stage: int = 2, s=1, inputscale=0, batch_stream: bool = False):
-        return super().compress(x, batch_stream=batch_stream, stage=stage, s=s, inputscale=inputscale, coder=True)
+    def compress(self, x, stage: int = 2, s=1, inputscale=0, batch_stream: bool = False, gain_map=None):
+        return super().compress(x, batch_stream=batch_stream, stage=stage, s=s, inputscale=inputscale, coder=True,
+                                gain_map=gain_map)
 
-    def decompress(self, strings, shape, stage: int = 2, s=1, inputscale=0):
-        return super().decompress(strings, shape, stage=stage, s=s, inputscale=inputscale, coder=True)
+    def decompress(self, strings, shape, stage: int = 2, s=1, inputscale=0, gain_map=None):
+        return super().decompress(strings, shape, stage=stage, s=s, inputscale=inputscale, coder=True,
+                                  gain_map=gain_map)
 
 
 class MLICPlusPlusSDVbr(MLICPlusPlusVbr):

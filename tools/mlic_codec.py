@@ -7,6 +7,10 @@
     ... --max-bpp X [--max-passes N]: encode under a budget of X bits per pixel (the whole file): while the file
         is above it, the 3x3 Gaussian prefilter and another encode, at most N times (default 8)
     ... --level auto (with --max-bpp): the highest level of a *_VBR model whose unfiltered file fits
+    ... --roi MASK --roi-levels LO HI (encode, a *_VBR model): ROI coding.  MASK is an image of the picture's size,
+        read as images are, first channel, nonzero = inside the region of interest: 64 x 64 blocks outside it are
+        coded at level LO, blocks inside at up to HI.  The file carries the level map; decode needs no flag
+    python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR      what the file says (and its level map)
 
 Binary PPM (P6, maxval 255) is read and written here; any other format goes through PIL when it imports.
 """
@@ -135,17 +139,34 @@ def _budget(v: str) -> float:
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["encode", "decode"])
+    ap.add_argument("mode", choices=["encode", "decode", "info"])
     ap.add_argument("src")
-    ap.add_argument("dst")
+    ap.add_argument("dst", nargs="?")
     ap.add_argument("--model", default="MLICPP_L")
-    g = ap.add_mutually_exclusive_group(required=True)
+    g = ap.add_mutually_exclusive_group()
     g.add_argument("--checkpoint")
     g.add_argument("--synthetic", type=int, metavar="SEED")
     ap.add_argument("--level", type=_level, default=None, metavar="N|auto")
     ap.add_argument("--max-bpp", type=_budget, default=None, metavar="X")
     ap.add_argument("--max-passes", type=int, default=8, metavar="N")
+    ap.add_argument("--roi", default=None, metavar="MASK")
+    ap.add_argument("--roi-levels", type=int, nargs=2, default=None, metavar=("LO", "HI"))
     args = ap.parse_args(argv)
+    if args.mode != "info" and args.dst is None:
+        ap.error(f"{args.mode} needs a destination file")
+    if args.mode != "info" and args.checkpoint is None and args.synthetic is None:
+        ap.error("one of the arguments --checkpoint --synthetic is required")
+    if args.mode == "info" and args.dst is not None:
+        ap.error("info takes one file")
+    if (args.roi is None) != (args.roi_levels is None):
+        ap.error("--roi and --roi-levels go together")
+    if args.roi is not None:
+        if args.mode != "encode":
+            ap.error("--roi goes with encode (a decode reads the map from the file)")
+        if args.max_bpp is not None or args.level is not None:
+            ap.error("--roi goes with --roi-levels alone, not with --level or --max-bpp")
+        if not 0 <= args.roi_levels[0] <= args.roi_levels[1]:
+            ap.error("--roi-levels: 0 <= LO <= HI expected")
     if args.level == "auto" and args.max_bpp is None:
         ap.error("--level auto needs --max-bpp")
     if args.max_passes < 0:
@@ -155,14 +176,36 @@ def parse_args(argv=None):
     return args
 
 
+def _map_lines(lv) -> str:
+    return "\n".join("  " + " ".join(f"{int(v):x}" for v in row) for row in lv)
+
+
 def main(argv=None):
     args = parse_args(argv)
     from mlic_amd import codec
+    if args.mode == "info":
+        from mlic_amd import spec
+        with open(args.src, "rb") as f:
+            data = f.read()
+        vbr = bool(spec.get_config(args.model).vbr)
+        d = codec.peek(data, vbr=vbr, n_levels=len(spec.vbr_lambdas(args.model)) if vbr else None)
+        print(f"{args.src}: {d['H']} x {d['W']}, level {d['level']}, z grid {d['shape'][0]} x {d['shape'][1]}, "
+              f"y {d['y_len']} B, z {d['z_len']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
+        if "roi_levels" in d:
+            print(f"level map ({d['shape'][0]} x {d['shape'][1]} cells of 64 x 64 pixels):\n" + _map_lines(d["roi_levels"]))
+        return
     if args.mode == "encode":
         img = load_image(args.src)
         net = load_model(args)
+        roi = None
+        if args.roi is not None:
+            roi = np.ascontiguousarray(load_image(args.roi)[:, :, 0])
+            if roi.shape != img.shape[:2]:
+                raise SystemExit(f"{args.roi}: the mask is {roi.shape[0]} x {roi.shape[1]}, the image "
+                                 f"{img.shape[0]} x {img.shape[1]}")
         files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
-                                          max_passes=args.max_passes, return_info=True)
+                                          max_passes=args.max_passes, return_info=True, roi=roi,
+                                          roi_levels=None if roi is None else tuple(args.roi_levels))
         data = files[0]
         with open(args.dst, "wb") as f:
             f.write(data)
@@ -171,6 +214,8 @@ def main(argv=None):
         if args.max_bpp is not None:
             line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
                      f"{'met' if info[0]['met'] else 'not met'}")
+        if roi is not None:
+            line += f", ROI levels {args.roi_levels[0]}..{args.roi_levels[1]}:\n" + _map_lines(info[0]["roi_levels"])
         print(line)
     else:
         with open(args.src, "rb") as f:
