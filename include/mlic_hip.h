@@ -152,7 +152,8 @@ int mlic_set_poison(mlic_model* m, int on);
  * one.  The environment is read once per process, at the library's first use.  A value of -1 (and for
  * "chain_nj" 0 too) returns an option to its environment variable or default; an unknown name, or an
  * "image_io_path" outside [-1, 2], is an error and changes nothing.  "x4_halo" = the conv_x4 kernel's
- * halo-staged B operand for K x K stride-1 convs (1 on, 0 off, -1 default = $MLIC_X4_HALO or on);
+ * halo-staged B operand for K x K stride-1 convs (1 on, 0 off, -1 default = $MLIC_X4_HALO or on for 5 x 5
+ * and 3 x 3; $MLIC_X4_HALO=5: 5 x 5 only) -- the same bits while the K loop is unsplit;
  * "linatt_fused" = the linear attention's output written straight into the
  * reprojection conv's packed operand ($MLIC_LINATT_FUSED); "dw_strip" = the register-strip depthwise
  * 3x3 for stride-1 planes up to 64 columns ($MLIC_DW_STRIP); "x4_splitk" = split-K for few-tile
@@ -183,8 +184,9 @@ int mlic_set_poison(mlic_model* m, int on);
  * $MLIC_GDN_SKIP or on; 0 = its own launch; the same bits) */
 int mlic_set_kernel_option(const char* name, int value);
 /* the effective value of a mlic_set_kernel_option name as the next call would see it, after the
- * option's own rule: what was set, else the environment, else the default ("x4_halo": 0 off, 1 = 5 x 5
- * only, 2 = 3 x 3 too; "chain_nj": 1 or 2; "narrow_limit": 1 .. 32767; the on / off switches: 0 or 1) */
+ * option's own rule: what was set, else the environment, else the default ("x4_halo": 0 off, 1 = the
+ * default forms, 2 = forced on, 5 = 5 x 5 only; "chain_nj": 1 or 2; "narrow_limit": 1 .. 32767; the on / off
+ * switches: 0 or 1) */
 int mlic_get_kernel_option(const char* name, int* value);
 /* 1 when this library holds the A/B-only kernel families (v1 split-fp16 tiles = precision 1, the halo
  * tiles = conv impl 6, the VALU local attention = local-attention impl 0; `make AB=1`), else 0: the

@@ -38,6 +38,42 @@ constexpr int BN = TR * TC;            // 256 pixels
 constexpr int ROWB = 128;              // LDS row: 32 hi + 32 lo halves
 constexpr int ROWH = 64;               // halves per row
 
+// The HALO form's B image (below): row pitch and granule placement, A/B builds.
+//   MLIC_X4_HALO_PITCH  144 (default): line L, granule g at L * 144 + hgran(g), no XOR -- a tap's shift is
+//                       a constant byte offset, so a step's B fragment reads are one per-lane base plus
+//                       immediates.  128: the XOR-swizzled 128-byte rows of the per-tap image (the round-4
+//                       form: line index and swizzle recomputed per read).
+//   MLIC_X4_HALO_SKEW   1 (default, pitch 144 only): odd granules sit 256 bytes further on (hgran), which
+//                       keeps the fragment reads conflict-free under ds_read_b128's lane groups ({0-3, 12-15,
+//                       20-27}, ...: a group mixes rows 0-3, 12-15 of granule G with rows 4-11 of granule
+//                       G + 1, and 36 r mod 64 collides with 36 r' + 4 for 7 of those 8 rows).  0: granule g
+//                       at g * 16 (2-way conflicts on those reads).
+#ifndef MLIC_X4_HALO_PITCH
+#define MLIC_X4_HALO_PITCH 144
+#endif
+#ifndef MLIC_X4_HALO_SKEW
+#define MLIC_X4_HALO_SKEW (MLIC_X4_HALO_PITCH == 144)
+#endif
+constexpr int HPITCH = MLIC_X4_HALO_PITCH;
+constexpr bool HPAD = HPITCH != ROWB;  // the padded, XOR-free image
+constexpr bool HSKEW = MLIC_X4_HALO_SKEW;
+static_assert(HPITCH == ROWB || (HPITCH >= ROWB + 16 && HPITCH % 16 == 0), "x4 halo pitch");
+static_assert(!HSKEW || HPITCH == 144, "x4 halo skew: 9-granule rows");
+// byte offset of logical granule g within its line (padded image).  Skewed, in 16-byte units: 0 16 1 17 |
+// 4 20 5 21 -- pairs (2i, 2i + 1) are 256 bytes apart (same banks: the 16 lanes of a ds_read_b128 group
+// then see 16 distinct rows at one granule offset), all 8 differ mod 9 (no two (line, granule) pieces
+// share a place, across both slots: the slots are one image of 2 * HLINES lines), and lo - hi = 64 bytes
+__host__ __device__ constexpr int hgran(int g) {
+  return (HSKEW ? ((g >> 1) & 1) + (g >> 2) * 4 + (g & 1) * 16 : g) * 16;
+}
+constexpr int HLO = hgran(4) - hgran(0);  // hi -> lo fragment of one lane
+static_assert(hgran(5) - hgran(1) == HLO && hgran(6) - hgran(2) == HLO && hgran(7) - hgran(3) == HLO, "x4 halo lo offset");
+constexpr int HTAIL = (HPAD && hgran(7) + 16 > HPITCH) ? hgran(7) + 16 - HPITCH : 0;  // bytes past the last line's row
+// LDS bytes of the HALO form: 2 A slots + 2 halo slots
+constexpr int x4_halo_lds(int K, int bm) {
+  return 2 * bm * ROWB + 2 * (TR + K - 1) * (TC + K - 1) * HPITCH + HTAIL;
+}
+
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
 
 __device__ __forceinline__ void glds16(const void* src, void* lds) {
@@ -74,7 +110,8 @@ __device__ __forceinline__ half8 lds_frag(const char* base, int row, int granule
 // chunk as the tile's (8 + K - 1) x (32 + K - 1) halo of packed lines (K = 3: 340 lines, 43.5 KB), and
 // every tap reads its fragments from that image at the tap's (ky, kx) shift -- instead of 256 lines
 // per tap (K^2 x the L2 -> LDS bytes and VMEM instructions for B).  The next chunk's halo is loaded one
-// piece per thread per step, spread over the current chunk's taps, into the other halo slot.
+// piece per thread per step, spread over the current chunk's taps, into the other halo slot.  The halo image
+// has its own layout (144-byte rows, no XOR: MLIC_X4_HALO_PITCH above), in which a tap's shift is a constant.
 // diagnostics builds only (-DMLIC_X4_ABL_RS=mask, never the product): 1 = no staging in the K loop
 // (the prologue's LDS images are re-read every step), 2 = no MFMAs (fragment reads kept alive), 4 = no
 // per-step barrier -- wrong results, timing decomposition of the register-staged loop
@@ -104,8 +141,9 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
   constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB;
   constexpr int NAB = RS ? 2 : 3;  // A ring slots
   constexpr int HR = TR + K - 1, HC = TC + K - 1, HLINES = HR * HC;  // HALO: the chunk's halo image
-  constexpr int BSLOT = HALO ? HLINES * ROWB : B_BYTES;
-  constexpr int B_OFF = NAB * A_BYTES, LDS = NAB * A_BYTES + 2 * BSLOT;
+  constexpr int BSLOT = HALO ? HLINES * HPITCH : B_BYTES;
+  constexpr int B_OFF = NAB * A_BYTES, LDS = NAB * A_BYTES + 2 * BSLOT + (HALO ? HTAIL : 0);
+  static_assert(!HALO || LDS == x4_halo_lds(K, BM), "x4 halo: the launch rule's footprint");
   constexpr int NA = A_BYTES / 1024 / 8;  // 1 KB glds instructions per wave for A
   constexpr int NB = B_BYTES / 1024 / 8;  // ... for B
   static_assert(NA >= 1 && NB == 4 && LDS <= 160 * 1024, "x4 tile");
@@ -211,7 +249,8 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
     };
     auto hdst = [&](int q, int slot) __attribute__((always_inline)) {
       const int id = q * X4T + tid, line = id >> 3;
-      return sm + B_OFF + slot * BSLOT + line * ROWB + (((id & 7) ^ swz(line)) << 4);
+      if constexpr (HPAD) return sm + B_OFF + slot * BSLOT + line * HPITCH + hgran(id & 7);
+      else return sm + B_OFF + slot * BSLOT + line * ROWB + (((id & 7) ^ swz(line)) << 4);
     };
     auto hvalid = [&](int q) __attribute__((always_inline)) { return q * X4T + tid < HLINES * 8; };
     // DIR: tile pixel dn = 64 (wave & 3) + lane (flat pixel dp, clamped into the image: the ragged
@@ -327,6 +366,9 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
     // hook: the step's staging work (next slot's LDS stores, the loads two steps ahead), issued after
     // the first pixel group's MFMAs, so that the step opens with its fragment reads and the LDS
     // latency they expose overlaps the staging's register waits instead of following them
+    // (hlane, padded halo image: byte offset of this lane's fragment of the wave's first pixel group at tap (0, 0))
+    static_assert(WN % TC == 0, "x4: a wave's pixels are whole tile rows");
+    const int hlane = (wn * (WN / TC) * HC + l16) * HPITCH + hgran(G);
     auto mfma_step = [&](int s, auto jh_c, auto&& hook) {
       constexpr int JH = decltype(jh_c)::value;  // the pixel group after whose MFMAs the staging runs
       const char* As = sm + (s & 1) * A_BYTES;
@@ -343,6 +385,13 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
       auto brow = [&](int n) __attribute__((always_inline)) {
         return HALO ? (n / TC) * HC + (n % TC) + tapoff : n;
       };
+      // padded halo image: the B fragment (hi, or lo) of pixel group j sits at the lane's base (hlane) plus
+      // the step's slot and tap shift -- one value per step -- plus compile-time offsets
+      constexpr bool HP = HALO && HPAD;
+      const char* Bp = HP ? Bs + hlane + tapoff * HPITCH : nullptr;
+      auto hfrag = [&](int j, int lo) __attribute__((always_inline)) {
+        return *reinterpret_cast<const half8*>(Bp + ((j * 16 / TC) * HC + j * 16 % TC) * HPITCH + lo * HLO);
+      };
       half8 ah[TM], al[TM];
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
@@ -351,14 +400,24 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
         al[i] = lds_frag(As, row, G + 4);
       }
       half8 bh[2], bl[2];
-      bh[0] = lds_frag(Bs, brow(wn * WN + l16), G);
-      bl[0] = lds_frag(Bs, brow(wn * WN + l16), G + 4);
+      if constexpr (HP) {
+        bh[0] = hfrag(0, 0);
+        bl[0] = hfrag(0, 1);
+      } else {
+        bh[0] = lds_frag(Bs, brow(wn * WN + l16), G);
+        bl[0] = lds_frag(Bs, brow(wn * WN + l16), G + 4);
+      }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         if (j + 1 < TN) {
-          const int n = brow(wn * WN + (j + 1) * 16 + l16);
-          bh[(j + 1) & 1] = lds_frag(Bs, n, G);
-          bl[(j + 1) & 1] = lds_frag(Bs, n, G + 4);
+          if constexpr (HP) {
+            bh[(j + 1) & 1] = hfrag(j + 1, 0);
+            bl[(j + 1) & 1] = hfrag(j + 1, 1);
+          } else {
+            const int n = brow(wn * WN + (j + 1) * 16 + l16);
+            bh[(j + 1) & 1] = lds_frag(Bs, n, G);
+            bl[(j + 1) & 1] = lds_frag(Bs, n, G + 4);
+          }
         }
         if constexpr ((MLIC_X4_ABL_RS & 2) != 0) {
           asm volatile("" :: "v"(bh[j & 1]), "v"(bl[j & 1]));
@@ -918,24 +977,29 @@ __global__ __launch_bounds__(256) void x4_split_reduce_kernel(ConvParams P, cons
 static bool x4_rs() { return opt(OPT_X4_RS) != 0; }
 
 // the halo-staged B operand (conv_x4_kernel HALO) for a packed K x K stride-1 conv whose LDS images fit;
-// $MLIC_X4_HALO=0: B staged per tap (A/B switch).  OPT_X4_HALO: 0 = off, 1 = 5 x 5 only (the default),
-// 2 = 3 x 3 too ($MLIC_X4_HALO=2; the option's 1 means 3 x 3 too)
+// $MLIC_X4_HALO=0: B staged per tap (A/B switch).  OPT_X4_HALO: 0 = off; 1 (the default) = every form that
+// measured faster, since round 10 both 5 x 5 and 3 x 3; 2 = every K x K that fits (what the option's 1 sets:
+// the same convs as 1 today); 5 = 5 x 5 only ($MLIC_X4_HALO=5: the default up to round 9, kept as an A/B arm)
 template <int K, int BM>
 constexpr bool x4_halo_fits() {
-  constexpr int a = 2 * BM * ROWB, h = 2 * (TR + K - 1) * (TC + K - 1) * ROWB;
-  return K > 1 && a + h <= 160 * 1024;
+  return K > 1 && x4_halo_lds(K, BM) <= 160 * 1024;
 }
-// Measured (tools/gpu/r4_halo.sh, 8 images, profiles/r04/ab/): 5x5 reprojection 320 -> 320 at 68 x 120
-// 1396 -> 1303 us; 3x3 g_s subpel conv 192 -> 768 at 272 x 480 7146 -> 7215 us and at 136 x 240 2133 ->
-// 2115 us (the per-tap fragment addresses become runtime: the swizzle of a tap-shifted line is
-// recomputed per read, which eats the saved B loads).  Default: 5x5 only; "x4_halo" = 1 forces it for
-// 3x3 too (A/B), 0 turns it off.
+// Round 4, on the XOR-swizzled image (pitch 128, profiles/r04/ab/, 8 images): 5x5 reprojection 320 -> 320 at
+// 68 x 120 1396 -> 1303 us; 3x3 g_s subpel conv 192 -> 768 at 272 x 480 7146 -> 7215 us (the swizzle of a
+// tap-shifted line is recomputed per read, which eats the saved B loads): 5x5 only.
+// Round 10, on the padded image (pitch 144 + skewed granules: the reads are a base plus immediates and
+// conflict-free; profiles/r10/): per tap | XOR halo | padded halo, conv + pack, one box, 3 rounds --
+// 3x3 192 -> 768 at 272 x 480 7.21-7.26 | 7.35-7.39 | 7.20-7.26 ms (equal to per tap), at 136 x 240
+// 1.99-2.00 | 2.02-2.03 | 1.97-1.98 ms; 5x5 288 -> 96 at 68 x 120 484-492 | 469-471 | 445-446 us.  In the timed
+// configuration, where other request streams share L2 and the address units, 3x3 on the halo form (1/9 of the
+// B loads) is worth +2 % (main line 114.5-115.1 against 112.1-112.5 img/s, four alternating rounds), so it is
+// on by default.
 static bool x4_halo(const ConvParams& P, bool hi) {
   const int setting = opt(OPT_X4_HALO);
   if (setting == 0 || P.K == 1 || P.stride != 1) return false;
-  if (P.K == 3 && setting != 2) return false;
+  if (P.K == 3 && setting == 5) return false;
   const int bm = x4_bm(P.Cout);
-  return 2 * bm * ROWB + 2 * (TR + P.K - 1) * (TC + P.K - 1) * ROWB <= 160 * 1024;
+  return x4_halo_lds(P.K, bm) <= 160 * 1024;
 }
 
 // $MLIC_X4_DIRECT=0: 1x1 layers read the packed copy too (A/B switch)

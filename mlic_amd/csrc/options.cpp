@@ -18,7 +18,8 @@ int flag(int v, const char* e, int d) { return v >= 0 ? v != 0 : env_int(e, d) !
 int lead0(int, const char* e, int) { return !(e && e[0] == '0'); }
 int is1(int, const char* e, int d) { return env_int(e, d) == 1; }
 int str(int, const char* e, int) { return e != nullptr; }  // a string switch: opt_str, parsed beside its user
-// internal 0 = off, 1 = 5 x 5 only, 2 = 3 x 3 too; the option's 1 means 3 x 3 too
+// internal 0 = off, 1 = the default forms (5 x 5 and, since round 10, 3 x 3: conv_x4.hip x4_halo), 2 = every
+// K x K that fits (the option's 1), 5 = 5 x 5 only ($MLIC_X4_HALO=5, an A/B arm)
 int halo(int v, const char* e, int d) { return v >= 0 ? (v == 0 ? 0 : 2) : env_int(e, d); }
 int nj(int v, const char* e, int d) { return (v > 0 ? v : env_int(e, d)) == 2 ? 2 : 1; }  // 0 reverts too
 int narrow(int v, const char*, int d) { return v <= 0 || v > d ? d : v; }
