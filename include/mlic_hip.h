@@ -422,6 +422,53 @@ int mlic_container_write_roi(uint32_t H, uint32_t W, int level, uint32_t hz, uin
 int mlic_container_parse_roi(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
                              mlic_container_roi_info* info, uint8_t* levels, size_t levels_cap);
 
+/* Tiled coding (DESIGN.md section 5 "Tiled coding"): a large image is coded as independent tiles, each a plain
+ * per-image file, held by a tiled file with an index; a decoder touches only the tiles a region needs.
+ * The grid, per axis of length L, tile T (a multiple of 64, 128 <= T <= 65472), overlap V (0, 16, 32 or 64,
+ * V <= T / 2), S = T - V: n = 1 if L <= T else ceil((L - V) / S); tile k starts at k S, extent min(T, L - k S).
+ * Tiles are numbered row-major.  In the V-wide strip shared by tiles k and k + 1, at position j, the later tile
+ * weighs (2 j + 1) / (2 V) and the earlier one 1 minus that; the 2-D weight is the product of the axis weights.
+ * mlic_tile_grid: *ny, *nx; rects (optional, rects_cap >= ny * nx entries of 4) receives {y0, x0, h, w} per tile. */
+int mlic_tile_grid(uint32_t H, uint32_t W, uint32_t T, uint32_t V, uint32_t* ny, uint32_t* nx, uint32_t* rects,
+                   size_t rects_cap);
+/* The blend egress, one launch: the h x w region at (y0, x0) of the H x W image as uint8 through dst_strides
+ * {row, column, channel} (dst = the region's first byte; only the region's bytes are written).  tiles_dev: device
+ * table of ny * nx pointers, tile index -> that tile's contiguous fp32 [3][pad64(h_t)][pad64(w_t)] x_hat planes
+ * (device) or NULL; tiles_host: the same table in host memory, from which a region whose covering tile is NULL
+ * is refused before any GPU call.  Per pixel and channel: acc (double) = sum over the covering tiles, tile row
+ * then tile column, of (double)(wy * wx) * (double)x_hat (each product exact, the sums rounded in that order);
+ * u = floor(clamp((float)acc, 0, 1) * 255), NaN -> 0.  Where one tile covers a pixel this is
+ * mlic_image_egress_u8 of that tile.  ref (optional: the region's crop of the original, device, its own {row,
+ * column, channel} strides) with sq_err (one device uint64): the exact sum of squared uint8 differences.
+ * Asynchronous on `stream`. */
+int mlic_image_tile_blend_u8(void* stream, const float* const* tiles_dev, const float* const* tiles_host, int H, int W,
+                             int T, int V, int y0, int x0, int h, int w, uint8_t* dst, const int64_t* dst_strides,
+                             const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err);
+/* The tiled file, big-endian:
+ *     "MLT1" | u8 version 0 | u8 flags (bit 0: the tiles carry a VBR level word) | u32 H, W | u16 T, V
+ *     u32 ny, nx | (ny nx + 1) x u64 offsets into the payload | payload: the tiles' files, row-major
+ * Each tile's file is exactly the file mlic_container_write makes for that tile's crop.  write: payload = the
+ * n_tiles files concatenated, lens = their lengths; the *len / out / cap protocol of mlic_container_write.
+ * parse: validating, never reads outside data[0, n), no copies.  Refused, each with its own message: a truncated
+ * header; bad magic, version or flags; T or V outside the rules; H or W zero; H * W > max_pixels (the whole
+ * image's bound); ny or nx off the grid formula; an offset table that cannot fit in n (checked before it is
+ * walked); a first offset that is not 0, offsets not strictly increasing, a last offset that is not the payload's
+ * length.  mlic_container_tiled_tile: tile k's file is data[*off, *off + *len); it then goes through
+ * mlic_container_parse, and its H, W must be the tile's extent.  mlic_container_parse keeps refusing a tiled
+ * file (the magic read as H is about 1.3e9).  There is no single-call encode or decode of a tiled file here:
+ * the tiles go through mlic_compress / mlic_decompress as batches (mlic_amd/codec.py does). */
+typedef struct mlic_container_tiled_info {
+  uint32_t H, W, T, V, ny, nx;
+  int32_t vbr; /* flags bit 0 */
+  int32_t reserved;
+  uint64_t table_off, payload_off, payload_len;
+} mlic_container_tiled_info;
+int mlic_container_write_tiled(uint32_t H, uint32_t W, uint32_t T, uint32_t V, int vbr, const uint8_t* payload,
+                               const uint64_t* lens, size_t n_tiles, uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_tiled(const uint8_t* data, size_t n, uint64_t max_pixels, mlic_container_tiled_info* info);
+int mlic_container_tiled_tile(const uint8_t* data, size_t n, const mlic_container_tiled_info* info, uint64_t k,
+                              uint64_t* off, uint64_t* len);
+
 /* One image, pixels to file bytes: ingest into a staging buffer the handle owns (it grows on demand and is
  * freed by mlic_destroy), mlic_compress with B = 1, the container.  rgb_dev: H x W x 3 bytes on the device
  * with strides {row, column, channel}; level >= 0 is written into the header (vbr_scale is that level's gain),

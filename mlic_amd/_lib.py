@@ -32,6 +32,13 @@ class ContainerRoiInfo(C.Structure):
     _fields_ = [("file", ContainerInfo), ("map_off", C.c_uint64), ("map_len", C.c_uint64)]
 
 
+class ContainerTiledInfo(C.Structure):
+    """mlic_container_tiled_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("T", C.c_uint32), ("V", C.c_uint32), ("ny", C.c_uint32),
+                ("nx", C.c_uint32), ("vbr", C.c_int32), ("reserved", C.c_int32), ("table_off", C.c_uint64),
+                ("payload_off", C.c_uint64), ("payload_len", C.c_uint64)]
+
+
 def _sig(lib):
     p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
     P = C.POINTER
@@ -109,6 +116,11 @@ def _sig(lib):
         "mlic_image_sq_err_roi_u8": [p, p, P(i64), p, P(i64), p, P(i64), i, i, i, p],
         "mlic_container_write_roi": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, p, sz, p, p, sz, P(sz)],
         "mlic_container_parse_roi": [p, sz, i, C.c_uint64, P(ContainerRoiInfo), p, sz],
+        "mlic_tile_grid": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32), p, sz],
+        "mlic_image_tile_blend_u8": [p, p, p, i, i, i, i, i, i, i, i, p, P(i64), p, P(i64), p],
+        "mlic_container_write_tiled": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i, p, p, sz, p, sz, P(sz)],
+        "mlic_container_parse_tiled": [p, sz, C.c_uint64, P(ContainerTiledInfo)],
+        "mlic_container_tiled_tile": [p, sz, P(ContainerTiledInfo), C.c_uint64, P(C.c_uint64), P(C.c_uint64)],
         "mlic_encode_image_u8": [p, p, p, P(i64), i, i, f, i, p, sz, P(sz)],
         "mlic_encode_image_u8_budget": [p, p, p, P(i64), i, i, f, i, C.c_double, i, p, sz, P(sz), P(i)],
         "mlic_decode_image_u8": [p, p, p, sz, i, C.c_uint64, p, p, P(i64), sz, P(i), P(i), P(i)],

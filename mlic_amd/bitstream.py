@@ -99,7 +99,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
-               dists=None, roi=None, roi_levels=None, **kw) -> Dict:
+               dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -114,9 +114,43 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     (codec.roi_levels -> codec.gain_plane -> compress(gain_map=)); the file is the ROI file with its level map,
     the decoder rebuilds the plane from the file alone, and the record also holds "psnr_roi" and "psnr_bg" (PSNR
     inside and outside the mask; None for a side without pixels) and "roi_levels", the map.  Not together with
-    max_bpp or s=; off by default."""
+    max_bpp or s=; off by default.
+    tile=T (with overlap=V): tiled coding (codec.encode_tiled / decode_tiled, DESIGN.md §5 "Tiled coding") of
+    to_u8(img): the file is the tiled file, x_hat the decoded uint8 image / 255, psnr comes from the decode's
+    exact squared error, and the record also holds "tile", "overlap", "grid" and "tile_bytes".  s= is the one
+    level of the image; not together with max_bpp or roi=; off by default."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
+    if tile is not None:
+        from . import codec
+        if max_bpp is not None or roi is not None or roi_levels is not None or set(kw) - {"s"}:
+            raise ValueError("code_image: tile= goes with overlap= and the level s= alone, not with max_bpp or roi=")
+        lv = kw.get("s")
+        if isinstance(lv, (list, tuple)):
+            if len(lv) != 1:
+                raise ValueError("code_image: tile= takes one level for the image")
+            lv = lv[0]
+        u8 = to_u8(img[0]).permute(1, 2, 0).contiguous()
+        t0 = time.time()
+        data, einfo = codec.encode_tiled(net, u8, tile=tile, overlap=overlap, level=lv, layout="hwc", return_info=True)
+        enc = time.time() - t0
+        t0 = time.time()
+        dec_u8, dinfo = codec.decode_tiled(net, data, ref=u8)
+        dect = time.time() - t0
+        x_hat = dec_u8.permute(2, 0, 1).unsqueeze(0).float().div(255)
+        r = {"H": H, "W": W, "bytes": len(data), "bpp": 8.0 * len(data) / (H * W), "psnr": dinfo["psnr"], "enc_s": enc,
+             "dec_s": dect, "x_hat": x_hat, "tile": einfo["tile"], "overlap": einfo["overlap"], "grid": einfo["grid"],
+             "tile_bytes": einfo["tile_bytes"]}
+        if ms_ssim:
+            from . import metrics
+            r["ms_ssim"] = metrics.ms_ssim_u8(img, x_hat).item() if min(H, W) > metrics.MIN_SIDE else None
+        if lpips is not None:
+            from . import metrics
+            r["lpips"] = lpips(img, x_hat).item() if min(H, W) >= metrics.LPIPS_MIN_SIDE else None
+        if dists is not None:
+            from . import metrics
+            r["dists"] = dists(img, x_hat).item() if min(H, W) >= metrics.DISTS_MIN_SIDE else None
+        return r
     x = pad64(img)
     level = kw.get("s") if kw else None
     buf = io.BytesIO()

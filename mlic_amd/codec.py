@@ -19,6 +19,11 @@ the ROI, hi inside), `gain_plane` expands it to the latent grid, and the map tra
 string, so `decode_images` needs nothing but the file.  `sq_err_roi` / `psnr_roi` score a decode inside and
 outside the mask.
 
+`encode_tiled` / `decode_tiled` code one image of any size as independent tiles (DESIGN.md §5 "Tiled coding"): the
+grid of `tile_grid`, each tile's file byte for byte `encode_images` of that crop, a tiled container with an index,
+a decoder that touches only the tiles a region needs, and `blend_tiles`, one launch that assembles the region from
+the overlapping tiles with feathered seams.
+
 CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
 """
@@ -256,11 +261,17 @@ def parse_container(data: bytes, vbr: bool = False, n_levels: Optional[int] = No
     return info
 
 
-def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> Dict:
+def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pixels: Optional[int] = None) -> Dict:
     """What a file says about itself, validated: H, W, level (None without one), the z grid `shape`, the
     padded size, the string lengths and the bpp of the whole file; for an ROI file also "roi_levels", its level
-    map (uint8 numpy [hz, wz])."""
+    map (uint8 numpy [hz, wz]).  A tiled file (is_tiled_file; its flags say whether the tiles carry a level word,
+    and max_pixels bounds the whole image's H * W) gives {"tiled": True, H, W,
+    tile, overlap, grid (ny, nx), vbr, level, bytes, bpp, "tiles": per tile index, y0, x0, H, W, level, bytes,
+    bpp}."""
     data = bytes(data)
+    if is_tiled_file(data):
+        return _peek_tiled(data, n_levels, MAX_IMAGE_PIXELS if max_pixels is None else max_pixels)
+    max_pixels = MAX_PIXELS if max_pixels is None else max_pixels
     lv = None
     if vbr and is_roi_file(data):
         c, lv = parse_container_roi(data, 16 if n_levels is None else n_levels, max_pixels)
@@ -611,6 +622,8 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
+    if any(is_tiled_file(f) for f in files):
+        raise ValueError("decode_images: a tiled file (MLT1) is decoded by decode_tiled, whole or by region")
     vbr = hasattr(net, "levels")
     maps = [None] * len(files)
     if vbr and any(is_roi_file(f) for f in files):
@@ -659,6 +672,345 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
             d["sq_err"] = int(sq[b])
             d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W)
         info.append(d)
+    return img, info
+
+
+# -------------------------------------------------------------------------------------------- tiles
+def _check_tile_params(tile, overlap):
+    ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (tile, overlap))
+    if not ok or tile % 64 or not 128 <= tile <= 65472:
+        raise ValueError(f"tile must be a multiple of 64 in [128, 65472], got {tile!r}")
+    if overlap not in (0, 16, 32, 64) or overlap > tile // 2:
+        raise ValueError(f"overlap must be 0, 16, 32 or 64 and at most tile / 2, got {overlap!r} (tile {tile})")
+
+
+def _tile_axis(L: int, T: int, V: int):
+    """[(start, extent)] of the tiles along an axis of length L."""
+    S = T - V
+    n = 1 if L <= T else -(-(L - V) // S)
+    return [(k * S, min(T, L - k * S)) for k in range(n)]
+
+
+def tile_grid(H: int, W: int, tile: int, overlap: int) -> Dict:
+    """The tile grid of an H x W image (DESIGN.md §5 "Tiled coding"; the same definition as mlic_tile_grid): per
+    axis of length L with S = tile - overlap, n = 1 if L <= tile else ceil((L - overlap) / S), tile k starts at k S
+    and has extent min(tile, L - k S).  -> {"H", "W", "tile", "overlap", "ny", "nx", "ys", "xs": [(start, extent)]
+    per axis, "rects": [(y0, x0, h, w)] row-major}."""
+    _check_tile_params(tile, overlap)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"tile_grid: a non-empty image expected, got {H} x {W}")
+    ys, xs = _tile_axis(H, tile, overlap), _tile_axis(W, tile, overlap)
+    return {"H": H, "W": W, "tile": int(tile), "overlap": int(overlap), "ny": len(ys), "nx": len(xs), "ys": ys, "xs": xs,
+            "rects": [(y0, x0, h, w) for y0, h in ys for x0, w in xs]}
+
+
+def tile_weights(L: int, tile: int, overlap: int, k: int) -> torch.Tensor:
+    """Tile k's feather weights along an axis of length L, fp32 [extent]: in the strip it shares with tile k - 1
+    (its first `overlap` positions j) (2 j + 1) / (2 overlap), in the strip it shares with tile k + 1 one minus that
+    tile's weight, 1 elsewhere.  Dyadic rationals: the two weights of a strip position sum to exactly 1."""
+    axis = _tile_axis(L, tile, overlap)
+    ext, V, S = axis[k][1], overlap, tile - overlap
+    w = torch.ones(ext, dtype=torch.float32)
+    if V:
+        ramp = (2 * torch.arange(V, dtype=torch.float32) + 1) / (2 * V)
+        if k > 0:
+            w[:V] = ramp
+        if k + 1 < len(axis):
+            w[S:] = 1 - ramp
+    return w
+
+
+def _region(region, H: int, W: int, what: str):
+    if region is None:
+        return 0, 0, H, W
+    try:
+        y0, x0, h, w = (int(v) for v in region)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: region must be (y0, x0, h, w), got {region!r}") from None
+    if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"{what}: region {(y0, x0, h, w)} is empty or outside the {H} x {W} image")
+    return y0, x0, h, w
+
+
+def _tiles_of_region(grid: Dict, region) -> List[int]:
+    """Sorted indices of the tiles that intersect the region."""
+    y0, x0, h, w = region
+    return [ky * grid["nx"] + kx for ky, (ty, th) in enumerate(grid["ys"]) if ty < y0 + h and ty + th > y0
+            for kx, (tx, tw) in enumerate(grid["xs"]) if tx < x0 + w and tx + tw > x0]
+
+
+def blend_tiles(tiles, H: int, W: int, tile: int, overlap: int, region=None, layout: str = "hwc", ref=None,
+                out: Optional[torch.Tensor] = None):
+    """The region (y0, x0, h, w) (None: the whole image) of an H x W image as uint8 ([h,w,3] for layout "hwc",
+    [3,h,w] for "chw"), blended from its tiles' x_hat.  tiles: ny * nx entries, row-major (or a dict index ->
+    tensor); entry k is tile k's contiguous fp32 [3, pad64(h_k), pad64(w_k)] or None; every tile that intersects
+    the region must be there, and all on one device.  Per pixel and channel acc (float64) = 0; acc += (wy * wx as
+    float64) * x_hat over the covering tiles, tile row then tile column (tile_weights; each product exact, the
+    sums rounded in that order); then floor(clamp(float32(acc), 0, 1) * 255), NaN -> 0.  A pixel one tile covers
+    is egress_u8 of that tile.  out: optional uint8 tensor of the result's shape, any strides (only the region's
+    bytes are written).  ref: the region's crop of the original, uint8 of the same shape and layout, any strides:
+    returns (image, sq_err), sq_err int64 [1], the exact sum of squared differences.  CUDA tensors: one launch of
+    the blend kernel on the current stream; CPU tensors: the torch restatement, bit for bit the same."""
+    grid = tile_grid(H, W, tile, overlap)
+    n = grid["ny"] * grid["nx"]
+    if isinstance(tiles, dict):
+        tiles = [tiles.get(k) for k in range(n)]
+    tiles = list(tiles)
+    if len(tiles) != n:
+        raise ValueError(f"blend_tiles: {n} entries ({grid['ny']} x {grid['nx']} tiles) expected, got {len(tiles)}")
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    y0, x0, h, w = _region(region, H, W, "blend_tiles")
+    need = _tiles_of_region(grid, (y0, x0, h, w))
+    for k, t in enumerate(tiles):
+        if t is None:
+            if k in need:
+                raise ValueError(f"blend_tiles: tile {k} covers the region and is missing")
+            continue
+        _, _, th, tw = grid["rects"][k]
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (3, _pad64(th), _pad64(tw)):
+            raise ValueError(f"blend_tiles: tile {k} must be fp32 {(3, _pad64(th), _pad64(tw))}")
+    dev = tiles[need[0]].device  # a region is never empty, so it has a covering tile, and that one is there
+    if any(t is not None and t.device != dev for t in tiles):
+        raise ValueError(f"blend_tiles: the tiles must be on one device ({dev})")
+    shape = (h, w, 3) if layout == "hwc" else (3, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != dev:
+        raise ValueError(f"blend_tiles: out must be uint8 {shape} on {dev}")
+    if ref is not None:
+        if isinstance(ref, np.ndarray):
+            ref = torch.from_numpy(np.ascontiguousarray(ref))
+        if not torch.is_tensor(ref) or ref.dtype != torch.uint8 or tuple(ref.shape) != shape:
+            raise ValueError(f"blend_tiles: ref must be uint8 {shape}")
+        ref = ref.to(dev)
+
+    def rcc(t):  # element strides {row, column, channel}
+        s = t.stride()
+        return (s[0], s[1], s[2]) if layout == "hwc" else (s[1], s[2], s[0])
+
+    if dev.type != "cuda":
+        acc = torch.zeros(3, h, w, dtype=torch.float64)
+        for k in need:
+            ty, tx, th, tw = grid["rects"][k]
+            ky, kx = divmod(k, grid["nx"])
+            a, b = max(ty, y0), min(ty + th, y0 + h)
+            c, d = max(tx, x0), min(tx + tw, x0 + w)
+            wy = tile_weights(H, tile, overlap, ky)[a - ty:b - ty]
+            wx = tile_weights(W, tile, overlap, kx)[c - tx:d - tx]
+            wgt = (wy[:, None] * wx[None, :]).double()  # the fp32 product is exact (at most 14 bits)
+            acc[:, a - y0:b - y0, c - x0:d - x0] += wgt * tiles[k][:, a - ty:b - ty, c - tx:d - tx].double()
+        v = acc.float()
+        v = torch.where(torch.isnan(v), torch.zeros_like(v), v)
+        u = (v.clamp(0, 1) * 255).floor().to(torch.uint8)
+        out.copy_(u.permute(1, 2, 0) if layout == "hwc" else u)
+        if ref is None:
+            return out
+        dd = out.to(torch.int64) - ref.to(torch.int64)
+        return out, (dd * dd).sum().reshape(1)
+    if 0 in rcc(out)[1:]:
+        raise ValueError("blend_tiles: out has a zero column or channel stride")
+    with torch.cuda.device(dev):
+        tiles = [None if t is None else t.contiguous() for t in tiles]
+        ptrs = [0 if t is None else t.data_ptr() for t in tiles]
+        table = torch.tensor(ptrs, dtype=torch.int64).to(dev)
+        host = (C.c_void_p * n)(*[p or None for p in ptrs])
+        sq = None
+        if ref is not None:
+            if 0 in rcc(ref)[1:]:
+                ref = ref.contiguous()
+            sq = torch.full((1,), -1, dtype=torch.int64, device=dev)
+        _lib.call("mlic_image_tile_blend_u8", _stream(), C.c_void_p(table.data_ptr()), host, H, W, int(tile),
+                  int(overlap), y0, x0, h, w, C.c_void_p(out.data_ptr()), (C.c_int64 * 3)(*rcc(out)),
+                  None if ref is None else C.c_void_p(ref.data_ptr()),
+                  None if ref is None else (C.c_int64 * 3)(*rcc(ref)),
+                  None if sq is None else C.c_void_p(sq.data_ptr()))
+        st = torch.cuda.current_stream()
+        for t in [table, ref] + tiles:
+            if t is not None:
+                t.record_stream(st)
+    return out if ref is None else (out, sq)
+
+
+TILED_MAGIC = b"MLT1"
+MAX_IMAGE_PIXELS = 1 << 32  # default bound on a tiled file's H * W (the tiles have MAX_PIXELS each)
+
+
+def is_tiled_file(data: bytes) -> bool:
+    """Whether the file starts with the tiled container's magic (read as a plain file's H it is about 1.3e9)."""
+    return bytes(data[:4]) == TILED_MAGIC
+
+
+def write_container_tiled(H: int, W: int, tile: int, overlap: int, files: Sequence[bytes], vbr: bool = False) -> bytes:
+    """The tiled file of an H x W image (mlic_container_write_tiled): files = the tiles' per-image files, row-major."""
+    files = [bytes(f) for f in files]
+    payload = b"".join(files)
+    lens = (C.c_uint64 * max(1, len(files)))(*[len(f) for f in files])
+    n = C.c_size_t()
+    args = (int(H), int(W), int(tile), int(overlap), int(vbr), payload, lens, len(files))
+    _lib.call("mlic_container_write_tiled", *args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_tiled", *args, buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_tiled(data: bytes, max_pixels: int = MAX_IMAGE_PIXELS) -> _lib.ContainerTiledInfo:
+    """The validating parser of a tiled file (mlic_container_parse_tiled): raises _lib.MlicError on any malformed
+    input.  max_pixels bounds H * W of the whole image."""
+    data = bytes(data)
+    info = _lib.ContainerTiledInfo()
+    _lib.call("mlic_container_parse_tiled", data, len(data), int(max_pixels), C.byref(info))
+    return info
+
+
+def tiled_tile(data: bytes, info: _lib.ContainerTiledInfo, k: int):
+    """(offset, length) of tile k's file inside a parsed tiled file (mlic_container_tiled_tile)."""
+    off, ln = C.c_uint64(), C.c_uint64()
+    _lib.call("mlic_container_tiled_tile", data, len(data), C.byref(info), int(k), C.byref(off), C.byref(ln))
+    return off.value, ln.value
+
+
+def _tile_file(data: bytes, t, grid: Dict, k: int, vbr: bool, n_levels):
+    """Tile k's file out of a parsed tiled file, through the per-image parser: (bytes, ContainerInfo)."""
+    off, ln = tiled_tile(data, t, k)
+    f = data[off:off + ln]
+    _, _, th, tw = grid["rects"][k]
+    c = parse_container(f, vbr, n_levels, _pad64(th) * _pad64(tw))
+    if (c.H, c.W) != (th, tw):
+        raise _lib.MlicError(f"tiled file: tile {k} says {c.H} x {c.W}, the grid {th} x {tw}")
+    return f, c
+
+
+def _peek_tiled(data: bytes, n_levels, max_pixels) -> Dict:
+    t = parse_container_tiled(data, max_pixels)
+    grid = tile_grid(t.H, t.W, t.T, t.V)
+    vbr = bool(t.vbr)
+    tiles = []
+    for k, (ty, tx, th, tw) in enumerate(grid["rects"]):
+        f, c = _tile_file(data, t, grid, k, vbr, n_levels)
+        tiles.append({"index": k, "y0": ty, "x0": tx, "H": th, "W": tw, "level": c.level if vbr else None,
+                      "bytes": len(f), "bpp": 8.0 * len(f) / (th * tw)})
+    return {"tiled": True, "H": t.H, "W": t.W, "tile": t.T, "overlap": t.V, "grid": (t.ny, t.nx), "vbr": vbr,
+            "level": tiles[0]["level"], "tiles": tiles, "bytes": len(data), "bpp": 8.0 * len(data) / (t.H * t.W)}
+
+
+def _refuse_with_tiles(what: str, max_bpp=None, level=None, roi=None, roi_levels=None):
+    if max_bpp is not None:
+        raise ValueError(f"{what}: max_bpp together with tiles is not supported (rate control per tiled image)")
+    if isinstance(level, str):
+        raise ValueError(f"{what}: level={level!r} together with tiles is not supported (it needs max_bpp)")
+    if roi is not None or roi_levels is not None:
+        raise ValueError(f"{what}: roi= together with tiles is not supported")
+    if level is not None and (isinstance(level, (list, tuple)) or np.ndim(level) != 0):
+        raise ValueError(f"{what}: per-tile levels are not supported: a VBR level is one level for the image")
+
+
+@torch.no_grad()
+def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, layout: Optional[str] = None,
+                 tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None):
+    """One uint8 image ([H,W,3] / [3,H,W], tensor or numpy array) -> one tiled file (DESIGN.md §5 "Tiled coding"):
+    the image is cut into the tiles of tile_grid(H, W, tile, overlap), each tile is coded by itself and its file
+    is byte for byte encode_images of that crop, and the tiled container holds them row-major with an index.
+    Tiles are ingested in place through strided views of the image (a run of equal tiles in a tile row is a batch
+    whose image stride is tile - overlap columns) and coded per shape group (interior, right column, bottom row,
+    corner) in chunks of at most tile_batch tiles, so device memory is the arena of tile_batch tiles plus the
+    uint8 image itself, which crosses to the model's device whole (3 bytes per pixel).  level: the one VBR level of the image.  max_bpp, level="auto", roi= and per-tile levels are
+    refused.  return_info=True: (file, info) with info = {"H", "W", "tile", "overlap", "grid", "bytes", "bpp",
+    "level", "tile_bytes"}."""
+    _refuse_with_tiles("encode_tiled", max_bpp, level, roi, roi_levels)
+    img, layout = _u8_batch(img_u8, layout, "encode_tiled")
+    if img.size(0) != 1:
+        raise ValueError(f"encode_tiled takes one image, got a batch of {img.size(0)}")
+    if isinstance(tile_batch, bool) or not isinstance(tile_batch, (int, np.integer)) or tile_batch < 1:
+        raise ValueError(f"tile_batch must be a positive integer, got {tile_batch!r}")
+    H, W = _hw(img, layout)
+    grid = tile_grid(H, W, tile, overlap)
+    lv, _ = _levels(net, level, 1)
+    img = _in_place(img.to(net.device), layout)
+    _, sr, sc, sch = _strides(img, layout)
+    S, nx = tile - overlap, grid["nx"]
+    groups: Dict = {}
+    for k, (_, _, th, tw) in enumerate(grid["rects"]):
+        groups.setdefault((th, tw), []).append(k)
+    files: List[Optional[bytes]] = [None] * len(grid["rects"])
+    for (th, tw), ks in groups.items():
+        for i in range(0, len(ks), tile_batch):
+            chunk = ks[i:i + tile_batch]
+            runs = [[chunk[0]]]  # consecutive tiles of one tile row
+            for k in chunk[1:]:
+                if k == runs[-1][-1] + 1 and k // nx == runs[-1][-1] // nx:
+                    runs[-1].append(k)
+                else:
+                    runs.append([k])
+            xs = []
+            for run in runs:
+                ty, tx = grid["rects"][run[0]][:2]
+                size, stride = ((len(run), th, tw, 3), (S * sc, sr, sc, sch)) if layout == "hwc" else \
+                               ((len(run), 3, th, tw), (S * sc, sch, sr, sc))
+                xs.append(ingest_u8(torch.as_strided(img, size, stride, img.storage_offset() + ty * sr + tx * sc), layout))
+            x = xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+            out = net.compress(x, **({} if lv is None else {"s": lv * len(chunk)}))
+            ys, zs = out["strings"]
+            for j, k in enumerate(chunk):
+                files[k] = write_container(th, tw, out["shape"], ys[j], zs[j], None if lv is None else lv[0])
+    data = write_container_tiled(H, W, tile, overlap, files, vbr=lv is not None)
+    if not return_info:
+        return data
+    return data, {"H": H, "W": W, "tile": int(tile), "overlap": int(overlap), "grid": (grid["ny"], grid["nx"]),
+                  "bytes": len(data), "bpp": 8.0 * len(data) / (H * W), "level": None if lv is None else lv[0],
+                  "tile_bytes": [len(f) for f in files]}
+
+
+@torch.no_grad()
+def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, max_pixels: int = MAX_IMAGE_PIXELS):
+    """A tiled file -> (uint8 [h,w,3] on the model's device, info): the region (y0, x0, h, w) of the image (None:
+    all of it).  Only the tiles that intersect the region are entropy-decoded and synthesised (per shape group,
+    in chunks of at most tile_batch tiles); their fp32 x_hat is kept (12 bytes per pixel of the decoded tiles, on top of the arena of
+    tile_batch tiles) and one blend_tiles launch writes the region.  The file and every tile's file go through the validating parsers first.  info: H, W, tile, overlap,
+    grid (ny, nx), region, tiles_decoded (sorted tile indices), level, bytes and bpp of the whole file and, with
+    ref (uint8 [h,w,3], the region's crop of the original), the exact sq_err and psnr."""
+    data = bytes(data)
+    if isinstance(tile_batch, bool) or not isinstance(tile_batch, (int, np.integer)) or tile_batch < 1:
+        raise ValueError(f"tile_batch must be a positive integer, got {tile_batch!r}")
+    if not is_tiled_file(data):
+        raise ValueError("decode_tiled: not a tiled file (no MLT1 magic): decode_images reads per-image files")
+    t = parse_container_tiled(data, max_pixels)
+    vbr = hasattr(net, "levels")
+    if bool(t.vbr) != vbr:
+        raise ValueError(f"decode_tiled: the file's tiles {'carry' if t.vbr else 'have no'} level word, the model is "
+                         f"{'variable' if vbr else 'fixed'}-rate")
+    H, W, T, V = t.H, t.W, t.T, t.V
+    grid = tile_grid(H, W, T, V)
+    reg = _region(region, H, W, "decode_tiled")
+    if ref is not None:
+        if isinstance(ref, np.ndarray):
+            ref = torch.from_numpy(np.ascontiguousarray(ref))
+        if not torch.is_tensor(ref) or ref.dtype != torch.uint8 or tuple(ref.shape) != (reg[2], reg[3], 3):
+            raise ValueError(f"decode_tiled: ref must be uint8 {(reg[2], reg[3], 3)}, the region's crop of the original")
+    need = _tiles_of_region(grid, reg)
+    parsed = {k: _tile_file(data, t, grid, k, vbr, net.levels if vbr else None) for k in need}
+    groups: Dict = {}
+    for k in need:
+        c = parsed[k][1]
+        groups.setdefault((c.hz, c.wz), []).append(k)
+    tiles: Dict = {}
+    for shape, ks in groups.items():
+        for i in range(0, len(ks), tile_batch):
+            chunk = ks[i:i + tile_batch]
+            pairs = [_strings(*parsed[k]) for k in chunk]
+            kw = {"s": [parsed[k][1].level for k in chunk]} if vbr else {}
+            x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], shape, **kw)["x_hat"]
+            x_hat = x_hat.float().contiguous()
+            for j, k in enumerate(chunk):
+                tiles[k] = x_hat[j]
+    r = blend_tiles(tiles, H, W, T, V, reg, "hwc", ref=ref)
+    img, sq = r if ref is not None else (r, None)
+    info = {"H": H, "W": W, "tile": T, "overlap": V, "grid": (t.ny, t.nx), "region": reg, "tiles_decoded": need,
+            "level": parsed[need[0]][1].level if vbr else None, "bytes": len(data), "bpp": 8.0 * len(data) / (H * W)}
+    if sq is not None:
+        info["sq_err"] = int(sq.cpu()[0])
+        info["psnr"] = psnr_from_sq_err(info["sq_err"], 3 * reg[2] * reg[3])
     return img, info
 
 

@@ -917,6 +917,72 @@ int mlic_container_parse_roi(const uint8_t* data, size_t n, int n_levels, uint64
   });
 }
 
+int mlic_tile_grid(uint32_t H, uint32_t W, uint32_t T, uint32_t V, uint32_t* ny, uint32_t* nx, uint32_t* rects,
+                   size_t rects_cap) {
+  return guard([&] {
+    MLIC_CHECK(ny != nullptr && nx != nullptr, "tile_grid: null ny or nx");
+    container_ok(tile_params_check(T, V));
+    MLIC_CHECK(H >= 1 && W >= 1, "tile_grid: H and W must be positive");
+    const uint32_t gy = tile_count(H, T, V), gx = tile_count(W, T, V);
+    *ny = gy;
+    *nx = gx;
+    if (rects == nullptr) return;
+    MLIC_CHECK((uint64_t)gy * gx <= rects_cap, "tile_grid: rects buffer too small (ny * nx entries of 4)");
+    for (uint32_t ky = 0; ky < gy; ++ky)
+      for (uint32_t kx = 0; kx < gx; ++kx) {
+        uint32_t* r = rects + 4 * ((size_t)ky * gx + kx);
+        r[0] = tile_start(ky, T, V);
+        r[1] = tile_start(kx, T, V);
+        r[2] = tile_extent(H, ky, T, V);
+        r[3] = tile_extent(W, kx, T, V);
+      }
+  });
+}
+
+int mlic_image_tile_blend_u8(void* stream, const float* const* tiles_dev, const float* const* tiles_host, int H, int W,
+                             int T, int V, int y0, int x0, int h, int w, uint8_t* dst, const int64_t* dst_strides,
+                             const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err) {
+  return guard([&] {
+    image_tile_blend_u8(tiles_dev, tiles_host, H, W, T, V, y0, x0, h, w, dst, dst_strides, ref, ref_strides, sq_err,
+                        (hipStream_t)stream);
+  });
+}
+
+int mlic_container_write_tiled(uint32_t H, uint32_t W, uint32_t T, uint32_t V, int vbr, const uint8_t* payload,
+                               const uint64_t* lens, size_t n_tiles, uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] { container_ok(container_write_tiled(H, W, T, V, vbr != 0, payload, lens, n_tiles, out, cap, len)); });
+}
+
+static TiledInfo from_abi(const mlic_container_tiled_info& o) {
+  TiledInfo t{};
+  t.H = o.H, t.W = o.W, t.T = o.T, t.V = o.V, t.ny = o.ny, t.nx = o.nx;
+  t.vbr = o.vbr != 0;
+  t.table_off = (size_t)o.table_off, t.payload_off = (size_t)o.payload_off, t.payload_len = (size_t)o.payload_len;
+  return t;
+}
+
+int mlic_container_parse_tiled(const uint8_t* data, size_t n, uint64_t max_pixels, mlic_container_tiled_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_tiled: null info");
+    TiledInfo t;
+    container_ok(container_parse_tiled(data, n, max_pixels, &t));
+    *info = mlic_container_tiled_info{t.H, t.W, t.T, t.V, t.ny, t.nx, t.vbr ? 1 : 0, 0,
+                                      t.table_off, t.payload_off, t.payload_len};
+  });
+}
+
+int mlic_container_tiled_tile(const uint8_t* data, size_t n, const mlic_container_tiled_info* info, uint64_t k,
+                              uint64_t* off, uint64_t* len) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr && off != nullptr && len != nullptr, "container_tiled_tile: null argument");
+    const TiledInfo t = from_abi(*info);
+    size_t o = 0, l = 0;
+    container_ok(container_tiled_tile(data, n, &t, k, &o, &l));
+    *off = o;
+    *len = l;
+  });
+}
+
 // the handle's staging image: at least `bytes`, grown by reallocation (hipFree waits for the device)
 static float* grow(float*& buf, size_t& have, size_t bytes) {
   if (have < bytes) {

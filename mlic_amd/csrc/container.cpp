@@ -171,6 +171,139 @@ const char* container_parse_roi(const uint8_t* data, size_t n, uint32_t n_levels
   return parse_file(data, n, true, n_levels, max_pixels, true, info, map_off, map_len);
 }
 
+// ------------------------------------------------------------------------------------------ tiled
+const char* tile_params_check(uint32_t T, uint32_t V) {
+  if (T % 64 != 0 || T < 128) return "tile grid: the tile must be a multiple of 64 and at least 128";
+  if (T > 65472) return "tile grid: the tile does not fit 16 bits (at most 65472)";
+  if (V != 0 && V != 16 && V != 32 && V != 64) return "tile grid: the overlap must be 0, 16, 32 or 64";
+  if (V > T / 2) return "tile grid: the overlap is above half the tile";
+  return nullptr;
+}
+
+uint32_t tile_count(uint32_t L, uint32_t T, uint32_t V) {
+  if (L <= T) return 1;
+  const uint64_t S = T - V;
+  return (uint32_t)(((uint64_t)L - V + S - 1) / S);
+}
+
+namespace {
+
+void put64(uint8_t* p, uint64_t v) {
+  put32(p, (uint32_t)(v >> 32));
+  put32(p + 4, (uint32_t)v);
+}
+
+uint64_t get64(const uint8_t* p) {
+  uint64_t v = 0;
+  for (int i = 0; i < 8; ++i) v = (v << 8) | p[i];
+  return v;
+}
+
+}  // namespace
+
+const char* container_write_tiled(uint32_t H, uint32_t W, uint32_t T, uint32_t V, bool vbr, const uint8_t* payload,
+                                  const uint64_t* lens, size_t n_tiles, uint8_t* out, size_t cap, size_t* len) {
+  if (len == nullptr) return "container_write_tiled: null len";
+  if (const char* err = tile_params_check(T, V)) return err;
+  if (H == 0 || W == 0) return "container_write_tiled: H or W is zero";
+  const uint32_t ny = tile_count(H, T, V), nx = tile_count(W, T, V);
+  if ((uint64_t)ny * nx != (uint64_t)n_tiles) return "container_write_tiled: n_tiles is not ny * nx of the grid";
+  if (lens == nullptr) return "container_write_tiled: null lens";
+  uint64_t total = 0;  // n_tiles <= 2^26 (the grid of 32-bit sides), each length <= 2^36: no overflow
+  for (size_t k = 0; k < n_tiles; ++k) {
+    if (lens[k] == 0) return "container_write_tiled: an empty tile file";
+    if (lens[k] > ((uint64_t)1 << 36)) return "container_write_tiled: a tile file above 2^36 bytes";
+    total += lens[k];
+  }
+  const uint64_t head = TILED_HEADER + 8 * ((uint64_t)n_tiles + 1);
+  if (head + total > (uint64_t)SIZE_MAX) return "container_write_tiled: the file does not fit size_t";
+  *len = (size_t)(head + total);
+  if (out == nullptr) return nullptr;
+  if (cap < *len) return "container_write_tiled: buffer too small";
+  if (payload == nullptr) return "container_write_tiled: null payload";
+  uint8_t* p = out;
+  std::memcpy(p, "MLT1", 4);
+  p[4] = 0;
+  p[5] = vbr ? 1 : 0;
+  put32(p + 6, H);
+  put32(p + 10, W);
+  p[14] = (uint8_t)(T >> 8);
+  p[15] = (uint8_t)T;
+  p[16] = (uint8_t)(V >> 8);
+  p[17] = (uint8_t)V;
+  put32(p + 18, ny);
+  put32(p + 22, nx);
+  p += TILED_HEADER;
+  uint64_t at = 0;
+  put64(p, 0);
+  p += 8;
+  for (size_t k = 0; k < n_tiles; ++k, p += 8) put64(p, at += lens[k]);
+  std::memcpy(p, payload, (size_t)total);
+  return nullptr;
+}
+
+const char* container_parse_tiled(const uint8_t* data, size_t n, uint64_t max_pixels, TiledInfo* info) {
+  if (info == nullptr) return "container_parse_tiled: null info";
+  if (data == nullptr && n != 0) return "container_parse_tiled: null data";
+  if (n < TILED_HEADER) return "container_parse_tiled: truncated header";
+  if (std::memcmp(data, "MLT1", 4) != 0) return "container_parse_tiled: bad magic (not a tiled file)";
+  if (data[4] != 0) return "container_parse_tiled: unknown version";
+  if (data[5] & ~1u) return "container_parse_tiled: unknown flags";
+  Reader r{data, n, 6};
+  TiledInfo t{};
+  t.vbr = (data[5] & 1u) != 0;
+  r.u32(&t.H);  // n >= TILED_HEADER: the header's reads succeed
+  r.u32(&t.W);
+  t.T = ((uint32_t)data[14] << 8) | data[15];
+  t.V = ((uint32_t)data[16] << 8) | data[17];
+  r.pos = 18;
+  r.u32(&t.ny);
+  r.u32(&t.nx);
+  if (const char* err = tile_params_check(t.T, t.V)) return err;
+  if (t.H == 0 || t.W == 0) return "container_parse_tiled: H or W is zero";
+  if ((uint64_t)t.H > max_pixels / (uint64_t)t.W) return "container_parse_tiled: image exceeds max_pixels";
+  if (t.ny != tile_count(t.H, t.T, t.V) || t.nx != tile_count(t.W, t.T, t.V))
+    return "container_parse_tiled: ny, nx are not the grid of H, W, T, V";
+  // ny, nx < 2^32 / 64 each: the product fits 64 bits; the table must fit before anything walks it
+  const uint64_t tiles = (uint64_t)t.ny * t.nx;
+  if (tiles + 1 > (uint64_t)(n - TILED_HEADER) / 8) return "container_parse_tiled: the offset table does not fit the file";
+  t.table_off = TILED_HEADER;
+  t.payload_off = TILED_HEADER + 8 * (size_t)(tiles + 1);
+  t.payload_len = n - t.payload_off;
+  const uint8_t* tab = data + t.table_off;
+  if (get64(tab) != 0) return "container_parse_tiled: the first offset is not 0";
+  uint64_t prev = 0;
+  for (uint64_t k = 1; k <= tiles; ++k) {
+    const uint64_t o = get64(tab + 8 * k);
+    if (o <= prev) return "container_parse_tiled: the offsets are not strictly increasing";
+    prev = o;
+  }
+  if (prev != (uint64_t)t.payload_len) return "container_parse_tiled: the last offset is not the payload's length";
+  *info = t;
+  return nullptr;
+}
+
+const char* container_tiled_tile(const uint8_t* data, size_t n, const TiledInfo* info, uint64_t k, size_t* off,
+                                 size_t* len) {
+  if (data == nullptr || info == nullptr || off == nullptr || len == nullptr) return "container_tiled_tile: null argument";
+  const uint64_t tiles = (uint64_t)info->ny * info->nx;
+  if (k >= tiles) return "container_tiled_tile: tile index outside the grid";
+  // info must be what container_parse_tiled made of these n bytes: the table inside them, the payload after it
+  bool own = n >= TILED_HEADER && tiles + 1 <= (uint64_t)(n - TILED_HEADER) / 8;
+  own = own && info->table_off == TILED_HEADER && info->payload_off == TILED_HEADER + 8 * (tiles + 1);
+  own = own && info->payload_off <= n && info->payload_len == n - info->payload_off;
+  uint64_t a = 0, b = 0;
+  if (own) {
+    a = get64(data + info->table_off + 8 * k);
+    b = get64(data + info->table_off + 8 * (k + 1));
+    own = a < b && b <= info->payload_len;
+  }
+  if (!own) return "container_tiled_tile: info is not the parse of this file";
+  *off = info->payload_off + (size_t)a;
+  *len = (size_t)(b - a);
+  return nullptr;
+}
+
 void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels) {
   for (uint64_t k = 0; k < cells; ++k) {
     const uint8_t byte = map[1 + (size_t)(k >> 1)];

@@ -13,6 +13,12 @@
 #include <cstddef>
 #include <cstdint>
 
+#if defined(__HIPCC__)
+#define MLIC_HOST_DEVICE __host__ __device__
+#else
+#define MLIC_HOST_DEVICE
+#endif
+
 namespace mlic {
 
 struct ContainerInfo {
@@ -56,6 +62,48 @@ const char* container_parse_roi(const uint8_t* data, size_t n, uint32_t n_levels
 
 // the packed map (version byte included) of a parsed file -> one byte per cell
 void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels);
+
+// ---- Tiled coding (DESIGN.md section 5 "Tiled coding").  The grid, per axis of length L with tile T and overlap V,
+// S = T - V: n = 1 if L <= T else ceil((L - V) / S); tile k starts at k * S and has extent min(T, L - k * S).
+// T: a multiple of 64, 128 <= T <= 65472 (16 bits in the file); V in {0, 16, 32, 64}, V <= T / 2.
+const char* tile_params_check(uint32_t T, uint32_t V);  // nullptr when T, V follow the rules
+uint32_t tile_count(uint32_t L, uint32_t T, uint32_t V);
+inline uint32_t tile_start(uint32_t k, uint32_t T, uint32_t V) { return k * (T - V); }
+inline uint32_t tile_extent(uint32_t L, uint32_t k, uint32_t T, uint32_t V) {
+  const uint32_t left = L - k * (T - V);
+  return left < T ? left : T;
+}
+// Numerator of tile k's feather weight at its local position l, over den = max(2 V, 1): in the strip shared with
+// tile k - 1 (l < V) the later tile's weight is (2 l + 1) / (2 V), in the strip shared with tile k + 1 (l >= S) it
+// is 1 minus that tile's weight, elsewhere 1.  n: tiles on the axis.
+MLIC_HOST_DEVICE inline uint32_t tile_weight_num(uint32_t l, uint32_t k, uint32_t n, uint32_t T, uint32_t V) {
+  const uint32_t S = T - V, den = V ? 2 * V : 1;
+  if (k > 0 && l < V) return 2 * l + 1;
+  if (k + 1 < n && l >= S) return den - (2 * (l - S) + 1);
+  return den;
+}
+
+// The tiled file.  All integers big-endian:
+//     4 bytes "MLT1" | >B version 0 | >B flags (bit 0: the tiles carry a VBR level word) | >II H, W | >HH T, V
+//     >II ny, nx (must equal the grid formula) | (ny nx + 1) x >Q offsets into the payload (offsets[0] = 0,
+//     strictly increasing, the last = the payload's length) | payload: the tiles' files, row-major
+constexpr size_t TILED_HEADER = 26;
+struct TiledInfo {
+  uint32_t H, W, T, V, ny, nx;
+  bool vbr;
+  size_t table_off, payload_off, payload_len;
+};
+// lens: n_tiles lengths (each > 0) of the tiles' files, concatenated row-major at payload.  The *len / out / cap
+// protocol of container_write (payload may be null for a size query).
+const char* container_write_tiled(uint32_t H, uint32_t W, uint32_t T, uint32_t V, bool vbr, const uint8_t* payload,
+                                  const uint64_t* lens, size_t n_tiles, uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: a truncated header, bad magic, version or flags, T or V outside the rules,
+// H or W zero, H * W > max_pixels, ny or nx off the formula, an offset table that cannot fit in n (checked before
+// it is walked), offsets[0] != 0, offsets not strictly increasing, a last offset that is not the payload's length.
+const char* container_parse_tiled(const uint8_t* data, size_t n, uint64_t max_pixels, TiledInfo* info);
+// tile k's file: data[*off, *off + *len), from a parsed file's table
+const char* container_tiled_tile(const uint8_t* data, size_t n, const TiledInfo* info, uint64_t k, size_t* off,
+                                 size_t* len);
 
 }  // namespace mlic
 #endif

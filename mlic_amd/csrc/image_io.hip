@@ -11,6 +11,7 @@
 // order-independent: one 64-bit integer atomic per block).
 // blur3_pad: the rate loop's 3x3 prefilter on the padded fp32 planes, with the gather that compacts the images
 // still over budget (its own comment below).
+// tile_blend: egress of a region of a tiled image from its overlapping tiles, feathered seams (its own comment).
 //
 // A block is four waves; a wave owns one image row of the tile and 256 pixels of it.  Byte rows start at
 // any address (W * 3 is odd for odd W), so the two canonical layouts go through LDS: the row segment sits
@@ -18,6 +19,7 @@
 // either end move as bytes -- nothing outside the segment is read or written.  The fp32 side is one
 // 256-byte row piece per wave instruction.  Any other stride set takes the general kernels (byte accesses
 // straight from / to global memory); all forms give the same bits.
+#include "container.h"
 #include "kernels.h"
 
 namespace mlic {
@@ -198,6 +200,162 @@ __global__ __launch_bounds__(256) void egress_u8_kernel(const float* __restrict_
   }
 }
 
+// Tiled decode's egress (DESIGN.md section 5 "Tiled coding"): the h x w region at (y0, x0) of the full image as
+// uint8, blended from the fp32 planes of the tiles that cover it.  tiles[ky * nx + kx] is tile (ky, kx)'s
+// contiguous [3][pad64(extent_y)][pad64(extent_x)] planes or null (the host checked that no covering tile is
+// null; a null is skipped all the same).  Per pixel and channel acc (double) = 0; acc += (double)(wy * wx) *
+// (double)v over the covering tiles, tile row then tile column; wy * wx is a dyadic rational of at most 14 bits
+// (exact in fp32), so each product is exact in double and the sums are rounded in that fixed order.  Then
+// (float)acc goes through egress_u8_kernel's conversion, staging and squared-error sum.  egress_u8_kernel's
+// structure: a wave owns one region row and 256 pixels of it.  Which tile rows and columns cover the piece is
+// decided once per piece (scalar); a lane only tests whether its pixel lies inside the tile column at hand, and a
+// piece that one tile covers outside every strip (most of them) skips the weights and the doubles altogether.
+struct BlendGrid {
+  int H, W, T, V, ny, nx;
+};
+
+template <int PATH, bool REF>
+__global__ __launch_bounds__(256) void tile_blend_u8_kernel(const float* const* __restrict__ tiles, BlendGrid q,
+                                                            int y0, int x0, int h, int w, uint8_t* __restrict__ dst,
+                                                            IoStride4 ds, const uint8_t* __restrict__ ref,
+                                                            IoStride4 rs, unsigned long long* __restrict__ sq_err,
+                                                            int tiles_x, int tiles_y) {
+  __shared__ uint32_t S[IO_ROWS][IO_LDS];
+  __shared__ unsigned int red[IO_ROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int G = REF ? IO_REF_GROUPS : 1;
+  const IoTile t = io_tile(tiles_x, tiles_y, G * IO_ROWS);  // one "image": t.img = 0
+  uint8_t* S8 = reinterpret_cast<uint8_t*>(S[wave]);
+  const int step = q.T - q.V, den = q.V ? 2 * q.V : 1;
+  const float inv = 1.0f / (float)(den * den);  // a power of two
+  unsigned int acc_sq = 0;
+  for (int g = 0; g < G; ++g) {
+    const int y = t.y + g * IO_ROWS;
+    const int nx = y < h ? min(IO_TW, w - t.x0) : 0;
+    uint8_t* row = dst + (int64_t)y * ds.row + (int64_t)t.x0 * ds.col;
+    const uint8_t* rrow = REF ? ref + (int64_t)y * rs.row + (int64_t)t.x0 * rs.col : nullptr;
+    float val[IO_TW / 64][3];  // (float)acc per pixel of this lane
+#pragma unroll
+    for (int j = 0; j < IO_TW / 64; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) val[j][c] = 0.0f;
+    if (nx > 0) {
+      const int Y = y0 + y, X0 = x0 + t.x0;  // Y < H, X0 + nx <= W: the host checked the region
+      const int ky1 = min(Y / step, q.ny - 1);
+      const int ky0 = (ky1 > 0 && Y - ky1 * step < q.V) ? ky1 - 1 : ky1;
+      int kxa = min(X0 / step, q.nx - 1);
+      if (kxa > 0 && X0 - kxa * step < q.V) --kxa;
+      const int kxb = min((X0 + nx - 1) / step, q.nx - 1);
+      if (ky0 == ky1 && kxa == kxb) {
+        // One tile covers the whole piece and no pixel of it lies in a strip (the row is in no strip with tile
+        // row ky1 - 1 and below the one with ky1 + 1; likewise the columns): every weight is 1 and acc = 0 + 1 * v
+        // is v (a -0 becomes +0, which the clamp does too), so this is egress_u8_kernel's read
+        const float* p = tiles[(int64_t)ky1 * q.nx + kxa];
+        if (p != nullptr) {
+          const int hp = (min(q.T, q.H - ky1 * step) + 63) & ~63, wp = (min(q.T, q.W - kxa * step) + 63) & ~63;
+          const int64_t plane = (int64_t)hp * wp;
+          const float* in = p + (int64_t)(Y - ky1 * step) * wp + (X0 - kxa * step);
+#pragma unroll
+          for (int j = 0; j < IO_TW / 64; ++j) {
+            const int px = lane + 64 * j;
+            if (px >= nx) break;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) val[j][c] = in[c * plane + px];
+          }
+        }
+      } else {
+        double acc[IO_TW / 64][3];
+#pragma unroll
+        for (int j = 0; j < IO_TW / 64; ++j)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[j][c] = 0.0;
+        for (int ky = ky0; ky <= ky1; ++ky) {
+          const int ly = Y - ky * step;  // 0 <= ly < extent of tile row ky
+          const int hp = (min(q.T, q.H - ky * step) + 63) & ~63;
+          const int numy = (int)tile_weight_num((uint32_t)ly, (uint32_t)ky, (uint32_t)q.ny, (uint32_t)q.T, (uint32_t)q.V);
+          for (int kx = kxa; kx <= kxb; ++kx) {
+            const float* p = tiles[(int64_t)ky * q.nx + kx];
+            if (p == nullptr) continue;
+            const int ext = min(q.T, q.W - kx * step), wp = (ext + 63) & ~63;
+            const int64_t plane = (int64_t)hp * wp;
+            const float* in = p + (int64_t)ly * wp;
+            // every lane loads from a position clamped into the tile's row, so the twelve loads of a tile column
+            // go out together; a pixel outside the tile keeps its sum (a select, not a product with 0)
+            float v[IO_TW / 64][3];
+            int lxs[IO_TW / 64];
+#pragma unroll
+            for (int j = 0; j < IO_TW / 64; ++j) {
+              lxs[j] = X0 + lane + 64 * j - kx * step;
+              const int at = min(max(lxs[j], 0), ext - 1);
+#pragma unroll
+              for (int c = 0; c < 3; ++c) v[j][c] = in[c * plane + at];
+            }
+#pragma unroll
+            for (int j = 0; j < IO_TW / 64; ++j) {
+              const int lx = lxs[j];
+              const bool inside = lane + 64 * j < nx && lx >= 0 && lx < ext;
+              const int numx = (int)tile_weight_num((uint32_t)min(max(lx, 0), ext - 1), (uint32_t)kx, (uint32_t)q.nx,
+                                                    (uint32_t)q.T, (uint32_t)q.V);
+              const double wgt = (double)((float)(numy * numx) * inv);
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                const double sum = __dadd_rn(acc[j][c], __dmul_rn(wgt, (double)v[j][c]));
+                acc[j][c] = inside ? sum : acc[j][c];
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < IO_TW / 64; ++j)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) val[j][c] = (float)acc[j][c];
+      }
+    }
+    int sh[3] = {0, 0, 0};
+    if (PATH == IO_HWC) sh[0] = addr_mod4(row);
+    if (PATH == IO_CHW) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sh[c] = addr_mod4(row + c * ds.ch);
+    }
+#pragma unroll
+    for (int j = 0; j < IO_TW / 64; ++j) {
+      const int px = lane + 64 * j;
+      if (px >= nx) break;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint8_t u = (uint8_t)floorf(fminf(fmaxf(val[j][c], 0.0f), 1.0f) * 255.0f);
+        if (PATH == IO_HWC) S8[sh[0] + 3 * px + c] = u;
+        else if (PATH == IO_CHW) S8[c * IO_SEG * 4 + sh[c] + px] = u;
+        else row[(int64_t)px * ds.col + c * ds.ch] = u;
+        if (REF) {
+          const int d = (int)u - (int)rrow[(int64_t)px * rs.col + c * rs.ch];
+          acc_sq += (unsigned int)(d * d);
+        }
+      }
+    }
+    if (PATH != IO_GENERAL) {
+      __syncthreads();
+      if (PATH == IO_HWC && nx > 0) stage_out(row, 3 * nx, S[wave], lane);
+      if (PATH == IO_CHW && nx > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) stage_out(row + c * ds.ch, nx, S[wave] + c * IO_SEG, lane);
+      }
+      if (G > 1) __syncthreads();
+    }
+  }
+  if (REF) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc_sq += __shfl_down(acc_sq, off, 64);
+    if (lane == 0) red[wave] = acc_sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned long long s =
+          (unsigned long long)red[0] + (unsigned long long)red[1] + (unsigned long long)red[2] + (unsigned long long)red[3];
+      if (s) atomicAdd(sq_err, s);
+    }
+  }
+}
+
 // The rate loop's prefilter (utils/testing.py:363-390: crop, 3x3 depthwise conv with padding 1, pad to 64
 // again) on the padded fp32 planes, one read and one write of the plane.  A thread owns BL_RUN consecutive
 // columns of BL_ROWS consecutive rows: 256 threads are whole row groups (Wp / BL_RUN is a multiple of 16), a
@@ -362,6 +520,66 @@ void image_egress_u8(const float* src, const int64_t* s, int B, int H, int W, ui
   if (path == IO_HWC) egress_launch<IO_HWC>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
   else if (path == IO_CHW) egress_launch<IO_CHW>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
   else egress_launch<IO_GENERAL>(blocks, st, src, ss, H, W, dst, ds, ref, rs, sq_err, tx, ty);
+  HIP_OK(hipGetLastError());
+}
+
+template <int PATH>
+static void blend_launch(unsigned blocks, hipStream_t st, const float* const* tiles, BlendGrid q, int y0, int x0, int h,
+                         int w, uint8_t* dst, IoStride4 ds, const uint8_t* ref, IoStride4 rs, uint64_t* sq, int tx,
+                         int ty) {
+  auto* sq64 = reinterpret_cast<unsigned long long*>(sq);
+  if (ref)
+    hipLaunchKernelGGL((tile_blend_u8_kernel<PATH, true>), dim3(blocks), dim3(256), 0, st, tiles, q, y0, x0, h, w, dst,
+                       ds, ref, rs, sq64, tx, ty);
+  else
+    hipLaunchKernelGGL((tile_blend_u8_kernel<PATH, false>), dim3(blocks), dim3(256), 0, st, tiles, q, y0, x0, h, w, dst,
+                       ds, ref, rs, sq64, tx, ty);
+}
+
+void image_tile_blend_u8(const float* const* tiles_dev, const float* const* tiles_host, int H, int W, int T, int V,
+                         int y0, int x0, int h, int w, uint8_t* dst, const int64_t* d, const uint8_t* ref,
+                         const int64_t* r, uint64_t* sq_err, hipStream_t st) {
+  MLIC_CHECK(tiles_dev != nullptr && tiles_host != nullptr && dst != nullptr && d != nullptr,
+             "image_tile_blend_u8: null argument");
+  MLIC_CHECK(H >= 1 && W >= 1 && H <= (1 << 24) && W <= (1 << 24), "image_tile_blend_u8: H, W in [1, 2^24] expected");
+  MLIC_CHECK(T >= 0 && V >= 0, "image_tile_blend_u8: negative tile or overlap");
+  if (const char* err = tile_params_check((uint32_t)T, (uint32_t)V))
+    throw Error(std::string("mlic: image_tile_blend_u8: ") + err);
+  MLIC_CHECK(h >= 1 && w >= 1 && y0 >= 0 && x0 >= 0 && y0 <= H - h && x0 <= W - w,
+             "image_tile_blend_u8: the region must be non-empty and inside the image");
+  MLIC_CHECK(d[1] != 0 && d[2] != 0, "image_tile_blend_u8: zero column or channel stride (dst)");
+  MLIC_CHECK((ref != nullptr) == (sq_err != nullptr), "image_tile_blend_u8: ref and sq_err go together");
+  MLIC_CHECK(ref == nullptr || (r != nullptr && r[1] != 0 && r[2] != 0),
+             "image_tile_blend_u8: ref needs strides with nonzero column and channel stride");
+  MLIC_CHECK(reinterpret_cast<uintptr_t>(tiles_dev) % 8 == 0 && reinterpret_cast<uintptr_t>(sq_err) % 8 == 0,
+             "image_tile_blend_u8: the tile table and sq_err must be 8-byte aligned");
+  const int ny = (int)tile_count((uint32_t)H, (uint32_t)T, (uint32_t)V);
+  const int nx = (int)tile_count((uint32_t)W, (uint32_t)T, (uint32_t)V);
+  // every tile that intersects the region must be there
+  const int step = T - V;
+  auto first = [&](int p, int n) {
+    int k = std::min(p / step, n - 1);
+    return (k > 0 && p - k * step < V) ? k - 1 : k;
+  };
+  const int ky0 = first(y0, ny), ky1 = std::min((y0 + h - 1) / step, ny - 1);
+  const int kx0 = first(x0, nx), kx1 = std::min((x0 + w - 1) / step, nx - 1);
+  for (int ky = ky0; ky <= ky1; ++ky)
+    for (int kx = kx0; kx <= kx1; ++kx) {
+      const float* p = tiles_host[(size_t)ky * nx + kx];
+      MLIC_CHECK(p != nullptr, "image_tile_blend_u8: a tile that covers the region is null");
+      MLIC_CHECK(reinterpret_cast<uintptr_t>(p) % 4 == 0, "image_tile_blend_u8: a tile is not 4-byte aligned");
+    }
+  const int64_t d4[4] = {0, d[0], d[1], d[2]};
+  const int path = io_path(d4);
+  int tx, ty;
+  const unsigned blocks = io_blocks(1, h, w, &tx, &ty, (ref ? IO_REF_GROUPS : 1) * IO_ROWS);
+  const BlendGrid q{H, W, T, V, ny, nx};
+  const IoStride4 ds{0, d[0], d[1], d[2]};
+  const IoStride4 rs = ref ? IoStride4{0, r[0], r[1], r[2]} : IoStride4{0, 0, 0, 0};
+  if (sq_err) HIP_OK(hipMemsetAsync(sq_err, 0, sizeof(uint64_t), st));
+  if (path == IO_HWC) blend_launch<IO_HWC>(blocks, st, tiles_dev, q, y0, x0, h, w, dst, ds, ref, rs, sq_err, tx, ty);
+  else if (path == IO_CHW) blend_launch<IO_CHW>(blocks, st, tiles_dev, q, y0, x0, h, w, dst, ds, ref, rs, sq_err, tx, ty);
+  else blend_launch<IO_GENERAL>(blocks, st, tiles_dev, q, y0, x0, h, w, dst, ds, ref, rs, sq_err, tx, ty);
   HIP_OK(hipGetLastError());
 }
 

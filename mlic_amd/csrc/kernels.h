@@ -311,6 +311,16 @@ void image_egress_u8(const float* src, const int64_t* src_strides, int B, int H,
 // overlap the n images at src, nor any image src_index names.  Checks its arguments before any HIP call.
 void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp, const float* w9,
                      float* dst, hipStream_t st);
+// tiled decode's egress: the h x w region at (y0, x0) of the H x W image, blended from the tiles of the grid
+// (container.h: tile T, overlap V) with feathered seams, as uint8 through dst's {row, column, channel} strides.
+// tiles_dev: the device table, tile index (row-major) -> that tile's contiguous fp32 [3][pad64(ey)][pad64(ex)]
+// planes or null; tiles_host: the same table on the host, from which a region whose covering tile is null is
+// refused.  Per value acc (double) = sum over the covering tiles, tile row then column, of (double)(wy * wx) *
+// (double)v; (float)acc then goes through egress's conversion.  With ref ({row, column, channel} strides of the
+// region's crop of the original), *sq_err = the exact sum of squared uint8 differences.
+void image_tile_blend_u8(const float* const* tiles_dev, const float* const* tiles_host, int H, int W, int T, int V,
+                         int y0, int x0, int h, int w, uint8_t* dst, const int64_t* dst_strides, const uint8_t* ref,
+                         const int64_t* ref_strides, uint64_t* sq_err, hipStream_t st);
 // ROI coding (roi.hip).  All three check their arguments before any HIP call and throw.
 // levels [B][hz][wz] (hz, wz = ceil(H / 64), ceil(W / 64)) of a uint8 mask read through element strides {image,
 // row, column}: level = lo + ceil((hi - lo) * count / area) per 64 x 64 cell clipped to the image, in integers

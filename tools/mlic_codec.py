@@ -10,7 +10,14 @@
     ... --roi MASK --roi-levels LO HI (encode, a *_VBR model): ROI coding.  MASK is an image of the picture's size,
         read as images are, first channel, nonzero = inside the region of interest: 64 x 64 blocks outside it are
         coded at level LO, blocks inside at up to HI.  The file carries the level map; decode needs no flag
-    python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR      what the file says (and its level map)
+    ... --tile T [--overlap V] (encode): tiled coding.  The image is cut into T x T tiles (T a multiple of 64, at
+        least 128) that overlap by V pixels (0, 16, 32 or 64; default 32), each tile is coded by itself, and the
+        file is the tiled container with an index.  Device memory is that of --tile-batch tiles (default 8)
+        whatever the image's size.  Goes with --level N; not with --max-bpp, --level auto or --roi
+    ... --region Y0 X0 H W (decode, a tiled file): decode that window only; the tiles outside it are not touched.
+        A tiled file is recognised by its magic; decode needs no --tile
+    python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR      what the file says (and its level map, or
+        for a tiled file its grid and per-tile sizes)
 
 Binary PPM (P6, maxval 255) is read and written here; any other format goes through PIL when it imports.
 """
@@ -151,7 +158,28 @@ def parse_args(argv=None):
     ap.add_argument("--max-passes", type=int, default=8, metavar="N")
     ap.add_argument("--roi", default=None, metavar="MASK")
     ap.add_argument("--roi-levels", type=int, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--tile", type=int, default=None, metavar="T")
+    ap.add_argument("--overlap", type=int, default=None, metavar="V")
+    ap.add_argument("--tile-batch", type=int, default=8, metavar="N")
+    ap.add_argument("--region", type=int, nargs=4, default=None, metavar=("Y0", "X0", "H", "W"))
     args = ap.parse_args(argv)
+    if args.tile is not None:
+        if args.mode != "encode":
+            ap.error("--tile goes with encode (a tiled file is recognised by its magic)")
+        if args.max_bpp is not None or args.level == "auto" or args.roi is not None or args.roi_levels is not None:
+            ap.error("--tile goes with --level N alone, not with --max-bpp, --level auto or --roi")
+        if args.tile % 64 or args.tile < 128:
+            ap.error("--tile: a multiple of 64, at least 128, expected")
+    elif args.overlap is not None:
+        ap.error("--overlap goes with --tile")
+    if args.overlap is None:
+        args.overlap = 32
+    if args.overlap not in (0, 16, 32, 64) or (args.tile is not None and args.overlap > args.tile // 2):
+        ap.error("--overlap: 0, 16, 32 or 64, at most half the tile, expected")
+    if args.tile_batch < 1:
+        ap.error("--tile-batch must be positive")
+    if args.region is not None and args.mode != "decode":
+        ap.error("--region goes with decode")
     if args.mode != "info" and args.dst is None:
         ap.error(f"{args.mode} needs a destination file")
     if args.mode != "info" and args.checkpoint is None and args.synthetic is None:
@@ -188,7 +216,19 @@ def main(argv=None):
         with open(args.src, "rb") as f:
             data = f.read()
         vbr = bool(spec.get_config(args.model).vbr)
+        if codec.is_tiled_file(data):  # the file's own flag against the model, before any tile is parsed
+            flag = bool(codec.parse_container_tiled(data).vbr)
+            if flag != vbr:
+                raise SystemExit(f"{args.src}: the tiles {'carry a' if flag else 'have no'} level word, "
+                                 f"{args.model} is {'variable' if vbr else 'fixed'}-rate")
         d = codec.peek(data, vbr=vbr, n_levels=len(spec.vbr_lambdas(args.model)) if vbr else None)
+        if d.get("tiled"):
+            print(f"{args.src}: {d['H']} x {d['W']}, tiled: tile {d['tile']}, overlap {d['overlap']}, grid "
+                  f"{d['grid'][0]} x {d['grid'][1]}, level {d['level']}, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
+            for t in d["tiles"]:
+                print(f"  tile {t['index']}: at ({t['y0']}, {t['x0']}), {t['H']} x {t['W']}, {t['bytes']} bytes, "
+                      f"{t['bpp']:.4f} bpp")
+            return
         print(f"{args.src}: {d['H']} x {d['W']}, level {d['level']}, z grid {d['shape'][0]} x {d['shape'][1]}, "
               f"y {d['y_len']} B, z {d['z_len']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
         if "roi_levels" in d:
@@ -197,6 +237,14 @@ def main(argv=None):
     if args.mode == "encode":
         img = load_image(args.src)
         net = load_model(args)
+        if args.tile is not None:
+            data, info = codec.encode_tiled(net, img, tile=args.tile, overlap=args.overlap, level=args.level,
+                                            layout="hwc", tile_batch=args.tile_batch, return_info=True)
+            with open(args.dst, "wb") as f:
+                f.write(data)
+            print(f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {len(data)} bytes, {info['bpp']:.4f} bpp, tile "
+                  f"{args.tile}, overlap {args.overlap}, grid {info['grid'][0]} x {info['grid'][1]}")
+            return
         roi = None
         if args.roi is not None:
             roi = np.ascontiguousarray(load_image(args.roi)[:, :, 0])
@@ -221,6 +269,16 @@ def main(argv=None):
         with open(args.src, "rb") as f:
             data = f.read()
         net = load_model(args)
+        if codec.is_tiled_file(data):
+            img, info = codec.decode_tiled(net, data, region=args.region, tile_batch=args.tile_batch)
+            save_image(args.dst, img.cpu().numpy())
+            y0, x0, h, w = info["region"]
+            print(f"{args.src}: {info['H']} x {info['W']}, level {info['level']}, {info['bpp']:.4f} bpp, region "
+                  f"{h} x {w} at ({y0}, {x0}), {len(info['tiles_decoded'])} of {info['grid'][0] * info['grid'][1]} tiles "
+                  f"decoded")
+            return
+        if args.region is not None:
+            raise SystemExit(f"{args.src}: --region needs a tiled file (encode --tile T)")
         img, info = codec.decode_images(net, [data])
         save_image(args.dst, img[0].cpu().numpy())
         print(f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp")
