@@ -249,6 +249,30 @@ int mlic_local_attn_packed_run(void* stream, const float* qkv, const float* rel_
    slice loop's LocalContext, whose only consumer reads the non-anchor pixels) */
 int mlic_local_attn_packed_half_run(void* stream, const float* qkv, const float* rel_table, const int32_t* rel_index,
                                     uint16_t* out, int H, int W, int B, float scale, int ckbd);
+/* the number of key splits the model runs the linear attention of an H*W = HW latent with (host logic
+ * only, no GPU touched): 1 <= *nsplit <= 64, every split of ceil(HW / *nsplit) keys non-empty */
+int mlic_linatt_splits(int HW, int* nsplit);
+/* linear attention (context.py:180-187 / 235-239), the model's three launches: k, v, q -> out, all fp32
+ * [B][heads*hd][H*W], hd 16 or 32; ctx_out: optional [B][heads][hd][hd], ctx = softmax_L(K) . V^T per head;
+ * nsplit <= 0: the model's choice (mlic_linatt_splits), else 1..64 key splits; kmask 1: only the anchor pixels
+ * ((y + x) odd) are keys; qmask 1: only the non-anchor pixels have queries (out is 0 at anchors).  The entry
+ * owns its workspace; synchronous on `stream` */
+int mlic_linear_attention_run(void* stream, const float* k, const float* v, const float* q, float* out, float* ctx_out,
+                              int B, int heads, int hd, int H, int W, int nsplit, int kmask, int qmask);
+/* the fused form's second half: ctx^T . softmax_c(q) written in conv_x4's packed split layout for a stride-1
+ * K x K conv (K 3 or 5, pad K/2) over [B][heads*hd][H][W] (heads*hd a multiple of 32): out_halves = uint16
+ * (fp16 bits) [B][heads*hd/32][(H+K-1)*(W+K-1)][64], one line per position of the zero-padded image, hi of the
+ * chunk's 32 channels at 0..31 and lo at 32..63; no range flag; synchronous on `stream` */
+int mlic_linatt_pack_run(void* stream, const float* q, const float* ctx, uint16_t* out_halves, int B, int heads, int hd,
+                         int H, int W, int K, int qmask);
+/* nn.LayerNorm(C) over the channel axis of x [B][C][HW] (eps 1e-5; gamma, beta [C]), C in {32, 64, 128};
+ * synchronous on `stream` */
+int mlic_ln_channels_run(void* stream, const float* x, const float* gamma, const float* beta, float* y, int B, int C,
+                         int HW);
+/* the tail of g_s: part [B][108][H][W] (row tap*12 + c: the per-tap partial products of the N -> 12 3x3 conv)
+ * -> out [B][3][2H][2W] = PixelShuffle(2)(bias + the nine shifted partials summed in tap order); bias [12] or
+ * NULL; synchronous on `stream` */
+int mlic_taps_gather_run(void* stream, const float* part, const float* bias, float* out, int B, int H, int W);
 int mlic_image_sq_err_u8(void* stream, const float* a, const float* b, int B, int64_t n_per, double* out);
 /* bytes of device scratch mlic_image_ms_ssim_u8 needs (pooled planes + partial sums); host logic only,
  * no GPU touched; nonzero rc with a message when C < 1, B < 1 or min(H, W) <= 160 */

@@ -85,6 +85,11 @@ def _sig(lib):
         "mlic_local_attn_run": [p, i, p, p, p, p, i, i, i, i, f],
         "mlic_local_attn_packed_run": [p, p, p, p, p, i, i, i, f],
         "mlic_local_attn_packed_half_run": [p, p, p, p, p, i, i, i, f, i],
+        "mlic_linatt_splits": [i, P(i)],
+        "mlic_linear_attention_run": [p, p, p, p, p, p, i, i, i, i, i, i, i, i],
+        "mlic_linatt_pack_run": [p, p, p, p, i, i, i, i, i, i, i],
+        "mlic_ln_channels_run": [p, p, p, p, p, i, i, i],
+        "mlic_taps_gather_run": [p, p, p, p, i, i, i],
         "mlic_image_sq_err_u8": [p, p, p, i, i64, p],
         "mlic_ms_ssim_scratch_bytes": [i, i, i, i, P(sz)],
         "mlic_image_ms_ssim_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, sz, p, p],

@@ -670,6 +670,88 @@ int mlic_local_attn_packed_half_run(void* stream, const float* qkv, const float*
   });
 }
 
+// one image's pixel count as the kernels index it (int, with a launch block of headroom), and the
+// launch grids' y / z extents
+static void check_grid(int B, int H, int W, int rows) {
+  MLIC_CHECK(B >= 1 && B <= 65535, "B must be in 1..65535");
+  MLIC_CHECK(H >= 1 && W >= 1 && (int64_t)H * W <= (int64_t)1 << 30, "H, W must be >= 1 and H * W <= 2^30");
+  MLIC_CHECK(rows >= 1 && (int64_t)rows * B <= 65535, "too many (image, head) rows for one launch");
+}
+
+int mlic_linatt_splits(int HW, int* nsplit) {
+  return guard([&] {
+    MLIC_CHECK(nsplit != nullptr, "null nsplit");
+    MLIC_CHECK(HW >= 1, "HW must be >= 1");
+    *nsplit = ctx_splits(HW);
+  });
+}
+
+int mlic_linear_attention_run(void* stream, const float* k, const float* v, const float* q, float* out, float* ctx_out,
+                              int B, int heads, int hd, int H, int W, int nsplit, int kmask, int qmask) {
+  return guard([&] {
+    MLIC_CHECK(k && v && q && out, "null tensor");
+    MLIC_CHECK(hd == 16 || hd == 32, "hd must be 16 or 32");
+    MLIC_CHECK(heads >= 1, "heads must be >= 1");
+    check_grid(B, H, W, heads);
+    MLIC_CHECK(nsplit <= 64, "nsplit must be <= 64 (<= 0: the model's choice)");
+    MLIC_CHECK((kmask == 0 || kmask == 1) && (qmask == 0 || qmask == 1), "kmask, qmask must be 0 or 1");
+    hipStream_t st = (hipStream_t)stream;
+    const int HW = H * W;
+    const int ns = nsplit <= 0 ? ctx_splits(HW) : nsplit;
+    const int64_t bs = (int64_t)heads * hd * HW, nctx = (int64_t)B * heads * hd * hd;
+    float *part = nullptr, *ctx = nullptr;
+    HIP_OK(hipMallocAsync((void**)&part, linear_attention_part_floats(heads, hd, B, ns) * 4, st));
+    HIP_OK(hipMallocAsync((void**)&ctx, nctx * 4, st));
+    linear_attention(k, bs, v, bs, q, bs, out, bs, part, ctx, heads, hd, H, W, B, ns, kmask, qmask, st);
+    if (ctx_out) HIP_OK(hipMemcpyAsync(ctx_out, ctx, nctx * 4, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipFreeAsync(part, st));
+    HIP_OK(hipFreeAsync(ctx, st));
+    HIP_OK(hipStreamSynchronize(st));
+  });
+}
+
+int mlic_linatt_pack_run(void* stream, const float* q, const float* ctx, uint16_t* out_halves, int B, int heads, int hd,
+                         int H, int W, int K, int qmask) {
+  return guard([&] {
+    MLIC_CHECK(q && ctx && out_halves, "null tensor");
+    MLIC_CHECK(hd == 16 || hd == 32, "hd must be 16 or 32");
+    MLIC_CHECK(heads >= 1 && (heads * (int64_t)hd) % 32 == 0, "heads * hd must be a multiple of 32");
+    MLIC_CHECK(K == 3 || K == 5, "K must be 3 or 5");
+    check_grid(B, H, W, heads * hd / 32);
+    check_grid(B, H + K - 1, W + K - 1, 1);  // the padded image's lines
+    MLIC_CHECK(qmask == 0 || qmask == 1, "qmask must be 0 or 1");
+    ConvParams P{};
+    P.nseg = 1;
+    P.seg[0] = {nullptr, heads * hd, (int64_t)heads * hd * H * W};  // geometry only: the pack reads q
+    P.Cin = heads * hd; P.H = H; P.W = W; P.Cout = P.Cin; P.Ho = H; P.Wo = W; P.K = K; P.stride = 1; P.pad = K / 2;
+    P.B = B;
+    P.rflag = nullptr;
+    linatt_pack(q, P.seg[0].bs, ctx, heads, hd, qmask, P, reinterpret_cast<_Float16*>(out_halves), (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_ln_channels_run(void* stream, const float* x, const float* gamma, const float* beta, float* y, int B, int C,
+                         int HW) {
+  return guard([&] {
+    MLIC_CHECK(x && gamma && beta && y, "null tensor");
+    MLIC_CHECK(C == 32 || C == 64 || C == 128, "C must be 32, 64 or 128");
+    check_grid(B, 1, HW, 1);
+    ln_channels(x, (int64_t)C * HW, y, (int64_t)C * HW, gamma, beta, C, HW, B, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_taps_gather_run(void* stream, const float* part, const float* bias, float* out, int B, int H, int W) {
+  return guard([&] {
+    MLIC_CHECK(part && out, "null tensor");
+    check_grid(B, H, W, 1);
+    MLIC_CHECK((H + 3) / 4 <= 65535, "H too large for one launch");
+    taps_gather(part, (int64_t)108 * H * W, bias, out, (int64_t)12 * H * W, H, W, B, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
 int mlic_local_attn_mask(void* stream, float* out, int H, int W) {
   return guard([&] { local_mask(out, H, W, (hipStream_t)stream); });
 }

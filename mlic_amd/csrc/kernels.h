@@ -173,6 +173,9 @@ void local_attn_packed(const LocalAttnParams& P, _Float16* out, int npos, hipStr
 
 // context.py:180-187 / 235-239 in three launches (no materialised softmax); kmask: anchor-only keys,
 // qmask: non-anchor-only queries; part: linear_attention_part_floats() floats
+// the model's split policy (also mlic_linatt_splits): splits of at least 256 keys, at most 64 of them, none
+// empty -- ctx_partial's loop bounds are ceil(HW / nsplit) keys per split
+inline int ctx_splits(int HW) { return std::max(1, std::min(64, HW / 256)); }
 int64_t linear_attention_part_floats(int heads, int hd, int B, int nsplit);
 void linear_attention(const float* K, int64_t k_bs, const float* V, int64_t v_bs, const float* Q, int64_t q_bs,
                       float* out, int64_t o_bs, float* part, float* ctx, int heads, int hd, int H, int W, int B,

@@ -1068,8 +1068,6 @@ View Model::qkv_branch(const View& x, const std::string& p) {
   return out;
 }
 
-static int ctx_splits(int HW) { return std::max(1, std::min(64, HW / 256)); }
-
 // context.py:195-245 LinearGlobalInterContext
 View Model::inter_context(const View& x, int i) {
   const std::string p = "global_inter_context." + std::to_string(i);

@@ -53,6 +53,61 @@ def test_conv_choice_is_batch_independent():
         assert len(got) == 1, (Cin, Cout, H, W, K, stride, got)
 
 
+def test_linatt_split_policy_never_leaves_a_split_empty():
+    """The linear attention's key-split policy (the function the model itself calls) over every latent
+    size up to 200 000 pixels: 1..64 splits, none of fewer than 256 keys unless there is only one, and
+    with ceil(HW / n) keys per split the last split still starts inside the image -- the contract
+    ctx_partial_kernel's loop bounds rest on (an empty split's record would carry the max sentinel)."""
+    fn = _lib.lib().mlic_linatt_splits
+    n = C.c_int()
+    ref = C.byref(n)
+    for HW in range(1, 200001):
+        assert fn(HW, ref) == 0, HW
+        v = n.value
+        assert 1 <= v <= 64, (HW, v)
+        assert v <= max(1, HW // 256), (HW, v)
+        assert (v - 1) * -(-HW // v) < HW, (HW, v)
+    assert [fn(hw, ref) or n.value for hw in (96, 511, 512, 68 * 120, 136 * 240)] == [1, 1, 2, 31, 64]
+    for bad in (0, -5):
+        with pytest.raises(_lib.MlicError, match="HW must be"):
+            _lib.call("mlic_linatt_splits", bad, ref)
+    with pytest.raises(_lib.MlicError, match="null nsplit"):
+        _lib.call("mlic_linatt_splits", 100, None)
+
+
+def test_kernel_entries_refuse_bad_arguments_before_any_gpu_call():
+    """The kernel-level entries of the linear attention, LayerNorm and tap gather check every argument
+    before they touch the GPU: each refusal below comes back as an error on a machine without one (the
+    pointers are never dereferenced)."""
+    x = C.c_void_p(64)  # non-null, never read
+    la = lambda **kw: _lib.call("mlic_linear_attention_run", None, kw.get("k", x), x, x, kw.get("out", x), None,  # noqa: E731
+                                kw.get("B", 1), kw.get("heads", 2), kw.get("hd", 32), kw.get("H", 8), kw.get("W", 8),
+                                kw.get("nsplit", 1), kw.get("kmask", 0), kw.get("qmask", 0))
+    for kw, msg in (({"hd": 17}, "hd must be"), ({"hd": 64}, "hd must be"), ({"nsplit": 65}, "nsplit must be"),
+                    ({"k": None}, "null tensor"), ({"out": None}, "null tensor"), ({"heads": 0}, "heads must be"),
+                    ({"B": 0}, "B must be"), ({"H": 0}, "H, W must be"), ({"W": -3}, "H, W must be"),
+                    ({"H": 1 << 16, "W": 1 << 16}, "H, W must be"), ({"B": 40000}, "too many"),
+                    ({"kmask": 2}, "kmask, qmask"), ({"qmask": -1}, "kmask, qmask")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            la(**kw)
+    pk = lambda **kw: _lib.call("mlic_linatt_pack_run", None, x, kw.get("ctx", x), x, 1, kw.get("heads", 2),  # noqa: E731
+                                kw.get("hd", 16), 8, kw.get("W", 8), kw.get("K", 5), kw.get("qmask", 0))
+    for kw, msg in (({"K": 1}, "K must be"), ({"K": 4}, "K must be"), ({"K": 7}, "K must be"), ({"hd": 8}, "hd must be"),
+                    ({"heads": 3}, "multiple of 32"), ({"ctx": None}, "null tensor"), ({"W": 0}, "H, W must be"),
+                    ({"qmask": 2}, "qmask must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            pk(**kw)
+    for args, msg in (((x, x, x, x, 1, 48, 10), "C must be"), ((x, x, x, x, 1, 256, 10), "C must be"),
+                      ((x, None, x, x, 1, 32, 10), "null tensor"), ((x, x, x, None, 1, 32, 10), "null tensor"),
+                      ((x, x, x, x, 1, 32, 0), "H, W must be"), ((x, x, x, x, 0, 32, 10), "B must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_ln_channels_run", None, *args)
+    for args, msg in (((None, x, x, 1, 4, 4), "null tensor"), ((x, None, None, 1, 4, 4), "null tensor"),
+                      ((x, x, x, 1, 0, 4), "H, W must be"), ((x, x, x, 70000, 4, 4), "B must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_taps_gather_run", None, *args)
+
+
 def test_gaussian_tables_match_reference_update(golden):
     g = golden("scale_table.npz")
     cdf, length, offset, table = entropy.gaussian_tables(entropy.get_scale_table())
