@@ -524,6 +524,76 @@ int mlic_encode_image_u8_budget(mlic_model* m, void* stream, const uint8_t* rgb_
 int mlic_decode_image_u8(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels, uint64_t max_pixels,
                          const float* vbr_gains, uint8_t* rgb_dev, const int64_t* strides, size_t cap_bytes, int* H,
                          int* W, int* level);
+
+/* ---- 8-bit Y'CbCr frames in and out (DESIGN.md section 5 "YCbCr I/O") ----
+ *
+ * A frame is three byte planes on the device, each a pointer plus element strides {image, row, column}: Y is
+ * H x W, Cb and Cr are ceil(H / sub_y) x ceil(W / sub_x) (odd H and W are legal).  The planes are independent, so
+ * one description covers I420 / YV12 (swap the chroma pointers), I422, I444, NV12 (cb = uv, cr = uv + 1, column
+ * stride 2) / NV21, row-padded pitches and crops of larger frames.  Matrix, range and siting are the caller's
+ * knowledge, as the VBR level word's presence is: they are not written into the file.  Bit depths above 8, alpha,
+ * other matrices (BT.2020) and 4:4:0 are out of scope and refused where reachable. */
+typedef struct mlic_yuv_desc {
+  int32_t sub_x, sub_y;  /* 1 or 2.  4:4:4 = {1,1}, 4:2:2 = {2,1}, 4:2:0 = {2,2}; {1,2} is refused */
+  int32_t matrix;        /* 0 = BT.601 (Kr .299, Kb .114), 1 = BT.709 (Kr .2126, Kb .0722) */
+  int32_t full_range;    /* 1: Y, C in 0..255 (JPEG);  0: Y = 16 + 219 Y', C = 128 + 224 C' */
+  int32_t site_x;        /* horizontal chroma siting when sub_x == 2: 0 = centre (JPEG / MPEG-1),
+                            1 = left, co-sited with the even luma column (MPEG-2, H.264 / HEVC default).
+                            Vertical siting is always centre.  Ignored when sub_x == 1 */
+  int32_t reserved[3];   /* must be 0 */
+} mlic_yuv_desc;
+/* ingest, one launch: dst = contiguous fp32 [B][3][Hp][Wp] (Hp >= H, Wp >= W multiples of 64), every element
+ * written, +0.0 in the right / bottom padding; nothing outside the planes' extents is read.  Per luma pixel (x, y)
+ * chroma is upsampled in integers, as sixteenths c16 in [0, 4080].  Across columns (sub_x == 2, i = x >> 1,
+ * indices clamped to the plane): centre siting 3 C[i] + C[i -+ 1] (- for even x, + for odd x); left siting 4 C[i]
+ * at even x, 2 C[i] + 2 C[i + 1] at odd x.  Down rows (sub_y == 2) the centre rule, 3 : 1.  An unsubsampled axis
+ * contributes the factor 4.  u = c16 / 16 - 128 (exact in fp32), v likewise from Cr, then in fp32 with every
+ * product and sum rounded once (no FMA):
+ *     a = cy (Y - yo);  R = a + crv v;  G = (a - cgu u) - cgv v;  B = a + cbu u;  out = min(max(., 0), 1)
+ *     yo = 0 | 16, ys = 255 | 219, cs = 255 | 224 (full | limited), Kg = 1 - Kr - Kb,
+ *     cy = 1 / ys, crv = 2 (1 - Kr) / cs, cbu = 2 (1 - Kb) / cs, cgu = 2 Kb (1 - Kb) / (Kg cs), cgv = 2 Kr (1 - Kr) / (Kg cs),
+ * each constant computed in double and rounded to fp32 once.  There is no intermediate 8-bit RGB.
+ * Refused before any GPU call, each with its own message: a null plane, dst, strides or desc; B, H or W < 1;
+ * Hp / Wp not multiples of 64 that cover H / W; sub_x / sub_y outside {1, 2} or {1, 2} together; matrix,
+ * full_range or site_x out of range; nonzero reserved; a zero column stride; dst not 4-byte aligned.
+ * Asynchronous on `stream`. */
+int mlic_image_ingest_yuv8(void* stream, const uint8_t* y, const int64_t* y_strides, const uint8_t* cb,
+                           const int64_t* cb_strides, const uint8_t* cr, const int64_t* cr_strides,
+                           const mlic_yuv_desc* desc, int B, int H, int W, float* dst, int Hp, int Wp);
+/* egress, one launch: the H x W crop of fp32 src (element strides {image, channel, row}, column stride 1: a padded
+ * x_hat is read in place) -> the three byte planes.  Per pixel r, g, b = min(max(v, 0), 1) (a NaN becomes 0);
+ *     t_Y  = (yo + ((ys Kr) r + (ys Kg) g)) + (ys Kb) b
+ *     t_Cb = ((-cs Kr / (2 (1 - Kb))) r + (-cs Kg / (2 (1 - Kb))) g) + (cs / 2) b
+ *     t_Cr = ((cs / 2) r + (-cs Kg / (2 (1 - Kr))) g) + (-cs Kb / (2 (1 - Kr))) b
+ * with the constants folded in double and rounded once and every operation rounded once.  Chroma is filtered at
+ * luma resolution before rounding: centre siting the mean of the sub_x x sub_y block; left siting [1 2 1] / 4
+ * across columns 2 i - 1, 2 i, 2 i + 1 and the mean down the sub_y rows; indices clamped into the image; the sum
+ * runs row-major from the first term (sums rounded; the products by 1, 2 and the final power of two are exact);
+ * then 128 is added.  Bytes: floor(min(max(t + 0.5, 0), 255)).  Only the planes' bytes inside their extents are
+ * written.  ref_y / ref_cb / ref_cr (device, their own strides) with sq_err ([B][3] uint64, device): sq_err[b][p] =
+ * the exact sum over plane p of image b of the squared byte differences (integer atomics: deterministic); all four
+ * given or all NULL.  Refusals as for the ingest, plus: ref_* / sq_err not all-or-none; src not 4-byte or sq_err
+ * not 8-byte aligned.  Asynchronous on `stream`. */
+int mlic_image_egress_yuv8(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W,
+                           const mlic_yuv_desc* desc, uint8_t* y, const int64_t* y_strides, uint8_t* cb,
+                           const int64_t* cb_strides, uint8_t* cr, const int64_t* cr_strides, const uint8_t* ref_y,
+                           const int64_t* ref_y_strides, const uint8_t* ref_cb, const int64_t* ref_cb_strides,
+                           const uint8_t* ref_cr, const int64_t* ref_cr_strides, uint64_t* sq_err);
+/* mlic_encode_image_u8 / mlic_decode_image_u8 with the Y'CbCr ingest / egress (the same staging buffer and the
+ * same out == NULL / source == NULL two-call protocol; the file is a plain per-image file).  Planes: device
+ * pointers with strides {row, column}.  encode: y_dev == NULL writes the handle's last file again.  decode:
+ * y_dev == NULL only parses and reports H, W, level (m and desc may be NULL then); *_cap = bytes addressable from
+ * each plane pointer, and a file whose planes need more is refused before any GPU call.  There is no budget
+ * variant. */
+int mlic_encode_image_yuv8(mlic_model* m, void* stream, const uint8_t* y_dev, const int64_t* y_strides,
+                           const uint8_t* cb_dev, const int64_t* cb_strides, const uint8_t* cr_dev,
+                           const int64_t* cr_strides, const mlic_yuv_desc* desc, int H, int W, float vbr_scale,
+                           int level, uint8_t* out, size_t cap, size_t* len);
+int mlic_decode_image_yuv8(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels,
+                           uint64_t max_pixels, const float* vbr_gains, const mlic_yuv_desc* desc, uint8_t* y_dev,
+                           const int64_t* y_strides, size_t y_cap, uint8_t* cb_dev, const int64_t* cb_strides,
+                           size_t cb_cap, uint8_t* cr_dev, const int64_t* cr_strides, size_t cr_cap, int* H, int* W,
+                           int* level);
 /* per-image sum of -log2(lik) over n_per elements (fixed reduction order); synchronous */
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out);
 /* GaussianConditional likelihood (compressai, eval; mlicpp.py:132,168) element-wise: lik = max(Phi((0.5-|v|)/s')

@@ -39,6 +39,12 @@ class ContainerTiledInfo(C.Structure):
                 ("payload_off", C.c_uint64), ("payload_len", C.c_uint64)]
 
 
+class YuvDesc(C.Structure):
+    """mlic_yuv_desc (include/mlic_hip.h)."""
+    _fields_ = [("sub_x", C.c_int32), ("sub_y", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
+                ("site_x", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 def _sig(lib):
     p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
     P = C.POINTER
@@ -129,6 +135,12 @@ def _sig(lib):
         "mlic_encode_image_u8": [p, p, p, P(i64), i, i, f, i, p, sz, P(sz)],
         "mlic_encode_image_u8_budget": [p, p, p, P(i64), i, i, f, i, C.c_double, i, p, sz, P(sz), P(i)],
         "mlic_decode_image_u8": [p, p, p, sz, i, C.c_uint64, p, p, P(i64), sz, P(i), P(i), P(i)],
+        "mlic_image_ingest_yuv8": [p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, p, i, i],
+        "mlic_image_egress_yuv8": [p, p, P(i64), i, i, i, P(YuvDesc), p, P(i64), p, P(i64), p, P(i64), p, P(i64), p,
+                                   P(i64), p, P(i64), p],
+        "mlic_encode_image_yuv8": [p, p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, f, i, p, sz, P(sz)],
+        "mlic_decode_image_yuv8": [p, p, p, sz, i, C.c_uint64, p, P(YuvDesc), p, P(i64), sz, p, P(i64), sz, p, P(i64),
+                                   sz, P(i), P(i), P(i)],
         "mlic_neglog2_sum": [p, p, i, i64, p],
         "mlic_gaussian_likelihood": [p, p, p, p, i64, f, p],
         "mlic_scale_indexes": [p, p, i64, p, i, p],

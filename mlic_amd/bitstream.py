@@ -99,7 +99,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
-               dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, **kw) -> Dict:
+               dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, yuv=None, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -118,9 +118,15 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     tile=T (with overlap=V): tiled coding (codec.encode_tiled / decode_tiled, DESIGN.md §5 "Tiled coding") of
     to_u8(img): the file is the tiled file, x_hat the decoded uint8 image / 255, psnr comes from the decode's
     exact squared error, and the record also holds "tile", "overlap", "grid" and "tile_bytes".  s= is the one
-    level of the image; not together with max_bpp or roi=; off by default."""
+    level of the image; not together with max_bpp or roi=; off by default.
+    yuv=fmt (a codec.YuvFormat): the record also holds "sq_err_yuv" (three ints), "psnr_y", "psnr_u", "psnr_v" and
+    "psnr_yuv" = (6 Y + U + V) / 8 of codec.egress_yuv(x_hat, fmt) against the source planes, which are taken as
+    codec.egress_yuv(img, fmt): the RGB image's 4:4:4 conversion through the same formula, filtered as fmt says.
+    Not together with tile=; off by default."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
+    if yuv is not None and tile is not None:
+        raise ValueError("code_image: yuv= together with tile= is not supported")
     if tile is not None:
         from . import codec
         if max_bpp is not None or roi is not None or roi_levels is not None or set(kw) - {"s"}:
@@ -204,6 +210,12 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     if roi is not None:
         p = codec.psnr_roi(to_u8(img), to_u8(x_hat), mask, layout="chw")[0]
         r["psnr_roi"], r["psnr_bg"], r["roi_levels"] = p["psnr_roi"], p["psnr_bg"], fmap
+    if yuv is not None:
+        from . import codec
+        src = codec.egress_yuv(img.float().contiguous(), H, W, yuv)
+        p = codec.psnr_yuv_from_sq_err(codec.egress_yuv(x_hat.float(), H, W, yuv, ref=src)[3][0].cpu().tolist(), H, W, yuv)
+        r["sq_err_yuv"] = p.pop("sq_err")
+        r.update(p)
     if ms_ssim:
         from . import metrics
         r["ms_ssim"] = metrics.ms_ssim_u8(img, x_hat).item() if min(H, W) > metrics.MIN_SIDE else None

@@ -1014,6 +1014,393 @@ def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, m
     return img, info
 
 
+# -------------------------------------------------------------------------------------------- YCbCr
+_YUV_MATRIX = {"bt601": (0, 0.299, 0.114), "bt709": (1, 0.2126, 0.0722)}
+_YUV_SUB = {"i420": (2, 2), "yv12": (2, 2), "nv12": (2, 2), "nv21": (2, 2), "i422": (2, 1), "i444": (1, 1)}
+
+
+class YuvFormat:
+    """What an 8-bit Y'CbCr frame means (mlic_yuv_desc; DESIGN.md §5 "YCbCr I/O"): sub = (sub_x, sub_y), (1, 1)
+    4:4:4, (2, 1) 4:2:2 or (2, 2) 4:2:0; matrix "bt709" or "bt601"; full_range (False: Y in 16..235, C in 16..240);
+    site_x, the horizontal chroma siting of a subsampled frame: "left" (co-sited with the even luma column: MPEG-2,
+    H.264 / HEVC) or "centre" (JPEG, MPEG-1).  Vertical siting is always centre.  None of this is in the file: it
+    is the caller's knowledge on both sides."""
+
+    def __init__(self, sub=(2, 2), matrix: str = "bt709", full_range: bool = False, site_x: str = "left"):
+        try:
+            sub = tuple(int(v) for v in sub)
+        except (TypeError, ValueError):
+            raise ValueError(f"YuvFormat: sub must be (sub_x, sub_y), got {sub!r}") from None
+        if sub not in ((1, 1), (2, 1), (2, 2)):
+            raise ValueError(f"YuvFormat: sub must be (1, 1), (2, 1) or (2, 2), got {sub!r}")
+        if matrix not in _YUV_MATRIX:
+            raise ValueError(f"YuvFormat: matrix must be 'bt601' or 'bt709', got {matrix!r} (other matrices are out "
+                             f"of scope)")
+        if not isinstance(full_range, (bool, np.bool_)):
+            raise ValueError(f"YuvFormat: full_range must be a bool, got {full_range!r}")
+        if site_x not in ("left", "centre"):
+            raise ValueError(f"YuvFormat: site_x must be 'left' or 'centre', got {site_x!r}")
+        self.sub, self.matrix, self.full_range, self.site_x = sub, matrix, bool(full_range), site_x
+
+    def __repr__(self):
+        return f"YuvFormat(sub={self.sub}, matrix={self.matrix!r}, full_range={self.full_range}, site_x={self.site_x!r})"
+
+    def __eq__(self, other):
+        return isinstance(other, YuvFormat) and (self.sub, self.matrix, self.full_range, self.site_x) == \
+            (other.sub, other.matrix, other.full_range, other.site_x)
+
+    @property
+    def left(self) -> bool:
+        return self.sub[0] == 2 and self.site_x == "left"
+
+    def chroma_size(self, H: int, W: int):
+        """(rows, columns) of the chroma planes of an H x W frame: the ceil rule."""
+        return (H + self.sub[1] - 1) // self.sub[1], (W + self.sub[0] - 1) // self.sub[0]
+
+    def desc(self) -> _lib.YuvDesc:
+        return _lib.YuvDesc(self.sub[0], self.sub[1], _YUV_MATRIX[self.matrix][0], int(self.full_range),
+                            int(self.site_x == "left"), (C.c_int32 * 3)(0, 0, 0))
+
+    def constants(self) -> Dict[str, float]:
+        """The kernels' fp32 constants, each folded in double and rounded to fp32 once (the library folds the same
+        expressions): ingest yo, cy, crv, cgu, cgv, cbu; egress yr, yg, yb | br, bg, bb | rr, rg, rb."""
+        _, Kr, Kb = _YUV_MATRIX[self.matrix]
+        Kg = 1.0 - Kr - Kb
+        ys, cs, yo = (255.0, 255.0, 0.0) if self.full_range else (219.0, 224.0, 16.0)
+        d = {"yo": yo, "cy": 1.0 / ys, "crv": 2.0 * (1.0 - Kr) / cs, "cgu": 2.0 * Kb * (1.0 - Kb) / (Kg * cs),
+             "cgv": 2.0 * Kr * (1.0 - Kr) / (Kg * cs), "cbu": 2.0 * (1.0 - Kb) / cs,
+             "yr": ys * Kr, "yg": ys * Kg, "yb": ys * Kb,
+             "br": -(cs * Kr) / (2.0 * (1.0 - Kb)), "bg": -(cs * Kg) / (2.0 * (1.0 - Kb)), "bb": cs / 2.0,
+             "rr": cs / 2.0, "rg": -(cs * Kg) / (2.0 * (1.0 - Kr)), "rb": -(cs * Kb) / (2.0 * (1.0 - Kr))}
+        return {k: float(np.float32(v)) for k, v in d.items()}
+
+
+def _check_fmt(fmt, what: str) -> YuvFormat:
+    if not isinstance(fmt, YuvFormat):
+        raise ValueError(f"{what}: fmt must be a YuvFormat, got {fmt!r}")
+    return fmt
+
+
+def yuv_frame_bytes(H: int, W: int, layout: str) -> int:
+    """Bytes of one H x W frame in a raw layout (the ceil rule for the chroma planes)."""
+    if layout not in _YUV_SUB:
+        raise ValueError(f"yuv layout must be one of {sorted(_YUV_SUB)}, got {layout!r}")
+    sx, sy = _YUV_SUB[layout]
+    return H * W + 2 * ((H + sy - 1) // sy) * ((W + sx - 1) // sx)
+
+
+def split_yuv(buf, H: int, W: int, layout: str):
+    """A raw frame buffer -> (y, cb, cr) as strided views of it, no copy.  buf: flat uint8 tensor or numpy array of
+    yuv_frame_bytes(H, W, layout) bytes, or [B, that many].  Layouts: "i420" (Y, Cb, Cr planes), "yv12" (Y, Cr, Cb),
+    "nv12" (Y, then interleaved Cb Cr rows: the chroma views have column stride 2), "nv21" (Cr Cb), "i422", "i444".
+    y is [H, W] (or [B, H, W]), cb and cr are [ceil(H / sub_y), ceil(W / sub_x)]."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"split_yuv: a non-empty frame expected, got {H} x {W}")
+    need = yuv_frame_bytes(H, W, layout)
+    is_np = isinstance(buf, np.ndarray)
+    if not (is_np or torch.is_tensor(buf)) or buf.dtype not in (np.uint8, torch.uint8) or buf.ndim not in (1, 2):
+        raise ValueError("split_yuv: a flat uint8 tensor or array (or [B, bytes]) expected")
+    if buf.shape[-1] != need:
+        raise ValueError(f"split_yuv: a {W}x{H} {layout} frame is {need} bytes, the buffer has {buf.shape[-1]}")
+    sx, sy = _YUV_SUB[layout]
+    ch, cw = (H + sy - 1) // sy, (W + sx - 1) // sx
+    lead = tuple(buf.shape[:-1])
+
+    def view(a, shape):
+        return a.reshape(lead + shape) if is_np else a.view(lead + shape)
+
+    if not is_np and buf.stride(-1) != 1:
+        raise ValueError("split_yuv: the buffer's bytes must be contiguous (views are returned, not copies)")
+    y = view(buf[..., :H * W], (H, W))
+    if layout in ("nv12", "nv21"):
+        uv = view(buf[..., H * W:], (ch, cw, 2))
+        a, b = uv[..., 0], uv[..., 1]
+    else:
+        a = view(buf[..., H * W:H * W + ch * cw], (ch, cw))
+        b = view(buf[..., H * W + ch * cw:], (ch, cw))
+    if is_np and not all(np.shares_memory(v, buf) for v in (y, a, b)):
+        raise ValueError("split_yuv: the buffer cannot be viewed in place (make it contiguous)")
+    return (y, b, a) if layout in ("yv12", "nv21") else (y, a, b)
+
+
+def _yuv_planes(y, cb, cr, fmt: YuvFormat, what: str):
+    """-> three 3-dim uint8 tensors [B,H,W], [B,ch,cw], [B,ch,cw] (one frame gains the batch dimension)."""
+    out = []
+    for name, t in (("y", y), ("cb", cb), ("cr", cr)):
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(t)
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() not in (2, 3):
+            raise ValueError(f"{what}: {name} must be a uint8 tensor or array [B,h,w] (or one [h,w]); bit depths above "
+                             f"8 are out of scope")
+        out.append(t.unsqueeze(0) if t.dim() == 2 else t)
+    y, cb, cr = out
+    if 0 in y.shape:
+        raise ValueError(f"{what}: empty frame {tuple(y.shape)}")
+    B, H, W = y.shape
+    want = (B,) + fmt.chroma_size(H, W)
+    if tuple(cb.shape) != want or tuple(cr.shape) != want:
+        raise ValueError(f"{what}: a {H} x {W} frame with sub={fmt.sub} has chroma planes {want}, got "
+                         f"{tuple(cb.shape)} and {tuple(cr.shape)}")
+    if len({t.device for t in out}) != 1:
+        raise ValueError(f"{what}: the three planes must be on one device")
+    return y, cb, cr
+
+
+def _k32(fmt: YuvFormat):
+    return {k: torch.tensor(v, dtype=torch.float32) for k, v in fmt.constants().items()}
+
+
+def yuv_upsample16(c: torch.Tensor, H: int, W: int, fmt: YuvFormat) -> torch.Tensor:
+    """One chroma plane [B,ch,cw] (integers) on the luma grid, in sixteenths: int32 [B,H,W] in [0, 4080].  Across
+    columns of a subsampled axis with i = x >> 1 and indices clamped: centre siting 3 C[i] + C[i -+ 1] (- at even
+    x), left siting 4 C[i] at even x and 2 C[i] + 2 C[i + 1] at odd x; down rows the centre rule; an unsubsampled
+    axis contributes the factor 4.  The ingest kernel's integer step, restated."""
+    c = c.to(torch.int32)
+    ch, cw = c.shape[-2:]
+    if fmt.sub[0] == 2:
+        x = torch.arange(W)
+        i, odd = x >> 1, (x & 1).bool()
+        if fmt.left:
+            nb = torch.where(odd, (i + 1).clamp(max=cw - 1), i)
+            wa, wb = torch.where(odd, 2, 4).to(torch.int32), torch.where(odd, 2, 0).to(torch.int32)
+        else:
+            nb = (i + torch.where(odd, 1, -1)).clamp(0, cw - 1)
+            wa, wb = torch.full((W,), 3, dtype=torch.int32), torch.ones(W, dtype=torch.int32)
+        h = wa * c[..., i] + wb * c[..., nb]
+    else:
+        h = 4 * c
+    if fmt.sub[1] == 2:
+        yy = torch.arange(H)
+        j, odd = yy >> 1, (yy & 1).bool()
+        nb = (j + torch.where(odd, 1, -1)).clamp(0, ch - 1)
+        return 3 * h[..., j, :] + h[..., nb, :]
+    return 4 * h
+
+
+def _ingest_yuv_cpu(y, cb, cr, fmt: YuvFormat) -> torch.Tensor:
+    B, H, W = y.shape
+    k = _k32(fmt)
+    u = yuv_upsample16(cb, H, W, fmt).float() * 0.0625 - 128.0  # exact
+    v = yuv_upsample16(cr, H, W, fmt).float() * 0.0625 - 128.0
+    a = k["cy"] * (y.float() - k["yo"])
+    r = a + k["crv"] * v
+    g = (a - k["cgu"] * u) - k["cgv"] * v
+    b = a + k["cbu"] * u
+    out = torch.zeros(B, 3, _pad64(H), _pad64(W), dtype=torch.float32)
+    out[:, :, :H, :W] = torch.stack([r, g, b], 1).clamp(0, 1)
+    return out
+
+
+def ingest_yuv(y, cb, cr, fmt: YuvFormat) -> torch.Tensor:
+    """An 8-bit Y'CbCr frame batch -> the model's input, contiguous fp32 [B,3,Hp,Wp], in one launch: y uint8
+    [B,H,W], cb and cr uint8 [B,ceil(H / sub_y),ceil(W / sub_x)] (or one frame without B), each with any strides
+    (split_yuv's views of an I420 / NV12 buffer, a row-padded pitch, a crop are read in place).  Chroma is
+    upsampled in integers (yuv_upsample16), then a = cy (Y - yo); R = a + crv v; G = (a - cgu u) - cgv v;
+    B = a + cbu u in fp32 with every operation rounded once, clamped to [0, 1]; +0 in the padding.  There is no
+    intermediate 8-bit RGB.  CUDA tensors run the kernel on the current stream, CPU tensors the torch restatement
+    (the same bits)."""
+    fmt = _check_fmt(fmt, "ingest_yuv")
+    y, cb, cr = _yuv_planes(y, cb, cr, fmt, "ingest_yuv")
+    B, H, W = y.shape
+    if not y.is_cuda:
+        return _ingest_yuv_cpu(y, cb, cr, fmt)
+    y, cb, cr = (t.contiguous() if t.stride(2) == 0 else t for t in (y, cb, cr))
+    Hp, Wp = _pad64(H), _pad64(W)
+    with torch.cuda.device(y.device):
+        x = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=y.device)
+        if _lib.poison():
+            x.fill_(float("nan"))
+        d = fmt.desc()
+        _lib.call("mlic_image_ingest_yuv8", _stream(), *_plane_args(y, cb, cr), C.byref(d), B, H, W,
+                  C.c_void_p(x.data_ptr()), Hp, Wp)
+    return x
+
+
+def _plane_args(*planes):
+    out = []
+    for t in planes:
+        out += [C.c_void_p(t.data_ptr()), (C.c_int64 * 3)(*t.stride())]
+    return out
+
+
+def _yuv_of_rgb(x: torch.Tensor, fmt: YuvFormat):
+    """fp32 [B,3,H,W] -> (t_Y, t_Cb, t_Cr) at full resolution, chroma without the 128: the egress kernel's order."""
+    k = _k32(fmt)
+    x = torch.where(torch.isnan(x), torch.zeros_like(x), x).clamp(0, 1)
+    r, g, b = x[:, 0], x[:, 1], x[:, 2]
+    ty = (k["yo"] + (k["yr"] * r + k["yg"] * g)) + k["yb"] * b
+    tb = (k["br"] * r + k["bg"] * g) + k["bb"] * b
+    tr = (k["rr"] * r + k["rg"] * g) + k["rb"] * b
+    return ty, tb, tr
+
+
+def yuv_downsample(t: torch.Tensor, fmt: YuvFormat) -> torch.Tensor:
+    """Full-resolution fp32 chroma [B,H,W] -> [B,ch,cw], the egress kernel's filter: centre siting the mean of the
+    sub_x x sub_y block, left siting [1 2 1] / 4 across columns 2 i - 1, 2 i, 2 i + 1 and the mean down the rows;
+    indices clamped into the image; the sum runs row-major from the first term, each sum rounded once."""
+    sx, sy = fmt.sub
+    if sx == 1:
+        return t.clone()
+    H, W = t.shape[-2:]
+    ch, cw = fmt.chroma_size(H, W)
+    i, j = torch.arange(cw), torch.arange(ch)
+    cols = [((2 * i + e).clamp(0, W - 1), 2.0 if (fmt.left and e == 0) else 1.0) for e in ((-1, 0, 1) if fmt.left else (0, 1))]
+    rows = [(sy * j + r).clamp(max=H - 1) for r in range(sy)]
+    acc = None
+    for rr in rows:
+        line = t[..., rr, :]
+        for cc, w in cols:
+            term = w * line[..., cc]
+            acc = term if acc is None else acc + term
+    return acc * ((0.25 if fmt.left else 1.0 / sx) / sy)
+
+
+def _yuv_byte(t: torch.Tensor) -> torch.Tensor:
+    return (t + 0.5).clamp(0, 255).floor().to(torch.uint8)
+
+
+def egress_yuv(x_hat: torch.Tensor, H: int, W: int, fmt: YuvFormat, ref=None, out=None):
+    """The top-left H x W crop of fp32 [B,3,>=H,>=W] (a padded x_hat, read in place) -> (y, cb, cr): uint8 [B,H,W]
+    and two [B,ceil(H / sub_y),ceil(W / sub_x)], in one launch.  Per pixel the clamped r, g, b (a NaN is 0) give
+    t_Y and the full-resolution chroma; chroma is filtered at luma resolution before rounding (yuv_downsample), 128
+    is added, and floor(clamp(t + 0.5, 0, 255)) is the byte.  out: optional (y, cb, cr) uint8 tensors of those
+    shapes with any strides (split_yuv's views of an NV12 buffer, windows of larger canvases): only the planes'
+    bytes are written.  ref: (y, cb, cr) of the original, any strides: returns (y, cb, cr, sq_err) with sq_err
+    int64 [B,3], the exact per-plane sums of squared byte differences.  CUDA tensors run the kernel on the current
+    stream, CPU tensors the torch restatement (the same bits)."""
+    fmt = _check_fmt(fmt, "egress_yuv")
+    if not torch.is_tensor(x_hat) or x_hat.dim() != 4 or x_hat.size(1) != 3 or x_hat.dtype != torch.float32:
+        raise ValueError("egress_yuv: fp32 [B,3,h,w] expected")
+    B = x_hat.size(0)
+    H, W = int(H), int(W)
+    if not (1 <= H <= x_hat.size(2) and 1 <= W <= x_hat.size(3)) or B < 1:
+        raise ValueError(f"egress_yuv: crop {H} x {W} of {tuple(x_hat.shape)}")
+    ch, cw = fmt.chroma_size(H, W)
+    shapes = ((B, H, W), (B, ch, cw), (B, ch, cw))
+    dev = x_hat.device
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+        if x_hat.is_cuda and _lib.poison():
+            for t in out:
+                t.fill_(0xFF)
+    else:
+        out = tuple(out)
+        if len(out) != 3 or any(not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != s or t.device != dev
+                                for t, s in zip(out, shapes)):
+            raise ValueError(f"egress_yuv: out must be three uint8 tensors {shapes} on {dev}")
+    if ref is not None:
+        ref = _yuv_planes(*ref, fmt, "egress_yuv ref")
+        if tuple(ref[0].shape) != shapes[0]:
+            raise ValueError(f"egress_yuv: ref must be a frame batch of {shapes[0]}, got {tuple(ref[0].shape)}")
+        ref = tuple(t.to(dev) for t in ref)
+    if not x_hat.is_cuda:
+        ty, tb, tr = _yuv_of_rgb(x_hat[:, :, :H, :W], fmt)
+        out[0].copy_(_yuv_byte(ty))
+        out[1].copy_(_yuv_byte(yuv_downsample(tb, fmt) + 128.0))
+        out[2].copy_(_yuv_byte(yuv_downsample(tr, fmt) + 128.0))
+        if ref is None:
+            return out
+        sq = torch.stack([((o.to(torch.int64) - r.to(torch.int64)) ** 2).flatten(1).sum(1) for o, r in zip(out, ref)], 1)
+        return out + (sq,)
+    if x_hat.stride(3) != 1:
+        x_hat = x_hat.contiguous()
+    if any(t.stride(2) == 0 for t in out):
+        raise ValueError("egress_yuv: an out plane has a zero column stride")
+    with torch.cuda.device(dev):
+        sq = None
+        if ref is not None:
+            ref = tuple(t.contiguous() if t.stride(2) == 0 else t for t in ref)
+            sq = torch.full((B, 3), -1, dtype=torch.int64, device=dev)
+        d = fmt.desc()
+        rargs = [None] * 6 if ref is None else _plane_args(*ref)
+        _lib.call("mlic_image_egress_yuv8", _stream(), C.c_void_p(x_hat.data_ptr()), (C.c_int64 * 3)(*x_hat.stride()[:3]),
+                  B, H, W, C.byref(d), *_plane_args(*out), *rargs, None if sq is None else C.c_void_p(sq.data_ptr()))
+        if ref is not None:
+            for t in ref:
+                t.record_stream(torch.cuda.current_stream())
+    return out if ref is None else out + (sq,)
+
+
+def psnr_yuv_from_sq_err(sq_err, H: int, W: int, fmt: YuvFormat) -> Dict:
+    """{"sq_err", "psnr_y", "psnr_u", "psnr_v", "psnr_yuv"} from the three per-plane sums of squared byte
+    differences of an H x W frame: PSNR per plane (max 255) and the 6 : 1 : 1 mean (6 Y + U + V) / 8."""
+    ch, cw = fmt.chroma_size(H, W)
+    sq = [int(v) for v in sq_err]
+    py, pu, pv = (psnr_from_sq_err(s, n) for s, n in zip(sq, (H * W, ch * cw, ch * cw)))
+    return {"sq_err": sq, "psnr_y": py, "psnr_u": pu, "psnr_v": pv, "psnr_yuv": (6.0 * py + pu + pv) / 8.0}
+
+
+@torch.no_grad()
+def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[float] = None, max_passes: int = 8,
+               return_info: bool = False, roi=None, roi_levels=None, tile=None):
+    """encode_images with the Y'CbCr ingest: a frame batch (ingest_yuv's planes; host arrays cross to the device as
+    bytes) -> one file per frame.  The files are plain per-image files: nothing of fmt is written, decode_images
+    decodes them to RGB and decode_yuv(fmt) to planes.  level, max_bpp, max_passes and return_info as in
+    encode_images (the rate loop works on the float image, so a budget and level="auto" work unchanged).  roi= and
+    tile= are refused: ROI and tiled coding together with Y'CbCr frames are out of scope."""
+    fmt = _check_fmt(fmt, "encode_yuv")
+    if roi is not None or roi_levels is not None:
+        raise ValueError("encode_yuv: roi= together with Y'CbCr frames is not supported")
+    if tile is not None:
+        raise ValueError("encode_yuv: tiles together with Y'CbCr frames are not supported")
+    y, cb, cr = _yuv_planes(y, cb, cr, fmt, "encode_yuv")
+    _check_budget(max_bpp, max_passes)
+    if isinstance(level, str) and max_bpp is None:
+        raise ValueError("level='auto' needs max_bpp (the level is chosen from the budget)")
+    B, H, W = y.shape
+    x = ingest_yuv(y.to(net.device), cb.to(net.device), cr.to(net.device), fmt)
+    if max_bpp is None:
+        lv, kw = _levels(net, level, B)
+        out = net.compress(x, **kw)
+        ys, zs = out["strings"]
+        files = [write_container(H, W, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
+        passes = [0] * B
+    else:
+        files, passes, lv = rate_loop(net, x, H, W, level, max_bpp, max_passes)
+    if not return_info:
+        return files
+    info = []
+    for b, f in enumerate(files):
+        bpp = 8.0 * len(f) / (H * W)
+        info.append({"bytes": len(f), "bpp": bpp, "passes": passes[b], "level": None if lv is None else lv[b],
+                     "met": max_bpp is None or bpp <= max_bpp})
+    return files, info
+
+
+@torch.no_grad()
+def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS):
+    """Files of one H x W -> ((y, cb, cr) on the model's device, info): decode_images with the Y'CbCr egress.
+    info[b] holds H, W, level, bytes and bpp and, with ref=(y, cb, cr) of the originals, sq_err (three ints: Y, Cb,
+    Cr), psnr_y, psnr_u, psnr_v and psnr_yuv = (6 Y + U + V) / 8.  ROI and tiled files are refused."""
+    fmt = _check_fmt(fmt, "decode_yuv")
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("decode_yuv: no files")
+    if any(is_tiled_file(f) for f in files):
+        raise ValueError("decode_yuv: tiled files together with Y'CbCr frames are not supported")
+    vbr = hasattr(net, "levels")
+    if vbr and any(is_roi_file(f) for f in files):
+        raise ValueError("decode_yuv: ROI files together with Y'CbCr frames are not supported")
+    cs = [parse_container(f, vbr, net.levels if vbr else None, max_pixels) for f in files]
+    if len({(c.H, c.W) for c in cs}) != 1:
+        raise ValueError(f"decode_yuv: the files must share one size, got {sorted({(c.H, c.W) for c in cs})}")
+    H, W = cs[0].H, cs[0].W
+    pairs = [_strings(f, c) for f, c in zip(files, cs)]
+    kw = {"s": [c.level for c in cs]} if vbr else {}
+    x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
+    r = egress_yuv(x_hat.float(), H, W, fmt, ref=ref)
+    sq = None if ref is None else r[3].cpu().tolist()
+    info = []
+    for b, c in enumerate(cs):
+        d = {"H": c.H, "W": c.W, "level": c.level if vbr else None, "bytes": len(files[b]),
+             "bpp": 8.0 * len(files[b]) / (c.H * c.W)}
+        if sq is not None:
+            d.update(psnr_yuv_from_sq_err(sq[b], H, W, fmt))
+        info.append(d)
+    return tuple(r[:3]), info
+
+
 def psnr_from_sq_err(sq_err: int, n: int) -> float:
     """PSNR (max 255, utils/metrics.py:32-33) from a sum of squared uint8 differences over n values."""
     return 10.0 * math.log10(255.0 ** 2 * n / sq_err) if sq_err > 0 else float("inf")

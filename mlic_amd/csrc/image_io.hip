@@ -20,6 +20,7 @@
 // 256-byte row piece per wave instruction.  Any other stride set takes the general kernels (byte accesses
 // straight from / to global memory); all forms give the same bits.
 #include "container.h"
+#include "image_stage.h"
 #include "kernels.h"
 
 namespace mlic {
@@ -41,37 +42,7 @@ struct IoStride4 {
   int64_t img, row, col, ch;
 };
 
-__device__ inline int addr_mod4(const void* p) { return (int)(reinterpret_cast<uintptr_t>(p) & 3); }
-
-// global bytes p[0, n) -> LDS bytes r[sh, sh + n), sh = p mod 4 (r is dword-aligned): one wave
-__device__ inline void stage_in(const uint8_t* __restrict__ p, int n, uint32_t* r, int lane) {
-  const int sh = addr_mod4(p);
-  uint8_t* r8 = reinterpret_cast<uint8_t*>(r);
-  const int end = sh + n, nd = (end + 3) >> 2;
-  for (int k = lane; k < nd; k += 64) {
-    const int lo = 4 * k, hi = lo + 4;
-    if (lo >= sh && hi <= end) {
-      r[k] = *reinterpret_cast<const uint32_t*>(p + (lo - sh));
-    } else {
-      for (int i = max(lo, sh); i < min(hi, end); ++i) r8[i] = p[i - sh];
-    }
-  }
-}
-
-// LDS bytes r[sh, sh + n) -> global bytes p[0, n), sh = p mod 4: one wave
-__device__ inline void stage_out(uint8_t* __restrict__ p, int n, const uint32_t* r, int lane) {
-  const int sh = addr_mod4(p);
-  const uint8_t* r8 = reinterpret_cast<const uint8_t*>(r);
-  const int end = sh + n, nd = (end + 3) >> 2;
-  for (int k = lane; k < nd; k += 64) {
-    const int lo = 4 * k, hi = lo + 4;
-    if (lo >= sh && hi <= end) {
-      *reinterpret_cast<uint32_t*>(p + (lo - sh)) = r[k];
-    } else {
-      for (int i = max(lo, sh); i < min(hi, end); ++i) p[i - sh] = r8[i];
-    }
-  }
-}
+// stage_in / stage_out / addr_mod4: image_stage.h
 
 // blockIdx.x = (image, row block, column tile), column tile fastest; y = this wave's row in the block's first
 // row group (a row block is `rows` rows)

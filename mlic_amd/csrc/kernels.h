@@ -314,6 +314,25 @@ void image_egress_u8(const float* src, const int64_t* src_strides, int B, int H,
 // overlap the n images at src, nor any image src_index names.  Checks its arguments before any HIP call.
 void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp, const float* w9,
                      float* dst, hipStream_t st);
+// 8-bit Y'CbCr frame I/O (image_yuv.hip; DESIGN.md section 5 "YCbCr I/O").  The fields of mlic_yuv_desc.
+struct YuvDesc {
+  int32_t sub_x, sub_y, matrix, full_range, site_x, reserved[3];
+};
+// ingest: three byte planes, each through its own element strides {image, row, column} (Y: H x W; Cb, Cr:
+// ceil(H / sub_y) x ceil(W / sub_x)) -> dst fp32 [B][3][Hp][Wp]: integer chroma upsampling to sixteenths, the
+// fp32 matrix with every operation rounded once, clamp to [0, 1]; +0 in the padding, every element written.
+// Checks its arguments before any HIP call and throws.
+void image_ingest_yuv8(const uint8_t* y, const int64_t* y_strides, const uint8_t* cb, const int64_t* cb_strides,
+                       const uint8_t* cr, const int64_t* cr_strides, const YuvDesc* desc, int B, int H, int W, float* dst,
+                       int Hp, int Wp, hipStream_t st);
+// egress: the H x W crop of src fp32 (element strides {image, channel, row}, column stride 1) -> the three byte
+// planes (chroma filtered at luma resolution before rounding); with the three ref planes, sq_err [B][3] = the
+// exact per-plane sums of squared byte differences.  Only the planes' bytes are written.
+void image_egress_yuv8(const float* src, const int64_t* src_strides, int B, int H, int W, const YuvDesc* desc,
+                       uint8_t* y, const int64_t* y_strides, uint8_t* cb, const int64_t* cb_strides, uint8_t* cr,
+                       const int64_t* cr_strides, const uint8_t* ref_y, const int64_t* ref_y_strides,
+                       const uint8_t* ref_cb, const int64_t* ref_cb_strides, const uint8_t* ref_cr,
+                       const int64_t* ref_cr_strides, uint64_t* sq_err, hipStream_t st);
 // tiled decode's egress: the h x w region at (y0, x0) of the H x W image, blended from the tiles of the grid
 // (container.h: tile T, overlap V) with feathered seams, as uint8 through dst's {row, column, channel} strides.
 // tiles_dev: the device table, tile index (row-major) -> that tile's contiguous fp32 [3][pad64(ey)][pad64(ex)]

@@ -16,7 +16,15 @@
         whatever the image's size.  Goes with --level N; not with --max-bpp, --level auto or --roi
     ... --region Y0 X0 H W (decode, a tiled file): decode that window only; the tiles outside it are not touched.
         A tiled file is recognised by its magic; decode needs no --tile
-    python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR      what the file says (and its level map, or
+    ... a source (encode) or destination (decode) named .y4m or .yuv is an 8-bit Y'CbCr frame, coded without an RGB
+        round trip (codec.encode_yuv / decode_yuv).  .y4m: C420jpeg (centre-sited chroma), C420mpeg2 / C420 (left),
+        C422, C444; any other colour space or bit depth is refused by its tag.  Raw .yuv: --yuv i420|nv12|nv21|yv12|
+        i422|i444 (default i420) and --size WxH.  --frame N picks the frame (default 0; one frame is coded).
+        --matrix 601|709 (default 709), --range full|limited (default limited) and --chroma-site left|centre (default:
+        the y4m tag's, else left) say what the bytes mean; none of it is written into the bitstream, so a decode
+        takes the same flags.  decode ... --ref SRC prints the PSNR per plane and the 6:1:1 mean against SRC.
+        Not together with --roi, --tile or --region
+    python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR     what the file says (and its level map, or
         for a tiled file its grid and per-tile sizes)
 
 Binary PPM (P6, maxval 255) is read and written here; any other format goes through PIL when it imports.
@@ -104,6 +112,135 @@ def save_image(path: str, img: np.ndarray):
     Image.fromarray(img, "RGB").save(path)
 
 
+# ---------------------------------------------------------------------------------------------- Y4M
+# colour space tag -> (raw layout, (sub_x, sub_y), horizontal chroma siting)
+Y4M_TAGS = {"420jpeg": ("i420", (2, 2), "centre"), "420mpeg2": ("i420", (2, 2), "left"), "420": ("i420", (2, 2), "left"),
+            "422": ("i422", (2, 1), "left"), "444": ("i444", (1, 1), "left")}
+
+
+def read_y4m(data: bytes, frame: int = 0):
+    """YUV4MPEG2 bytes -> (y, cb, cr, tag, params): frame `frame` as uint8 arrays [H, W] and two chroma planes (the
+    ceil rule), the colour space tag without its 'C' ("420jpeg" when the header has none) and the header's other
+    parameters as a list of strings.  8-bit 4:2:0 / 4:2:2 / 4:4:4 only: any other tag is refused by name."""
+    end = data.find(b"\n")
+    if not data.startswith(b"YUV4MPEG2 ") or end < 0:
+        raise ValueError("Y4M: not a YUV4MPEG2 file")
+    W = H = None
+    tag, params = "420jpeg", []
+    for tok in data[10:end].decode("ascii", "replace").split():
+        if tok[0] == "W" or tok[0] == "H":
+            try:
+                v = int(tok[1:])
+            except ValueError:
+                raise ValueError(f"Y4M: bad header field {tok!r}") from None
+            W, H = (v, H) if tok[0] == "W" else (W, v)
+        elif tok[0] == "C":
+            tag = tok[1:]
+        else:
+            params.append(tok)
+    if tag not in Y4M_TAGS:
+        raise ValueError(f"Y4M: colour space C{tag} is not supported (8-bit C420jpeg, C420mpeg2, C420, C422, C444)")
+    if W is None or H is None or W < 1 or H < 1:
+        raise ValueError("Y4M: the header needs positive W and H")
+    if frame < 0:
+        raise ValueError(f"Y4M: frame {frame}")
+    sx, sy = Y4M_TAGS[tag][1]
+    ch, cw = (H + sy - 1) // sy, (W + sx - 1) // sx
+    n = H * W + 2 * ch * cw
+    pos = end + 1
+    for k in range(frame + 1):
+        e = data.find(b"\n", pos)
+        if not data.startswith(b"FRAME", pos) or e < 0:
+            raise ValueError(f"Y4M: no frame {k} (the file ends or the FRAME marker is missing)")
+        pos = e + 1
+        if len(data) - pos < n:
+            raise ValueError(f"Y4M: frame {k} is truncated ({len(data) - pos} of {n} bytes)")
+        if k < frame:
+            pos += n
+    a = np.frombuffer(data, np.uint8, n, pos).copy()
+    return (a[:H * W].reshape(H, W), a[H * W:H * W + ch * cw].reshape(ch, cw), a[H * W + ch * cw:].reshape(ch, cw), tag,
+            params)
+
+
+def write_y4m(y: np.ndarray, cb: np.ndarray, cr: np.ndarray, tag: str, params=("F25:1", "Ip", "A1:1")) -> bytes:
+    """One frame -> YUV4MPEG2 bytes with the colour space tag `tag`."""
+    if tag not in Y4M_TAGS:
+        raise ValueError(f"Y4M: colour space C{tag} is not supported (8-bit C420jpeg, C420mpeg2, C420, C422, C444)")
+    H, W = y.shape
+    sx, sy = Y4M_TAGS[tag][1]
+    want = ((H + sy - 1) // sy, (W + sx - 1) // sx)
+    if any(p.dtype != np.uint8 for p in (y, cb, cr)) or cb.shape != want or cr.shape != want:
+        raise ValueError(f"Y4M: uint8 planes {(H, W)} and two of {want} expected for C{tag}")
+    head = " ".join(["YUV4MPEG2", f"W{W}", f"H{H}"] + list(params) + [f"C{tag}"])
+    return head.encode("ascii") + b"\nFRAME\n" + b"".join(np.ascontiguousarray(p).tobytes() for p in (y, cb, cr))
+
+
+def _ext(path: str) -> str:
+    return os.path.splitext(path)[1].lower()
+
+
+def _is_yuv(path: str) -> bool:
+    return _ext(path) in (".y4m", ".yuv")
+
+
+def _size(v: str):
+    try:
+        w, h = (int(t) for t in v.lower().split("x"))
+    except ValueError:
+        w = h = 0
+    if w < 1 or h < 1:
+        raise argparse.ArgumentTypeError(f"WxH expected, got {v!r}")
+    return w, h
+
+
+def _yuv_format(args, sub, site):
+    from mlic_amd import codec
+    return codec.YuvFormat(sub=sub, matrix="bt" + args.matrix, full_range=args.range == "full",
+                           site_x=args.chroma_site or site)
+
+
+def load_yuv(path: str, args, size=None):
+    """A .y4m or raw .yuv file -> ((y, cb, cr) numpy planes of frame --frame, YuvFormat).  size: (W, H) of a raw
+    file when --size is not given (a decode knows it from the bitstream)."""
+    from mlic_amd import codec
+    with open(path, "rb") as f:
+        data = f.read()
+    if _ext(path) == ".y4m":
+        try:
+            y, cb, cr, tag, _ = read_y4m(data, args.frame)
+        except ValueError as e:
+            raise SystemExit(f"{path}: {e}") from None
+        _, sub, site = Y4M_TAGS[tag]
+        return (y, cb, cr), _yuv_format(args, sub, site)
+    size = args.size or size
+    if size is None:
+        raise SystemExit(f"{path}: a raw .yuv file needs --size WxH")
+    W, H = size
+    n = codec.yuv_frame_bytes(H, W, args.yuv)
+    if len(data) < (args.frame + 1) * n:
+        raise SystemExit(f"{path}: frame {args.frame} of {W}x{H} {args.yuv} needs {(args.frame + 1) * n} bytes, the file "
+                         f"has {len(data)}")
+    buf = np.frombuffer(data, np.uint8, n, args.frame * n).copy()
+    return codec.split_yuv(buf, H, W, args.yuv), _yuv_format(args, codec._YUV_SUB[args.yuv], "left")
+
+
+def save_yuv(path: str, planes, fmt, args):
+    """(y, cb, cr) numpy planes -> a .y4m file (planar, the tag from the format) or a raw .yuv file in --yuv."""
+    from mlic_amd import codec
+    y, cb, cr = planes
+    H, W = y.shape
+    if _ext(path) == ".y4m":
+        tag = {(2, 2): "420jpeg" if fmt.site_x == "centre" else "420mpeg2", (2, 1): "422", (1, 1): "444"}[fmt.sub]
+        data = write_y4m(y, cb, cr, tag)
+    else:
+        buf = np.zeros(codec.yuv_frame_bytes(H, W, args.yuv), np.uint8)
+        for dst, src in zip(codec.split_yuv(buf, H, W, args.yuv), planes):
+            dst[...] = src
+        data = buf.tobytes()
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 # -------------------------------------------------------------------------------------------- model
 def load_model(args):
     import torch
@@ -162,7 +299,27 @@ def parse_args(argv=None):
     ap.add_argument("--overlap", type=int, default=None, metavar="V")
     ap.add_argument("--tile-batch", type=int, default=8, metavar="N")
     ap.add_argument("--region", type=int, nargs=4, default=None, metavar=("Y0", "X0", "H", "W"))
+    ap.add_argument("--yuv", choices=["i420", "nv12", "nv21", "yv12", "i422", "i444"], default=None)
+    ap.add_argument("--size", type=_size, default=None, metavar="WxH")
+    ap.add_argument("--matrix", choices=["601", "709"], default="709")
+    ap.add_argument("--range", choices=["full", "limited"], default="limited")
+    ap.add_argument("--chroma-site", choices=["left", "centre"], default=None)
+    ap.add_argument("--frame", type=int, default=0, metavar="N")
+    ap.add_argument("--ref", default=None, metavar="SRC")
     args = ap.parse_args(argv)
+    frame_file = args.mode != "info" and _is_yuv(args.src if args.mode == "encode" else (args.dst or ""))
+    if frame_file:
+        if args.roi is not None or args.roi_levels is not None or args.tile is not None or args.region is not None:
+            ap.error("ROI and tiled coding together with Y'CbCr frames are not supported")
+        if args.frame < 0:
+            ap.error("--frame must not be negative")
+        if args.yuv is None:
+            args.yuv = "i420"
+    elif args.yuv is not None or args.size is not None or args.chroma_site is not None or args.frame != 0:
+        ap.error("--yuv, --size, --chroma-site and --frame go with a .y4m or .yuv frame file")
+    if args.ref is not None and not (frame_file and args.mode == "decode"):
+        ap.error("--ref goes with decode to a .y4m or .yuv file")
+    args.frame_file = frame_file
     if args.tile is not None:
         if args.mode != "encode":
             ap.error("--tile goes with encode (a tiled file is recognised by its magic)")
@@ -233,6 +390,41 @@ def main(argv=None):
               f"y {d['y_len']} B, z {d['z_len']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
         if "roi_levels" in d:
             print(f"level map ({d['shape'][0]} x {d['shape'][1]} cells of 64 x 64 pixels):\n" + _map_lines(d["roi_levels"]))
+        return
+    if args.mode == "encode" and args.frame_file:
+        planes, fmt = load_yuv(args.src, args)
+        net = load_model(args)
+        files, info = codec.encode_yuv(net, *planes, fmt, level=args.level, max_bpp=args.max_bpp,
+                                       max_passes=args.max_passes, return_info=True)
+        with open(args.dst, "wb") as f:
+            f.write(files[0])
+        H, W = planes[0].shape
+        line = f"{args.src}: {H} x {W} {fmt!r} -> {len(files[0])} bytes, {info[0]['bpp']:.4f} bpp"
+        if args.max_bpp is not None:
+            line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
+                     f"{'met' if info[0]['met'] else 'not met'}")
+        print(line)
+        return
+    if args.mode == "decode" and args.frame_file:
+        with open(args.src, "rb") as f:
+            data = f.read()
+        if codec.is_tiled_file(data):
+            raise SystemExit(f"{args.src}: a tiled file decodes to an RGB image, not to Y'CbCr planes")
+        net = load_model(args)
+        fmt = _yuv_format(args, codec._YUV_SUB[args.yuv], "left")
+        ref = None
+        if args.ref is not None:
+            d = codec.peek(data, vbr=hasattr(net, "levels"))
+            ref, rfmt = load_yuv(args.ref, args, size=(d["W"], d["H"]))
+            if _ext(args.ref) == ".y4m":
+                fmt = rfmt  # the source's subsampling and siting
+        planes, info = codec.decode_yuv(net, [data], fmt, ref=ref)
+        save_yuv(args.dst, [p[0].cpu().numpy() for p in planes], fmt, args)
+        line = f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp, {fmt!r}"
+        if ref is not None:
+            line += (f"\nPSNR Y {info[0]['psnr_y']:.4f} dB, U {info[0]['psnr_u']:.4f} dB, V {info[0]['psnr_v']:.4f} dB, "
+                     f"YUV (6:1:1) {info[0]['psnr_yuv']:.4f} dB")
+        print(line)
         return
     if args.mode == "encode":
         img = load_image(args.src)
