@@ -531,8 +531,9 @@ int mlic_decode_image_u8(mlic_model* m, void* stream, const uint8_t* file, size_
  * H x W, Cb and Cr are ceil(H / sub_y) x ceil(W / sub_x) (odd H and W are legal).  The planes are independent, so
  * one description covers I420 / YV12 (swap the chroma pointers), I422, I444, NV12 (cb = uv, cr = uv + 1, column
  * stride 2) / NV21, row-padded pitches and crops of larger frames.  Matrix, range and siting are the caller's
- * knowledge, as the VBR level word's presence is: they are not written into the file.  Bit depths above 8, alpha,
- * other matrices (BT.2020) and 4:4:0 are out of scope and refused where reachable. */
+ * knowledge, as the VBR level word's presence is: they are not written into the file.  Alpha and 4:4:0 are out of scope
+ * and refused where reachable; bit depths above 8 and BT.2020 go through the *_yuv16 calls below, and these
+ * 8-bit calls keep refusing matrix 2. */
 typedef struct mlic_yuv_desc {
   int32_t sub_x, sub_y;  /* 1 or 2.  4:4:4 = {1,1}, 4:2:2 = {2,1}, 4:2:0 = {2,2}; {1,2} is refused */
   int32_t matrix;        /* 0 = BT.601 (Kr .299, Kb .114), 1 = BT.709 (Kr .2126, Kb .0722) */
@@ -594,6 +595,71 @@ int mlic_decode_image_yuv8(mlic_model* m, void* stream, const uint8_t* file, siz
                            const int64_t* y_strides, size_t y_cap, uint8_t* cb_dev, const int64_t* cb_strides,
                            size_t cb_cap, uint8_t* cr_dev, const int64_t* cr_strides, size_t cr_cap, int* H, int* W,
                            int* level);
+
+/* ---- 9..16-bit samples in and out (DESIGN.md section 5 "High-bit-depth I/O") ----
+ *
+ * The four image calls above for samples deeper than a byte.  The model takes fp32 in [0, 1] and returns fp32, the
+ * bitstream and the file do not change and do not know the depth: these are front doors only.
+ * Sample format, shared by every call below: samples are uint16_t words in native byte order; depth d in [8, 16],
+ * maxv = 2^d - 1, half = 2^(d-1), s = 2^(d-8).  msb = 0: LSB-aligned (y4m p10, I010, PPM), the sample is
+ * min(word, maxv).  msb = 1: MSB-aligned (P010 / P016), the sample is word >> (16 - d), the low bits of an input
+ * word are ignored; an output word is sample << (16 - d), its low bits zero.  Strides are in ELEMENTS (uint16), in
+ * the orders of the 8-bit calls: RGB images {image, row, column, channel}, planes {image, row, column}.  Sample
+ * pointers must be 2-byte aligned.  Refused before any GPU call, each with its own message: everything the 8-bit
+ * counterpart refuses; depth outside [8, 16]; msb not 0 or 1; a misaligned sample pointer; (Y'CbCr) matrix outside
+ * {0, 1, 2}.  Fast forms (rows through LDS) exist for unit column stride, interleaved HWC, and interleaved chroma
+ * with column stride 2 (P010); any other stride set takes the general form; the kernel option image_io_path forces
+ * one as for the 8-bit kernels; all forms give the same bits.
+ *
+ * mlic_image_ingest_u16: dst fp32 [B][3][Hp][Wp]; inside the image v = (float)sample / (float)maxv, a true IEEE
+ * division (torch's CPU t.to(float32).div(maxv) bit for bit); +0.0 in the padding; every element written.
+ * mlic_image_egress_u16: sample = floor(min(max(v, 0), 1) * maxv), NaN -> 0: mlic_image_egress_u8's expression with
+ * 255 replaced by maxv (equal to it at d = 8; egress(ingest(v)) == v for every sample value at every depth).
+ * Only the crop's words are written.  ref + sq_err ([B] uint64): the exact per-image sum of squared sample
+ * differences, the reference read by the same msb rule, accumulated in 64 bits throughout.
+ * There is no one-image encode / decode call for 16-bit RGB: compose mlic_image_ingest_u16, mlic_compress and
+ * mlic_container_write (mlic_amd/codec.py does). */
+int mlic_image_ingest_u16(void* stream, const uint16_t* src, const int64_t* src_strides, int depth, int msb, int B,
+                          int H, int W, float* dst, int Hp, int Wp);
+int mlic_image_egress_u16(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W, int depth,
+                          int msb, uint16_t* dst, const int64_t* dst_strides, const uint16_t* ref,
+                          const int64_t* ref_strides, uint64_t* sq_err);
+/* mlic_image_ingest_yuv8's rules verbatim at depth d: integer chroma upsampling to sixteenths c16 in [0, 16 maxv]
+ * (below 2^20: exact in fp32) with the same siting rules, u = c16 / 16 - half (exact), then
+ *     a = cy (Y - yo);  R = a + crv v;  G = (a - cgu u) - cgv v;  B = a + cbu u;  out = min(max(., 0), 1)
+ *     yo = 0 | 16 s, ys = maxv | 219 s, cs = maxv | 224 s (full | limited)
+ * with cy, crv, cbu, cgu, cgv as for mlic_image_ingest_yuv8 from this ys, cs.  desc->matrix may also be 2 = BT.2020
+ * non-constant-luminance (Kr .2627, Kb .0593); the 8-bit calls keep refusing it.  mlic_yuv_desc is unchanged and its
+ * reserved words must be 0: depth and alignment are arguments.  At d = 8 the bits are those of the 8-bit calls. */
+int mlic_image_ingest_yuv16(void* stream, const uint16_t* y, const int64_t* y_strides, const uint16_t* cb,
+                            const int64_t* cb_strides, const uint16_t* cr, const int64_t* cr_strides,
+                            const mlic_yuv_desc* desc, int depth, int msb, int B, int H, int W, float* dst, int Hp,
+                            int Wp);
+/* mlic_image_egress_yuv8's rules at depth d: the same t_Y / t_Cb / t_Cr expressions with the constants folded from
+ * ys, cs, yo of depth d, the same chroma filter, siting, clamping and summation order, half added in place of 128;
+ * word = floor(min(max(t + 0.5, 0), maxv)) (shifted up for msb = 1).  Optional three reference planes with sq_err
+ * ([B][3] uint64): exact, accumulated in 64 bits. */
+int mlic_image_egress_yuv16(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W,
+                            const mlic_yuv_desc* desc, int depth, int msb, uint16_t* y, const int64_t* y_strides,
+                            uint16_t* cb, const int64_t* cb_strides, uint16_t* cr, const int64_t* cr_strides,
+                            const uint16_t* ref_y, const int64_t* ref_y_strides, const uint16_t* ref_cb,
+                            const int64_t* ref_cb_strides, const uint16_t* ref_cr, const int64_t* ref_cr_strides,
+                            uint64_t* sq_err);
+/* mlic_encode_image_yuv8 / mlic_decode_image_yuv8 for uint16 planes (a hardware decoder's P010 surface: cb = uv,
+ * cr = uv + 1, column stride 2, depth 10, msb 1): the same staging buffer, the same two-call protocol, a plain
+ * per-image file.  Strides {row, column} in elements; *_cap stay in BYTES addressable from each plane pointer.
+ * Every argument (depth, msb, plane alignment, the whole descriptor, strides, capacities) is checked before the
+ * handle is looked at: a refused call makes no device call and leaves the handle's last encoded image as it was.
+ * There is no budget variant. */
+int mlic_encode_image_yuv16(mlic_model* m, void* stream, const uint16_t* y_dev, const int64_t* y_strides,
+                            const uint16_t* cb_dev, const int64_t* cb_strides, const uint16_t* cr_dev,
+                            const int64_t* cr_strides, const mlic_yuv_desc* desc, int depth, int msb, int H, int W,
+                            float vbr_scale, int level, uint8_t* out, size_t cap, size_t* len);
+int mlic_decode_image_yuv16(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels,
+                            uint64_t max_pixels, const float* vbr_gains, const mlic_yuv_desc* desc, int depth, int msb,
+                            uint16_t* y_dev, const int64_t* y_strides, size_t y_cap, uint16_t* cb_dev,
+                            const int64_t* cb_strides, size_t cb_cap, uint16_t* cr_dev, const int64_t* cr_strides,
+                            size_t cr_cap, int* H, int* W, int* level);
 /* per-image sum of -log2(lik) over n_per elements (fixed reduction order); synchronous */
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out);
 /* GaussianConditional likelihood (compressai, eval; mlicpp.py:132,168) element-wise: lik = max(Phi((0.5-|v|)/s')

@@ -8,6 +8,7 @@ from .metrics import DISTS, LPIPS, dists_synthetic_weights, lpips_synthetic_weig
 from .codec import blur3_pad, decode_images, egress_u8, encode_images, ingest_u8, peek, rate_loop  # noqa: F401
 from .codec import blend_tiles, decode_tiled, encode_tiled, tile_grid  # noqa: F401
 from .codec import YuvFormat, decode_yuv, egress_yuv, encode_yuv, ingest_yuv, split_yuv  # noqa: F401
+from .codec import egress_u16, ingest_u16  # noqa: F401
 from .spec import CONFIGS  # noqa: F401
 
 __all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusVbr", "get_model", "model_config", "CONFIGS",

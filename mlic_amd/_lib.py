@@ -141,6 +141,14 @@ def _sig(lib):
         "mlic_encode_image_yuv8": [p, p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, f, i, p, sz, P(sz)],
         "mlic_decode_image_yuv8": [p, p, p, sz, i, C.c_uint64, p, P(YuvDesc), p, P(i64), sz, p, P(i64), sz, p, P(i64),
                                    sz, P(i), P(i), P(i)],
+        "mlic_image_ingest_u16": [p, p, P(i64), i, i, i, i, i, p, i, i],
+        "mlic_image_egress_u16": [p, p, P(i64), i, i, i, i, i, p, P(i64), p, P(i64), p],
+        "mlic_image_ingest_yuv16": [p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, i, i, p, i, i],
+        "mlic_image_egress_yuv16": [p, p, P(i64), i, i, i, P(YuvDesc), i, i, p, P(i64), p, P(i64), p, P(i64), p,
+                                    P(i64), p, P(i64), p, P(i64), p],
+        "mlic_encode_image_yuv16": [p, p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, i, f, i, p, sz, P(sz)],
+        "mlic_decode_image_yuv16": [p, p, p, sz, i, C.c_uint64, p, P(YuvDesc), i, i, p, P(i64), sz, p, P(i64), sz, p,
+                                    P(i64), sz, P(i), P(i), P(i)],
         "mlic_neglog2_sum": [p, p, i, i64, p],
         "mlic_gaussian_likelihood": [p, p, p, p, i64, f, p],
         "mlic_scale_indexes": [p, p, i64, p, i, p],

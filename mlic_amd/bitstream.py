@@ -122,11 +122,14 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     yuv=fmt (a codec.YuvFormat): the record also holds "sq_err_yuv" (three ints), "psnr_y", "psnr_u", "psnr_v" and
     "psnr_yuv" = (6 Y + U + V) / 8 of codec.egress_yuv(x_hat, fmt) against the source planes, which are taken as
     codec.egress_yuv(img, fmt): the RGB image's 4:4:4 conversion through the same formula, filtered as fmt says.
-    Not together with tile=; off by default."""
+    Not together with tile=, and refused for a format of depth > 8; off by default."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
     if yuv is not None and tile is not None:
         raise ValueError("code_image: yuv= together with tile= is not supported")
+    if yuv is not None and getattr(yuv, "depth", 8) > 8:
+        raise ValueError(f"code_image: yuv= at depth {yuv.depth} is not supported: the record's PSNR fields are "
+                         f"defined on 8-bit planes (score a high-depth decode with codec.decode_yuv(ref=))")
     if tile is not None:
         from . import codec
         if max_bpp is not None or roi is not None or roi_levels is not None or set(kw) - {"s"}:

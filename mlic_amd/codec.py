@@ -24,6 +24,11 @@ grid of `tile_grid`, each tile's file byte for byte `encode_images` of that crop
 a decoder that touches only the tiles a region needs, and `blend_tiles`, one launch that assembles the region from
 the overlapping tiles with feathered seams.
 
+`ingest_u16` / `egress_u16`, `encode_images(depth=)` / `decode_images(depth=)` and `YuvFormat(depth=, msb=)` are
+the same front doors for samples of 9 to 16 bits in uint16 words (DESIGN.md §5 "High-bit-depth I/O",
+csrc/image_io16.hip): nothing is rounded to 8 bits on the way, the file does not know its depth, and PSNR is
+computed at the peak 2^depth - 1.  uint16 tensors are only moved and viewed on the device, never computed with.
+
 CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
 """
@@ -164,6 +169,147 @@ def egress_u8(x_hat: torch.Tensor, H: int, W: int, layout: str = "hwc", ref=None
                   None if ref is None else C.c_void_p(ref.data_ptr()),
                   None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)),
                   None if sq is None else C.c_void_p(sq.data_ptr()))
+    return out if ref is None else (out, sq)
+
+
+# --------------------------------------------------------------------------- samples deeper than a byte
+def _check_depth(depth, what: str, lo: int = 8) -> int:
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not lo <= depth <= 16:
+        raise ValueError(f"{what}: depth must be an integer in [{lo}, 16], got {depth!r}")
+    return int(depth)
+
+
+def _check_msb(msb, what: str) -> bool:
+    if not isinstance(msb, (bool, np.bool_)):
+        raise ValueError(f"{what}: msb must be a bool (False: LSB-aligned samples, True: MSB-aligned, P010 style), "
+                         f"got {msb!r}")
+    return bool(msb)
+
+
+def _as_u16(t, what: str) -> torch.Tensor:
+    """A numpy uint16 array or torch.uint16 tensor -> torch.uint16 tensor sharing the memory."""
+    if isinstance(t, np.ndarray):
+        if t.dtype != np.uint16:
+            raise ValueError(f"{what}: a uint16 array expected, got {t.dtype}")
+        t = torch.from_numpy(t if t.flags.writeable else t.copy())
+    if not torch.is_tensor(t) or t.dtype != torch.uint16:
+        raise ValueError(f"{what}: a uint16 tensor or array expected, got "
+                         f"{t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    return t
+
+
+def _u16_batch(img, layout: Optional[str], what: str):
+    """_u8_batch for uint16 images."""
+    img = _as_u16(img, what)
+    if img.dim() not in (3, 4):
+        raise ValueError(f"{what}: a uint16 tensor or array [B,H,W,3] / [B,3,H,W] (or one image) expected")
+    if img.dim() == 3:
+        img = img.unsqueeze(0)
+    layout = _layout(img, layout)
+    if img.size(3 if layout == "hwc" else 1) != 3:
+        raise ValueError(f"{what}: {layout} image with 3 channels expected, got shape {tuple(img.shape)}")
+    if 0 in img.shape:
+        raise ValueError(f"{what}: empty image {tuple(img.shape)}")
+    return img, layout
+
+
+def samples_of_words(w: torch.Tensor, depth: int, msb: bool = False) -> torch.Tensor:
+    """uint16 words (CPU) -> int32 samples: min(word, 2^depth - 1), or word >> (16 - depth) for msb."""
+    w = w.to(torch.int32)
+    return w >> (16 - depth) if msb else w.clamp(max=(1 << depth) - 1)
+
+
+def words_of_samples(s: torch.Tensor, depth: int, msb: bool = False) -> torch.Tensor:
+    """Integer samples in [0, 2^depth - 1] (CPU) -> uint16 words (shifted up for msb, the low bits zero)."""
+    s = s.to(torch.int32)
+    return (s << (16 - depth) if msb else s).to(torch.uint16)
+
+
+def _dense_u16(t: torch.Tensor, zero_dims) -> torch.Tensor:
+    """A contiguous copy when one of the dims in zero_dims has stride 0 (an expanded tensor); through the host for
+    a device tensor, where uint16 is only moved."""
+    if not any(t.stride(d) == 0 for d in zero_dims):
+        return t
+    return t.cpu().contiguous().to(t.device) if t.is_cuda else t.contiguous()
+
+
+def ingest_u16(img, depth: int, layout: Optional[str] = None, msb: bool = False) -> torch.Tensor:
+    """ingest_u8 for samples of `depth` bits (8..16) in uint16 words (numpy uint16 arrays or torch.uint16 tensors,
+    [B,H,W,3] / [B,3,H,W] or one image, any strides): the model's input, contiguous fp32 [B,3,Hp,Wp], sample /
+    (2^depth - 1) inside the image as a true division (torch's CPU `t.to(torch.float32).div(maxv)` bit for bit) and
+    +0 in the padding.  msb=False: the samples are LSB-aligned (PPM, y4m p10), a word above maxv reads as maxv;
+    msb=True: MSB-aligned (P010 / P016 style), the low 16 - depth bits of a word are ignored.  CUDA tensors run the
+    kernel (csrc/image_io16.hip) on the current stream, CPU tensors the torch restatement (the same bits)."""
+    depth, msb = _check_depth(depth, "ingest_u16"), _check_msb(msb, "ingest_u16")
+    img, layout = _u16_batch(img, layout, "ingest_u16")
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    if not img.is_cuda:
+        s = samples_of_words(_nchw(img, layout), depth, msb)
+        return bitstream.pad64(s.to(torch.float32).div((1 << depth) - 1)).contiguous()
+    img = _dense_u16(img, (2, 3) if layout == "hwc" else (3, 1))
+    Hp, Wp = _pad64(H), _pad64(W)
+    with torch.cuda.device(img.device):
+        x = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=img.device)
+        if _lib.poison():
+            x.fill_(float("nan"))
+        _lib.call("mlic_image_ingest_u16", _stream(), C.c_void_p(img.data_ptr()), (C.c_int64 * 4)(*_strides(img, layout)),
+                  depth, int(msb), B, H, W, C.c_void_p(x.data_ptr()), Hp, Wp)
+    return x
+
+
+def egress_u16(x_hat: torch.Tensor, H: int, W: int, depth: int, layout: str = "hwc", msb: bool = False, ref=None,
+               out: Optional[torch.Tensor] = None):
+    """egress_u8 for samples of `depth` bits: the top-left H x W crop of fp32 [B,3,>=H,>=W] as uint16 words,
+    sample = floor(clamp(v, 0, 1) * (2^depth - 1)) (a NaN gives 0), shifted up by 16 - depth for msb=True.  out: an
+    optional uint16 tensor of the result's shape with any strides; only the crop's words are written.  ref: a uint16
+    image batch of that shape in the same sample format: returns (image, sq_err) with sq_err int64 [B], the exact
+    per-image sum of squared sample differences."""
+    depth, msb = _check_depth(depth, "egress_u16"), _check_msb(msb, "egress_u16")
+    layout = _layout(x_hat, layout)
+    if x_hat.dim() != 4 or x_hat.size(1) != 3 or x_hat.dtype != torch.float32:
+        raise ValueError(f"egress_u16: fp32 [B,3,h,w] expected, got {x_hat.dtype} {tuple(x_hat.shape)}")
+    B = x_hat.size(0)
+    if not (1 <= H <= x_hat.size(2) and 1 <= W <= x_hat.size(3)) or B < 1:
+        raise ValueError(f"egress_u16: crop {H} x {W} of {tuple(x_hat.shape)}")
+    shape = (B, H, W, 3) if layout == "hwc" else (B, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=x_hat.device)  # uint16 is only viewed on the device
+        if x_hat.is_cuda and _lib.poison():
+            out.fill_(-1)
+        out = out.view(torch.uint16)
+    elif out.dtype != torch.uint16 or tuple(out.shape) != shape or out.device != x_hat.device:
+        raise ValueError(f"egress_u16: out must be uint16 {shape} on {x_hat.device}")
+    if ref is not None:
+        ref, _ = _u16_batch(ref, layout, "egress_u16 ref")
+        if tuple(ref.shape) != shape:
+            raise ValueError(f"egress_u16: ref must have shape {shape}, got {tuple(ref.shape)}")
+        ref = ref.to(x_hat.device)  # uint16 is only moved and viewed on the device, never computed with
+    maxv = (1 << depth) - 1
+    if not x_hat.is_cuda:
+        x = x_hat[:, :, :H, :W]
+        s = (torch.where(torch.isnan(x), torch.zeros_like(x), x).clamp(0, 1) * maxv).floor().to(torch.int32)
+        out.copy_(words_of_samples(s.permute(0, 2, 3, 1) if layout == "hwc" else s, depth, msb))
+        if ref is None:
+            return out
+        d = (s.permute(0, 2, 3, 1) if layout == "hwc" else s).to(torch.int64) - samples_of_words(ref, depth, msb).to(torch.int64)
+        return out, (d * d).flatten(1).sum(1)
+    if x_hat.stride(3) != 1:
+        x_hat = x_hat.contiguous()
+    if 0 in _strides(out, layout)[2:]:
+        raise ValueError("egress_u16: out has a zero column or channel stride")
+    with torch.cuda.device(x_hat.device):
+        sq = None
+        if ref is not None:
+            ref = _dense_u16(ref, (2, 3) if layout == "hwc" else (3, 1))
+            sq = torch.full((B,), -1, dtype=torch.int64, device=x_hat.device)
+        _lib.call("mlic_image_egress_u16", _stream(), C.c_void_p(x_hat.data_ptr()), (C.c_int64 * 3)(*x_hat.stride()[:3]),
+                  B, H, W, depth, int(msb), C.c_void_p(out.data_ptr()), (C.c_int64 * 4)(*_strides(out, layout)),
+                  None if ref is None else C.c_void_p(ref.data_ptr()),
+                  None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)),
+                  None if sq is None else C.c_void_p(sq.data_ptr()))
+        if ref is not None:
+            ref.record_stream(torch.cuda.current_stream())
     return out if ref is None else (out, sq)
 
 
@@ -544,7 +690,8 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
 
 @torch.no_grad()
 def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
-                  max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None):
+                  max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None, depth: Optional[int] = None,
+                  msb: bool = False):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
@@ -557,8 +704,19 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     roi=masks with roi_levels=(lo, hi) (a *_VBR model; not together with max_bpp or level): ROI coding.  masks:
     uint8 / bool [B,H,W] (or one [H,W]), nonzero = inside the ROI.  Each 64 x 64 block of the image is coded at
     level lo where it holds no ROI pixel and up to hi where it is all ROI (codec.roi_levels), and the file carries
-    the level map as a third string (its header level is hi); info[b] gains "roi_levels", the map."""
-    img, layout = _u8_batch(imgs_u8, layout, "encode_images")
+    the level map as a third string (its header level is hi); info[b] gains "roi_levels", the map.
+    depth=d (8..16) with msb: the images are uint16 (ingest_u16's sample format) and go through ingest_u16;
+    everything after the ingest works on the float image, so level, max_bpp, level="auto" and roi= compose
+    unchanged, and the file does not know its depth.  depth=None is the uint8 path."""
+    if depth is None:
+        img, layout = _u8_batch(imgs_u8, layout, "encode_images")
+        ingest = ingest_u8
+    else:
+        depth, msb = _check_depth(depth, "encode_images"), _check_msb(msb, "encode_images")
+        img, layout = _u16_batch(imgs_u8, layout, "encode_images")
+
+        def ingest(t, lay):
+            return ingest_u16(t, depth, lay, msb)
     _check_budget(max_bpp, max_passes)
     if isinstance(level, str) and max_bpp is None:
         raise ValueError("level='auto' needs max_bpp (the level is chosen from the budget)")
@@ -584,7 +742,7 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         if tuple(mask.shape) != (B, H, W):
             raise ValueError(f"encode_images: roi must be a mask of shape {(B, H, W)}, got {tuple(mask.shape)}")
         lmap = _roi_level_map(mask.to(net.device), int(lo), int(hi))
-        out = net.compress(ingest_u8(img.to(net.device), layout), gain_map=gain_plane(net, lmap))
+        out = net.compress(ingest(img.to(net.device), layout), gain_map=gain_plane(net, lmap))
         ys, zs = out["strings"]
         lmap = lmap.cpu().numpy()
         files = [write_container_roi(H, W, out["shape"], ys[b], zs[b], int(hi), lmap[b]) for b in range(B)]
@@ -595,12 +753,12 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     img = img.to(net.device)
     if max_bpp is None:
         lv, kw = _levels(net, level, B)
-        out = net.compress(ingest_u8(img, layout), **kw)
+        out = net.compress(ingest(img, layout), **kw)
         ys, zs = out["strings"]
         files = [write_container(H, W, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
         passes = [0] * B
     else:
-        files, passes, lv = rate_loop(net, ingest_u8(img, layout), H, W, level, max_bpp, max_passes)
+        files, passes, lv = rate_loop(net, ingest(img, layout), H, W, level, max_bpp, max_passes)
     if not return_info:
         return files
     info = []
@@ -612,13 +770,19 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
 
 
 @torch.no_grad()
-def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS):
+def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS, depth: Optional[int] = None,
+                  msb: bool = False):
     """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
     (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
     image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
     [B,max H,max W,3] tensor.  Every file goes through the validating parser first.  An ROI file (a *_VBR file
     with a level map, encode_images(roi=...)) is decoded through the gain plane of its own map, and info[b] then
-    holds the map as "roi_levels"."""
+    holds the map as "roi_levels".
+    depth=d (8..16) with msb: the image comes back as uint16 words of that sample format (egress_u16), ref is
+    uint16 likewise, and psnr is computed with peak 2^d - 1.  The file does not know its depth: any file decodes at
+    any depth."""
+    if depth is not None:
+        depth, msb = _check_depth(depth, "decode_images"), _check_msb(msb, "decode_images")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
@@ -646,19 +810,27 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
     H, W = max(c.H for c in cs), max(c.W for c in cs)
     if ref is not None:
-        ref, _ = _u8_batch(ref, "hwc", "decode_images ref")
+        ref, _ = (_u8_batch if depth is None else _u16_batch)(ref, "hwc", "decode_images ref")
         if tuple(ref.shape) != (B, H, W, 3):
-            raise ValueError(f"decode_images: ref must be uint8 {(B, H, W, 3)}, got {tuple(ref.shape)}")
+            raise ValueError(f"decode_images: ref must be {'uint8' if depth is None else 'uint16'} {(B, H, W, 3)}, "
+                             f"got {tuple(ref.shape)}")
         ref = ref.to(x_hat.device)
+
+    def egress(x, h, w, **kw):
+        if depth is None:
+            return egress_u8(x, h, w, "hwc", **kw)
+        return egress_u16(x.float(), h, w, depth, "hwc", msb, **kw)
+
     if all((c.H, c.W) == (H, W) for c in cs):
-        r = egress_u8(x_hat, H, W, "hwc", ref=ref)
+        r = egress(x_hat, H, W, ref=ref)
         img, sq = r if ref is not None else (r, None)
     else:
-        img = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=x_hat.device)
+        img = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=x_hat.device) if depth is None else \
+            torch.zeros(B, H, W, 3, dtype=torch.int16, device=x_hat.device).view(torch.uint16)
         sq = None if ref is None else torch.zeros(B, dtype=torch.int64, device=x_hat.device)
         for b, c in enumerate(cs):
-            r = egress_u8(x_hat[b:b + 1], c.H, c.W, "hwc", out=img[b:b + 1, :c.H, :c.W],
-                          ref=None if ref is None else ref[b:b + 1, :c.H, :c.W])
+            r = egress(x_hat[b:b + 1], c.H, c.W, out=img[b:b + 1, :c.H, :c.W],
+                       ref=None if ref is None else ref[b:b + 1, :c.H, :c.W])
             if ref is not None:
                 sq[b] = r[1][0]
     sq = None if sq is None else sq.cpu().tolist()
@@ -670,7 +842,7 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
             d["roi_levels"] = maps[b]
         if sq is not None:
             d["sq_err"] = int(sq[b])
-            d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W)
+            d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W, 255 if depth is None else (1 << depth) - 1)
         info.append(d)
     return img, info
 
@@ -906,9 +1078,18 @@ def _refuse_with_tiles(what: str, max_bpp=None, level=None, roi=None, roi_levels
         raise ValueError(f"{what}: per-tile levels are not supported: a VBR level is one level for the image")
 
 
+def _refuse_deep_tiles(what: str, depth):
+    """depth= exists on the tiled calls only to be refused by name: any depth means uint16 words (depth=8 too, as in
+    encode_images(depth=8)), and tiles are uint8 images alone."""
+    if depth is not None:
+        raise ValueError(f"{what}: depth {_check_depth(depth, what)} together with tiles is not supported: the blend "
+                         f"kernel (mlic_image_tile_blend_u8) writes bytes, there is no 16-bit blend egress (uint8 "
+                         f"images take no depth=)")
+
+
 @torch.no_grad()
 def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, layout: Optional[str] = None,
-                 tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None):
+                 tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None, depth=None):
     """One uint8 image ([H,W,3] / [3,H,W], tensor or numpy array) -> one tiled file (DESIGN.md §5 "Tiled coding"):
     the image is cut into the tiles of tile_grid(H, W, tile, overlap), each tile is coded by itself and its file
     is byte for byte encode_images of that crop, and the tiled container holds them row-major with an index.
@@ -916,9 +1097,10 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
     whose image stride is tile - overlap columns) and coded per shape group (interior, right column, bottom row,
     corner) in chunks of at most tile_batch tiles, so device memory is the arena of tile_batch tiles plus the
     uint8 image itself, which crosses to the model's device whole (3 bytes per pixel).  level: the one VBR level of the image.  max_bpp, level="auto", roi= and per-tile levels are
-    refused.  return_info=True: (file, info) with info = {"H", "W", "tile", "overlap", "grid", "bytes", "bpp",
-    "level", "tile_bytes"}."""
+    refused, and so is any depth= (uint16 words: the blend kernel writes bytes).  return_info=True: (file, info) with info =
+    {"H", "W", "tile", "overlap", "grid", "bytes", "bpp", "level", "tile_bytes"}."""
     _refuse_with_tiles("encode_tiled", max_bpp, level, roi, roi_levels)
+    _refuse_deep_tiles("encode_tiled", depth)
     img, layout = _u8_batch(img_u8, layout, "encode_tiled")
     if img.size(0) != 1:
         raise ValueError(f"encode_tiled takes one image, got a batch of {img.size(0)}")
@@ -963,13 +1145,15 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
 
 
 @torch.no_grad()
-def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, max_pixels: int = MAX_IMAGE_PIXELS):
+def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, max_pixels: int = MAX_IMAGE_PIXELS,
+                 depth=None):
     """A tiled file -> (uint8 [h,w,3] on the model's device, info): the region (y0, x0, h, w) of the image (None:
     all of it).  Only the tiles that intersect the region are entropy-decoded and synthesised (per shape group,
     in chunks of at most tile_batch tiles); their fp32 x_hat is kept (12 bytes per pixel of the decoded tiles, on top of the arena of
     tile_batch tiles) and one blend_tiles launch writes the region.  The file and every tile's file go through the validating parsers first.  info: H, W, tile, overlap,
     grid (ny, nx), region, tiles_decoded (sorted tile indices), level, bytes and bpp of the whole file and, with
     ref (uint8 [h,w,3], the region's crop of the original), the exact sq_err and psnr."""
+    _refuse_deep_tiles("decode_tiled", depth)
     data = bytes(data)
     if isinstance(tile_batch, bool) or not isinstance(tile_batch, (int, np.integer)) or tile_batch < 1:
         raise ValueError(f"tile_batch must be a positive integer, got {tile_batch!r}")
@@ -1015,39 +1199,61 @@ def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, m
 
 
 # -------------------------------------------------------------------------------------------- YCbCr
-_YUV_MATRIX = {"bt601": (0, 0.299, 0.114), "bt709": (1, 0.2126, 0.0722)}
+_YUV_MATRIX = {"bt601": (0, 0.299, 0.114), "bt709": (1, 0.2126, 0.0722), "bt2020": (2, 0.2627, 0.0593)}
 _YUV_SUB = {"i420": (2, 2), "yv12": (2, 2), "nv12": (2, 2), "nv21": (2, 2), "i422": (2, 1), "i444": (1, 1)}
 
 
 class YuvFormat:
-    """What an 8-bit Y'CbCr frame means (mlic_yuv_desc; DESIGN.md §5 "YCbCr I/O"): sub = (sub_x, sub_y), (1, 1)
-    4:4:4, (2, 1) 4:2:2 or (2, 2) 4:2:0; matrix "bt709" or "bt601"; full_range (False: Y in 16..235, C in 16..240);
+    """What a Y'CbCr frame means (mlic_yuv_desc; DESIGN.md §5 "YCbCr I/O" and "High-bit-depth I/O"): sub = (sub_x,
+    sub_y), (1, 1) 4:4:4, (2, 1) 4:2:2 or (2, 2) 4:2:0; matrix "bt709" or "bt601" (and "bt2020", non-constant
+    luminance, when depth > 8); full_range (False: Y in 16..235, C in 16..240, times 2^(depth-8));
     site_x, the horizontal chroma siting of a subsampled frame: "left" (co-sited with the even luma column: MPEG-2,
-    H.264 / HEVC) or "centre" (JPEG, MPEG-1).  Vertical siting is always centre.  None of this is in the file: it
-    is the caller's knowledge on both sides."""
+    H.264 / HEVC) or "centre" (JPEG, MPEG-1).  Vertical siting is always centre.  depth: bits per sample, 8 (uint8
+    planes, the 8-bit kernels) or 9..16 (uint16 planes, csrc/image_io16.hip); msb: the samples of a uint16 word are
+    MSB-aligned (P010 / P016) instead of LSB-aligned (y4m p10, I010).  None of this is in the file: it is the
+    caller's knowledge on both sides."""
 
-    def __init__(self, sub=(2, 2), matrix: str = "bt709", full_range: bool = False, site_x: str = "left"):
+    def __init__(self, sub=(2, 2), matrix: str = "bt709", full_range: bool = False, site_x: str = "left",
+                 depth: int = 8, msb: bool = False):
         try:
             sub = tuple(int(v) for v in sub)
         except (TypeError, ValueError):
             raise ValueError(f"YuvFormat: sub must be (sub_x, sub_y), got {sub!r}") from None
         if sub not in ((1, 1), (2, 1), (2, 2)):
             raise ValueError(f"YuvFormat: sub must be (1, 1), (2, 1) or (2, 2), got {sub!r}")
+        depth, msb = _check_depth(depth, "YuvFormat"), _check_msb(msb, "YuvFormat")
+        if msb and depth == 8:
+            raise ValueError("YuvFormat: msb=True needs depth > 8 (8-bit samples are bytes)")
         if matrix not in _YUV_MATRIX:
-            raise ValueError(f"YuvFormat: matrix must be 'bt601' or 'bt709', got {matrix!r} (other matrices are out "
-                             f"of scope)")
+            raise ValueError(f"YuvFormat: matrix must be 'bt601', 'bt709' or 'bt2020', got {matrix!r} (other matrices "
+                             f"are out of scope)")
+        if matrix == "bt2020" and depth == 8:
+            raise ValueError("YuvFormat: matrix must be 'bt601' or 'bt709' at depth 8, got 'bt2020' (BT.2020 needs "
+                             "depth > 8: the 8-bit kernels refuse it)")
         if not isinstance(full_range, (bool, np.bool_)):
             raise ValueError(f"YuvFormat: full_range must be a bool, got {full_range!r}")
         if site_x not in ("left", "centre"):
             raise ValueError(f"YuvFormat: site_x must be 'left' or 'centre', got {site_x!r}")
         self.sub, self.matrix, self.full_range, self.site_x = sub, matrix, bool(full_range), site_x
+        self.depth, self.msb = depth, msb
 
     def __repr__(self):
-        return f"YuvFormat(sub={self.sub}, matrix={self.matrix!r}, full_range={self.full_range}, site_x={self.site_x!r})"
+        deep = f", depth={self.depth}, msb={self.msb}" if self.depth > 8 else ""
+        return (f"YuvFormat(sub={self.sub}, matrix={self.matrix!r}, full_range={self.full_range}, "
+                f"site_x={self.site_x!r}{deep})")
 
     def __eq__(self, other):
-        return isinstance(other, YuvFormat) and (self.sub, self.matrix, self.full_range, self.site_x) == \
-            (other.sub, other.matrix, other.full_range, other.site_x)
+        return isinstance(other, YuvFormat) and \
+            (self.sub, self.matrix, self.full_range, self.site_x, self.depth, self.msb) == \
+            (other.sub, other.matrix, other.full_range, other.site_x, other.depth, other.msb)
+
+    @property
+    def maxv(self) -> int:
+        return (1 << self.depth) - 1
+
+    @property
+    def dtype(self):
+        return torch.uint8 if self.depth == 8 else torch.uint16
 
     @property
     def left(self) -> bool:
@@ -1061,12 +1267,19 @@ class YuvFormat:
         return _lib.YuvDesc(self.sub[0], self.sub[1], _YUV_MATRIX[self.matrix][0], int(self.full_range),
                             int(self.site_x == "left"), (C.c_int32 * 3)(0, 0, 0))
 
-    def constants(self) -> Dict[str, float]:
+    def constants(self, depth: Optional[int] = None) -> Dict[str, float]:
         """The kernels' fp32 constants, each folded in double and rounded to fp32 once (the library folds the same
-        expressions): ingest yo, cy, crv, cgu, cgv, cbu; egress yr, yg, yb | br, bg, bb | rr, rg, rb."""
+        expressions): ingest yo, cy, crv, cgu, cgv, cbu; egress yr, yg, yb | br, bg, bb | rr, rg, rb.  depth: the
+        sample depth they are folded for (default: the format's own): ys, cs, yo scale with 2^(depth-8) in limited
+        range and are 2^depth - 1, 2^depth - 1, 0 in full range."""
         _, Kr, Kb = _YUV_MATRIX[self.matrix]
         Kg = 1.0 - Kr - Kb
-        ys, cs, yo = (255.0, 255.0, 0.0) if self.full_range else (219.0, 224.0, 16.0)
+        depth = self.depth if depth is None else depth
+        if depth == 8:
+            ys, cs, yo = (255.0, 255.0, 0.0) if self.full_range else (219.0, 224.0, 16.0)
+        else:
+            m, sc = float((1 << depth) - 1), float(1 << (depth - 8))
+            ys, cs, yo = (m, m, 0.0) if self.full_range else (219.0 * sc, 224.0 * sc, 16.0 * sc)
         d = {"yo": yo, "cy": 1.0 / ys, "crv": 2.0 * (1.0 - Kr) / cs, "cgu": 2.0 * Kb * (1.0 - Kb) / (Kg * cs),
              "cgv": 2.0 * Kr * (1.0 - Kr) / (Kg * cs), "cbu": 2.0 * (1.0 - Kb) / cs,
              "yr": ys * Kr, "yg": ys * Kg, "yb": ys * Kb,
@@ -1081,28 +1294,41 @@ def _check_fmt(fmt, what: str) -> YuvFormat:
     return fmt
 
 
-def yuv_frame_bytes(H: int, W: int, layout: str) -> int:
-    """Bytes of one H x W frame in a raw layout (the ceil rule for the chroma planes)."""
+def yuv_frame_samples(H: int, W: int, layout: str) -> int:
+    """Samples of one H x W frame in a raw layout (the ceil rule for the chroma planes)."""
     if layout not in _YUV_SUB:
         raise ValueError(f"yuv layout must be one of {sorted(_YUV_SUB)}, got {layout!r}")
     sx, sy = _YUV_SUB[layout]
     return H * W + 2 * ((H + sy - 1) // sy) * ((W + sx - 1) // sx)
 
 
-def split_yuv(buf, H: int, W: int, layout: str):
+def yuv_frame_bytes(H: int, W: int, layout: str, depth: int = 8) -> int:
+    """Bytes of one H x W frame in a raw layout: one byte a sample at depth 8, two (a uint16 word) above."""
+    return yuv_frame_samples(H, W, layout) * (1 if _check_depth(depth, "yuv_frame_bytes") == 8 else 2)
+
+
+def split_yuv(buf, H: int, W: int, layout: str, depth: int = 8):
     """A raw frame buffer -> (y, cb, cr) as strided views of it, no copy.  buf: flat uint8 tensor or numpy array of
-    yuv_frame_bytes(H, W, layout) bytes, or [B, that many].  Layouts: "i420" (Y, Cb, Cr planes), "yv12" (Y, Cr, Cb),
+    yuv_frame_bytes(H, W, layout) bytes, or [B, that many]; or, for samples deeper than 8 bits, a uint16 buffer of
+    yuv_frame_samples(H, W, layout) words together with depth= above 8 (P010 is layout "nv12" on a uint16 buffer
+    with depth=10, and YuvFormat(depth=10, msb=True) says what the words mean).  Layouts: "i420" (Y, Cb, Cr planes), "yv12" (Y, Cr, Cb),
     "nv12" (Y, then interleaved Cb Cr rows: the chroma views have column stride 2), "nv21" (Cr Cb), "i422", "i444".
     y is [H, W] (or [B, H, W]), cb and cr are [ceil(H / sub_y), ceil(W / sub_x)]."""
     H, W = int(H), int(W)
     if H < 1 or W < 1:
         raise ValueError(f"split_yuv: a non-empty frame expected, got {H} x {W}")
-    need = yuv_frame_bytes(H, W, layout)
+    need = yuv_frame_samples(H, W, layout)
     is_np = isinstance(buf, np.ndarray)
-    if not (is_np or torch.is_tensor(buf)) or buf.dtype not in (np.uint8, torch.uint8) or buf.ndim not in (1, 2):
-        raise ValueError("split_yuv: a flat uint8 tensor or array (or [B, bytes]) expected")
+    if not (is_np or torch.is_tensor(buf)) or buf.dtype not in (np.uint8, torch.uint8, np.uint16, torch.uint16) or \
+            buf.ndim not in (1, 2):
+        raise ValueError("split_yuv: a flat uint8 or uint16 tensor or array (or [B, samples]) expected")
+    deep = _check_depth(depth, "split_yuv") > 8
+    if deep != (buf.dtype in (np.uint16, torch.uint16)):
+        raise ValueError(f"split_yuv: a frame of depth {depth} is a {'uint16' if deep else 'uint8'} buffer, got "
+                         f"{buf.dtype} (uint8 bytes at depth 8, uint16 words with depth= above 8)")
     if buf.shape[-1] != need:
-        raise ValueError(f"split_yuv: a {W}x{H} {layout} frame is {need} bytes, the buffer has {buf.shape[-1]}")
+        unit = "bytes" if buf.dtype in (np.uint8, torch.uint8) else "uint16 words"
+        raise ValueError(f"split_yuv: a {W}x{H} {layout} frame is {need} {unit}, the buffer has {buf.shape[-1]}")
     sx, sy = _YUV_SUB[layout]
     ch, cw = (H + sy - 1) // sy, (W + sx - 1) // sx
     lead = tuple(buf.shape[:-1])
@@ -1125,14 +1351,16 @@ def split_yuv(buf, H: int, W: int, layout: str):
 
 
 def _yuv_planes(y, cb, cr, fmt: YuvFormat, what: str):
-    """-> three 3-dim uint8 tensors [B,H,W], [B,ch,cw], [B,ch,cw] (one frame gains the batch dimension)."""
+    """-> three 3-dim tensors [B,H,W], [B,ch,cw], [B,ch,cw] (one frame gains the batch dimension) of the format's
+    sample type: uint8 at depth 8, uint16 above."""
     out = []
     for name, t in (("y", y), ("cb", cb), ("cr", cr)):
         if isinstance(t, np.ndarray):
-            t = torch.from_numpy(t)
-        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() not in (2, 3):
-            raise ValueError(f"{what}: {name} must be a uint8 tensor or array [B,h,w] (or one [h,w]); bit depths above "
-                             f"8 are out of scope")
+            t = torch.from_numpy(t if t.flags.writeable else t.copy())
+        if not torch.is_tensor(t) or t.dtype != fmt.dtype or t.dim() not in (2, 3):
+            kind = "uint8" if fmt.depth == 8 else "uint16"
+            raise ValueError(f"{what}: {name} must be a {kind} tensor or array [B,h,w] (or one [h,w]) for a format of "
+                             f"depth {fmt.depth}; bit depths above 8 are uint16 planes with YuvFormat(depth=)")
         out.append(t.unsqueeze(0) if t.dim() == 2 else t)
     y, cb, cr = out
     if 0 in y.shape:
@@ -1147,12 +1375,12 @@ def _yuv_planes(y, cb, cr, fmt: YuvFormat, what: str):
     return y, cb, cr
 
 
-def _k32(fmt: YuvFormat):
-    return {k: torch.tensor(v, dtype=torch.float32) for k, v in fmt.constants().items()}
+def _k32(fmt: YuvFormat, depth: Optional[int] = None):
+    return {k: torch.tensor(v, dtype=torch.float32) for k, v in fmt.constants(depth).items()}
 
 
 def yuv_upsample16(c: torch.Tensor, H: int, W: int, fmt: YuvFormat) -> torch.Tensor:
-    """One chroma plane [B,ch,cw] (integers) on the luma grid, in sixteenths: int32 [B,H,W] in [0, 4080].  Across
+    """One chroma plane [B,ch,cw] (integers) on the luma grid, in sixteenths: int32 [B,H,W] in [0, 16 maxv].  Across
     columns of a subsampled axis with i = x >> 1 and indices clamped: centre siting 3 C[i] + C[i -+ 1] (- at even
     x), left siting 4 C[i] at even x and 2 C[i] + 2 C[i + 1] at odd x; down rows the centre rule; an unsubsampled
     axis contributes the factor 4.  The ingest kernel's integer step, restated."""
@@ -1192,8 +1420,28 @@ def _ingest_yuv_cpu(y, cb, cr, fmt: YuvFormat) -> torch.Tensor:
     return out
 
 
+def _ingest_yuv16_cpu(y, cb, cr, fmt: YuvFormat, depth: int, msb: bool) -> torch.Tensor:
+    """The restatement of mlic_image_ingest_yuv16: _ingest_yuv_cpu on the samples of uint16 words, with half =
+    2^(depth-1) in place of 128 and the constants of that depth.  Takes depth 8 too (the words are then bytes
+    widened), where it gives _ingest_yuv_cpu's bits."""
+    B, H, W = y.shape
+    k = _k32(fmt, depth)
+    half = float(1 << (depth - 1))
+    ys, cbs, crs = (samples_of_words(t, depth, msb) for t in (y, cb, cr))
+    u = yuv_upsample16(cbs, H, W, fmt).float() * 0.0625 - half  # exact: sixteenths below 2^20
+    v = yuv_upsample16(crs, H, W, fmt).float() * 0.0625 - half
+    a = k["cy"] * (ys.float() - k["yo"])
+    r = a + k["crv"] * v
+    g = (a - k["cgu"] * u) - k["cgv"] * v
+    b = a + k["cbu"] * u
+    out = torch.zeros(B, 3, _pad64(H), _pad64(W), dtype=torch.float32)
+    out[:, :, :H, :W] = torch.stack([r, g, b], 1).clamp(0, 1)
+    return out
+
+
 def ingest_yuv(y, cb, cr, fmt: YuvFormat) -> torch.Tensor:
-    """An 8-bit Y'CbCr frame batch -> the model's input, contiguous fp32 [B,3,Hp,Wp], in one launch: y uint8
+    """A Y'CbCr frame batch (uint8 planes at fmt.depth 8, uint16 words above: mlic_image_ingest_yuv16, with 128 ->
+    2^(depth-1) and the constants of that depth) -> the model's input, contiguous fp32 [B,3,Hp,Wp], in one launch: y uint8
     [B,H,W], cb and cr uint8 [B,ceil(H / sub_y),ceil(W / sub_x)] (or one frame without B), each with any strides
     (split_yuv's views of an I420 / NV12 buffer, a row-padded pitch, a crop are read in place).  Chroma is
     upsampled in integers (yuv_upsample16), then a = cy (Y - yo); R = a + crv v; G = (a - cgu u) - cgv v;
@@ -1204,16 +1452,23 @@ def ingest_yuv(y, cb, cr, fmt: YuvFormat) -> torch.Tensor:
     y, cb, cr = _yuv_planes(y, cb, cr, fmt, "ingest_yuv")
     B, H, W = y.shape
     if not y.is_cuda:
-        return _ingest_yuv_cpu(y, cb, cr, fmt)
-    y, cb, cr = (t.contiguous() if t.stride(2) == 0 else t for t in (y, cb, cr))
+        return _ingest_yuv_cpu(y, cb, cr, fmt) if fmt.depth == 8 else _ingest_yuv16_cpu(y, cb, cr, fmt, fmt.depth, fmt.msb)
+    if fmt.depth == 8:
+        y, cb, cr = (t.contiguous() if t.stride(2) == 0 else t for t in (y, cb, cr))
+    else:
+        y, cb, cr = (_dense_u16(t, (2,)) for t in (y, cb, cr))
     Hp, Wp = _pad64(H), _pad64(W)
     with torch.cuda.device(y.device):
         x = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=y.device)
         if _lib.poison():
             x.fill_(float("nan"))
         d = fmt.desc()
-        _lib.call("mlic_image_ingest_yuv8", _stream(), *_plane_args(y, cb, cr), C.byref(d), B, H, W,
-                  C.c_void_p(x.data_ptr()), Hp, Wp)
+        if fmt.depth == 8:
+            _lib.call("mlic_image_ingest_yuv8", _stream(), *_plane_args(y, cb, cr), C.byref(d), B, H, W,
+                      C.c_void_p(x.data_ptr()), Hp, Wp)
+        else:
+            _lib.call("mlic_image_ingest_yuv16", _stream(), *_plane_args(y, cb, cr), C.byref(d), fmt.depth, int(fmt.msb),
+                      B, H, W, C.c_void_p(x.data_ptr()), Hp, Wp)
     return x
 
 
@@ -1224,9 +1479,9 @@ def _plane_args(*planes):
     return out
 
 
-def _yuv_of_rgb(x: torch.Tensor, fmt: YuvFormat):
+def _yuv_of_rgb(x: torch.Tensor, fmt: YuvFormat, depth: Optional[int] = None):
     """fp32 [B,3,H,W] -> (t_Y, t_Cb, t_Cr) at full resolution, chroma without the 128: the egress kernel's order."""
-    k = _k32(fmt)
+    k = _k32(fmt, depth)
     x = torch.where(torch.isnan(x), torch.zeros_like(x), x).clamp(0, 1)
     r, g, b = x[:, 0], x[:, 1], x[:, 2]
     ty = (k["yo"] + (k["yr"] * r + k["yg"] * g)) + k["yb"] * b
@@ -1260,6 +1515,18 @@ def _yuv_byte(t: torch.Tensor) -> torch.Tensor:
     return (t + 0.5).clamp(0, 255).floor().to(torch.uint8)
 
 
+def _egress_yuv16_cpu(x: torch.Tensor, fmt: YuvFormat, depth: int):
+    """The restatement of mlic_image_egress_yuv16 up to the samples: fp32 [B,3,H,W] -> int32 (y, cb, cr) samples in
+    [0, 2^depth - 1] (words_of_samples makes the words).  At depth 8 these are egress_yuv's bytes."""
+    maxv, half = float((1 << depth) - 1), float(1 << (depth - 1))
+    ty, tb, tr = _yuv_of_rgb(x, fmt, depth)
+
+    def sample(t):
+        return (t + 0.5).clamp(0, maxv).floor().to(torch.int32)
+
+    return sample(ty), sample(yuv_downsample(tb, fmt) + half), sample(yuv_downsample(tr, fmt) + half)
+
+
 def egress_yuv(x_hat: torch.Tensor, H: int, W: int, fmt: YuvFormat, ref=None, out=None):
     """The top-left H x W crop of fp32 [B,3,>=H,>=W] (a padded x_hat, read in place) -> (y, cb, cr): uint8 [B,H,W]
     and two [B,ceil(H / sub_y),ceil(W / sub_x)], in one launch.  Per pixel the clamped r, g, b (a NaN is 0) give
@@ -1268,7 +1535,9 @@ def egress_yuv(x_hat: torch.Tensor, H: int, W: int, fmt: YuvFormat, ref=None, ou
     shapes with any strides (split_yuv's views of an NV12 buffer, windows of larger canvases): only the planes'
     bytes are written.  ref: (y, cb, cr) of the original, any strides: returns (y, cb, cr, sq_err) with sq_err
     int64 [B,3], the exact per-plane sums of squared byte differences.  CUDA tensors run the kernel on the current
-    stream, CPU tensors the torch restatement (the same bits)."""
+    stream, CPU tensors the torch restatement (the same bits).  A format of depth > 8 gives uint16 words
+    (mlic_image_egress_yuv16: 2^(depth-1) in place of 128, 2^depth - 1 in place of 255, shifted up for msb) and takes
+    uint16 out / ref planes; sq_err then sums squared sample differences."""
     fmt = _check_fmt(fmt, "egress_yuv")
     if not torch.is_tensor(x_hat) or x_hat.dim() != 4 or x_hat.size(1) != 3 or x_hat.dtype != torch.float32:
         raise ValueError("egress_yuv: fp32 [B,3,h,w] expected")
@@ -1280,20 +1549,35 @@ def egress_yuv(x_hat: torch.Tensor, H: int, W: int, fmt: YuvFormat, ref=None, ou
     shapes = ((B, H, W), (B, ch, cw), (B, ch, cw))
     dev = x_hat.device
     if out is None:
-        out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+        if fmt.depth == 8:
+            out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+        else:  # uint16 is only moved and viewed on the device: allocate (and poison) as int16
+            out = tuple(torch.empty(s, dtype=torch.int16, device=dev) for s in shapes)
         if x_hat.is_cuda and _lib.poison():
             for t in out:
-                t.fill_(0xFF)
+                t.fill_(0xFF if fmt.depth == 8 else -1)
+        if fmt.depth > 8:
+            out = tuple(t.view(torch.uint16) for t in out)
     else:
         out = tuple(out)
-        if len(out) != 3 or any(not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != s or t.device != dev
+        if len(out) != 3 or any(not torch.is_tensor(t) or t.dtype != fmt.dtype or tuple(t.shape) != s or t.device != dev
                                 for t, s in zip(out, shapes)):
-            raise ValueError(f"egress_yuv: out must be three uint8 tensors {shapes} on {dev}")
+            raise ValueError(f"egress_yuv: out must be three {'uint8' if fmt.depth == 8 else 'uint16'} tensors "
+                             f"{shapes} on {dev}")
     if ref is not None:
         ref = _yuv_planes(*ref, fmt, "egress_yuv ref")
         if tuple(ref[0].shape) != shapes[0]:
             raise ValueError(f"egress_yuv: ref must be a frame batch of {shapes[0]}, got {tuple(ref[0].shape)}")
         ref = tuple(t.to(dev) for t in ref)
+    if not x_hat.is_cuda and fmt.depth > 8:
+        smp = _egress_yuv16_cpu(x_hat[:, :, :H, :W], fmt, fmt.depth)
+        for o, v in zip(out, smp):
+            o.copy_(words_of_samples(v, fmt.depth, fmt.msb))
+        if ref is None:
+            return out
+        sq = torch.stack([((v.to(torch.int64) - samples_of_words(r, fmt.depth, fmt.msb).to(torch.int64)) ** 2)
+                          .flatten(1).sum(1) for v, r in zip(smp, ref)], 1)
+        return out + (sq,)
     if not x_hat.is_cuda:
         ty, tb, tr = _yuv_of_rgb(x_hat[:, :, :H, :W], fmt)
         out[0].copy_(_yuv_byte(ty))
@@ -1310,12 +1594,19 @@ def egress_yuv(x_hat: torch.Tensor, H: int, W: int, fmt: YuvFormat, ref=None, ou
     with torch.cuda.device(dev):
         sq = None
         if ref is not None:
-            ref = tuple(t.contiguous() if t.stride(2) == 0 else t for t in ref)
+            ref = tuple(t.contiguous() if t.stride(2) == 0 else t for t in ref) if fmt.depth == 8 else \
+                tuple(_dense_u16(t, (2,)) for t in ref)
             sq = torch.full((B, 3), -1, dtype=torch.int64, device=dev)
         d = fmt.desc()
         rargs = [None] * 6 if ref is None else _plane_args(*ref)
-        _lib.call("mlic_image_egress_yuv8", _stream(), C.c_void_p(x_hat.data_ptr()), (C.c_int64 * 3)(*x_hat.stride()[:3]),
-                  B, H, W, C.byref(d), *_plane_args(*out), *rargs, None if sq is None else C.c_void_p(sq.data_ptr()))
+        if fmt.depth == 8:
+            _lib.call("mlic_image_egress_yuv8", _stream(), C.c_void_p(x_hat.data_ptr()),
+                      (C.c_int64 * 3)(*x_hat.stride()[:3]), B, H, W, C.byref(d), *_plane_args(*out), *rargs,
+                      None if sq is None else C.c_void_p(sq.data_ptr()))
+        else:
+            _lib.call("mlic_image_egress_yuv16", _stream(), C.c_void_p(x_hat.data_ptr()),
+                      (C.c_int64 * 3)(*x_hat.stride()[:3]), B, H, W, C.byref(d), fmt.depth, int(fmt.msb),
+                      *_plane_args(*out), *rargs, None if sq is None else C.c_void_p(sq.data_ptr()))
         if ref is not None:
             for t in ref:
                 t.record_stream(torch.cuda.current_stream())
@@ -1323,11 +1614,12 @@ def egress_yuv(x_hat: torch.Tensor, H: int, W: int, fmt: YuvFormat, ref=None, ou
 
 
 def psnr_yuv_from_sq_err(sq_err, H: int, W: int, fmt: YuvFormat) -> Dict:
-    """{"sq_err", "psnr_y", "psnr_u", "psnr_v", "psnr_yuv"} from the three per-plane sums of squared byte
-    differences of an H x W frame: PSNR per plane (max 255) and the 6 : 1 : 1 mean (6 Y + U + V) / 8."""
+    """{"sq_err", "psnr_y", "psnr_u", "psnr_v", "psnr_yuv"} from the three per-plane sums of squared sample
+    differences of an H x W frame: PSNR per plane (peak 2^depth - 1: 255 at depth 8) and the 6 : 1 : 1 mean
+    (6 Y + U + V) / 8."""
     ch, cw = fmt.chroma_size(H, W)
     sq = [int(v) for v in sq_err]
-    py, pu, pv = (psnr_from_sq_err(s, n) for s, n in zip(sq, (H * W, ch * cw, ch * cw)))
+    py, pu, pv = (psnr_from_sq_err(s, n, fmt.maxv) for s, n in zip(sq, (H * W, ch * cw, ch * cw)))
     return {"sq_err": sq, "psnr_y": py, "psnr_u": pu, "psnr_v": pv, "psnr_yuv": (6.0 * py + pu + pv) / 8.0}
 
 
@@ -1338,7 +1630,8 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
     bytes) -> one file per frame.  The files are plain per-image files: nothing of fmt is written, decode_images
     decodes them to RGB and decode_yuv(fmt) to planes.  level, max_bpp, max_passes and return_info as in
     encode_images (the rate loop works on the float image, so a budget and level="auto" work unchanged).  roi= and
-    tile= are refused: ROI and tiled coding together with Y'CbCr frames are out of scope."""
+    tile= are refused: ROI and tiled coding together with Y'CbCr frames are out of scope.  The planes follow the
+    format's depth: uint8 at depth 8, uint16 words above (a P010 frame: YuvFormat(depth=10, msb=True))."""
     fmt = _check_fmt(fmt, "encode_yuv")
     if roi is not None or roi_levels is not None:
         raise ValueError("encode_yuv: roi= together with Y'CbCr frames is not supported")
@@ -1372,7 +1665,8 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
 def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS):
     """Files of one H x W -> ((y, cb, cr) on the model's device, info): decode_images with the Y'CbCr egress.
     info[b] holds H, W, level, bytes and bpp and, with ref=(y, cb, cr) of the originals, sq_err (three ints: Y, Cb,
-    Cr), psnr_y, psnr_u, psnr_v and psnr_yuv = (6 Y + U + V) / 8.  ROI and tiled files are refused."""
+    Cr), psnr_y, psnr_u, psnr_v and psnr_yuv = (6 Y + U + V) / 8 (peak 2^depth - 1).  The planes are uint8 for a
+    format of depth 8 and uint16 words above; the file does not know its depth.  ROI and tiled files are refused."""
     fmt = _check_fmt(fmt, "decode_yuv")
     files = [bytes(f) for f in files]
     if not files:
@@ -1401,6 +1695,7 @@ def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels
     return tuple(r[:3]), info
 
 
-def psnr_from_sq_err(sq_err: int, n: int) -> float:
-    """PSNR (max 255, utils/metrics.py:32-33) from a sum of squared uint8 differences over n values."""
-    return 10.0 * math.log10(255.0 ** 2 * n / sq_err) if sq_err > 0 else float("inf")
+def psnr_from_sq_err(sq_err: int, n: int, peak: int = 255) -> float:
+    """PSNR (utils/metrics.py:32-33; peak 255, or 2^depth - 1 for deeper samples) from a sum of squared sample
+    differences over n values."""
+    return 10.0 * math.log10(float(peak) ** 2 * n / sq_err) if sq_err > 0 else float("inf")

@@ -1286,6 +1286,127 @@ int mlic_decode_image_yuv8(mlic_model* m, void* stream, const uint8_t* file, siz
   });
 }
 
+int mlic_image_ingest_u16(void* stream, const uint16_t* src, const int64_t* src_strides, int depth, int msb, int B,
+                          int H, int W, float* dst, int Hp, int Wp) {
+  return guard([&] { image_ingest_u16(src, src_strides, depth, msb, B, H, W, dst, Hp, Wp, (hipStream_t)stream); });
+}
+
+int mlic_image_egress_u16(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W, int depth,
+                          int msb, uint16_t* dst, const int64_t* dst_strides, const uint16_t* ref,
+                          const int64_t* ref_strides, uint64_t* sq_err) {
+  return guard([&] {
+    image_egress_u16(src, src_strides, B, H, W, depth, msb, dst, dst_strides, ref, ref_strides, sq_err,
+                     (hipStream_t)stream);
+  });
+}
+
+int mlic_image_ingest_yuv16(void* stream, const uint16_t* y, const int64_t* y_strides, const uint16_t* cb,
+                            const int64_t* cb_strides, const uint16_t* cr, const int64_t* cr_strides,
+                            const mlic_yuv_desc* desc, int depth, int msb, int B, int H, int W, float* dst, int Hp,
+                            int Wp) {
+  return guard([&] {
+    const YuvDesc d = yuv_desc(desc);
+    image_ingest_yuv16(y, y_strides, cb, cb_strides, cr, cr_strides, &d, depth, msb, B, H, W, dst, Hp, Wp,
+                       (hipStream_t)stream);
+  });
+}
+
+int mlic_image_egress_yuv16(void* stream, const float* src, const int64_t* src_strides, int B, int H, int W,
+                            const mlic_yuv_desc* desc, int depth, int msb, uint16_t* y, const int64_t* y_strides,
+                            uint16_t* cb, const int64_t* cb_strides, uint16_t* cr, const int64_t* cr_strides,
+                            const uint16_t* ref_y, const int64_t* ref_y_strides, const uint16_t* ref_cb,
+                            const int64_t* ref_cb_strides, const uint16_t* ref_cr, const int64_t* ref_cr_strides,
+                            uint64_t* sq_err) {
+  return guard([&] {
+    const YuvDesc d = yuv_desc(desc);
+    image_egress_yuv16(src, src_strides, B, H, W, &d, depth, msb, y, y_strides, cb, cb_strides, cr, cr_strides, ref_y,
+                       ref_y_strides, ref_cb, ref_cb_strides, ref_cr, ref_cr_strides, sq_err, (hipStream_t)stream);
+  });
+}
+
+int mlic_encode_image_yuv16(mlic_model* m, void* stream, const uint16_t* y_dev, const int64_t* y_strides,
+                            const uint16_t* cb_dev, const int64_t* cb_strides, const uint16_t* cr_dev,
+                            const int64_t* cr_strides, const mlic_yuv_desc* desc, int depth, int msb, int H, int W,
+                            float vbr_scale, int level, uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    // every argument is checked before the handle is touched: a refused call keeps the handle's last encoded image
+    // and makes no device call
+    MLIC_CHECK(len != nullptr, "encode_image_yuv16: null len");
+    YuvDesc d{};
+    if (y_dev != nullptr) {
+      MLIC_CHECK(cb_dev != nullptr && cr_dev != nullptr, "encode_image_yuv16: null chroma plane");
+      MLIC_CHECK(y_strides != nullptr && cb_strides != nullptr && cr_strides != nullptr && H >= 1 && W >= 1,
+                 "encode_image_yuv16: strides, H >= 1 and W >= 1 expected");
+      MLIC_CHECK(H <= (1 << 24) && W <= (1 << 24), "encode_image_yuv16: image side above 2^24");
+      MLIC_CHECK(y_strides[1] != 0 && cb_strides[1] != 0 && cr_strides[1] != 0,
+                 "encode_image_yuv16: zero column stride");
+      d = yuv_desc(desc);
+      image_yuv16_check(&d, depth, msb, y_dev, cb_dev, cr_dev, "encode_image_yuv16");
+    }
+    Model& mod = impl(m);
+    if (y_dev != nullptr) {
+      const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64;
+      const int64_t ys[3] = {0, y_strides[0], y_strides[1]}, bs[3] = {0, cb_strides[0], cb_strides[1]},
+                    rs[3] = {0, cr_strides[0], cr_strides[1]};
+      m->enc_H = 0;
+      float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
+      image_ingest_yuv16(y_dev, ys, cb_dev, bs, cr_dev, rs, &d, depth, msb, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
+      const float sc[1] = {vbr_scale};
+      mod.compress(x, 1, Hp, Wp, sc, (hipStream_t)stream);
+      m->enc_H = H;
+      m->enc_W = W;
+      m->enc_level = level < 0 ? -1 : level;
+      m->enc_passes = 0;
+    }
+    MLIC_CHECK(m->enc_H > 0, "encode_image_yuv16: y_dev is NULL and the handle has no encoded image");
+    write_encoded(m, mod, out, cap, len);
+  });
+}
+
+int mlic_decode_image_yuv16(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels,
+                            uint64_t max_pixels, const float* vbr_gains, const mlic_yuv_desc* desc, int depth, int msb,
+                            uint16_t* y_dev, const int64_t* y_strides, size_t y_cap, uint16_t* cb_dev,
+                            const int64_t* cb_strides, size_t cb_cap, uint16_t* cr_dev, const int64_t* cr_strides,
+                            size_t cr_cap, int* H, int* W, int* level) {
+  return guard([&] {
+    MLIC_CHECK(file != nullptr || n == 0, "decode_image_yuv16: null file");
+    const bool vbr = n_levels > 0;
+    ContainerInfo c;
+    container_ok(container_parse(file, n, vbr, (uint32_t)std::max(n_levels, 0), max_pixels, &c));
+    MLIC_CHECK(c.H <= (1u << 24) && c.W <= (1u << 24), "decode_image_yuv16: image side above 2^24");
+    if (H) *H = (int)c.H;
+    if (W) *W = (int)c.W;
+    if (level) *level = c.level;
+    if (y_dev == nullptr) return;
+    // every argument is checked before the handle is touched: a refused call makes no device call
+    MLIC_CHECK(cb_dev != nullptr && cr_dev != nullptr, "decode_image_yuv16: null chroma plane");
+    const YuvDesc d = yuv_desc(desc);
+    image_yuv16_check(&d, depth, msb, y_dev, cb_dev, cr_dev, "decode_image_yuv16");
+    const int64_t* st[3] = {y_strides, cb_strides, cr_strides};
+    const size_t caps[3] = {y_cap, cb_cap, cr_cap};
+    for (int p = 0; p < 3; ++p) {
+      MLIC_CHECK(st[p] != nullptr && st[p][0] >= 0 && st[p][1] > 0,
+                 "decode_image_yuv16: strides {row, column} must be non-negative, column nonzero");
+      const uint64_t ph = p ? (c.H + d.sub_y - 1) / d.sub_y : c.H, pw = p ? (c.W + d.sub_x - 1) / d.sub_x : c.W;
+      const uint64_t extent = 1 + (ph - 1) * (uint64_t)st[p][0] + (pw - 1) * (uint64_t)st[p][1];  // elements
+      MLIC_CHECK(extent <= caps[p] / sizeof(uint16_t), "decode_image_yuv16: the file's plane does not fit its cap_bytes");
+    }
+    Model& mod = impl(m);
+    const int Hp = (int)c.hz * 64, Wp = (int)c.wz * 64;
+    float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
+    const uint8_t* ys[1] = {file + c.y_off};
+    const uint8_t* zs[1] = {file + c.z_off};
+    const size_t yl[1] = {c.y_len}, zl[1] = {c.z_len};
+    const float sc[1] = {vbr && vbr_gains ? vbr_gains[c.level] : 1.0f};
+    mod.decompress(ys, yl, zs, zl, 1, (int)c.hz, (int)c.wz, x, sc, (hipStream_t)stream);
+    const int64_t s3[3] = {0, (int64_t)Hp * Wp, Wp};
+    const int64_t y3[3] = {0, y_strides[0], y_strides[1]}, b3[3] = {0, cb_strides[0], cb_strides[1]},
+                  r3[3] = {0, cr_strides[0], cr_strides[1]};
+    image_egress_yuv16(x, s3, 1, (int)c.H, (int)c.W, &d, depth, msb, y_dev, y3, cb_dev, b3, cr_dev, r3, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  });
+}
+
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out) {
   return guard([&] {
     double* part = nullptr;

@@ -333,6 +333,29 @@ void image_egress_yuv8(const float* src, const int64_t* src_strides, int B, int 
                        const int64_t* cr_strides, const uint8_t* ref_y, const int64_t* ref_y_strides,
                        const uint8_t* ref_cb, const int64_t* ref_cb_strides, const uint8_t* ref_cr,
                        const int64_t* ref_cr_strides, uint64_t* sq_err, hipStream_t st);
+// 9..16-bit sample I/O (image_io16.hip; DESIGN.md section 5 "High-bit-depth I/O"): the four calls above for uint16
+// words of depth d in [8, 16], LSB-aligned (msb 0: the sample is min(word, 2^d - 1)) or MSB-aligned (msb 1: the
+// sample is word >> (16 - d); output words have zero low bits).  Strides in elements, pointers 2-byte aligned.
+// The Y'CbCr calls take matrix 2 (BT.2020 non-constant-luminance) as well.  They check their arguments before any
+// HIP call and throw.
+void image_ingest_u16(const uint16_t* src, const int64_t* src_strides, int depth, int msb, int B, int H, int W,
+                      float* dst, int Hp, int Wp, hipStream_t st);
+void image_egress_u16(const float* src, const int64_t* src_strides, int B, int H, int W, int depth, int msb,
+                      uint16_t* dst, const int64_t* dst_strides, const uint16_t* ref, const int64_t* ref_strides,
+                      uint64_t* sq_err, hipStream_t st);
+void image_ingest_yuv16(const uint16_t* y, const int64_t* y_strides, const uint16_t* cb, const int64_t* cb_strides,
+                        const uint16_t* cr, const int64_t* cr_strides, const YuvDesc* desc, int depth, int msb, int B,
+                        int H, int W, float* dst, int Hp, int Wp, hipStream_t st);
+void image_egress_yuv16(const float* src, const int64_t* src_strides, int B, int H, int W, const YuvDesc* desc,
+                        int depth, int msb, uint16_t* y, const int64_t* y_strides, uint16_t* cb,
+                        const int64_t* cb_strides, uint16_t* cr, const int64_t* cr_strides, const uint16_t* ref_y,
+                        const int64_t* ref_y_strides, const uint16_t* ref_cb, const int64_t* ref_cb_strides,
+                        const uint16_t* ref_cr, const int64_t* ref_cr_strides, uint64_t* sq_err, hipStream_t st);
+// host logic only: the refusals of the two calls above that do not need the shapes (depth, msb, the descriptor with
+// matrix in {0, 1, 2}, 2-byte alignment of the three plane pointers), each thrown with `who` in front, for callers
+// that must refuse before they touch a device
+void image_yuv16_check(const YuvDesc* desc, int depth, int msb, const void* y, const void* cb, const void* cr,
+                       const char* who);
 // tiled decode's egress: the h x w region at (y0, x0) of the H x W image, blended from the tiles of the grid
 // (container.h: tile T, overlap V) with feathered seams, as uint8 through dst's {row, column, channel} strides.
 // tiles_dev: the device table, tile index (row-major) -> that tile's contiguous fp32 [3][pad64(ey)][pad64(ex)]

@@ -20,14 +20,23 @@
         round trip (codec.encode_yuv / decode_yuv).  .y4m: C420jpeg (centre-sited chroma), C420mpeg2 / C420 (left),
         C422, C444; any other colour space or bit depth is refused by its tag.  Raw .yuv: --yuv i420|nv12|nv21|yv12|
         i422|i444 (default i420) and --size WxH.  --frame N picks the frame (default 0; one frame is coded).
-        --matrix 601|709 (default 709), --range full|limited (default limited) and --chroma-site left|centre (default:
+        --matrix 601|709|2020 (default 709), --range full|limited (default limited) and --chroma-site left|centre (default:
         the y4m tag's, else left) say what the bytes mean; none of it is written into the bitstream, so a decode
         takes the same flags.  decode ... --ref SRC prints the PSNR per plane and the 6:1:1 mean against SRC.
         Not together with --roi, --tile or --region
     python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR     what the file says (and its level map, or
         for a tiled file its grid and per-tile sizes)
 
-Binary PPM (P6, maxval 255) is read and written here; any other format goes through PIL when it imports.
+    ... samples deeper than 8 bits (codec.encode_images(depth=) / YuvFormat(depth=); the bitstream does not know
+        its depth).  A binary PPM of maxval 2^d - 1, d from 9 to 16 (16-bit big-endian samples), is encoded at depth d;
+        decode IN.bit OUT.ppm --depth D writes one.  .y4m: C420pN / C422pN / C444pN for N in 9, 10, 12, 14, 16
+        (little-endian, LSB-aligned samples; 4:2:0 left-sited), decode --depth N writes that tag.  Raw .yuv: --depth D
+        says the file holds 16-bit little-endian words of D-bit samples, LSB-aligned or, with --msb, MSB-aligned
+        (P010 is --yuv nv12 --depth 10 --msb).  --matrix 2020 (BT.2020 non-constant-luminance) needs a depth above
+        8.  decode --ref prints the PSNRs at the peak 2^D - 1.  Not together with --tile / --region
+
+Binary PPM (P6, maxval 255 or 2^d - 1) is read and written here; any other format goes through PIL (8-bit) when it
+imports.
 """
 import argparse
 import os
@@ -61,8 +70,10 @@ def _ppm_tokens(data: bytes, count: int):
     return toks, pos + 1
 
 
-def read_ppm(data: bytes) -> np.ndarray:
-    """Binary PPM (P6, maxval 255) bytes -> uint8 [H, W, 3]."""
+def read_ppm_deep(data: bytes):
+    """Binary PPM (P6) bytes -> (image [H, W, 3], depth): uint8 and 8 for maxval 255; for a maxval from 256 to
+    65535, which must be 2^depth - 1, uint16 in native byte order (the file's samples are 16-bit big-endian, per
+    Netpbm) and that depth."""
     toks, off = _ppm_tokens(data, 4)
     if toks[0] != b"P6":
         raise ValueError("PPM: not a binary P6 file")
@@ -70,41 +81,70 @@ def read_ppm(data: bytes) -> np.ndarray:
         W, H, maxval = (int(t) for t in toks[1:])
     except ValueError:
         raise ValueError("PPM: header fields are not numbers") from None
-    if W < 1 or H < 1 or maxval != 255:
-        raise ValueError(f"PPM: {W} x {H}, maxval {maxval}: a non-empty 8-bit image expected")
-    if len(data) - off < H * W * 3:
+    if W < 1 or H < 1:
+        raise ValueError(f"PPM: {W} x {H}, maxval {maxval}: a non-empty image expected")
+    depth = maxval.bit_length()
+    if not 8 <= depth <= 16 or maxval != (1 << depth) - 1:
+        raise ValueError(f"PPM: maxval {maxval} is not 2^d - 1 for a depth d in [8, 16]")
+    if depth == 8:
+        if len(data) - off < H * W * 3:
+            raise ValueError("PPM: pixel data truncated")
+        return np.frombuffer(data, np.uint8, H * W * 3, off).reshape(H, W, 3).copy(), 8
+    if len(data) - off < H * W * 6:
         raise ValueError("PPM: pixel data truncated")
-    return np.frombuffer(data, np.uint8, H * W * 3, off).reshape(H, W, 3).copy()
+    return np.frombuffer(data, ">u2", H * W * 3, off).reshape(H, W, 3).astype(np.uint16), depth
 
 
-def write_ppm(img: np.ndarray) -> bytes:
-    """uint8 [H, W, 3] -> binary PPM bytes."""
+def read_ppm(data: bytes) -> np.ndarray:
+    """Binary PPM (P6, maxval 255) bytes -> uint8 [H, W, 3].  A deeper file is read by read_ppm_deep."""
+    img, depth = read_ppm_deep(data)
+    if depth != 8:
+        raise ValueError(f"PPM: maxval {(1 << depth) - 1}: an 8-bit image expected (read_ppm_deep reads deeper ones)")
+    return img
+
+
+def write_ppm(img: np.ndarray, depth: int = 8) -> bytes:
+    """uint8 [H, W, 3] -> binary PPM bytes; or, with depth in 9..16, uint16 [H, W, 3] samples (at most 2^depth - 1)
+    -> a PPM of maxval 2^depth - 1 with 16-bit big-endian samples."""
     img = np.ascontiguousarray(img)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError(f"PPM: uint8 [H, W, 3] expected, got {img.dtype} {img.shape}")
-    return b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes()
+    if depth == 8:
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"PPM: uint8 [H, W, 3] expected, got {img.dtype} {img.shape}")
+        return b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes()
+    if not isinstance(depth, int) or not 9 <= depth <= 16:
+        raise ValueError(f"PPM: depth must be in [8, 16], got {depth!r}")
+    if img.dtype != np.uint16 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"PPM: uint16 [H, W, 3] expected at depth {depth}, got {img.dtype} {img.shape}")
+    maxval = (1 << depth) - 1
+    if img.size and int(img.max()) > maxval:
+        raise ValueError(f"PPM: a sample above maxval {maxval}")
+    return b"P6\n%d %d\n%d\n" % (img.shape[1], img.shape[0], maxval) + img.astype(">u2").tobytes()
 
 
 def _is_ppm(path: str) -> bool:
     return os.path.splitext(path)[1].lower() in (".ppm", ".pnm")
 
 
-def load_image(path: str) -> np.ndarray:
+def load_image(path: str, deep: bool = False):
+    """-> uint8 [H, W, 3]; deep=True: (image, depth), uint16 for a PPM of more than 8 bits."""
     if _is_ppm(path):
         with open(path, "rb") as f:
-            return read_ppm(f.read())
+            return read_ppm_deep(f.read()) if deep else read_ppm(f.read())
     try:
         from PIL import Image
     except ImportError:
         raise SystemExit(f"{path}: only binary PPM is read without PIL") from None
-    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+    img = np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+    return (img, 8) if deep else img
 
 
-def save_image(path: str, img: np.ndarray):
+def save_image(path: str, img: np.ndarray, depth: int = 8):
     if _is_ppm(path):
         with open(path, "wb") as f:
-            f.write(write_ppm(img))
+            f.write(write_ppm(img, depth))
         return
+    if depth != 8:
+        raise SystemExit(f"{path}: an image of depth {depth} is written as binary PPM only")
     try:
         from PIL import Image
     except ImportError:
@@ -118,10 +158,28 @@ Y4M_TAGS = {"420jpeg": ("i420", (2, 2), "centre"), "420mpeg2": ("i420", (2, 2), 
             "422": ("i422", (2, 1), "left"), "444": ("i444", (1, 1), "left")}
 
 
-def read_y4m(data: bytes, frame: int = 0):
-    """YUV4MPEG2 bytes -> (y, cb, cr, tag, params): frame `frame` as uint8 arrays [H, W] and two chroma planes (the
-    ceil rule), the colour space tag without its 'C' ("420jpeg" when the header has none) and the header's other
-    parameters as a list of strings.  8-bit 4:2:0 / 4:2:2 / 4:4:4 only: any other tag is refused by name."""
+Y4M_DEPTHS = (9, 10, 12, 14, 16)
+_Y4M_REFUSAL = ("is not supported (8-bit C420jpeg, C420mpeg2, C420, C422, C444, and C420pN, C422pN, C444pN for N in "
+                "9, 10, 12, 14, 16)")
+
+
+def y4m_tag(tag: str):
+    """A colour space tag without its 'C' -> (raw layout, (sub_x, sub_y), siting, depth); ValueError by name for a tag
+    that is not supported.  C420pN is left-sited, as plain C420 is."""
+    if tag in Y4M_TAGS:
+        return Y4M_TAGS[tag] + (8,)
+    base, p, n = tag.partition("p")
+    if p and base in ("420", "422", "444") and n.isdigit() and int(n) in Y4M_DEPTHS and n == str(int(n)):
+        return Y4M_TAGS[base] + (int(n),)
+    raise ValueError(f"Y4M: colour space C{tag} {_Y4M_REFUSAL}")
+
+
+def read_y4m(data: bytes, frame: int = 0, max_depth: int = 8):
+    """YUV4MPEG2 bytes -> (y, cb, cr, tag, params): frame `frame` as arrays [H, W] and two chroma planes (the ceil
+    rule), the colour space tag without its 'C' ("420jpeg" when the header has none) and the header's other
+    parameters as a list of strings.  4:2:0 / 4:2:2 / 4:4:4 only: any other tag is refused by name.  A tag of more
+    than max_depth bits is refused too (8 by default: the planes are then uint8); with max_depth=16 a C420p10 file
+    gives uint16 planes (the file's samples are little-endian and LSB-aligned)."""
     end = data.find(b"\n")
     if not data.startswith(b"YUV4MPEG2 ") or end < 0:
         raise ValueError("Y4M: not a YUV4MPEG2 file")
@@ -138,15 +196,16 @@ def read_y4m(data: bytes, frame: int = 0):
             tag = tok[1:]
         else:
             params.append(tok)
-    if tag not in Y4M_TAGS:
-        raise ValueError(f"Y4M: colour space C{tag} is not supported (8-bit C420jpeg, C420mpeg2, C420, C422, C444)")
+    _, (sx, sy), _, depth = y4m_tag(tag)
+    if depth > max_depth:
+        raise ValueError(f"Y4M: colour space C{tag} is {depth} bits deep, above max_depth {max_depth}")
     if W is None or H is None or W < 1 or H < 1:
         raise ValueError("Y4M: the header needs positive W and H")
     if frame < 0:
         raise ValueError(f"Y4M: frame {frame}")
-    sx, sy = Y4M_TAGS[tag][1]
     ch, cw = (H + sy - 1) // sy, (W + sx - 1) // sx
-    n = H * W + 2 * ch * cw
+    ns = H * W + 2 * ch * cw              # samples
+    n = ns * (1 if depth == 8 else 2)     # bytes
     pos = end + 1
     for k in range(frame + 1):
         e = data.find(b"\n", pos)
@@ -157,22 +216,27 @@ def read_y4m(data: bytes, frame: int = 0):
             raise ValueError(f"Y4M: frame {k} is truncated ({len(data) - pos} of {n} bytes)")
         if k < frame:
             pos += n
-    a = np.frombuffer(data, np.uint8, n, pos).copy()
+    a = np.frombuffer(data, np.uint8, n, pos).copy() if depth == 8 else \
+        np.frombuffer(data, "<u2", ns, pos).astype(np.uint16)
     return (a[:H * W].reshape(H, W), a[H * W:H * W + ch * cw].reshape(ch, cw), a[H * W + ch * cw:].reshape(ch, cw), tag,
             params)
 
 
 def write_y4m(y: np.ndarray, cb: np.ndarray, cr: np.ndarray, tag: str, params=("F25:1", "Ip", "A1:1")) -> bytes:
-    """One frame -> YUV4MPEG2 bytes with the colour space tag `tag`."""
-    if tag not in Y4M_TAGS:
-        raise ValueError(f"Y4M: colour space C{tag} is not supported (8-bit C420jpeg, C420mpeg2, C420, C422, C444)")
+    """One frame -> YUV4MPEG2 bytes with the colour space tag `tag`: uint8 planes for an 8-bit tag, uint16 planes
+    (LSB-aligned samples, written little-endian) for C420pN / C422pN / C444pN."""
+    _, (sx, sy), _, depth = y4m_tag(tag)
     H, W = y.shape
-    sx, sy = Y4M_TAGS[tag][1]
     want = ((H + sy - 1) // sy, (W + sx - 1) // sx)
-    if any(p.dtype != np.uint8 for p in (y, cb, cr)) or cb.shape != want or cr.shape != want:
-        raise ValueError(f"Y4M: uint8 planes {(H, W)} and two of {want} expected for C{tag}")
+    dt = np.uint8 if depth == 8 else np.uint16
+    if any(p.dtype != dt for p in (y, cb, cr)) or cb.shape != want or cr.shape != want:
+        raise ValueError(f"Y4M: {np.dtype(dt).name} planes {(H, W)} and two of {want} expected for C{tag} (its depth is "
+                         f"{depth})")
+    if depth > 8 and any(p.size and int(p.max()) >= 1 << depth for p in (y, cb, cr)):
+        raise ValueError(f"Y4M: a sample above {(1 << depth) - 1} in a C{tag} frame")
     head = " ".join(["YUV4MPEG2", f"W{W}", f"H{H}"] + list(params) + [f"C{tag}"])
-    return head.encode("ascii") + b"\nFRAME\n" + b"".join(np.ascontiguousarray(p).tobytes() for p in (y, cb, cr))
+    return head.encode("ascii") + b"\nFRAME\n" + b"".join(
+        np.ascontiguousarray(p).astype(p.dtype if depth == 8 else "<u2").tobytes() for p in (y, cb, cr))
 
 
 def _ext(path: str) -> str:
@@ -193,10 +257,16 @@ def _size(v: str):
     return w, h
 
 
-def _yuv_format(args, sub, site):
+def _yuv_format(args, sub, site, depth=None):
+    """depth: that of a y4m tag; None: --depth (a raw file's, with --msb)."""
     from mlic_amd import codec
-    return codec.YuvFormat(sub=sub, matrix="bt" + args.matrix, full_range=args.range == "full",
-                           site_x=args.chroma_site or site)
+    msb = bool(args.msb) if depth is None else False
+    depth = (args.depth or 8) if depth is None else depth
+    try:
+        return codec.YuvFormat(sub=sub, matrix="bt" + args.matrix, full_range=args.range == "full",
+                               site_x=args.chroma_site or site, depth=depth, msb=msb)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
 
 
 def load_yuv(path: str, args, size=None):
@@ -207,21 +277,27 @@ def load_yuv(path: str, args, size=None):
         data = f.read()
     if _ext(path) == ".y4m":
         try:
-            y, cb, cr, tag, _ = read_y4m(data, args.frame)
+            y, cb, cr, tag, _ = read_y4m(data, args.frame, max_depth=16)
         except ValueError as e:
             raise SystemExit(f"{path}: {e}") from None
-        _, sub, site = Y4M_TAGS[tag]
-        return (y, cb, cr), _yuv_format(args, sub, site)
+        _, sub, site, depth = y4m_tag(tag)
+        if args.depth is not None and args.depth != depth:
+            raise SystemExit(f"{path}: the file is C{tag}, {depth} bits deep, --depth says {args.depth}")
+        return (y, cb, cr), _yuv_format(args, sub, site, depth)
     size = args.size or size
     if size is None:
         raise SystemExit(f"{path}: a raw .yuv file needs --size WxH")
     W, H = size
-    n = codec.yuv_frame_bytes(H, W, args.yuv)
+    depth = args.depth or 8
+    n = codec.yuv_frame_bytes(H, W, args.yuv, depth)
     if len(data) < (args.frame + 1) * n:
-        raise SystemExit(f"{path}: frame {args.frame} of {W}x{H} {args.yuv} needs {(args.frame + 1) * n} bytes, the file "
-                         f"has {len(data)}")
-    buf = np.frombuffer(data, np.uint8, n, args.frame * n).copy()
-    return codec.split_yuv(buf, H, W, args.yuv), _yuv_format(args, codec._YUV_SUB[args.yuv], "left")
+        raise SystemExit(f"{path}: frame {args.frame} of {W}x{H} {args.yuv} at depth {depth} needs "
+                         f"{(args.frame + 1) * n} bytes, the file has {len(data)}")
+    if depth == 8:
+        buf = np.frombuffer(data, np.uint8, n, args.frame * n).copy()
+    else:  # little-endian words, as a decoder's P010 surface or an I010 file on disk
+        buf = np.frombuffer(data, "<u2", n // 2, args.frame * n).astype(np.uint16)
+    return codec.split_yuv(buf, H, W, args.yuv, depth), _yuv_format(args, codec._YUV_SUB[args.yuv], "left")
 
 
 def save_yuv(path: str, planes, fmt, args):
@@ -230,13 +306,19 @@ def save_yuv(path: str, planes, fmt, args):
     y, cb, cr = planes
     H, W = y.shape
     if _ext(path) == ".y4m":
-        tag = {(2, 2): "420jpeg" if fmt.site_x == "centre" else "420mpeg2", (2, 1): "422", (1, 1): "444"}[fmt.sub]
+        if fmt.depth == 8:
+            tag = {(2, 2): "420jpeg" if fmt.site_x == "centre" else "420mpeg2", (2, 1): "422", (1, 1): "444"}[fmt.sub]
+        else:
+            if fmt.msb or fmt.depth not in Y4M_DEPTHS or (fmt.sub == (2, 2) and fmt.site_x != "left"):
+                raise SystemExit(f"{path}: a .y4m file holds LSB-aligned samples of {Y4M_DEPTHS} bits, 4:2:0 left-sited; "
+                                 f"got {fmt!r}")
+            tag = {(2, 2): "420", (2, 1): "422", (1, 1): "444"}[fmt.sub] + f"p{fmt.depth}"
         data = write_y4m(y, cb, cr, tag)
     else:
-        buf = np.zeros(codec.yuv_frame_bytes(H, W, args.yuv), np.uint8)
-        for dst, src in zip(codec.split_yuv(buf, H, W, args.yuv), planes):
+        buf = np.zeros(codec.yuv_frame_samples(H, W, args.yuv), np.uint8 if fmt.depth == 8 else np.uint16)
+        for dst, src in zip(codec.split_yuv(buf, H, W, args.yuv, fmt.depth), planes):
             dst[...] = src
-        data = buf.tobytes()
+        data = buf.tobytes() if fmt.depth == 8 else buf.astype("<u2").tobytes()
     with open(path, "wb") as f:
         f.write(data)
 
@@ -301,7 +383,9 @@ def parse_args(argv=None):
     ap.add_argument("--region", type=int, nargs=4, default=None, metavar=("Y0", "X0", "H", "W"))
     ap.add_argument("--yuv", choices=["i420", "nv12", "nv21", "yv12", "i422", "i444"], default=None)
     ap.add_argument("--size", type=_size, default=None, metavar="WxH")
-    ap.add_argument("--matrix", choices=["601", "709"], default="709")
+    ap.add_argument("--matrix", choices=["601", "709", "2020"], default="709")
+    ap.add_argument("--depth", type=int, default=None, metavar="D")
+    ap.add_argument("--msb", action="store_true")
     ap.add_argument("--range", choices=["full", "limited"], default="limited")
     ap.add_argument("--chroma-site", choices=["left", "centre"], default=None)
     ap.add_argument("--frame", type=int, default=0, metavar="N")
@@ -315,8 +399,19 @@ def parse_args(argv=None):
             ap.error("--frame must not be negative")
         if args.yuv is None:
             args.yuv = "i420"
-    elif args.yuv is not None or args.size is not None or args.chroma_site is not None or args.frame != 0:
-        ap.error("--yuv, --size, --chroma-site and --frame go with a .y4m or .yuv frame file")
+    elif args.yuv is not None or args.size is not None or args.chroma_site is not None or args.frame != 0 or args.msb:
+        ap.error("--yuv, --size, --chroma-site, --frame and --msb go with a .y4m or .yuv frame file")
+    if args.depth is not None and not 8 <= args.depth <= 16:
+        ap.error("--depth: 8 to 16 expected")
+    if args.msb and (args.depth is None or args.depth == 8):
+        ap.error("--msb goes with --depth above 8 (a raw .yuv file of MSB-aligned 16-bit words, P010 style)")
+    if args.depth is not None and not frame_file and args.mode != "decode":
+        ap.error("--depth goes with a raw .yuv frame file, or with decode (an image file knows its own depth)")
+    if args.matrix == "2020" and frame_file and args.mode == "encode" and _ext(args.src) == ".yuv" and \
+            (args.depth or 8) == 8:
+        ap.error("--matrix 2020 needs --depth above 8")
+    if (args.depth or 8) > 8 and (args.tile is not None or args.region is not None):
+        ap.error("tiled coding at a depth above 8 is not supported (the blend kernel writes bytes)")
     if args.ref is not None and not (frame_file and args.mode == "decode"):
         ap.error("--ref goes with decode to a .y4m or .yuv file")
     args.frame_file = frame_file
@@ -412,6 +507,8 @@ def main(argv=None):
             raise SystemExit(f"{args.src}: a tiled file decodes to an RGB image, not to Y'CbCr planes")
         net = load_model(args)
         fmt = _yuv_format(args, codec._YUV_SUB[args.yuv], "left")
+        if _ext(args.dst) == ".y4m" and args.msb:
+            raise SystemExit(f"{args.dst}: a .y4m file holds LSB-aligned samples (--msb goes with a raw .yuv file)")
         ref = None
         if args.ref is not None:
             d = codec.peek(data, vbr=hasattr(net, "levels"))
@@ -427,11 +524,15 @@ def main(argv=None):
         print(line)
         return
     if args.mode == "encode":
-        img = load_image(args.src)
+        img, depth = load_image(args.src, deep=True)
+        deep = {} if depth == 8 else {"depth": depth}  # a PPM's samples are LSB-aligned
         net = load_model(args)
         if args.tile is not None:
-            data, info = codec.encode_tiled(net, img, tile=args.tile, overlap=args.overlap, level=args.level,
-                                            layout="hwc", tile_batch=args.tile_batch, return_info=True)
+            try:
+                data, info = codec.encode_tiled(net, img, tile=args.tile, overlap=args.overlap, level=args.level,
+                                                layout="hwc", tile_batch=args.tile_batch, return_info=True, **deep)
+            except ValueError as e:
+                raise SystemExit(f"{args.src}: {e}") from None
             with open(args.dst, "wb") as f:
                 f.write(data)
             print(f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {len(data)} bytes, {info['bpp']:.4f} bpp, tile "
@@ -445,12 +546,14 @@ def main(argv=None):
                                  f"{img.shape[0]} x {img.shape[1]}")
         files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
                                           max_passes=args.max_passes, return_info=True, roi=roi,
-                                          roi_levels=None if roi is None else tuple(args.roi_levels))
+                                          roi_levels=None if roi is None else tuple(args.roi_levels), **deep)
         data = files[0]
         with open(args.dst, "wb") as f:
             f.write(data)
         line = (f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {len(data)} bytes, "
                 f"{8.0 * len(data) / (img.shape[0] * img.shape[1]):.4f} bpp")
+        if depth != 8:
+            line += f", depth {depth}"
         if args.max_bpp is not None:
             line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
                      f"{'met' if info[0]['met'] else 'not met'}")
@@ -471,8 +574,9 @@ def main(argv=None):
             return
         if args.region is not None:
             raise SystemExit(f"{args.src}: --region needs a tiled file (encode --tile T)")
-        img, info = codec.decode_images(net, [data])
-        save_image(args.dst, img[0].cpu().numpy())
+        depth = args.depth or 8
+        img, info = codec.decode_images(net, [data], **({} if depth == 8 else {"depth": depth}))
+        save_image(args.dst, img[0].cpu().numpy(), depth)
         print(f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp")
 
 
