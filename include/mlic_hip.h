@@ -273,6 +273,82 @@ int mlic_ln_channels_run(void* stream, const float* x, const float* gamma, const
  * -> out [B][3][2H][2W] = PixelShuffle(2)(bias + the nine shifted partials summed in tap order); bias [12] or
  * NULL; synchronous on `stream` */
 int mlic_taps_gather_run(void* stream, const float* part, const float* bias, float* out, int B, int H, int W);
+
+/* ---- the entropy front's kernels alone (no model handle).  Every argument is checked before any GPU call;
+ * each entry is synchronous on `stream`. ----
+ *
+ * The slice loop's quantisation of one checkerboard phase of one latent slice, all device pointers.  Anchor
+ * pixels are those with (h + w) odd; phase 0 codes the anchors, phase 1 the others.  Element strides between
+ * images (`*_bs`) are the caller's: the model passes slices of wider tensors.  The squeezed streams (sym, idx,
+ * sym16, idx8) are contiguous [B][C][H][W/2], an element of the phase at ((c * H + h) * (W / 2) + (w >> 1)).
+ *   params    [2C][H][W] per image: scales at [0, C), means at [C, 2C), the phase's entropy parameters
+ *   params_a  the anchor phase's, read for `lik` only: the likelihood takes (s, m) from params_a at anchor
+ *             pixels and from params elsewhere
+ *   vbr 0     q = rint(y - m), yh = q + m, index from s
+ *   vbr 1     q = rint((y - m) * g), yh = q * r + m, index from s * g, likelihood at (y, s, m) * g; the gain g
+ *             and its reciprocal r per image (sc, rs: [B]) or per latent pixel (scp, rsp: [B][H][W], which
+ *             take precedence)
+ *   index     (ntable - 1) - #{t in table[:-1] : max(s', 0.11) <= t}
+ *   sym16     q saturated to [-nlim - 1, nlim]; *ovf is set to 1 if some symbol did not fit and is not
+ *             written otherwise
+ * mlic_quant_phase_run writes yh (phase 0: +0 at the other parity; phase 1: the anchor pixels are left as
+ * they are), lik at every pixel when given, and whichever of sym, idx, sym16 + idx8 + ovf are given.  It
+ * refuses: a null y, params, yh or table; W odd; phase outside {0, 1}; lik without params_a; sym16 without
+ * idx8 and ovf (or those without sym16); idx without sym or sym16; one gain plane without the other; planes
+ * without vbr; vbr with neither sc and rs nor planes; nlim outside 1..32767; ntable outside 2..256; B outside
+ * 1..65535, H or W < 1, H * W or C * H * W above 2^30; a batch stride smaller than the tensor it strides.
+ * mlic_phase_indexes_run (decoder) reads params, table, phase, vbr, sc or scp and the geometry and writes idx8
+ * when given, else idx.  mlic_phase_dequant_run (decoder) reads sym16 when given, else sym, and params, phase,
+ * vbr, rs or rsp, and writes yh as mlic_quant_phase_run does. */
+typedef struct mlic_quant_desc {
+  const float* y;
+  int64_t y_bs;
+  const float* params;
+  int64_t params_bs;
+  const float* params_a;
+  int64_t params_a_bs;
+  float* yh;
+  int64_t yh_bs;
+  float* lik;
+  int64_t lik_bs;
+  int32_t* sym;
+  int32_t* idx;
+  int16_t* sym16;
+  uint8_t* idx8;
+  int32_t* ovf;
+  int32_t nlim;
+  int32_t ntable;
+  const float* table;
+  int32_t phase;
+  int32_t vbr;
+  const float* sc;
+  const float* rs;
+  const float* scp;
+  const float* rsp;
+  int32_t B, C, H, W;
+} mlic_quant_desc;
+int mlic_quant_phase_run(void* stream, const mlic_quant_desc* d);
+int mlic_phase_indexes_run(void* stream, const mlic_quant_desc* d);
+int mlic_phase_dequant_run(void* stream, const mlic_quant_desc* d);
+/* r[i] = 1 / g[i], the correctly rounded fp32 quotient, i < n (the reciprocal of a gain plane); 1 <= n <= 2^31 */
+int mlic_recip_plane_run(void* stream, const float* g, float* r, int64_t n);
+/* EntropyBottleneck (eval) on z [B][C][H][W]: r = rint(z - med[c]), z_hat = r + med[c], sym = (int32) r, lik =
+ * max(sigmoid(logits(z_hat + 0.5)) - sigmoid(logits(z_hat - 0.5)), 1e-9) with the factorised cumulative's
+ * parameters quantiles [C][1][3] (med = [:, 0, 1]), _matrix0..4 (m0 [C][3][1], m1..m3 [C][3][3], m4 [C][1][3]),
+ * _bias0..4 (b0..b3 [C][3][1], b4 [C][1][1]), _factor0..3 ([C][3][1]).  z_hat, lik and sym are each optional,
+ * at least one must be given; B * C * H * W <= 2^31 */
+int mlic_eb_forward_run(void* stream, const float* z, float* z_hat, float* lik, int32_t* sym, const float* quantiles,
+                        const float* m0, const float* m1, const float* m2, const float* m3, const float* m4,
+                        const float* b0, const float* b1, const float* b2, const float* b3, const float* b4,
+                        const float* f0, const float* f1, const float* f2, const float* f3, int B, int C, int H,
+                        int W);
+/* the decoder's z_hat = (float) sym + med[c] on [B][C][H][W] */
+int mlic_eb_dequant_run(void* stream, const int32_t* sym, const float* quantiles, float* z_hat, int B, int C, int H,
+                        int W);
+/* y = x at the anchor pixels ((h + w) odd) when keep_anchor is 1, at the others when 0, and +0 elsewhere; x, y
+ * [C][H][W] per image with element strides x_bs, y_bs between images (each >= C * H * W) */
+int mlic_ckbd_mask_run(void* stream, const float* x, int64_t x_bs, float* y, int64_t y_bs, int B, int C, int H, int W,
+                       int keep_anchor);
 int mlic_image_sq_err_u8(void* stream, const float* a, const float* b, int B, int64_t n_per, double* out);
 /* bytes of device scratch mlic_image_ms_ssim_u8 needs (pooled planes + partial sums); host logic only,
  * no GPU touched; nonzero rc with a message when C < 1, B < 1 or min(H, W) <= 160 */

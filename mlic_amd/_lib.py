@@ -45,6 +45,17 @@ class YuvDesc(C.Structure):
                 ("site_x", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class QuantDesc(C.Structure):
+    """mlic_quant_desc (include/mlic_hip.h)."""
+    _fields_ = [("y", C.c_void_p), ("y_bs", C.c_int64), ("params", C.c_void_p), ("params_bs", C.c_int64),
+                ("params_a", C.c_void_p), ("params_a_bs", C.c_int64), ("yh", C.c_void_p), ("yh_bs", C.c_int64),
+                ("lik", C.c_void_p), ("lik_bs", C.c_int64), ("sym", C.c_void_p), ("idx", C.c_void_p),
+                ("sym16", C.c_void_p), ("idx8", C.c_void_p), ("ovf", C.c_void_p), ("nlim", C.c_int32),
+                ("ntable", C.c_int32), ("table", C.c_void_p), ("phase", C.c_int32), ("vbr", C.c_int32),
+                ("sc", C.c_void_p), ("rs", C.c_void_p), ("scp", C.c_void_p), ("rsp", C.c_void_p),
+                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 def _sig(lib):
     p, i, i64, f, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
     P = C.POINTER
@@ -96,6 +107,13 @@ def _sig(lib):
         "mlic_linatt_pack_run": [p, p, p, p, i, i, i, i, i, i, i],
         "mlic_ln_channels_run": [p, p, p, p, p, i, i, i],
         "mlic_taps_gather_run": [p, p, p, p, i, i, i],
+        "mlic_quant_phase_run": [p, P(QuantDesc)],
+        "mlic_phase_indexes_run": [p, P(QuantDesc)],
+        "mlic_phase_dequant_run": [p, P(QuantDesc)],
+        "mlic_recip_plane_run": [p, p, p, i64],
+        "mlic_eb_forward_run": [p] * 20 + [i, i, i, i],
+        "mlic_eb_dequant_run": [p, p, p, p, i, i, i, i],
+        "mlic_ckbd_mask_run": [p, p, i64, p, i64, i, i, i, i, i],
         "mlic_image_sq_err_u8": [p, p, p, i, i64, p],
         "mlic_ms_ssim_scratch_bytes": [i, i, i, i, P(sz)],
         "mlic_image_ms_ssim_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, sz, p, p],

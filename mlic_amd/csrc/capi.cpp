@@ -752,6 +752,143 @@ int mlic_taps_gather_run(void* stream, const float* part, const float* bias, flo
   });
 }
 
+// ---- the entropy front alone: quantisation, scale indexes, dequantisation, the bottleneck, the masks ----
+// the geometry the three slice-loop kernels share: one image's C * H * W elements as they index them, the
+// squeezed streams' W / 2, and every batch stride at least the tensor it strides
+static QuantParams quant_params(const mlic_quant_desc* d) {
+  MLIC_CHECK(d != nullptr, "null descriptor");
+  MLIC_CHECK(d->params && d->table, "null tensor");
+  check_grid(d->B, d->H, d->W, 1);
+  MLIC_CHECK(d->C >= 1 && (int64_t)d->C * d->H * d->W <= (int64_t)1 << 30, "C must be >= 1 and C * H * W <= 2^30");
+  MLIC_CHECK(d->W % 2 == 0, "W must be even");
+  MLIC_CHECK(d->phase == 0 || d->phase == 1, "phase must be 0 (anchor) or 1 (non-anchor)");
+  MLIC_CHECK(d->ntable >= 2 && d->ntable <= 256, "ntable must be in 2..256");
+  MLIC_CHECK(d->vbr == 0 || d->vbr == 1, "vbr must be 0 or 1");
+  MLIC_CHECK(d->vbr || (!d->scp && !d->rsp), "gain planes need vbr");
+  const int64_t n = (int64_t)d->C * d->H * d->W;
+  MLIC_CHECK(d->params_bs >= 2 * n, "params_bs smaller than [2C][H][W]");
+  QuantParams Q{};
+  Q.y = d->y; Q.y_bs = d->y_bs;
+  Q.params = d->params; Q.params_bs = d->params_bs;
+  Q.params_a = d->params_a; Q.params_a_bs = d->params_a_bs;
+  Q.yh = d->yh; Q.yh_bs = d->yh_bs;
+  Q.lik = d->lik; Q.lik_bs = d->lik_bs;
+  Q.sym = d->sym; Q.idx = d->idx;
+  Q.sym16 = d->sym16; Q.idx8 = d->idx8; Q.ovf = d->ovf;
+  Q.nlim = d->nlim;
+  Q.table = d->table; Q.ntable = d->ntable;
+  Q.phase = d->phase; Q.vbr = d->vbr;
+  Q.sc = d->sc; Q.rs = d->rs;
+  Q.C = d->C; Q.H = d->H; Q.W = d->W; Q.B = d->B;
+  Q.scp = d->scp; Q.rsp = d->rsp;
+  return Q;
+}
+
+int mlic_quant_phase_run(void* stream, const mlic_quant_desc* d) {
+  return guard([&] {
+    const QuantParams Q = quant_params(d);
+    const int64_t n = (int64_t)Q.C * Q.H * Q.W;
+    MLIC_CHECK(Q.y && Q.yh, "null tensor");
+    MLIC_CHECK(Q.y_bs >= n, "y_bs smaller than [C][H][W]");
+    MLIC_CHECK(Q.yh_bs >= n, "yh_bs smaller than [C][H][W]");
+    MLIC_CHECK(!Q.lik || Q.params_a, "lik needs params_a");
+    MLIC_CHECK(!Q.lik || Q.lik_bs >= n, "lik_bs smaller than [C][H][W]");
+    MLIC_CHECK(!Q.params_a || Q.params_a_bs >= 2 * n, "params_a_bs smaller than [2C][H][W]");
+    MLIC_CHECK(!Q.sym16 || (Q.idx8 && Q.ovf), "sym16 needs idx8 and ovf");
+    MLIC_CHECK(Q.sym16 || (!Q.idx8 && !Q.ovf), "idx8 and ovf need sym16");
+    MLIC_CHECK(!Q.idx || Q.sym || Q.sym16, "idx needs sym or sym16");
+    MLIC_CHECK((Q.scp != nullptr) == (Q.rsp != nullptr), "scp and rsp: both or neither");
+    MLIC_CHECK(!Q.vbr || Q.scp || (Q.sc && Q.rs), "vbr needs sc and rs, or gain planes");
+    MLIC_CHECK(Q.nlim >= 1 && Q.nlim <= 32767, "nlim must be in 1..32767");
+    quant_phase(Q, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_phase_indexes_run(void* stream, const mlic_quant_desc* d) {
+  return guard([&] {
+    const QuantParams Q = quant_params(d);
+    MLIC_CHECK(Q.idx8 || Q.idx, "null output: idx8 or idx");
+    MLIC_CHECK(!Q.vbr || Q.scp || Q.sc, "vbr needs sc, or the gain plane scp");
+    phase_indexes(Q, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_phase_dequant_run(void* stream, const mlic_quant_desc* d) {
+  return guard([&] {
+    const QuantParams Q = quant_params(d);
+    const int64_t n = (int64_t)Q.C * Q.H * Q.W;
+    MLIC_CHECK(Q.yh, "null tensor");
+    MLIC_CHECK(Q.yh_bs >= n, "yh_bs smaller than [C][H][W]");
+    MLIC_CHECK(Q.sym16 || Q.sym, "null input: sym16 or sym");
+    MLIC_CHECK(!Q.vbr || Q.rsp || Q.rs, "vbr needs rs, or the reciprocal plane rsp");
+    phase_dequant(Q, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_recip_plane_run(void* stream, const float* g, float* r, int64_t n) {
+  return guard([&] {
+    MLIC_CHECK(g && r, "null tensor");
+    MLIC_CHECK(n >= 1 && n <= (int64_t)1 << 31, "n must be in 1..2^31");
+    recip_plane(g, r, n, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+// B * C * H * W elements in one 1-D launch
+static void check_eb_grid(int B, int C, int H, int W) {
+  check_grid(B, H, W, 1);
+  MLIC_CHECK(C >= 1 && (int64_t)B * C * H * W <= (int64_t)1 << 31, "C must be >= 1 and B * C * H * W <= 2^31");
+}
+
+int mlic_eb_forward_run(void* stream, const float* z, float* z_hat, float* lik, int32_t* sym, const float* quantiles,
+                        const float* m0, const float* m1, const float* m2, const float* m3, const float* m4,
+                        const float* b0, const float* b1, const float* b2, const float* b3, const float* b4,
+                        const float* f0, const float* f1, const float* f2, const float* f3, int B, int C, int H,
+                        int W) {
+  return guard([&] {
+    MLIC_CHECK(z && quantiles, "null tensor");
+    MLIC_CHECK(m0 && m1 && m2 && m3 && m4 && b0 && b1 && b2 && b3 && b4 && f0 && f1 && f2 && f3, "null parameter");
+    MLIC_CHECK(z_hat || lik || sym, "null outputs: at least one of z_hat, lik, sym");
+    check_eb_grid(B, C, H, W);
+    EbParams P{};
+    P.z = z; P.z_hat = z_hat; P.lik = lik; P.sym = sym;
+    P.quantiles = quantiles;
+    P.m0 = m0; P.m1 = m1; P.m2 = m2; P.m3 = m3; P.m4 = m4;
+    P.b0 = b0; P.b1 = b1; P.b2 = b2; P.b3 = b3; P.b4 = b4;
+    P.f0 = f0; P.f1 = f1; P.f2 = f2; P.f3 = f3;
+    P.C = C; P.H = H; P.W = W; P.B = B;
+    eb_forward(P, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_eb_dequant_run(void* stream, const int32_t* sym, const float* quantiles, float* z_hat, int B, int C, int H,
+                        int W) {
+  return guard([&] {
+    MLIC_CHECK(sym && quantiles && z_hat, "null tensor");
+    check_eb_grid(B, C, H, W);
+    eb_dequant(sym, quantiles, z_hat, C, H * W, B, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+int mlic_ckbd_mask_run(void* stream, const float* x, int64_t x_bs, float* y, int64_t y_bs, int B, int C, int H, int W,
+                       int keep_anchor) {
+  return guard([&] {
+    MLIC_CHECK(x && y, "null tensor");
+    check_grid(B, H, W, 1);
+    MLIC_CHECK(C >= 1 && (int64_t)C * H * W <= (int64_t)1 << 30, "C must be >= 1 and C * H * W <= 2^30");
+    MLIC_CHECK(keep_anchor == 0 || keep_anchor == 1, "keep_anchor must be 0 or 1");
+    MLIC_CHECK(x_bs >= (int64_t)C * H * W, "x_bs smaller than [C][H][W]");
+    MLIC_CHECK(y_bs >= (int64_t)C * H * W, "y_bs smaller than [C][H][W]");
+    ckbd_mask(x, x_bs, y, y_bs, C, H, W, B, keep_anchor, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
 int mlic_local_attn_mask(void* stream, float* out, int H, int W) {
   return guard([&] { local_mask(out, H, W, (hipStream_t)stream); });
 }

@@ -805,9 +805,11 @@ __global__ void quant_phase_kernel(QuantParams P) {
   }
   const float s = pp[(int64_t)c * HW + p];
   const float m = pp[(int64_t)(c + P.C) * HW + p];
+  // + 0.0f: a tie that rounds to -0 (y - m = -0.5) becomes +0, the value the decoder rebuilds from the
+  // symbol 0 -- otherwise y_hat = -0 + m keeps the sign at m = -0 and the two sides differ in that bit
   float q;
-  if (P.vbr) q = rintf((y - m) * sc);
-  else q = rintf(y - m);
+  if (P.vbr) q = rintf((y - m) * sc) + 0.0f;
+  else q = rintf(y - m) + 0.0f;
   *yh = P.vbr ? q * rs + m : q + m;
   if (P.sym || P.sym16) {
     const int64_t sq = (int64_t)b * P.C * HW / 2 + ((int64_t)c * P.H + h) * (P.W / 2) + (w >> 1);
@@ -955,7 +957,7 @@ __global__ void eb_forward_kernel(EbParams P) {
   const int c = (int)((i / HW) % P.C);
   const float med = P.quantiles[c * 3 + 1];
   const float z = P.z[i];
-  const float r = rintf(z - med);
+  const float r = rintf(z - med) + 0.0f;  // -0 -> +0: eb_dequant's (float)sym (see quant_phase)
   const float zh = r + med;
   if (P.z_hat) P.z_hat[i] = zh;
   if (P.sym) P.sym[i] = (int32_t)r;

@@ -76,9 +76,10 @@ def test_linatt_split_policy_never_leaves_a_split_empty():
 
 
 def test_kernel_entries_refuse_bad_arguments_before_any_gpu_call():
-    """The kernel-level entries of the linear attention, LayerNorm and tap gather check every argument
-    before they touch the GPU: each refusal below comes back as an error on a machine without one (the
-    pointers are never dereferenced)."""
+    """The kernel-level entries of the linear attention, LayerNorm, tap gather and the entropy front
+    (quantisation, scale indexes, dequantisation, reciprocal plane, bottleneck, checkerboard mask) check
+    every argument before they touch the GPU: each refusal below comes back as an error on a machine
+    without one (the pointers are never dereferenced)."""
     x = C.c_void_p(64)  # non-null, never read
     la = lambda **kw: _lib.call("mlic_linear_attention_run", None, kw.get("k", x), x, x, kw.get("out", x), None,  # noqa: E731
                                 kw.get("B", 1), kw.get("heads", 2), kw.get("hd", 32), kw.get("H", 8), kw.get("W", 8),
@@ -106,6 +107,71 @@ def test_kernel_entries_refuse_bad_arguments_before_any_gpu_call():
                       ((x, x, x, 1, 0, 4), "H, W must be"), ((x, x, x, 70000, 4, 4), "B must be")):
         with pytest.raises(_lib.MlicError, match=msg):
             _lib.call("mlic_taps_gather_run", None, *args)
+    # the entropy front's entries.  A complete, valid descriptor (phase 1 with a likelihood, the narrow streams,
+    # per-image gains) with one field changed per case
+    n = 3 * 4 * 6
+    base = dict(y=64, y_bs=n, params=64, params_bs=2 * n, params_a=64, params_a_bs=2 * n, yh=64, yh_bs=n, lik=64,
+                lik_bs=n, sym=64, idx=64, sym16=64, idx8=64, ovf=64, nlim=32767, ntable=64, table=64, phase=1, vbr=1,
+                sc=64, rs=64, scp=None, rsp=None, B=2, C=3, H=4, W=6)
+    planes = dict(sc=None, rs=None, scp=64, rsp=64)
+    quant = [({"y": None}, "null tensor"), ({"params": None}, "null tensor"), ({"yh": None}, "null tensor"),
+             ({"table": None}, "null tensor"), ({"W": 5}, "W must be even"), ({"phase": 2}, "phase must be"),
+             ({"phase": -1}, "phase must be"), ({"params_a": None}, "lik needs params_a"),
+             ({"idx8": None}, "sym16 needs idx8 and ovf"), ({"ovf": None}, "sym16 needs idx8 and ovf"),
+             ({"sym16": None}, "idx8 and ovf need sym16"),
+             ({"sym": None, "sym16": None, "idx8": None, "ovf": None}, "idx needs sym"),
+             ({**planes, "rsp": None}, "both or neither"), ({**planes, "scp": None}, "both or neither"),
+             ({**planes, "vbr": 0}, "gain planes need vbr"), ({"sc": None}, "vbr needs sc and rs"),
+             ({"rs": None}, "vbr needs sc and rs"), ({"vbr": 2}, "vbr must be"), ({"nlim": 0}, "nlim must be"),
+             ({"nlim": 32768}, "nlim must be"), ({"ntable": 1}, "ntable must be"), ({"ntable": 257}, "ntable must be"),
+             ({"B": 0}, "B must be"), ({"B": 65536}, "B must be"), ({"H": 0}, "H, W must be"),
+             ({"W": 0}, "H, W must be"), ({"H": 1 << 16, "W": 1 << 16}, "H, W must be"), ({"C": 0}, "C must be"),
+             ({"C": 1 << 27}, "C must be"), ({"y_bs": n - 1}, "y_bs smaller"),
+             ({"params_bs": 2 * n - 1}, "params_bs smaller"), ({"params_a_bs": 2 * n - 1}, "params_a_bs smaller"),
+             ({"yh_bs": n - 1}, "yh_bs smaller"), ({"lik_bs": n - 1}, "lik_bs smaller")]
+    for kw, msg in quant:
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_quant_phase_run", None, C.byref(_lib.QuantDesc(**{**base, **kw})))
+    with pytest.raises(_lib.MlicError, match="null descriptor"):
+        _lib.call("mlic_quant_phase_run", None, None)
+    for kw, msg in (({"idx8": None, "idx": None}, "null output"), ({"params": None}, "null tensor"),
+                    ({"table": None}, "null tensor"), ({"W": 3}, "W must be even"), ({"phase": 3}, "phase must be"),
+                    ({"sc": None}, "vbr needs sc"), ({**planes, "vbr": 0}, "gain planes need vbr"),
+                    ({"ntable": 300}, "ntable must be"), ({"params_bs": n}, "params_bs smaller"),
+                    ({"B": -1}, "B must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_phase_indexes_run", None, C.byref(_lib.QuantDesc(**{**base, **kw})))
+    for kw, msg in (({"sym16": None, "sym": None}, "null input"), ({"yh": None}, "null tensor"),
+                    ({"params": None}, "null tensor"), ({"W": 7}, "W must be even"), ({"phase": 2}, "phase must be"),
+                    ({"rs": None}, "vbr needs rs"), ({**planes, "vbr": 0}, "gain planes need vbr"),
+                    ({"yh_bs": 1}, "yh_bs smaller"), ({"params_bs": 0}, "params_bs smaller"), ({"H": -2}, "H, W must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_phase_dequant_run", None, C.byref(_lib.QuantDesc(**{**base, **kw})))
+    for args, msg in (((None, x, 4), "null tensor"), ((x, None, 4), "null tensor"), ((x, x, 0), "n must be"),
+                      ((x, x, (1 << 31) + 1), "n must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_recip_plane_run", None, *args)
+    eb = lambda **kw: _lib.call("mlic_eb_forward_run", None, kw.get("z", x), kw.get("z_hat", x), kw.get("lik", x),  # noqa: E731
+                                kw.get("sym", x), kw.get("q", x), *[None if kw.get("hole") == j else x for j in range(14)],
+                                kw.get("B", 2), kw.get("C", 5), kw.get("H", 3), kw.get("W", 7))
+    for kw, msg in [({"z": None}, "null tensor"), ({"q": None}, "null tensor"),
+                    ({"z_hat": None, "lik": None, "sym": None}, "at least one"), ({"B": 0}, "B must be"),
+                    ({"C": 0}, "C must be"), ({"W": 0}, "H, W must be"),
+                    ({"B": 4096, "C": 4096, "H": 64, "W": 64}, "C must be")] + [({"hole": j}, "null parameter")
+                                                                                 for j in range(14)]:
+        with pytest.raises(_lib.MlicError, match=msg):
+            eb(**kw)
+    for args, msg in (((None, x, x, 1, 2, 3, 4), "null tensor"), ((x, None, x, 1, 2, 3, 4), "null tensor"),
+                      ((x, x, None, 1, 2, 3, 4), "null tensor"), ((x, x, x, 0, 2, 3, 4), "B must be"),
+                      ((x, x, x, 1, 0, 3, 4), "C must be"), ((x, x, x, 1, 2, 0, 4), "H, W must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_eb_dequant_run", None, *args)
+    for args, msg in (((None, 24, x, 24, 1, 2, 3, 4, 0), "null tensor"), ((x, 24, None, 24, 1, 2, 3, 4, 0), "null tensor"),
+                      ((x, 23, x, 24, 1, 2, 3, 4, 0), "x_bs smaller"), ((x, 24, x, 23, 1, 2, 3, 4, 1), "y_bs smaller"),
+                      ((x, 24, x, 24, 1, 2, 3, 4, 2), "keep_anchor must be"), ((x, 24, x, 24, 0, 2, 3, 4, 0), "B must be"),
+                      ((x, 24, x, 24, 1, 0, 3, 4, 0), "C must be"), ((x, 24, x, 24, 1, 2, 3, 0, 0), "H, W must be")):
+        with pytest.raises(_lib.MlicError, match=msg):
+            _lib.call("mlic_ckbd_mask_run", None, *args)
 
 
 def test_gaussian_tables_match_reference_update(golden):
