@@ -601,6 +601,71 @@ int mlic_decode_image_u8(mlic_model* m, void* stream, const uint8_t* file, size_
                          const float* vbr_gains, uint8_t* rgb_dev, const int64_t* strides, size_t cap_bytes, int* H,
                          int* W, int* level);
 
+/* ---- Scaled coding: code at reduced resolution, decode at a chosen size (DESIGN.md section 5 "Scaled coding") ----
+ *
+ * One separable, antialiased polyphase resampler (the rule of PIL's resize and of torch's
+ * interpolate(antialias=True)), fused into the ingest and egress kernels.  filter: 0 lanczos3, 1 bicubic (Keys
+ * a = -0.5), 2 triangle.  Per axis, input length Li, output length Lo, 1/8 <= Lo / Li <= 8, both <= 2^24:
+ * s = Li / Lo, fs = max(s, 1), support = radius * fs; output o has centre c = (o + 0.5) s, first tap
+ * x0 = max(0, int(c - support + 0.5)), n = min(Li, int(c + support + 0.5)) - x0 taps and weights
+ * k((j + x0 - c + 0.5) / fs) / sum, computed in double and rounded once to fp32.  Lo == Li is the identity table.
+ * No table has more than 49 taps.
+ * mlic_resample_table: *taps = the largest n.  start, count (Lo entries) and weights (Lo rows of `stride` floats,
+ * zero from column n) are filled when all three are given and stride >= *taps; all three NULL is the size query.
+ * Host only. */
+int mlic_resample_table(int filter, int Li, int Lo, int32_t* start, int32_t* count, float* weights, int stride,
+                        int* taps);
+/* mlic_image_ingest_u8 with the resampler: Hi x Wi x 3 bytes (strides {image, row, column, channel}) -> v / 255,
+ * resampled to h x w (horizontal pass first, nothing rounded in between; per pass acc = +0, acc = acc + w * v over
+ * the taps in ascending order, product and sum rounded once each), clamped to [0, 1], written as fp32
+ * [B][3][Hp][Wp] with +0 in the padding; every element of dst is written.  One launch.  The first call with a new
+ * (filter, Li, Lo) builds that table on the device (a blocking copy); it is kept for later calls. */
+int mlic_image_ingest_u8_scaled(void* stream, const uint8_t* src, const int64_t* src_strides, int B, int Hi, int Wi,
+                                int filter, int h, int w, float* dst, int Hp, int Wp);
+/* mlic_image_egress_u8 with the resampler: the h x w crop of src (strides {image, channel, row}), clamped to
+ * [0, 1] (NaN -> 0), resampled to Ho x Wo by the same arithmetic, floor(clamp(v, 0, 1) * 255), written through
+ * dst_strides; only the image's bytes are written.  ref / sq_err as in mlic_image_egress_u8, ref being Ho x Wo.
+ * With Ho x Wo == h x w the bytes are those of mlic_image_egress_u8. */
+int mlic_image_egress_u8_scaled(void* stream, const float* src, const int64_t* src_strides, int B, int h, int w,
+                                int filter, int Ho, int Wo, uint8_t* dst, const int64_t* dst_strides, const uint8_t* ref,
+                                const int64_t* ref_strides, uint64_t* sq_err);
+/* The scaled file, big-endian:
+ *     "MLS1" | u8 version 0 | u8 flags (bit 0: the inner file has a VBR level word) | u8 filter | u8 reserved 0
+ *     u32 H, W (display size) | the inner file, to the end
+ * The inner file is exactly the file mlic_container_write makes for the coded image.  write: the *len / out / cap
+ * protocol of mlic_container_write; the inner file is copied, not parsed.  parse: validating, never reads outside
+ * data[0, n).  Refused, each with its own message: a truncated header; bad magic, version, flags, filter or
+ * reserved byte; H or W zero; H * W > max_pixels; whatever mlic_container_parse refuses in the inner file (the
+ * flags say whether it has a level word; n_levels bounds it); a coded size whose ratio to the display size leaves
+ * [1/8, 8] on either axis.  info->inner's offsets are relative to the inner file, data + inner_off.
+ * mlic_container_parse keeps refusing a scaled file (the magic read as H is about 1.3e9). */
+typedef struct mlic_container_scaled_info {
+  uint32_t H, W; /* display size */
+  int32_t filter;
+  int32_t vbr; /* flags bit 0 */
+  uint64_t inner_off, inner_len;
+  mlic_container_info inner;
+} mlic_container_scaled_info;
+int mlic_container_write_scaled(uint32_t H, uint32_t W, int vbr, int filter, const uint8_t* inner, size_t inner_len,
+                                uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_scaled(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                mlic_container_scaled_info* info);
+/* mlic_encode_image_u8 at reduced (or raised) resolution: the H x W image is resampled to coded_H x coded_W on
+ * the way in, coded as mlic_encode_image_u8 codes an image of that size, and wrapped in the scaled file with H, W
+ * as the display size.  The out == NULL / rgb_dev == NULL protocol is that of mlic_encode_image_u8. */
+int mlic_encode_image_u8_scaled(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H,
+                                int W, int coded_H, int coded_W, int filter, float vbr_scale, int level, uint8_t* out,
+                                size_t cap, size_t* len);
+/* mlic_decode_image_u8 at a chosen output size, for a plain, VBR or scaled file (told apart by the magic).
+ * out_H x out_W: the size of the image written to rgb_dev; 0 x 0 = the file's display size (a plain file's own
+ * H x W).  filter: the resampler from the coded to the output size; -1 = the file's filter (lanczos3 for a plain
+ * file).  *H, *W report the output size, *coded_H, *coded_W the size the model decodes; rgb_dev == NULL only
+ * parses, checks and reports.  Everything else as mlic_decode_image_u8. */
+int mlic_decode_image_u8_sized(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels,
+                               uint64_t max_pixels, const float* vbr_gains, int out_H, int out_W, int filter,
+                               uint8_t* rgb_dev, const int64_t* strides, size_t cap_bytes, int* H, int* W, int* level,
+                               int* coded_H, int* coded_W);
+
 /* ---- 8-bit Y'CbCr frames in and out (DESIGN.md section 5 "YCbCr I/O") ----
  *
  * A frame is three byte planes on the device, each a pointer plus element strides {image, row, column}: Y is

@@ -39,6 +39,12 @@ class ContainerTiledInfo(C.Structure):
                 ("payload_off", C.c_uint64), ("payload_len", C.c_uint64)]
 
 
+class ContainerScaledInfo(C.Structure):
+    """mlic_container_scaled_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("filter", C.c_int32), ("vbr", C.c_int32),
+                ("inner_off", C.c_uint64), ("inner_len", C.c_uint64), ("inner", ContainerInfo)]
+
+
 class YuvDesc(C.Structure):
     """mlic_yuv_desc (include/mlic_hip.h)."""
     _fields_ = [("sub_x", C.c_int32), ("sub_y", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
@@ -153,6 +159,14 @@ def _sig(lib):
         "mlic_encode_image_u8": [p, p, p, P(i64), i, i, f, i, p, sz, P(sz)],
         "mlic_encode_image_u8_budget": [p, p, p, P(i64), i, i, f, i, C.c_double, i, p, sz, P(sz), P(i)],
         "mlic_decode_image_u8": [p, p, p, sz, i, C.c_uint64, p, p, P(i64), sz, P(i), P(i), P(i)],
+        "mlic_resample_table": [i, i, i, p, p, p, i, P(i)],
+        "mlic_image_ingest_u8_scaled": [p, p, P(i64), i, i, i, i, i, i, p, i, i],
+        "mlic_image_egress_u8_scaled": [p, p, P(i64), i, i, i, i, i, i, p, P(i64), p, P(i64), p],
+        "mlic_container_write_scaled": [C.c_uint32, C.c_uint32, i, i, p, sz, p, sz, P(sz)],
+        "mlic_container_parse_scaled": [p, sz, i, C.c_uint64, P(ContainerScaledInfo)],
+        "mlic_encode_image_u8_scaled": [p, p, p, P(i64), i, i, i, i, i, f, i, p, sz, P(sz)],
+        "mlic_decode_image_u8_sized": [p, p, p, sz, i, C.c_uint64, p, i, i, i, p, P(i64), sz, P(i), P(i), P(i), P(i),
+                                       P(i)],
         "mlic_image_ingest_yuv8": [p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, p, i, i],
         "mlic_image_egress_yuv8": [p, p, P(i64), i, i, i, P(YuvDesc), p, P(i64), p, P(i64), p, P(i64), p, P(i64), p,
                                    P(i64), p, P(i64), p],

@@ -413,10 +413,14 @@ def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pix
     map (uint8 numpy [hz, wz]).  A tiled file (is_tiled_file; its flags say whether the tiles carry a level word,
     and max_pixels bounds the whole image's H * W) gives {"tiled": True, H, W,
     tile, overlap, grid (ny, nx), vbr, level, bytes, bpp, "tiles": per tile index, y0, x0, H, W, level, bytes,
-    bpp}."""
+    bpp}.  A scaled file (is_scaled_file; its flags say whether the inner file has a level word) gives {"scaled":
+    True, H, W (the display size), "coded" (h, w), "filter", vbr, level, shape, Hp, Wp (of the coded image), y_len,
+    z_len, bytes, bpp (the whole file over the display pixels)}."""
     data = bytes(data)
     if is_tiled_file(data):
         return _peek_tiled(data, n_levels, MAX_IMAGE_PIXELS if max_pixels is None else max_pixels)
+    if is_scaled_file(data):
+        return _peek_scaled(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
     max_pixels = MAX_PIXELS if max_pixels is None else max_pixels
     lv = None
     if vbr and is_roi_file(data):
@@ -470,6 +474,200 @@ def parse_container_roi(data: bytes, n_levels: int = 16, max_pixels: int = MAX_P
 
 def _strings(data: bytes, c: _lib.ContainerInfo):
     return data[c.y_off:c.y_off + c.y_len], data[c.z_off:c.z_off + c.z_len]
+
+
+# ------------------------------------------------------------------------------------ scaled coding
+FILTERS = ("lanczos3", "bicubic", "triangle")  # the file's filter byte is the index
+SCALED_MAGIC = b"MLS1"
+MAX_SCALE_RATIO = 8  # per axis, 1/8 <= output / input <= 8
+
+
+def _filter_id(filter, what: str) -> int:
+    if filter not in FILTERS:
+        raise ValueError(f"{what}: filter must be one of {FILTERS}, got {filter!r}")
+    return FILTERS.index(filter)
+
+
+def _check_size(size, what: str):
+    try:
+        h, w = size
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a pair (height, width) expected, got {size!r}") from None
+    for v in (h, w):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{what}: a pair of positive integers (height, width) expected, got {size!r}")
+    return int(h), int(w)
+
+
+def _check_ratio(Li: int, Lo: int, what: str):
+    if Lo > MAX_SCALE_RATIO * Li or Li > MAX_SCALE_RATIO * Lo:
+        raise ValueError(f"{what}: {Li} -> {Lo} leaves the ratio range [1/{MAX_SCALE_RATIO}, {MAX_SCALE_RATIO}]")
+
+
+def resample_table(filter: str, Li: int, Lo: int):
+    """One axis' table of the resampler (mlic_resample_table; the definition is in DESIGN.md §5 "Scaled coding" and
+    csrc/resample_table.h) -> (start int32 [Lo], count int32 [Lo], weights float32 [Lo, taps]): output o is
+    sum_j weights[o, j] * input[start[o] + j] over j < count[o]; weights[o, count[o]:] is 0.  1/8 <= Lo / Li <= 8."""
+    f = _filter_id(filter, "resample_table")
+    taps = C.c_int()
+    _lib.call("mlic_resample_table", f, int(Li), int(Lo), None, None, None, 0, C.byref(taps))
+    start, count = np.zeros(Lo, np.int32), np.zeros(Lo, np.int32)
+    w = np.zeros((Lo, taps.value), np.float32)
+    _lib.call("mlic_resample_table", f, int(Li), int(Lo), C.c_void_p(start.ctypes.data), C.c_void_p(count.ctypes.data),
+              C.c_void_p(w.ctypes.data), taps.value, C.byref(taps))
+    return start, count, w
+
+
+def _resample_axis_cpu(v: torch.Tensor, table) -> torch.Tensor:
+    """The last axis of fp32 v through one table: acc = +0; acc = acc + w * v over the taps in ascending order,
+    the product and the sum rounded once each (two torch operations), taps j >= count left out of the sum."""
+    start, count, w = (torch.from_numpy(a) for a in table)
+    start, count = start.long(), count.long()
+    Li = v.size(-1)
+    acc = torch.zeros(v.shape[:-1] + (w.size(0),), dtype=torch.float32)
+    for j in range(w.size(1)):
+        live = count > j
+        term = w[:, j] * v[..., (start + j).clamp(max=Li - 1)]
+        acc = torch.where(live, acc + term, acc)
+    return acc
+
+
+def _resample_cpu(v: torch.Tensor, size, filter: str) -> torch.Tensor:
+    """fp32 [..., Hi, Wi] -> [..., Ho, Wo]: the horizontal pass, then the vertical one (the kernels' arithmetic)."""
+    t = _resample_axis_cpu(v, resample_table(filter, v.size(-1), size[1]))
+    return _resample_axis_cpu(t.transpose(-1, -2), resample_table(filter, v.size(-2), size[0])).transpose(-1, -2)
+
+
+def ingest_u8_scaled(img, size, filter: str = "lanczos3", layout: Optional[str] = "hwc") -> torch.Tensor:
+    """ingest_u8 with the resampler in the same launch: uint8 images of any strides -> v / 255, resampled to
+    size = (h, w) with `filter` (horizontal pass first, fp32, nothing rounded to 8 bits), clamped to [0, 1] ->
+    contiguous fp32 [B,3,pad64(h),pad64(w)] with exactly 0 in the padding.  size equal to the image's size gives
+    ingest_u8's tensor bit for bit."""
+    img, layout = _u8_batch(img, layout, "ingest_u8_scaled")
+    f = _filter_id(filter, "ingest_u8_scaled")
+    h, w = _check_size(size, "ingest_u8_scaled size")
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    _check_ratio(H, h, "ingest_u8_scaled")
+    _check_ratio(W, w, "ingest_u8_scaled")
+    if not img.is_cuda:
+        v = _resample_cpu(_nchw(img, layout).float().div(255), (h, w), filter).clamp(0, 1)
+        return bitstream.pad64(v).contiguous()
+    img = _in_place(img, layout)
+    Hp, Wp = _pad64(h), _pad64(w)
+    with torch.cuda.device(img.device):
+        x = torch.empty(B, 3, Hp, Wp, dtype=torch.float32, device=img.device)
+        if _lib.poison():
+            x.fill_(float("nan"))
+        _lib.call("mlic_image_ingest_u8_scaled", _stream(), C.c_void_p(img.data_ptr()),
+                  (C.c_int64 * 4)(*_strides(img, layout)), B, H, W, f, h, w, C.c_void_p(x.data_ptr()), Hp, Wp)
+    return x
+
+
+def egress_u8_scaled(x_hat: torch.Tensor, h: int, w: int, size, filter: str = "lanczos3", layout: str = "hwc", ref=None,
+                     out: Optional[torch.Tensor] = None):
+    """egress_u8 with the resampler in the same launch: the top-left h x w crop of fp32 [B,3,>=h,>=w], clamped to
+    [0, 1] (a NaN gives 0), resampled to size = (Ho, Wo), then floor(clamp(v, 0, 1) * 255) as uint8 in `layout`.
+    out / ref as in egress_u8, both of the output size; with ref returns (image, sq_err).  size == (h, w) gives
+    egress_u8's bytes."""
+    layout = _layout(x_hat, layout)
+    f = _filter_id(filter, "egress_u8_scaled")
+    if x_hat.dim() != 4 or x_hat.size(1) != 3 or x_hat.dtype != torch.float32:
+        raise ValueError(f"egress_u8_scaled: fp32 [B,3,h,w] expected, got {x_hat.dtype} {tuple(x_hat.shape)}")
+    B = x_hat.size(0)
+    if not (1 <= h <= x_hat.size(2) and 1 <= w <= x_hat.size(3)) or B < 1:
+        raise ValueError(f"egress_u8_scaled: crop {h} x {w} of {tuple(x_hat.shape)}")
+    Ho, Wo = _check_size(size, "egress_u8_scaled size")
+    _check_ratio(h, Ho, "egress_u8_scaled")
+    _check_ratio(w, Wo, "egress_u8_scaled")
+    shape = (B, Ho, Wo, 3) if layout == "hwc" else (B, 3, Ho, Wo)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x_hat.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x_hat.device:
+        raise ValueError(f"egress_u8_scaled: out must be uint8 {shape} on {x_hat.device}")
+    if ref is not None:
+        ref, _ = _u8_batch(ref, layout, "egress_u8_scaled ref")
+        if tuple(ref.shape) != shape:
+            raise ValueError(f"egress_u8_scaled: ref must have shape {shape}, got {tuple(ref.shape)}")
+        ref = ref.to(x_hat.device)
+    if not x_hat.is_cuda:
+        v = x_hat[:, :, :h, :w]
+        v = torch.where(torch.isnan(v), torch.zeros((), dtype=v.dtype), v).clamp(0, 1)
+        u = bitstream.to_u8(_resample_cpu(v, (Ho, Wo), filter))
+        out.copy_(u.permute(0, 2, 3, 1) if layout == "hwc" else u)
+        if ref is None:
+            return out
+        d = out.to(torch.int64) - ref.to(torch.int64)
+        return out, (d * d).flatten(1).sum(1)
+    if x_hat.stride(3) != 1:
+        x_hat = x_hat.contiguous()
+    if 0 in _strides(out, layout)[2:]:
+        raise ValueError("egress_u8_scaled: out has a zero column or channel stride")
+    with torch.cuda.device(x_hat.device):
+        sq = None
+        if ref is not None:
+            ref = _in_place(ref, layout)
+            sq = torch.full((B,), -1, dtype=torch.int64, device=x_hat.device)
+        _lib.call("mlic_image_egress_u8_scaled", _stream(), C.c_void_p(x_hat.data_ptr()),
+                  (C.c_int64 * 3)(*x_hat.stride()[:3]), B, h, w, f, Ho, Wo, C.c_void_p(out.data_ptr()),
+                  (C.c_int64 * 4)(*_strides(out, layout)), None if ref is None else C.c_void_p(ref.data_ptr()),
+                  None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)),
+                  None if sq is None else C.c_void_p(sq.data_ptr()))
+    return out if ref is None else (out, sq)
+
+
+def is_scaled_file(data: bytes) -> bool:
+    return bytes(data[:4]) == SCALED_MAGIC
+
+
+def write_container_scaled(H: int, W: int, inner: bytes, filter: str = "lanczos3", vbr: bool = False) -> bytes:
+    """The scaled file (mlic_container_write_scaled): a 16-byte header -- "MLS1", version, flags (bit 0: vbr),
+    filter, reserved, the display size H, W -- around `inner`, the coded image's plain or VBR file, unchanged."""
+    inner = bytes(inner)
+    f = _filter_id(filter, "write_container_scaled")
+    n = C.c_size_t()
+    buf = C.create_string_buffer(16 + max(1, len(inner)))
+    _lib.call("mlic_container_write_scaled", H, W, int(bool(vbr)), f, inner, len(inner), buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_scaled(data: bytes, n_levels: Optional[int] = None,
+                           max_pixels: int = MAX_PIXELS) -> _lib.ContainerScaledInfo:
+    """The validating parser of a scaled file (mlic_container_parse_scaled): raises _lib.MlicError on any malformed
+    input.  The file's flags say whether the inner file has a level word; n_levels bounds it (None: any level).
+    info.inner is the inner file's ContainerInfo, its offsets relative to data[info.inner_off:]."""
+    data = bytes(data)
+    info = _lib.ContainerScaledInfo()
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call("mlic_container_parse_scaled", data, len(data), nl, int(max_pixels), C.byref(info))
+    return info
+
+
+def coded_size(H: int, W: int, scale):
+    """The coded size of an H x W image at `scale` (a Fraction, an int, a string "N/D", or a float taken at its
+    exact binary value): per axis max(1, floor(L * scale + 1/2)) in exact rational arithmetic -- round to nearest,
+    a tie goes up."""
+    from fractions import Fraction
+    if isinstance(scale, bool):
+        raise ValueError(f"scale: a positive rational expected, got {scale!r}")
+    try:
+        s = Fraction(scale)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError(f"scale: a positive rational (Fraction, int, 'N/D') expected, got {scale!r}") from None
+    if s <= 0:
+        raise ValueError(f"scale: a positive rational expected, got {scale!r}")
+    return tuple(max(1, math.floor(L * s + Fraction(1, 2))) for L in (H, W))
+
+
+_scaled_size = coded_size  # encode_images has a parameter of that name
+
+
+def _peek_scaled(data: bytes, n_levels, max_pixels) -> Dict:
+    s = parse_container_scaled(data, n_levels, max_pixels)
+    c = s.inner
+    return {"scaled": True, "H": s.H, "W": s.W, "coded": (c.H, c.W), "filter": FILTERS[s.filter], "vbr": bool(s.vbr),
+            "level": c.level if s.vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz, "Wp": 64 * c.wz,
+            "y_len": c.y_len, "z_len": c.z_len, "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
 
 
 # ---------------------------------------------------------------------------------------------- ROI
@@ -622,7 +820,8 @@ def _check_budget(max_bpp, max_passes):
 
 
 @torch.no_grad()
-def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_passes: int = 8):
+def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_passes: int = 8,
+              pixels: Optional[int] = None, overhead: int = 0):
     """The reference's rate constraint (utils/testing.py:363-390, VBR :467-527) on the padded float images x
     [B,3,Hp,Wp] of H x W images: code the batch; the images whose whole file is above max_bpp bits per pixel
     (8 * len(file) / (H * W), header included) and that had fewer than max_passes filter passes are filtered and
@@ -633,10 +832,13 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
     unfiltered file fits, found by scanning down from net.levels - 1 with the images that fit leaving the batch
     (no monotonicity assumed: the first fit from the top is the definition); an image over the budget at level
     0 goes on into the filter loop at level 0.  -> (files, passes, levels) in input order; levels is None for
-    a fixed-rate model."""
+    a fixed-rate model.
+    pixels / overhead (scaled coding): the budget counts 8 * (len(file) + overhead) bits over `pixels` pixels --
+    the display size and the scaled header -- while H x W, the coded size, is what is coded and filtered."""
     _check_budget(max_bpp, max_passes)
     if max_bpp is None:
         raise ValueError("rate_loop: max_bpp expected")
+    pixels = H * W if pixels is None else int(pixels)
     B = x.size(0)
     auto = isinstance(level, str)
     if auto:
@@ -658,7 +860,7 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
             files[b] = write_container(H, W, out["shape"], ys[j], zs[j], None if lv is None else lv[b])
 
     def over(b):
-        return 8.0 * len(files[b]) / (H * W) > max_bpp
+        return 8.0 * (len(files[b]) + overhead) / pixels > max_bpp
 
     def keep(cur, ids, sub):
         """The images `sub` of the batch `cur` (which holds `ids`), compacted."""
@@ -691,7 +893,7 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
 @torch.no_grad()
 def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
                   max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None, depth: Optional[int] = None,
-                  msb: bool = False):
+                  msb: bool = False, coded_size=None, scale=None, filter: str = "lanczos3"):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
@@ -707,7 +909,22 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     the level map as a third string (its header level is hi); info[b] gains "roi_levels", the map.
     depth=d (8..16) with msb: the images are uint16 (ingest_u16's sample format) and go through ingest_u16;
     everything after the ingest works on the float image, so level, max_bpp, level="auto" and roi= compose
-    unchanged, and the file does not know its depth.  depth=None is the uint8 path."""
+    unchanged, and the file does not know its depth.  depth=None is the uint8 path.
+    coded_size=(h, w) or scale=Fraction (one of the two; codec.coded_size states the rounding), with filter: scaled
+    coding (DESIGN.md §5 "Scaled coding").  ingest_u8_scaled resamples the H x W image to h x w in the ingest
+    launch, the model codes that image exactly as it codes any h x w image, and the file is the scaled file
+    (write_container_scaled: the display size H x W and the filter around the coded image's file).  level and
+    max_bpp act on the coded image; bpp, in the budget and in info, is the whole file over the display pixels;
+    info[b] gains "coded" and "filter".  Refused together with roi= and depth=."""
+    scaled = coded_size is not None or scale is not None
+    if scaled:
+        if coded_size is not None and scale is not None:
+            raise ValueError("encode_images: coded_size= and scale= are two ways to say one thing: pass one")
+        if roi is not None or roi_levels is not None:
+            raise ValueError("encode_images: scaled coding together with roi= is not supported")
+        if depth is not None:
+            raise ValueError("encode_images: scaled coding together with depth= (uint16 samples) is not supported")
+        _filter_id(filter, "encode_images")
     if depth is None:
         img, layout = _u8_batch(imgs_u8, layout, "encode_images")
         ingest = ingest_u8
@@ -751,14 +968,26 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         return files, [{"bytes": len(f), "bpp": 8.0 * len(f) / (H * W), "passes": 0, "level": int(hi), "met": True,
                         "roi_levels": lmap[b]} for b, f in enumerate(files)]
     img = img.to(net.device)
+    h, w = H, W  # the size the model codes
+    if scaled:
+        h, w = _check_size(coded_size, "encode_images coded_size") if scale is None else _scaled_size(H, W, scale)
+        _check_ratio(H, h, "encode_images")
+        _check_ratio(W, w, "encode_images")
+        x = ingest_u8_scaled(img, (h, w), filter, layout)
+    else:
+        x = ingest(img, layout)
     if max_bpp is None:
         lv, kw = _levels(net, level, B)
-        out = net.compress(ingest(img, layout), **kw)
+        out = net.compress(x, **kw)
         ys, zs = out["strings"]
-        files = [write_container(H, W, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
+        files = [write_container(h, w, out["shape"], ys[b], zs[b], None if lv is None else lv[b]) for b in range(B)]
         passes = [0] * B
+    elif scaled:
+        files, passes, lv = rate_loop(net, x, h, w, level, max_bpp, max_passes, pixels=H * W, overhead=16)
     else:
-        files, passes, lv = rate_loop(net, ingest(img, layout), H, W, level, max_bpp, max_passes)
+        files, passes, lv = rate_loop(net, x, H, W, level, max_bpp, max_passes)
+    if scaled:
+        files = [write_container_scaled(H, W, f, filter, vbr=lv is not None) for f in files]
     if not return_info:
         return files
     info = []
@@ -766,12 +995,14 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         bpp = 8.0 * len(f) / (H * W)
         info.append({"bytes": len(f), "bpp": bpp, "passes": passes[b], "level": None if lv is None else lv[b],
                      "met": max_bpp is None or bpp <= max_bpp})
+        if scaled:
+            info[-1].update(coded=(h, w), filter=filter)
     return files, info
 
 
 @torch.no_grad()
 def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS, depth: Optional[int] = None,
-                  msb: bool = False):
+                  msb: bool = False, out_size=None, filter: Optional[str] = None):
     """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
     (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
     image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
@@ -780,7 +1011,13 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     holds the map as "roi_levels".
     depth=d (8..16) with msb: the image comes back as uint16 words of that sample format (egress_u16), ref is
     uint16 likewise, and psnr is computed with peak 2^d - 1.  The file does not know its depth: any file decodes at
-    any depth."""
+    any depth.
+    A scaled file (encode_images(coded_size=...) / (scale=...)) decodes to its display size: the model decodes the
+    coded image and egress_u8_scaled resamples it in the egress launch with the file's filter.  out_size=(H', W')
+    overrides the output size of every file, plain, VBR or scaled (the thumbnail decode; a plain file is resampled
+    with lanczos3); filter= overrides the filter.  ref, sq_err and psnr are at the output size; info[b] then holds
+    the output size as H, W, and "display", "coded" and "filter"; bpp stays the file over its display pixels.
+    Refused together with depth= and for ROI files."""
     if depth is not None:
         depth, msb = _check_depth(depth, "decode_images"), _check_msb(msb, "decode_images")
     files = [bytes(f) for f in files]
@@ -789,6 +1026,16 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     if any(is_tiled_file(f) for f in files):
         raise ValueError("decode_images: a tiled file (MLT1) is decoded by decode_tiled, whole or by region")
     vbr = hasattr(net, "levels")
+    if out_size is not None:
+        out_size = _check_size(out_size, "decode_images out_size")
+    if filter is not None:
+        _filter_id(filter, "decode_images")
+    if out_size is not None or any(is_scaled_file(f) for f in files):
+        if depth is not None:
+            raise ValueError("decode_images: scaled coding together with depth= (uint16 samples) is not supported")
+        return _decode_scaled(net, files, ref, max_pixels, out_size, filter)
+    if filter is not None:
+        raise ValueError("decode_images: filter= given, but no file is scaled and there is no out_size=")
     maps = [None] * len(files)
     if vbr and any(is_roi_file(f) for f in files):
         # ROI files carry a level map; a plain VBR file beside them decodes through a constant map of its level
@@ -843,6 +1090,71 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
         if sq is not None:
             d["sq_err"] = int(sq[b])
             d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W, 255 if depth is None else (1 << depth) - 1)
+        info.append(d)
+    return img, info
+
+
+def _decode_scaled(net, files, ref, max_pixels, out_size, filter):
+    """decode_images for scaled files and / or an out_size: every image leaves through egress_u8_scaled."""
+    vbr = hasattr(net, "levels")
+    n_levels = net.levels if vbr else None
+    if vbr and any(not is_scaled_file(f) and is_roi_file(f) for f in files):
+        raise ValueError("decode_images: scaled coding together with ROI files is not supported")
+    cs, inner, disp, flt = [], [], [], []
+    for f in files:
+        if is_scaled_file(f):
+            s = parse_container_scaled(f, n_levels, max_pixels)
+            if bool(s.vbr) != vbr:
+                raise ValueError(f"decode_images: the scaled file's inner file {'carries a' if s.vbr else 'has no'} "
+                                 f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+            cs.append(s.inner)
+            inner.append(f[s.inner_off:s.inner_off + s.inner_len])
+            disp.append((s.H, s.W))
+            flt.append(FILTERS[s.filter] if filter is None else filter)
+        else:
+            c = parse_container(f, vbr, n_levels, max_pixels)
+            cs.append(c)
+            inner.append(f)
+            disp.append((c.H, c.W))
+            flt.append("lanczos3" if filter is None else filter)
+    if len({(c.hz, c.wz) for c in cs}) != 1:
+        raise ValueError(f"decode_images: the files must share one padded (coded) size, got z grids "
+                         f"{sorted({(c.hz, c.wz) for c in cs})}")
+    B = len(files)
+    sizes = [disp[b] if out_size is None else out_size for b in range(B)]
+    for c, (Ho, Wo) in zip(cs, sizes):
+        _check_ratio(c.H, Ho, "decode_images")
+        _check_ratio(c.W, Wo, "decode_images")
+    pairs = [_strings(f, c) for f, c in zip(inner, cs)]
+    kw = {"s": [c.level for c in cs]} if vbr else {}
+    x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
+    H, W = max(s[0] for s in sizes), max(s[1] for s in sizes)
+    if ref is not None:
+        ref, _ = _u8_batch(ref, "hwc", "decode_images ref")
+        if tuple(ref.shape) != (B, H, W, 3):
+            raise ValueError(f"decode_images: ref must be uint8 {(B, H, W, 3)} (the output size), got {tuple(ref.shape)}")
+        ref = ref.to(x_hat.device)
+    if len({(c.H, c.W, sz, fl) for c, sz, fl in zip(cs, sizes, flt)}) == 1:
+        r = egress_u8_scaled(x_hat, cs[0].H, cs[0].W, (H, W), flt[0], "hwc", ref=ref)
+        img, sq = r if ref is not None else (r, None)
+    else:
+        img = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=x_hat.device)
+        sq = None if ref is None else torch.zeros(B, dtype=torch.int64, device=x_hat.device)
+        for b, (c, (Ho, Wo)) in enumerate(zip(cs, sizes)):
+            r = egress_u8_scaled(x_hat[b:b + 1], c.H, c.W, (Ho, Wo), flt[b], "hwc", out=img[b:b + 1, :Ho, :Wo],
+                                 ref=None if ref is None else ref[b:b + 1, :Ho, :Wo])
+            if ref is not None:
+                sq[b] = r[1][0]
+    sq = None if sq is None else sq.cpu().tolist()
+    info = []
+    for b, c in enumerate(cs):
+        Ho, Wo = sizes[b]
+        d = {"H": Ho, "W": Wo, "display": disp[b], "coded": (c.H, c.W), "filter": flt[b],
+             "level": c.level if vbr else None, "bytes": len(files[b]),
+             "bpp": 8.0 * len(files[b]) / (disp[b][0] * disp[b][1])}
+        if sq is not None:
+            d["sq_err"] = int(sq[b])
+            d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * Ho * Wo)
         info.append(d)
     return img, info
 
@@ -1078,6 +1390,11 @@ def _refuse_with_tiles(what: str, max_bpp=None, level=None, roi=None, roi_levels
         raise ValueError(f"{what}: per-tile levels are not supported: a VBR level is one level for the image")
 
 
+def _refuse_scaled(what: str, other: str, *given):
+    if any(g is not None for g in given):
+        raise ValueError(f"{what}: scaled coding together with {other} is not supported")
+
+
 def _refuse_deep_tiles(what: str, depth):
     """depth= exists on the tiled calls only to be refused by name: any depth means uint16 words (depth=8 too, as in
     encode_images(depth=8)), and tiles are uint8 images alone."""
@@ -1089,7 +1406,8 @@ def _refuse_deep_tiles(what: str, depth):
 
 @torch.no_grad()
 def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, layout: Optional[str] = None,
-                 tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None, depth=None):
+                 tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None, depth=None,
+                 coded_size=None, scale=None):
     """One uint8 image ([H,W,3] / [3,H,W], tensor or numpy array) -> one tiled file (DESIGN.md §5 "Tiled coding"):
     the image is cut into the tiles of tile_grid(H, W, tile, overlap), each tile is coded by itself and its file
     is byte for byte encode_images of that crop, and the tiled container holds them row-major with an index.
@@ -1101,6 +1419,7 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
     {"H", "W", "tile", "overlap", "grid", "bytes", "bpp", "level", "tile_bytes"}."""
     _refuse_with_tiles("encode_tiled", max_bpp, level, roi, roi_levels)
     _refuse_deep_tiles("encode_tiled", depth)
+    _refuse_scaled("encode_tiled", "tiles", coded_size, scale)
     img, layout = _u8_batch(img_u8, layout, "encode_tiled")
     if img.size(0) != 1:
         raise ValueError(f"encode_tiled takes one image, got a batch of {img.size(0)}")
@@ -1146,7 +1465,7 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
 
 @torch.no_grad()
 def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, max_pixels: int = MAX_IMAGE_PIXELS,
-                 depth=None):
+                 depth=None, out_size=None):
     """A tiled file -> (uint8 [h,w,3] on the model's device, info): the region (y0, x0, h, w) of the image (None:
     all of it).  Only the tiles that intersect the region are entropy-decoded and synthesised (per shape group,
     in chunks of at most tile_batch tiles); their fp32 x_hat is kept (12 bytes per pixel of the decoded tiles, on top of the arena of
@@ -1154,7 +1473,11 @@ def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, m
     grid (ny, nx), region, tiles_decoded (sorted tile indices), level, bytes and bpp of the whole file and, with
     ref (uint8 [h,w,3], the region's crop of the original), the exact sq_err and psnr."""
     _refuse_deep_tiles("decode_tiled", depth)
+    _refuse_scaled("decode_tiled", "tiles", out_size)
     data = bytes(data)
+    if is_scaled_file(data):
+        raise ValueError("decode_tiled: a scaled file (MLS1): scaled coding together with tiles is not supported; "
+                         "decode_images reads it")
     if isinstance(tile_batch, bool) or not isinstance(tile_batch, (int, np.integer)) or tile_batch < 1:
         raise ValueError(f"tile_batch must be a positive integer, got {tile_batch!r}")
     if not is_tiled_file(data):
@@ -1625,7 +1948,7 @@ def psnr_yuv_from_sq_err(sq_err, H: int, W: int, fmt: YuvFormat) -> Dict:
 
 @torch.no_grad()
 def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[float] = None, max_passes: int = 8,
-               return_info: bool = False, roi=None, roi_levels=None, tile=None):
+               return_info: bool = False, roi=None, roi_levels=None, tile=None, coded_size=None, scale=None):
     """encode_images with the Y'CbCr ingest: a frame batch (ingest_yuv's planes; host arrays cross to the device as
     bytes) -> one file per frame.  The files are plain per-image files: nothing of fmt is written, decode_images
     decodes them to RGB and decode_yuv(fmt) to planes.  level, max_bpp, max_passes and return_info as in
@@ -1637,6 +1960,7 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
         raise ValueError("encode_yuv: roi= together with Y'CbCr frames is not supported")
     if tile is not None:
         raise ValueError("encode_yuv: tiles together with Y'CbCr frames are not supported")
+    _refuse_scaled("encode_yuv", "Y'CbCr frames", coded_size, scale)
     y, cb, cr = _yuv_planes(y, cb, cr, fmt, "encode_yuv")
     _check_budget(max_bpp, max_passes)
     if isinstance(level, str) and max_bpp is None:
@@ -1662,7 +1986,7 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
 
 
 @torch.no_grad()
-def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS):
+def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS, out_size=None):
     """Files of one H x W -> ((y, cb, cr) on the model's device, info): decode_images with the Y'CbCr egress.
     info[b] holds H, W, level, bytes and bpp and, with ref=(y, cb, cr) of the originals, sq_err (three ints: Y, Cb,
     Cr), psnr_y, psnr_u, psnr_v and psnr_yuv = (6 Y + U + V) / 8 (peak 2^depth - 1).  The planes are uint8 for a
@@ -1673,6 +1997,7 @@ def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels
         raise ValueError("decode_yuv: no files")
     if any(is_tiled_file(f) for f in files):
         raise ValueError("decode_yuv: tiled files together with Y'CbCr frames are not supported")
+    _refuse_scaled("decode_yuv", "Y'CbCr frames", out_size, True if any(is_scaled_file(f) for f in files) else None)
     vbr = hasattr(net, "levels")
     if vbr and any(is_roi_file(f) for f in files):
         raise ValueError("decode_yuv: ROI files together with Y'CbCr frames are not supported")

@@ -10,6 +10,7 @@
 #include "container.h"
 #include "model.h"
 #include "options.h"
+#include "resample_table.h"
 
 using namespace mlic;
 
@@ -24,6 +25,9 @@ struct mlic_model {
   size_t stage2_bytes = 0;
   int enc_H = 0, enc_W = 0, enc_level = -1;  // enc_H == 0: nothing encoded yet
   int enc_passes = 0;                        // filter passes of the last encode
+  // mlic_encode_image_u8_scaled: the display size and filter of the last encode when it was a scaled one (enc_H,
+  // enc_W are then the coded size); sc_H == 0: it was not
+  int sc_H = 0, sc_W = 0, sc_filter = 0;
 };
 
 struct mlic_lpips {
@@ -1234,7 +1238,7 @@ int mlic_encode_image_u8(mlic_model* m, void* stream, const uint8_t* rgb_dev, co
       MLIC_CHECK(H <= (1 << 24) && W <= (1 << 24), "encode_image_u8: image side above 2^24");
       const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64;
       const int64_t s4[4] = {0, strides[0], strides[1], strides[2]};
-      m->enc_H = 0;
+      m->enc_H = m->sc_H = 0;
       float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
       image_ingest_u8(rgb_dev, s4, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
       const float sc[1] = {vbr_scale};
@@ -1264,7 +1268,7 @@ int mlic_encode_image_u8_budget(mlic_model* m, void* stream, const uint8_t* rgb_
       const size_t bytes = sizeof(float) * 3 * (size_t)Hp * (size_t)Wp;
       const int64_t s4[4] = {0, strides[0], strides[1], strides[2]};
       const float sc[1] = {vbr_scale};
-      m->enc_H = 0;
+      m->enc_H = m->sc_H = 0;
       float* x = stage(m, bytes);
       image_ingest_u8(rgb_dev, s4, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
       int k = 0;
@@ -1322,6 +1326,151 @@ int mlic_decode_image_u8(mlic_model* m, void* stream, const uint8_t* file, size_
   });
 }
 
+// ---- scaled coding (DESIGN.md section 5 "Scaled coding")
+int mlic_resample_table(int filter, int Li, int Lo, int32_t* start, int32_t* count, float* weights, int stride,
+                        int* taps) {
+  return guard([&] { container_ok(resample_table(filter, Li, Lo, start, count, weights, stride, taps)); });
+}
+
+int mlic_image_ingest_u8_scaled(void* stream, const uint8_t* src, const int64_t* src_strides, int B, int Hi, int Wi,
+                                int filter, int h, int w, float* dst, int Hp, int Wp) {
+  return guard(
+      [&] { image_ingest_u8_scaled(src, src_strides, B, Hi, Wi, filter, h, w, dst, Hp, Wp, (hipStream_t)stream); });
+}
+
+int mlic_image_egress_u8_scaled(void* stream, const float* src, const int64_t* src_strides, int B, int h, int w,
+                                int filter, int Ho, int Wo, uint8_t* dst, const int64_t* dst_strides, const uint8_t* ref,
+                                const int64_t* ref_strides, uint64_t* sq_err) {
+  return guard([&] {
+    image_egress_u8_scaled(src, src_strides, B, h, w, filter, Ho, Wo, dst, dst_strides, ref, ref_strides, sq_err,
+                           (hipStream_t)stream);
+  });
+}
+
+int mlic_container_write_scaled(uint32_t H, uint32_t W, int vbr, int filter, const uint8_t* inner, size_t inner_len,
+                                uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    MLIC_CHECK(filter >= 0, "container_write_scaled: negative filter");
+    container_ok(container_write_scaled(H, W, vbr != 0, (uint32_t)filter, inner, inner_len, out, cap, len));
+  });
+}
+
+int mlic_container_parse_scaled(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                mlic_container_scaled_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_scaled: null info");
+    ScaledInfo s;
+    container_ok(container_parse_scaled(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &s));
+    info->H = s.H;
+    info->W = s.W;
+    info->filter = (int32_t)s.filter;
+    info->vbr = s.vbr ? 1 : 0;
+    info->inner_off = s.inner_off;
+    info->inner_len = s.inner_len;
+    to_abi(s.inner, &info->inner);
+  });
+}
+
+int mlic_encode_image_u8_scaled(mlic_model* m, void* stream, const uint8_t* rgb_dev, const int64_t* strides, int H,
+                                int W, int coded_H, int coded_W, int filter, float vbr_scale, int level, uint8_t* out,
+                                size_t cap, size_t* len) {
+  return guard([&] {
+    Model& mod = impl(m);
+    MLIC_CHECK(len != nullptr, "encode_image_u8_scaled: null len");
+    if (rgb_dev != nullptr) {
+      MLIC_CHECK(strides != nullptr && H >= 1 && W >= 1, "encode_image_u8_scaled: strides, H >= 1 and W >= 1 expected");
+      MLIC_CHECK(coded_H >= 1 && coded_W >= 1, "encode_image_u8_scaled: the coded size must be positive");
+      const char* err = resample_axis_check(filter, H, coded_H);
+      if (!err) err = resample_axis_check(filter, W, coded_W);
+      if (err) throw Error(std::string("mlic: encode_image_u8_scaled: ") + err);
+      const int Hp = (coded_H + 63) / 64 * 64, Wp = (coded_W + 63) / 64 * 64;
+      const int64_t s4[4] = {0, strides[0], strides[1], strides[2]};
+      m->enc_H = m->sc_H = 0;
+      float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
+      image_ingest_u8_scaled(rgb_dev, s4, 1, H, W, filter, coded_H, coded_W, x, Hp, Wp, (hipStream_t)stream);
+      const float sc[1] = {vbr_scale};
+      mod.compress(x, 1, Hp, Wp, sc, (hipStream_t)stream);
+      m->enc_H = coded_H;
+      m->enc_W = coded_W;
+      m->enc_level = level < 0 ? -1 : level;
+      m->enc_passes = 0;
+      m->sc_H = H;
+      m->sc_W = W;
+      m->sc_filter = filter;
+    }
+    MLIC_CHECK(m->enc_H > 0 && m->sc_H > 0,
+               "encode_image_u8_scaled: rgb_dev is NULL and the handle's last encode was not a scaled one");
+    size_t inner = 0;
+    write_encoded(m, mod, nullptr, 0, &inner);
+    *len = SCALED_HEADER + inner;
+    if (out == nullptr) return;
+    MLIC_CHECK(cap >= *len, "encode_image_u8_scaled: buffer too small");
+    std::vector<uint8_t> file(inner);
+    write_encoded(m, mod, file.data(), file.size(), &inner);
+    container_ok(container_write_scaled((uint32_t)m->sc_H, (uint32_t)m->sc_W, m->enc_level >= 0,
+                                        (uint32_t)m->sc_filter, file.data(), file.size(), out, cap, len));
+  });
+}
+
+int mlic_decode_image_u8_sized(mlic_model* m, void* stream, const uint8_t* file, size_t n, int n_levels,
+                               uint64_t max_pixels, const float* vbr_gains, int out_H, int out_W, int filter,
+                               uint8_t* rgb_dev, const int64_t* strides, size_t cap_bytes, int* H, int* W, int* level,
+                               int* coded_H, int* coded_W) {
+  return guard([&] {
+    MLIC_CHECK(file != nullptr || n == 0, "decode_image_u8_sized: null file");
+    MLIC_CHECK((out_H == 0) == (out_W == 0) && out_H >= 0 && out_W >= 0,
+               "decode_image_u8_sized: out_H, out_W must both be positive or both be 0 (the file's display size)");
+    MLIC_CHECK(filter >= -1 && filter < RESAMPLE_FILTERS,
+               "decode_image_u8_sized: filter must be -1 (the file's; lanczos3 for a plain file), 0, 1 or 2");
+    const bool vbr = n_levels > 0;
+    ContainerInfo c;
+    uint32_t dH, dW;
+    int flt = filter < 0 ? RESAMPLE_LANCZOS3 : filter;
+    const uint8_t* inner = file;
+    if (is_scaled_file(file, n)) {
+      ScaledInfo s;
+      container_ok(container_parse_scaled(file, n, (uint32_t)std::max(n_levels, 0), max_pixels, &s));
+      MLIC_CHECK(s.vbr == vbr, "decode_image_u8_sized: the file's VBR flag does not match n_levels");
+      c = s.inner;
+      inner = file + s.inner_off;
+      dH = s.H, dW = s.W;
+      if (filter < 0) flt = (int)s.filter;
+    } else {
+      container_ok(container_parse(file, n, vbr, (uint32_t)std::max(n_levels, 0), max_pixels, &c));
+      dH = c.H, dW = c.W;
+    }
+    MLIC_CHECK(c.H <= (1u << 24) && c.W <= (1u << 24) && dH <= (1u << 24) && dW <= (1u << 24),
+               "decode_image_u8_sized: image side above 2^24");
+    const int oH = out_H ? out_H : (int)dH, oW = out_W ? out_W : (int)dW;
+    if (H) *H = oH;
+    if (W) *W = oW;
+    if (level) *level = c.level;
+    if (coded_H) *coded_H = (int)c.H;
+    if (coded_W) *coded_W = (int)c.W;
+    const char* err = resample_axis_check(flt, (int)c.H, oH);
+    if (!err) err = resample_axis_check(flt, (int)c.W, oW);
+    if (err) throw Error(std::string("mlic: decode_image_u8_sized: ") + err);
+    if (rgb_dev == nullptr) return;
+    Model& mod = impl(m);
+    MLIC_CHECK(strides != nullptr && strides[0] >= 0 && strides[1] > 0 && strides[2] > 0,
+               "decode_image_u8_sized: strides {row, column, channel} must be non-negative, column and channel nonzero");
+    const uint64_t extent = 1 + (uint64_t)(oH - 1) * (uint64_t)strides[0] + (uint64_t)(oW - 1) * (uint64_t)strides[1] +
+                            2 * (uint64_t)strides[2];
+    MLIC_CHECK(extent <= cap_bytes, "decode_image_u8_sized: the output image does not fit cap_bytes");
+    const int Hp = (int)c.hz * 64, Wp = (int)c.wz * 64;
+    float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
+    const uint8_t* ys[1] = {inner + c.y_off};
+    const uint8_t* zs[1] = {inner + c.z_off};
+    const size_t yl[1] = {c.y_len}, zl[1] = {c.z_len};
+    const float sc[1] = {vbr && vbr_gains ? vbr_gains[c.level] : 1.0f};
+    mod.decompress(ys, yl, zs, zl, 1, (int)c.hz, (int)c.wz, x, sc, (hipStream_t)stream);
+    const int64_t s3[3] = {0, (int64_t)Hp * Wp, Wp};
+    const int64_t d4[4] = {0, strides[0], strides[1], strides[2]};
+    image_egress_u8_scaled(x, s3, 1, (int)c.H, (int)c.W, flt, oH, oW, rgb_dev, d4, nullptr, nullptr, nullptr,
+                           (hipStream_t)stream);
+  });
+}
+
 static YuvDesc yuv_desc(const mlic_yuv_desc* d) {
   MLIC_CHECK(d != nullptr, "null mlic_yuv_desc");
   return YuvDesc{d->sub_x, d->sub_y, d->matrix, d->full_range, d->site_x, {d->reserved[0], d->reserved[1], d->reserved[2]}};
@@ -1364,7 +1513,7 @@ int mlic_encode_image_yuv8(mlic_model* m, void* stream, const uint8_t* y_dev, co
       const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64;
       const int64_t ys[3] = {0, y_strides[0], y_strides[1]}, bs[3] = {0, cb_strides[0], cb_strides[1]},
                     rs[3] = {0, cr_strides[0], cr_strides[1]};
-      m->enc_H = 0;
+      m->enc_H = m->sc_H = 0;
       float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
       image_ingest_yuv8(y_dev, ys, cb_dev, bs, cr_dev, rs, &d, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
       const float sc[1] = {vbr_scale};
@@ -1485,7 +1634,7 @@ int mlic_encode_image_yuv16(mlic_model* m, void* stream, const uint16_t* y_dev, 
       const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64;
       const int64_t ys[3] = {0, y_strides[0], y_strides[1]}, bs[3] = {0, cb_strides[0], cb_strides[1]},
                     rs[3] = {0, cr_strides[0], cr_strides[1]};
-      m->enc_H = 0;
+      m->enc_H = m->sc_H = 0;
       float* x = stage(m, sizeof(float) * 3 * (size_t)Hp * (size_t)Wp);
       image_ingest_yuv16(y_dev, ys, cb_dev, bs, cr_dev, rs, &d, depth, msb, 1, H, W, x, Hp, Wp, (hipStream_t)stream);
       const float sc[1] = {vbr_scale};

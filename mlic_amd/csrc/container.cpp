@@ -304,6 +304,63 @@ const char* container_tiled_tile(const uint8_t* data, size_t n, const TiledInfo*
   return nullptr;
 }
 
+// ----------------------------------------------------------------------------------------- scaled
+const char* scaled_ratio_check(uint64_t display, uint64_t coded) {
+  if (display == 0 || coded == 0) return "scaled file: a size is zero";
+  if (coded > 8 * display || display > 8 * coded)
+    return "scaled file: the ratio of coded to display size leaves [1/8, 8]";
+  return nullptr;
+}
+
+const char* container_write_scaled(uint32_t H, uint32_t W, bool vbr, uint32_t filter, const uint8_t* inner,
+                                   size_t inner_len, uint8_t* out, size_t cap, size_t* len) {
+  if (len == nullptr) return "container_write_scaled: null len";
+  if (H == 0 || W == 0) return "container_write_scaled: H or W is zero";
+  if (filter > 2) return "container_write_scaled: unknown filter (0 lanczos3, 1 bicubic, 2 triangle)";
+  if (inner_len == 0) return "container_write_scaled: an empty inner file";
+  if (inner_len > SIZE_MAX - SCALED_HEADER) return "container_write_scaled: the file does not fit size_t";
+  *len = SCALED_HEADER + inner_len;
+  if (out == nullptr) return nullptr;
+  if (cap < *len) return "container_write_scaled: buffer too small";
+  if (inner == nullptr) return "container_write_scaled: null inner file";
+  std::memcpy(out, "MLS1", 4);
+  out[4] = 0;
+  out[5] = vbr ? 1 : 0;
+  out[6] = (uint8_t)filter;
+  out[7] = 0;
+  put32(out + 8, H);
+  put32(out + 12, W);
+  std::memcpy(out + SCALED_HEADER, inner, inner_len);
+  return nullptr;
+}
+
+const char* container_parse_scaled(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                   ScaledInfo* info) {
+  if (info == nullptr) return "container_parse_scaled: null info";
+  if (data == nullptr && n != 0) return "container_parse_scaled: null data";
+  if (n < SCALED_HEADER) return "container_parse_scaled: truncated header";
+  if (std::memcmp(data, "MLS1", 4) != 0) return "container_parse_scaled: bad magic (not a scaled file)";
+  if (data[4] != 0) return "container_parse_scaled: unknown version";
+  if (data[5] & ~1u) return "container_parse_scaled: unknown flags";
+  if (data[6] > 2) return "container_parse_scaled: unknown filter";
+  if (data[7] != 0) return "container_parse_scaled: the reserved byte is not 0";
+  Reader r{data, n, 8};
+  ScaledInfo s{};
+  s.vbr = (data[5] & 1u) != 0;
+  s.filter = data[6];
+  r.u32(&s.H);  // n >= SCALED_HEADER: the header's reads succeed
+  r.u32(&s.W);
+  if (s.H == 0 || s.W == 0) return "container_parse_scaled: H or W is zero";
+  if ((uint64_t)s.H > max_pixels / (uint64_t)s.W) return "container_parse_scaled: image exceeds max_pixels";
+  s.inner_off = SCALED_HEADER;
+  s.inner_len = n - SCALED_HEADER;
+  if (const char* err = container_parse(data + s.inner_off, s.inner_len, s.vbr, n_levels, max_pixels, &s.inner)) return err;
+  if (scaled_ratio_check(s.H, s.inner.H) || scaled_ratio_check(s.W, s.inner.W))
+    return "container_parse_scaled: the ratio of coded to display size leaves [1/8, 8]";
+  *info = s;
+  return nullptr;
+}
+
 void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels) {
   for (uint64_t k = 0; k < cells; ++k) {
     const uint8_t byte = map[1 + (size_t)(k >> 1)];

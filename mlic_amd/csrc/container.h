@@ -105,5 +105,33 @@ const char* container_parse_tiled(const uint8_t* data, size_t n, uint64_t max_pi
 const char* container_tiled_tile(const uint8_t* data, size_t n, const TiledInfo* info, uint64_t k, size_t* off,
                                  size_t* len);
 
+// ---- Scaled coding (DESIGN.md section 5 "Scaled coding").  The scaled file, all integers big-endian:
+//     4 bytes "MLS1" | >B version 0 | >B flags (bit 0: the inner file has a VBR level word)
+//     >B filter (0 lanczos3, 1 bicubic, 2 triangle) | >B reserved 0 | >II H, W (display size) | the inner file
+// The inner file is the plain or VBR file above of the coded size, unchanged, to the end.  As H, "MLS1" exceeds
+// every max_pixels, so container_parse refuses a scaled file as it refuses a tiled one.
+constexpr size_t SCALED_HEADER = 16;
+struct ScaledInfo {
+  uint32_t H, W;  // display size
+  uint32_t filter;
+  bool vbr;
+  size_t inner_off, inner_len;  // the inner file: data[inner_off, inner_off + inner_len)
+  ContainerInfo inner;          // its parse, offsets relative to the inner file
+};
+inline bool is_scaled_file(const uint8_t* data, size_t n) {
+  return n >= 4 && data[0] == 'M' && data[1] == 'L' && data[2] == 'S' && data[3] == '1';
+}
+// nullptr when display / coded lie in [1/8, 8] (one axis)
+const char* scaled_ratio_check(uint64_t display, uint64_t coded);
+// inner: the coded image's file (container_write's), inner_len bytes.  The *len / out / cap protocol of
+// container_write (inner may be null for a size query).  The inner file is not parsed here.
+const char* container_write_scaled(uint32_t H, uint32_t W, bool vbr, uint32_t filter, const uint8_t* inner,
+                                   size_t inner_len, uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: a truncated header, bad magic, version, flags, filter or reserved byte, H or W
+// zero, H * W > max_pixels, whatever container_parse (vbr from the flags, n_levels, max_pixels) refuses in the inner
+// file, a coded size whose ratio to the display size leaves [1/8, 8] on either axis.
+const char* container_parse_scaled(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                   ScaledInfo* info);
+
 }  // namespace mlic
 #endif

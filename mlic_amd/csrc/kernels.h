@@ -314,6 +314,18 @@ void image_egress_u8(const float* src, const int64_t* src_strides, int B, int H,
 // overlap the n images at src, nor any image src_index names.  Checks its arguments before any HIP call.
 void image_blur3_pad(const float* src, const int32_t* src_index, int n, int H, int W, int Hp, int Wp, const float* w9,
                      float* dst, hipStream_t st);
+// Scaled coding's edge kernels (resample.hip; DESIGN.md section 5 "Scaled coding"): image_ingest_u8 / image_egress_u8
+// with the separable polyphase resampler of resample_table.h fused in (filter 0 lanczos3, 1 bicubic, 2 triangle).
+// ingest: Hi x Wi bytes -> the h x w coded image, clamped to [0, 1], in fp32 [B][3][Hp][Wp] with +0 padding.
+// egress: the h x w crop of src, clamped, -> Ho x Wo bytes, with the exact squared error against ref.  Strides as
+// in the plain calls; every ratio output / input must lie in [1/8, 8].  The tables are device arrays built on
+// first use of a (filter, input length, output length) triple (a blocking copy) and kept.  Both check their
+// arguments before any HIP call and throw.
+void image_ingest_u8_scaled(const uint8_t* src, const int64_t* src_strides, int B, int Hi, int Wi, int filter, int h,
+                            int w, float* dst, int Hp, int Wp, hipStream_t st);
+void image_egress_u8_scaled(const float* src, const int64_t* src_strides, int B, int h, int w, int filter, int Ho,
+                            int Wo, uint8_t* dst, const int64_t* dst_strides, const uint8_t* ref,
+                            const int64_t* ref_strides, uint64_t* sq_err, hipStream_t st);
 // 8-bit Y'CbCr frame I/O (image_yuv.hip; DESIGN.md section 5 "YCbCr I/O").  The fields of mlic_yuv_desc.
 struct YuvDesc {
   int32_t sub_x, sub_y, matrix, full_range, site_x, reserved[3];

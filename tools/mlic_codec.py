@@ -16,6 +16,14 @@
         whatever the image's size.  Goes with --level N; not with --max-bpp, --level auto or --roi
     ... --region Y0 X0 H W (decode, a tiled file): decode that window only; the tiles outside it are not touched.
         A tiled file is recognised by its magic; decode needs no --tile
+    ... --scale N/D | --coded-size WxH [--filter lanczos3|bicubic|triangle] (encode): scaled coding.  The image is
+        resampled to the coded size (per axis max(1, floor(L * N/D + 1/2)), ratio 1/8 to 8) in the ingest launch,
+        coded at that size, and the scaled file records the display size and the filter; --level and --max-bpp act
+        on the coded image, bpp is the whole file over the display pixels.  A scaled file is recognised by its
+        magic and decodes to its display size
+    ... --out-size WxH [--filter F] (decode): the output size of any plain, VBR or scaled file (a thumbnail
+        without the full-size image; a plain file is resampled with lanczos3 unless --filter says otherwise).
+        Scaled coding is not together with --roi, --tile, --region, frame files or a depth above 8
     ... a source (encode) or destination (decode) named .y4m or .yuv is an 8-bit Y'CbCr frame, coded without an RGB
         round trip (codec.encode_yuv / decode_yuv).  .y4m: C420jpeg (centre-sited chroma), C420mpeg2 / C420 (left),
         C422, C444; any other colour space or bit depth is refused by its tag.  Raw .yuv: --yuv i420|nv12|nv21|yv12|
@@ -390,7 +398,12 @@ def parse_args(argv=None):
     ap.add_argument("--chroma-site", choices=["left", "centre"], default=None)
     ap.add_argument("--frame", type=int, default=0, metavar="N")
     ap.add_argument("--ref", default=None, metavar="SRC")
+    ap.add_argument("--scale", default=None, metavar="N/D")
+    ap.add_argument("--coded-size", type=_size, default=None, metavar="WxH")
+    ap.add_argument("--filter", choices=["lanczos3", "bicubic", "triangle"], default=None)
+    ap.add_argument("--out-size", type=_size, default=None, metavar="WxH")
     args = ap.parse_args(argv)
+    scaling = args.scale is not None or args.coded_size is not None
     frame_file = args.mode != "info" and _is_yuv(args.src if args.mode == "encode" else (args.dst or ""))
     if frame_file:
         if args.roi is not None or args.roi_levels is not None or args.tile is not None or args.region is not None:
@@ -415,6 +428,25 @@ def parse_args(argv=None):
     if args.ref is not None and not (frame_file and args.mode == "decode"):
         ap.error("--ref goes with decode to a .y4m or .yuv file")
     args.frame_file = frame_file
+    if scaling or args.out_size is not None:
+        if args.scale is not None and args.coded_size is not None:
+            ap.error("--scale and --coded-size are two ways to say one thing: pass one")
+        if scaling and args.mode != "encode":
+            ap.error("--scale and --coded-size go with encode (a scaled file is recognised by its magic)")
+        if args.out_size is not None and args.mode != "decode":
+            ap.error("--out-size goes with decode")
+        if frame_file or args.roi is not None or args.tile is not None or args.region is not None or (args.depth or 8) > 8:
+            ap.error("scaled coding together with Y'CbCr frames, ROI, tiles or a depth above 8 is not supported")
+        if args.scale is not None:
+            from fractions import Fraction
+            try:
+                args.scale = Fraction(args.scale)
+            except (ValueError, ZeroDivisionError):
+                ap.error("--scale: a fraction N/D expected")
+            if not Fraction(1, 8) <= args.scale <= 8:
+                ap.error("--scale: 1/8 to 8 expected")
+    elif args.filter is not None and args.mode != "decode":
+        ap.error("--filter goes with --scale, --coded-size or decode")
     if args.tile is not None:
         if args.mode != "encode":
             ap.error("--tile goes with encode (a tiled file is recognised by its magic)")
@@ -481,6 +513,11 @@ def main(argv=None):
                 print(f"  tile {t['index']}: at ({t['y0']}, {t['x0']}), {t['H']} x {t['W']}, {t['bytes']} bytes, "
                       f"{t['bpp']:.4f} bpp")
             return
+        if d.get("scaled"):
+            print(f"{args.src}: {d['H']} x {d['W']}, scaled: coded at {d['coded'][0]} x {d['coded'][1]}, filter "
+                  f"{d['filter']}, level {d['level']}, z grid {d['shape'][0]} x {d['shape'][1]}, y {d['y_len']} B, "
+                  f"z {d['z_len']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
+            return
         print(f"{args.src}: {d['H']} x {d['W']}, level {d['level']}, z grid {d['shape'][0]} x {d['shape'][1]}, "
               f"y {d['y_len']} B, z {d['z_len']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
         if "roi_levels" in d:
@@ -544,9 +581,20 @@ def main(argv=None):
             if roi.shape != img.shape[:2]:
                 raise SystemExit(f"{args.roi}: the mask is {roi.shape[0]} x {roi.shape[1]}, the image "
                                  f"{img.shape[0]} x {img.shape[1]}")
-        files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
-                                          max_passes=args.max_passes, return_info=True, roi=roi,
-                                          roi_levels=None if roi is None else tuple(args.roi_levels), **deep)
+        scaled = {}
+        if args.scale is not None or args.coded_size is not None:
+            if depth != 8:
+                raise SystemExit(f"{args.src}: scaled coding of an image deeper than 8 bits is not supported")
+            scaled = {"scale": args.scale, "filter": args.filter or "lanczos3",
+                      "coded_size": None if args.coded_size is None else (args.coded_size[1], args.coded_size[0])}
+        try:
+            files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
+                                              max_passes=args.max_passes, return_info=True, roi=roi,
+                                              roi_levels=None if roi is None else tuple(args.roi_levels), **deep, **scaled)
+        except ValueError as e:
+            if not scaled:
+                raise
+            raise SystemExit(f"{args.src}: {e}") from None
         data = files[0]
         with open(args.dst, "wb") as f:
             f.write(data)
@@ -554,6 +602,8 @@ def main(argv=None):
                 f"{8.0 * len(data) / (img.shape[0] * img.shape[1]):.4f} bpp")
         if depth != 8:
             line += f", depth {depth}"
+        if scaled:
+            line += f", coded at {info[0]['coded'][0]} x {info[0]['coded'][1]} ({info[0]['filter']})"
         if args.max_bpp is not None:
             line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
                      f"{'met' if info[0]['met'] else 'not met'}")
@@ -575,9 +625,23 @@ def main(argv=None):
         if args.region is not None:
             raise SystemExit(f"{args.src}: --region needs a tiled file (encode --tile T)")
         depth = args.depth or 8
-        img, info = codec.decode_images(net, [data], **({} if depth == 8 else {"depth": depth}))
+        kw = {} if depth == 8 else {"depth": depth}
+        if args.out_size is not None:
+            kw["out_size"] = (args.out_size[1], args.out_size[0])
+        if args.filter is not None:
+            kw["filter"] = args.filter
+        try:
+            img, info = codec.decode_images(net, [data], **kw)
+        except ValueError as e:
+            if not (args.out_size or args.filter or codec.is_scaled_file(data)):
+                raise
+            raise SystemExit(f"{args.src}: {e}") from None
         save_image(args.dst, img[0].cpu().numpy(), depth)
-        print(f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp")
+        line = f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp"
+        if "coded" in info[0]:
+            line += (f", display {info[0]['display'][0]} x {info[0]['display'][1]}, coded at {info[0]['coded'][0]} x "
+                     f"{info[0]['coded'][1]} ({info[0]['filter']})")
+        print(line)
 
 
 if __name__ == "__main__":
