@@ -128,6 +128,44 @@ int mlic_image_sq_err_roi_u8(void* stream, const uint8_t* a, const int64_t* a_st
                              const int64_t* b_strides, const uint8_t* mask, const int64_t* mask_strides, int B, int H,
                              int W, uint64_t* out);
 
+/* Rate maps: where the entropy model's bits lie.  y_lik: fp32 [B][M][h][w] and z_lik: fp32 [B][N][h/4][w/4] on the
+ * device (mlic_forward's likelihood tensors), each image dense, y_bs / z_bs the batch strides in floats.  Outputs
+ * (device doubles; each may be NULL, at least one is given):
+ *   y_map [B][S][h][w]   per latent pixel, the sum over the slice's M / S channels, ascending, from +0.0, of
+ *                        -(double)log2f(lik) -- the per-element term of mlic_neglog2_sum and mlic_encoded_bits
+ *   z_map [B][h/4][w/4]  the same sum over the N channels of z
+ *   cell_bits [B][h][w]  ((z_map[i/4][j/4] / 16 + y_map[0][i][j]) + y_map[1][i][j]) + ... + y_map[S-1][i][j]
+ *   slice_bits [B][S+1]  the total of y_map[0 .. S-1] and, last, of z_map.  Per row, lane l of 64 adds elements l,
+ *                        l + 64, ... from +0.0, the 64 sums are folded in halves (l += l + 32, 16, 8, 4, 2, 1);
+ *                        the row sums are added top to bottom from +0.0.
+ * A likelihood of 1 adds +0.0 (no -0.0 reaches an output), a NaN likelihood gives a NaN cell, every element is
+ * written, and the bits do not depend on B, the image's place in the batch or the strides.  Two launches on
+ * `stream`.  With y_map and z_map both given the call is asynchronous; a missing one that cell_bits / slice_bits
+ * need is computed into scratch the call allocates, and the call then waits for the stream before it frees it.
+ * Refused before any GPU call: null likelihoods or no output; B, M, S, N, h or w < 1; M % S; h % 4 or w % 4; a
+ * batch stride below one image; B, M or N above 2^20. */
+int mlic_rate_map_run(void* stream, const float* y_lik, int64_t y_bs, const float* z_lik, int64_t z_bs, int B, int M,
+                      int S, int h, int w, int N, double* y_map, double* z_map, double* cell_bits, double* slice_bits);
+/* Error map: out [B][ceil(H / block)][ceil(W / block)] uint32 (device) = the sum of squared byte differences of the
+ * uint8 images a and b ({image, row, column, channel} strides each, read in place) over each block x block square
+ * clipped to H x W, three channels (<= 64 * 64 * 3 * 255^2).  Integers; the grid's sum is mlic_image_egress_u8's
+ * sq_err.  One launch, asynchronous.  Refused: null arguments; B, H or W < 1; a block other than 8, 16, 32, 64; a
+ * zero column or channel stride; strides whose last byte offset overflows int64. */
+int mlic_image_sq_err_blocks_u8(void* stream, const uint8_t* a, const int64_t* a_strides, const uint8_t* b,
+                                const int64_t* b_strides, int B, int H, int W, int block, uint32_t* out);
+/* Heat map: plane [B][ph][pw] (device doubles; ph * cell >= H, pw * cell >= W) drawn at H x W as uint8 RGB through
+ * dst's {image, row, column, channel} strides.  Pixel (y, x) shows cell (y / cell, x / cell); cell in {8, 16, 32,
+ * 64} (16: cell_bits / y_map, 64: z_map, block: an error map converted to double).
+ *     q = clamp(floor((v - lo) / (hi - lo) * 255 + 0.5), 0, 255)      each operation a rounded double operation
+ * (+-inf clamp), cmap 0 = gray: (q, q, q); 1 = hot: (min(255, 3q), clamp(3q - 255, 0, 255), clamp(3q - 510, 0, 255)).
+ * With `under` (uint8, its own strides; NULL: none) out = (alpha * colour + (256 - alpha) * under + 128) >> 8,
+ * alpha in [0, 256]; a NaN cell is (255, 0, 255), unblended.  One launch, asynchronous; only the image's bytes are
+ * written.  Refused: null plane / dst / strides; sizes < 1; a bad cell, cmap or alpha; a plane that does not cover
+ * the image; lo or hi not finite, or hi <= lo; alpha < 256 without `under`; zero or overflowing strides. */
+int mlic_image_heat_u8(void* stream, const double* plane, int B, int ph, int pw, int cell, double lo, double hi,
+                       int cmap, int H, int W, uint8_t* dst, const int64_t* dst_strides, const uint8_t* under,
+                       const int64_t* under_strides, int alpha);
+
 /* module-level entry points (tests / profiling): which = local|chan|inter|intra|epa|epn|lrpa|lrpn|g_a|h_a|h_s|g_s|rbu|rbws */
 int mlic_run_module(mlic_model* m, void* stream, const char* which, int idx, const float* in0, const float* in1,
                     int B, int Cin, int H, int W, float* out);

@@ -11,10 +11,11 @@ from .codec import (coded_size, egress_u8_scaled, ingest_u8_scaled, is_scaled_fi
 from .codec import blend_tiles, decode_tiled, encode_tiled, tile_grid  # noqa: F401
 from .codec import YuvFormat, decode_yuv, egress_yuv, encode_yuv, ingest_yuv, split_yuv  # noqa: F401
 from .codec import egress_u16, ingest_u16  # noqa: F401
+from .codec import heat_u8, rate_map, rate_maps, sq_err_blocks  # noqa: F401
 from .spec import CONFIGS  # noqa: F401
 
 __all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusVbr", "get_model", "model_config", "CONFIGS",
            "ms_ssim_u8", "ms_ssim_db", "LPIPS", "lpips_synthetic_weights", "DISTS", "dists_synthetic_weights", "ingest_u8", "egress_u8", "encode_images", "decode_images", "peek",
            "blur3_pad", "rate_loop", "tile_grid", "blend_tiles", "encode_tiled", "decode_tiled",
            "resample_table", "ingest_u8_scaled", "egress_u8_scaled", "write_container_scaled", "parse_container_scaled",
-           "is_scaled_file", "coded_size"]
+           "is_scaled_file", "coded_size", "rate_maps", "rate_map", "sq_err_blocks", "heat_u8"]

@@ -149,6 +149,9 @@ def _sig(lib):
         "mlic_image_roi_levels_u8": [p, p, P(i64), i, i, i, i, i, p],
         "mlic_roi_gain_plane": [p, p, i, i, i, P(f), i, p],
         "mlic_image_sq_err_roi_u8": [p, p, P(i64), p, P(i64), p, P(i64), i, i, i, p],
+        "mlic_rate_map_run": [p, p, i64, p, i64, i, i, i, i, i, i, p, p, p, p],
+        "mlic_image_sq_err_blocks_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p],
+        "mlic_image_heat_u8": [p, p, i, i, i, i, C.c_double, C.c_double, i, i, i, p, P(i64), p, P(i64), i],
         "mlic_container_write_roi": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, p, sz, p, p, sz, P(sz)],
         "mlic_container_parse_roi": [p, sz, i, C.c_uint64, P(ContainerRoiInfo), p, sz],
         "mlic_tile_grid": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32), p, sz],

@@ -99,7 +99,8 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
-               dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, yuv=None, **kw) -> Dict:
+               dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, yuv=None, rate_map: bool = False,
+               **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -122,9 +123,20 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     yuv=fmt (a codec.YuvFormat): the record also holds "sq_err_yuv" (three ints), "psnr_y", "psnr_u", "psnr_v" and
     "psnr_yuv" = (6 Y + U + V) / 8 of codec.egress_yuv(x_hat, fmt) against the source planes, which are taken as
     codec.egress_yuv(img, fmt): the RGB image's 4:4:4 conversion through the same formula, filtered as fmt says.
-    Not together with tile=, and refused for a format of depth > 8; off by default."""
+    Not together with tile=, and refused for a format of depth > 8; off by default.
+    rate_map=True: the record also holds "slice_bits" (one float per slice: the sum of -log2 of that slice's y
+    likelihoods) and "z_bits" (the same for z), codec.rate_maps' slice_bits of one extra forward() of the padded
+    image with the coder's arguments (s=, or the ROI gain plane).  Not together with tile=, yuv=, max_bpp= (the loop
+    codes a filtered image), scale= / coded_size= or depth=; off by default, and the file bytes are the same either
+    way."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
+    if rate_map:
+        given = {"tile": tile, "yuv": yuv, "max_bpp": max_bpp, "scale": kw.get("scale"),
+                 "coded_size": kw.get("coded_size"), "depth": kw.get("depth")}
+        for k, v in given.items():
+            if v is not None:
+                raise ValueError(f"code_image: rate_map=True together with {k}= is not supported")
     if yuv is not None and tile is not None:
         raise ValueError("code_image: yuv= together with tile= is not supported")
     if yuv is not None and getattr(yuv, "depth", 8) > 8:
@@ -213,6 +225,12 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     if roi is not None:
         p = codec.psnr_roi(to_u8(img), to_u8(x_hat), mask, layout="chw")[0]
         r["psnr_roi"], r["psnr_bg"], r["roi_levels"] = p["psnr_roi"], p["psnr_bg"], fmap
+    if rate_map:
+        from . import codec
+        fkw = {"gain_map": codec.gain_plane(net, lmap)} if roi is not None else \
+            {k: v for k, v in kw.items() if k != "batch_stream"}
+        sb = net.rate_map(x.contiguous().float(), **fkw)["slice_bits"][0].cpu().tolist()
+        r["slice_bits"], r["z_bits"] = sb[:-1], sb[-1]
     if yuv is not None:
         from . import codec
         src = codec.egress_yuv(img.float().contiguous(), H, W, yuv)

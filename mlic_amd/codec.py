@@ -29,6 +29,11 @@ the same front doors for samples of 9 to 16 bits in uint16 words (DESIGN.md §5 
 csrc/image_io16.hip): nothing is rounded to 8 bits on the way, the file does not know its depth, and PSNR is
 computed at the peak 2^depth - 1.  uint16 tensors are only moved and viewed on the device, never computed with.
 
+`rate_maps` / `rate_map` say where the entropy model's bits lie (DESIGN.md §5 "Rate maps", csrc/ratemap.hip): per
+latent pixel and slice the sum of -log2 of forward()'s likelihoods, the per-cell total with z's share, and the
+per-slice totals; `sq_err_blocks` is the matching error map (squared uint8 error per block) and `heat_u8` draws either
+as a heat map, optionally blended over the image.
+
 CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
 """
@@ -792,6 +797,297 @@ def psnr_roi(a, b, mask, layout: Optional[str] = None) -> List[Dict]:
     return out
 
 
+def _roi_map(net, roi, roi_levels, shape, what: str):
+    """roi= / roi_levels= of a *_VBR model, checked -> (the level map on the model's device, hi)."""
+    if not hasattr(net, "levels"):
+        raise ValueError("roi= given for a fixed-rate model: ROI coding needs a *_VBR model")
+    try:
+        lo, hi = roi_levels
+    except (TypeError, ValueError):
+        raise ValueError(f"roi_levels: a pair (lo, hi) expected, got {roi_levels!r}") from None
+    _check_roi_levels(lo, hi, "roi_levels")
+    if hi >= min(int(net.levels), 16):
+        raise ValueError(f"roi_levels: levels in [0, {min(int(net.levels), 16)}) expected, got ({lo}, {hi})")
+    mask = _mask_batch(roi, f"{what} roi")
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"{what}: roi must be a mask of shape {tuple(shape)}, got {tuple(mask.shape)}")
+    return _roi_level_map(mask.to(net.device), int(lo), int(hi)), hi
+
+
+# ---------------------------------------------------------------------------------------- rate maps
+CMAPS = ("gray", "hot")  # heat_u8's colour maps; the library's cmap argument is the index
+MAP_BLOCKS = (8, 16, 32, 64)  # sq_err_blocks' block sizes and heat_u8's cell sizes
+
+
+def _lik_batch(t, what: str) -> torch.Tensor:
+    """A likelihood tensor the kernel can read in place: fp32 [B,C,h,w], every image dense (any batch stride)."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 4 or 0 in t.shape:
+        raise ValueError(f"rate_maps: {what}: a float32 tensor [B,C,h,w] expected")
+    return t if t[0].is_contiguous() and t.stride(0) >= t[0].numel() else t.contiguous()
+
+
+def _cell_bits_cpu(y_map: torch.Tensor, z_map: torch.Tensor) -> torch.Tensor:
+    """cell_bits [B,h,w] from y_map [B,S,h,w] and z_map [B,h/4,w/4], the kernel's sequence in CPU doubles:
+    ((z / 16 + y[0]) + y[1]) + ... + y[S-1], a z pixel standing for its 4 x 4 latent pixels."""
+    y, z = y_map.detach().cpu().double(), z_map.detach().cpu().double()
+    v = z.repeat_interleave(4, 1).repeat_interleave(4, 2) / 16.0
+    for s in range(y.size(1)):
+        v = v + y[:, s]
+    return v
+
+
+def _plane_sum_cpu(p: torch.Tensor) -> torch.Tensor:
+    """[..., ph, pw] doubles -> [...]: the kernel's order.  Per row, lane l of 64 adds the elements l, l + 64, ... from
+    +0.0, the 64 lane sums are folded in halves (l += l + 32, then 16, 8, 4, 2, 1), and the row sums are added top
+    to bottom from +0.0."""
+    p = p.detach().cpu().double()
+    lead, (ph, pw) = p.shape[:-2], p.shape[-2:]
+    n = (pw + 63) // 64
+    q = torch.zeros(*lead, ph, n * 64, dtype=torch.float64)  # a lane past the row's end adds nothing: + 0.0 is exact
+    q[..., :pw] = p
+    q = q.reshape(*lead, ph, n, 64)
+    v = torch.zeros(*lead, ph, 64, dtype=torch.float64)
+    for k in range(n):
+        v = v + q[..., k, :]
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v[..., :off] + v[..., off:2 * off]
+    total = torch.zeros(lead, dtype=torch.float64)
+    for r in range(ph):
+        total = total + v[..., r, 0]
+    return total
+
+
+def _slice_bits_cpu(y_map: torch.Tensor, z_map: torch.Tensor) -> torch.Tensor:
+    """slice_bits [B,S+1] from the two maps: _plane_sum_cpu of each y_map[s], then of z_map."""
+    return torch.cat([_plane_sum_cpu(y_map), _plane_sum_cpu(z_map).unsqueeze(1)], 1)
+
+
+def rate_maps(y_lik: torch.Tensor, z_lik: torch.Tensor, slices: int) -> Dict[str, torch.Tensor]:
+    """Where the entropy model's bits lie (DESIGN.md §5 "Rate maps").  y_lik fp32 [B,M,h,w] and z_lik fp32
+    [B,N,h/4,w/4] -- forward()'s likelihood tensors, or batch-strided views of them, read in place -> float64
+    tensors on their device:
+        "y_map" [B,S,h,w]    per latent pixel and slice (M / S channels each), the sum in ascending channel order of
+                             -(double)log2f(lik), the term mlic_encoded_bits / likelihood_bits sum
+        "z_map" [B,h/4,w/4]  the same over z's N channels
+        "cell_bits" [B,h,w]  z_map / 16 (a z pixel covers 4 x 4 latent pixels) + y_map[0] + ... + y_map[S-1]
+        "slice_bits" [B,S+1] the totals of y_map[0 .. S-1] and of z_map (_plane_sum_cpu's order)
+    A latent pixel is 16 x 16 image pixels.  Two launches (csrc/ratemap.hip); bit-identical across batch size,
+    batch position and strides.  CPU tensors run the same sums on torch's fp32 log2 (the device's log2f may differ
+    from it in the last bit of a term)."""
+    y_lik, z_lik = _lik_batch(y_lik, "y_lik"), _lik_batch(z_lik, "z_lik")
+    B, M, h, w = y_lik.shape
+    S = int(slices)
+    if S < 1 or M % S:
+        raise ValueError(f"rate_maps: {M} channels do not split into {slices} slices")
+    if h % 4 or w % 4 or tuple(z_lik.shape[::3]) != (B, w // 4) or z_lik.size(2) != h // 4 or z_lik.device != y_lik.device:
+        raise ValueError(f"rate_maps: z_lik [B,N,h/4,w/4] on y_lik's device expected for y_lik {tuple(y_lik.shape)}, got "
+                         f"{tuple(z_lik.shape)} on {z_lik.device}")
+    N = z_lik.size(1)
+    if not y_lik.is_cuda:
+        ty, tz = -torch.log2(y_lik), -torch.log2(z_lik)
+        y_map = torch.zeros(B, S, h, w, dtype=torch.float64)
+        z_map = torch.zeros(B, h // 4, w // 4, dtype=torch.float64)
+        for c in range(M // S):
+            y_map = y_map + ty[:, c::M // S].double()
+        for c in range(N):
+            z_map = z_map + tz[:, c].double()
+        return {"y_map": y_map, "z_map": z_map, "cell_bits": _cell_bits_cpu(y_map, z_map),
+                "slice_bits": _slice_bits_cpu(y_map, z_map)}
+    dev = y_lik.device
+    with torch.cuda.device(dev):
+        out = {"y_map": (B, S, h, w), "z_map": (B, h // 4, w // 4), "cell_bits": (B, h, w), "slice_bits": (B, S + 1)}
+        out = {k: torch.empty(v, dtype=torch.float64, device=dev) for k, v in out.items()}
+        if _lib.poison():
+            for t in out.values():
+                t.fill_(float("nan"))
+        y_bs, z_bs = ((t.stride(0) if B > 1 else t[0].numel()) for t in (y_lik, z_lik))  # one image: no stride
+        _lib.call("mlic_rate_map_run", _stream(), C.c_void_p(y_lik.data_ptr()), y_bs,
+                  C.c_void_p(z_lik.data_ptr()), z_bs, B, M, S, h, w, N, C.c_void_p(out["y_map"].data_ptr()),
+                  C.c_void_p(out["z_map"].data_ptr()), C.c_void_p(out["cell_bits"].data_ptr()),
+                  C.c_void_p(out["slice_bits"].data_ptr()))
+    return out
+
+
+def _check_block(block, what: str) -> int:
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in MAP_BLOCKS:
+        raise ValueError(f"{what} must be one of {MAP_BLOCKS}, got {block!r}")
+    return int(block)
+
+
+def _sq_err_blocks_cpu(a: torch.Tensor, b: torch.Tensor, block: int, layout: str) -> torch.Tensor:
+    """sq_err_blocks in torch integers: 4-dim uint8 batches of one shape -> int64 [B,ceil(H/block),ceil(W/block)]."""
+    d = _nchw(a, layout).to(torch.int64) - _nchw(b, layout).to(torch.int64)
+    sq = (d * d).sum(1)
+    B, H, W = sq.shape
+    nby, nbx = -(-H // block), -(-W // block)
+    full = torch.zeros(B, nby * block, nbx * block, dtype=torch.int64, device=sq.device)
+    full[:, :H, :W] = sq
+    return full.reshape(B, nby, block, nbx, block).sum((2, 4))
+
+
+def sq_err_blocks(a, b, block: int = 16, layout: Optional[str] = None) -> torch.Tensor:
+    """Two uint8 image batches of one shape (any strides, read in place) -> int64 [B,ceil(H/block),ceil(W/block)] on
+    their device: per block x block square (the last ones cropped to the image) the sum of squared byte differences
+    over its pixels and three channels, in integers.  block: 8, 16, 32 or 64.  The grid's sum is egress_u8's sq_err
+    and sq_err_roi's inside + outside.  One launch."""
+    a, layout = _u8_batch(a, layout, "sq_err_blocks")
+    b, _ = _u8_batch(b, layout, "sq_err_blocks")
+    block = _check_block(block, "sq_err_blocks: block")
+    if tuple(b.shape) != tuple(a.shape):
+        raise ValueError(f"sq_err_blocks: images of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    b = b.to(a.device)
+    if not a.is_cuda:
+        return _sq_err_blocks_cpu(a, b, block, layout)
+    a, b = _in_place(a, layout), _in_place(b, layout)
+    B = a.size(0)
+    H, W = _hw(a, layout)
+    with torch.cuda.device(a.device):
+        out = torch.full((B, -(-H // block), -(-W // block)), -1, dtype=torch.int32, device=a.device)  # < 2^30 each
+        _lib.call("mlic_image_sq_err_blocks_u8", _stream(), C.c_void_p(a.data_ptr()),
+                  (C.c_int64 * 4)(*_strides(a, layout)), C.c_void_p(b.data_ptr()), (C.c_int64 * 4)(*_strides(b, layout)),
+                  B, H, W, block, C.c_void_p(out.data_ptr()))
+        b.record_stream(torch.cuda.current_stream())
+    return out.to(torch.int64)
+
+
+def _check_heat(plane, H, W, cell, lo, hi, cmap, under, alpha, layout):
+    """heat_u8's arguments, checked -> (plane float64 [B,ph,pw], cell, lo, hi, cmap index, under or None, alpha)."""
+    if isinstance(plane, np.ndarray):
+        plane = torch.from_numpy(np.ascontiguousarray(plane))
+    if not torch.is_tensor(plane) or plane.dtype != torch.float64 or plane.dim() not in (2, 3) or 0 in plane.shape:
+        raise ValueError("heat_u8: a float64 plane [B,ph,pw] (or one [ph,pw]) expected")
+    if plane.dim() == 2:
+        plane = plane.unsqueeze(0)
+    cell = _check_block(cell, "heat_u8: cell")
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"heat_u8: layout must be 'hwc' or 'chw', got {layout!r}")
+    B, ph, pw = plane.shape
+    if not (1 <= H <= ph * cell and 1 <= W <= pw * cell):
+        raise ValueError(f"heat_u8: a {ph} x {pw} plane of {cell}-pixel cells does not cover {H} x {W}")
+    if cmap not in CMAPS:
+        raise ValueError(f"heat_u8: cmap must be one of {CMAPS}, got {cmap!r}")
+    lo = float(lo)
+    if hi is None:  # the plane's largest finite value, or lo + 1 for a plane that has none above lo
+        fin = plane[torch.isfinite(plane)]
+        hi = float(fin.max()) if fin.numel() else lo
+        if not hi > lo:
+            hi = lo + 1.0
+    hi = float(hi)
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo and math.isfinite(hi - lo)):
+        raise ValueError(f"heat_u8: finite lo < hi expected, got ({lo!r}, {hi!r})")
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, np.integer)) or not 0 <= alpha <= 256:
+        raise ValueError(f"heat_u8: alpha must be an integer in [0, 256], got {alpha!r}")
+    if under is None:
+        if alpha != 256:
+            raise ValueError("heat_u8: alpha below 256 blends with an under-image: pass under=")
+    else:
+        under, _ = _u8_batch(under, layout, "heat_u8 under")
+        shape = (B, H, W, 3) if layout == "hwc" else (B, 3, H, W)
+        if tuple(under.shape) != shape:
+            raise ValueError(f"heat_u8: under must have shape {shape}, got {tuple(under.shape)}")
+    return plane, cell, lo, hi, CMAPS.index(cmap), under, int(alpha)
+
+
+def _heat_colours(q: np.ndarray, cmap: int) -> np.ndarray:
+    """q int64 [...] in [0, 255] -> int64 [..., 3], the library's integer colour maps."""
+    if cmap == 0:
+        return np.stack([q, q, q], -1)
+    return np.stack([np.minimum(255, 3 * q), np.clip(3 * q - 255, 0, 255), np.clip(3 * q - 510, 0, 255)], -1)
+
+
+def _heat_u8_cpu(plane, H: int, W: int, cell: int, lo: float, hi: float, cmap: int, under, alpha: int,
+                 layout: str) -> torch.Tensor:
+    """heat_u8 in NumPy (checked arguments, cmap as the index): the kernel's operations one by one."""
+    p = plane.detach().cpu().numpy()
+    v = p[:, np.arange(H) // cell][:, :, np.arange(W) // cell]  # [B,H,W]
+    with np.errstate(all="ignore"):
+        f = np.floor((v - lo) / (hi - lo) * 255.0 + 0.5)
+    nan = np.isnan(v)
+    q = np.where(nan, 0.0, np.clip(f, 0.0, 255.0)).astype(np.int64)
+    col = _heat_colours(q, cmap)  # [B,H,W,3]
+    if under is not None:
+        u = _nchw(under.detach().cpu(), layout).permute(0, 2, 3, 1).numpy().astype(np.int64)
+        col = (alpha * col + (256 - alpha) * u + 128) >> 8
+    col = np.where(nan[..., None], np.array([255, 0, 255]), col).astype(np.uint8)
+    out = torch.from_numpy(col)
+    return out if layout == "hwc" else out.permute(0, 3, 1, 2).contiguous()
+
+
+def heat_u8(plane, H: int, W: int, cell: int, lo: float = 0.0, hi: Optional[float] = None, cmap: str = "hot",
+            under=None, alpha: int = 256, layout: str = "hwc") -> torch.Tensor:
+    """A float64 plane [B,ph,pw] (or one [ph,pw]) drawn at H x W as a uint8 RGB heat map in `layout`: [B,H,W,3] or
+    [B,3,H,W].  Pixel (y, x) shows cell (y // cell, x // cell); cell is 16 for cell_bits / y_map[s], 64 for z_map,
+    the block for an error map (sq_err_blocks(...).double()).
+        q = clamp(floor((v - lo) / (hi - lo) * 255 + 0.5), 0, 255)       (+-inf clamp; hi=None: the plane's maximum)
+    cmap "gray" is (q, q, q); "hot" is (min(255, 3q), clamp(3q - 255, 0, 255), clamp(3q - 510, 0, 255)).  under: a
+    uint8 image batch of the output's shape (any strides) to blend over, out = (alpha * colour + (256 - alpha) *
+    under + 128) >> 8 with alpha in [0, 256]; a NaN cell is drawn (255, 0, 255) unblended.  One launch on the
+    plane's device (csrc/ratemap.hip); a CPU plane runs the NumPy restatement."""
+    plane, cell, lo, hi, cm, under, alpha = _check_heat(plane, H, W, cell, lo, hi, cmap, under, alpha, layout)
+    if not plane.is_cuda:
+        return _heat_u8_cpu(plane, H, W, cell, lo, hi, cm, under, alpha, layout)
+    plane = plane.contiguous()
+    B, ph, pw = plane.shape
+    with torch.cuda.device(plane.device):
+        out = torch.empty((B, H, W, 3) if layout == "hwc" else (B, 3, H, W), dtype=torch.uint8, device=plane.device)
+        if under is not None:
+            under = _in_place(under.to(plane.device), layout)
+        _lib.call("mlic_image_heat_u8", _stream(), C.c_void_p(plane.data_ptr()), B, ph, pw, cell, lo, hi, cm, H, W,
+                  C.c_void_p(out.data_ptr()), (C.c_int64 * 4)(*_strides(out, layout)),
+                  None if under is None else C.c_void_p(under.data_ptr()),
+                  None if under is None else (C.c_int64 * 4)(*_strides(under, layout)), alpha)
+        if under is not None:
+            under.record_stream(torch.cuda.current_stream())
+    return out
+
+
+_RATE_MAP_REFUSED = {"tile": "tiled coding", "overlap": "tiled coding", "scale": "scaled coding",
+                     "coded_size": "scaled coding", "filter": "scaled coding", "depth": "samples deeper than 8 bits",
+                     "msb": "samples deeper than 8 bits", "yuv": "Y'CbCr frames", "fmt": "Y'CbCr frames",
+                     "max_bpp": "the rate loop", "max_passes": "the rate loop"}
+
+
+def _refuse_rate_map(what: str, names):
+    """Rate maps exist for plain and ROI coding of 8-bit RGB: any other coding option is refused by its name."""
+    for k in names:
+        if k not in _RATE_MAP_REFUSED:
+            raise TypeError(f"{what}: unexpected argument {k!r}")
+        raise ValueError(f"{what}: rate maps together with {k}= ({_RATE_MAP_REFUSED[k]}) are not supported")
+
+
+@torch.no_grad()
+def rate_map(net, imgs_u8, level=None, layout: Optional[str] = None, roi=None, roi_levels=None, **refused) -> List[Dict]:
+    """uint8 images (encode_images' forms) -> per image the rate maps of one net.rate_map over the batch (one ingest
+    launch, one forward, the two map launches): {"y_map" [S,h,w], "z_map" [h/4,w/4], "cell_bits" [h,w],
+    "slice_bits" [S+1]} (float64, on the model's device, on the padded image's grids: cells wholly in the padding
+    included), "bits" (slice_bits added left to right, a float), "bpp" = bits / (H * W), "x_hat" (the padded fp32
+    reconstruction [3,Hp,Wp]), "H", "W".  level / roi= with roi_levels= as encode_images takes them (roi not
+    together with level).  tile=, scale= / coded_size=, depth=, yuv= and max_bpp= are refused by name."""
+    _refuse_rate_map("rate_map", refused)
+    img, layout = _u8_batch(imgs_u8, layout, "rate_map")
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    if (roi is None) != (roi_levels is None):
+        raise ValueError("roi= and roi_levels=(lo, hi) go together")
+    if roi is not None:
+        if level is not None:
+            raise ValueError("roi= together with level=: the levels of an ROI encode are roi_levels=(lo, hi)")
+        lmap, _ = _roi_map(net, roi, roi_levels, (B, H, W), "rate_map")
+        kw = {"gain_map": gain_plane(net, lmap)}
+    else:
+        _, kw = _levels(net, level, B)
+    m = net.rate_map(ingest_u8(img.to(net.device), layout), **kw)
+    out = []
+    for b, sb in enumerate(m["slice_bits"].cpu().tolist()):
+        bits = 0.0
+        for v in sb:
+            bits = bits + v
+        out.append({"y_map": m["y_map"][b], "z_map": m["z_map"][b], "cell_bits": m["cell_bits"][b],
+                    "slice_bits": m["slice_bits"][b], "bits": bits, "bpp": bits / (H * W), "x_hat": m["x_hat"][b],
+                    "H": H, "W": W})
+    return out
+
+
 # -------------------------------------------------------------------------------------------- codec
 def _levels(net, level, B: int):
     """-> (per-image level list or None, kwargs of net.compress / net.decompress)."""
@@ -946,19 +1242,7 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
             raise ValueError("roi= together with max_bpp is not supported (ROI coding inside the rate loop)")
         if level is not None:
             raise ValueError("roi= together with level=: the levels of an ROI encode are roi_levels=(lo, hi)")
-        if not hasattr(net, "levels"):
-            raise ValueError("roi= given for a fixed-rate model: ROI coding needs a *_VBR model")
-        try:
-            lo, hi = roi_levels
-        except (TypeError, ValueError):
-            raise ValueError(f"roi_levels: a pair (lo, hi) expected, got {roi_levels!r}") from None
-        _check_roi_levels(lo, hi, "roi_levels")
-        if hi >= min(int(net.levels), 16):
-            raise ValueError(f"roi_levels: levels in [0, {min(int(net.levels), 16)}) expected, got ({lo}, {hi})")
-        mask = _mask_batch(roi, "encode_images roi")
-        if tuple(mask.shape) != (B, H, W):
-            raise ValueError(f"encode_images: roi must be a mask of shape {(B, H, W)}, got {tuple(mask.shape)}")
-        lmap = _roi_level_map(mask.to(net.device), int(lo), int(hi))
+        lmap, hi = _roi_map(net, roi, roi_levels, (B, H, W), "encode_images")
         out = net.compress(ingest(img.to(net.device), layout), gain_map=gain_plane(net, lmap))
         ys, zs = out["strings"]
         lmap = lmap.cpu().numpy()

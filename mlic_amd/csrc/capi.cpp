@@ -281,6 +281,44 @@ int mlic_image_sq_err_roi_u8(void* stream, const uint8_t* a, const int64_t* a_st
   });
 }
 
+int mlic_rate_map_run(void* stream, const float* y_lik, int64_t y_bs, const float* z_lik, int64_t z_bs, int B, int M,
+                      int S, int h, int w, int N, double* y_map, double* z_map, double* cell_bits, double* slice_bits) {
+  return guard([&] {
+    rate_map_check(y_lik, y_bs, z_lik, z_bs, B, M, S, h, w, N, y_map, z_map, cell_bits, slice_bits);
+    // cell_bits and slice_bits are computed from the two maps: a map the caller leaves out goes into scratch
+    const size_t ny = y_map ? 0 : (size_t)B * S * h * w, nz = z_map ? 0 : (size_t)B * (h / 4) * (w / 4);
+    if (ny + nz == 0) {
+      rate_map(y_lik, y_bs, z_lik, z_bs, B, M, S, h, w, N, y_map, z_map, cell_bits, slice_bits, (hipStream_t)stream);
+      return;
+    }
+    double* scratch = nullptr;
+    HIP_OK(hipMalloc(&scratch, sizeof(double) * (ny + nz)));
+    try {
+      rate_map(y_lik, y_bs, z_lik, z_bs, B, M, S, h, w, N, y_map ? y_map : scratch, z_map ? z_map : scratch + ny,
+               cell_bits, slice_bits, (hipStream_t)stream);
+      HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    } catch (...) {
+      (void)hipFree(scratch);
+      throw;
+    }
+    HIP_OK(hipFree(scratch));
+  });
+}
+
+int mlic_image_sq_err_blocks_u8(void* stream, const uint8_t* a, const int64_t* a_strides, const uint8_t* b,
+                                const int64_t* b_strides, int B, int H, int W, int block, uint32_t* out) {
+  return guard([&] { sq_err_blocks_u8(a, a_strides, b, b_strides, B, H, W, block, out, (hipStream_t)stream); });
+}
+
+int mlic_image_heat_u8(void* stream, const double* plane, int B, int ph, int pw, int cell, double lo, double hi,
+                       int cmap, int H, int W, uint8_t* dst, const int64_t* dst_strides, const uint8_t* under,
+                       const int64_t* under_strides, int alpha) {
+  return guard([&] {
+    image_heat_u8(plane, B, ph, pw, cell, lo, hi, cmap, H, W, dst, dst_strides, under, under_strides, alpha,
+                  (hipStream_t)stream);
+  });
+}
+
 int mlic_run_module(mlic_model* m, void* stream, const char* which, int idx, const float* in0, const float* in1,
                     int B, int Cin, int H, int W, float* out) {
   return guard([&] { impl(m).run_module(which, idx, in0, in1, B, Cin, H, W, out, (hipStream_t)stream); });

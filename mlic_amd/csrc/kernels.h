@@ -392,6 +392,31 @@ void roi_gain_plane(const uint8_t* levels, int B, int hz, int wz, const float* g
 void sq_err_roi_u8(const uint8_t* a, const int64_t* a_strides, const uint8_t* b, const int64_t* b_strides,
                    const uint8_t* mask, const int64_t* mask_strides, int B, int H, int W, uint64_t* out,
                    hipStream_t st);
+// Rate and error maps (ratemap.hip; DESIGN.md §5 "Rate maps").  All check their arguments before any HIP call
+// and throw.
+// y_lik [B][M][h][w], z_lik [B][N][h/4][w/4] (dense per image, batch strides y_bs / z_bs in floats) ->
+// y_map [B][S][h][w] (per latent pixel the slice's M / S channel terms -(double)log2f(lik), ascending, from +0.0),
+// z_map [B][h/4][w/4] (the N terms likewise), cell_bits [B][h][w] = ((z_map[i/4][j/4] / 16 + y_map[0]) + ...) +
+// y_map[S-1], slice_bits [B][S+1] (the sum of each y_map[s] and of z_map in ratemap.hip's fixed order).  y_map and
+// z_map are required here (the C entry puts scratch in a missing one's place); cell_bits / slice_bits may be null.
+// rate_map_check alone: the refusals, with every output optional but one.
+void rate_map_check(const float* y_lik, int64_t y_bs, const float* z_lik, int64_t z_bs, int B, int M, int S, int h, int w,
+                    int N, const double* y_map, const double* z_map, const double* cell_bits, const double* slice_bits);
+void rate_map(const float* y_lik, int64_t y_bs, const float* z_lik, int64_t z_bs, int B, int M, int S, int h, int w,
+              int N, double* y_map, double* z_map, double* cell_bits, double* slice_bits, hipStream_t st);
+// out [B][ceil(H / block)][ceil(W / block)] = the sum of squared byte differences of two uint8 images ({image, row,
+// column, channel} strides each) over each block x block square clipped to H x W, three channels; block in
+// {8, 16, 32, 64}; integers, every element written
+void sq_err_blocks_u8(const uint8_t* a, const int64_t* a_strides, const uint8_t* b, const int64_t* b_strides, int B,
+                      int H, int W, int block, uint32_t* out, hipStream_t st);
+// plane [B][ph][pw] (doubles) drawn at H x W as uint8 RGB through dst's {image, row, column, channel} strides: pixel
+// (y, x) shows cell (y / cell, x / cell), q = clamp(floor((v - lo) / (hi - lo) * 255 + 0.5), 0, 255) in separately
+// rounded double operations, cmap 0 = gray (q, q, q), 1 = hot (min(255, 3q), clamp(3q - 255), clamp(3q - 510)),
+// blended over `under` (optional, its own strides) as (alpha * colour + (256 - alpha) * under + 128) >> 8; a NaN
+// cell is (255, 0, 255) unblended.  One launch.
+void image_heat_u8(const double* plane, int B, int ph, int pw, int cell, double lo, double hi, int cmap, int H, int W,
+                   uint8_t* dst, const int64_t* dst_strides, const uint8_t* under, const int64_t* under_strides,
+                   int alpha, hipStream_t st);
 // mlic_set_kernel_option("image_io_path"): -1 = by layout (default), 0 = the general-stride kernels, 1 = the
 // interleaved (HWC) form, 2 = the planar (CHW) form; a forced form the layout does not fit is an error
 // GaussianConditional likelihood (vbr_scale != 1: of y*sc, s*sc, m*sc) and build_indexes, element-wise

@@ -251,6 +251,17 @@ class MLICPlusPlus(nn.Module):
                       z_lik.data_ptr(), sc.ctypes.data)
         return {"x_hat": x_hat, "likelihoods": {"y_likelihoods": y_lik, "z_likelihoods": z_lik}}
 
+    @torch.no_grad()
+    def rate_map(self, x: torch.Tensor, **kw):
+        """One forward(x, **kw) and codec.rate_maps of its likelihood tensors: {"y_map", "z_map", "cell_bits",
+        "slice_bits"} (where the bits lie, per latent pixel and slice; DESIGN.md §5 "Rate maps") plus "x_hat"."""
+        from . import codec
+        out = self.forward(x, **kw)
+        lik = out["likelihoods"]
+        maps = codec.rate_maps(lik["y_likelihoods"], lik["z_likelihoods"], self.slice_num)
+        maps["x_hat"] = out["x_hat"]
+        return maps
+
     def update(self, scale_table=None, force: bool = False) -> bool:
         """mlicpp.py:470-475: build the GaussianConditional (64 scales) and EntropyBottleneck CDFs."""
         gc = self.gaussian_conditional

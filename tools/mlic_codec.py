@@ -34,6 +34,14 @@
         Not together with --roi, --tile or --region
     python tools/mlic_codec.py info IN.bit --model MLICPP_L_VBR     what the file says (and its level map, or
         for a tiled file its grid and per-tile sizes)
+    python tools/mlic_codec.py ratemap IMAGE -o HEAT.png --model M --checkpoint C [--level L | --roi MASK --roi-levels
+        LO HI] [--what bits|slice K|z|error] [--cmap hot|gray] [--alpha A] [--hi X] [--csv FILE]
+        where the bits go (codec.rate_map: one forward of the model, no file is written): a heat map of the image's
+        size.  --what bits (default): bits per 16 x 16 cell, z's share included; slice K: slice K's bits per cell;
+        z: the hyper latent's bits per 64 x 64 cell; error: the squared error of the reconstruction per 16 x 16
+        block.  --hi X: the value drawn at full scale (default: the plane's maximum; 0 is the other end).  --alpha A
+        (0..256, default 256): blend the map over the image, 256 = the map alone.  --csv FILE: the per-slice bit
+        totals and the plane, as text.  An 8-bit RGB image; not together with any other coding option
 
     ... samples deeper than 8 bits (codec.encode_images(depth=) / YuvFormat(depth=); the bitstream does not know
         its depth).  A binary PPM of maxval 2^d - 1, d from 9 to 16 (16-bit big-endian samples), is encoded at depth d;
@@ -371,9 +379,16 @@ def _budget(v: str) -> float:
     return x
 
 
+def _full_scale(v: str) -> float:
+    try:
+        return _budget(v)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError(f"a positive finite value expected, got {v!r}") from None
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["encode", "decode", "info"])
+    ap.add_argument("mode", choices=["encode", "decode", "info", "ratemap"])
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("--model", default="MLICPP_L")
@@ -402,7 +417,38 @@ def parse_args(argv=None):
     ap.add_argument("--coded-size", type=_size, default=None, metavar="WxH")
     ap.add_argument("--filter", choices=["lanczos3", "bicubic", "triangle"], default=None)
     ap.add_argument("--out-size", type=_size, default=None, metavar="WxH")
+    ap.add_argument("-o", "--output", default=None, metavar="HEAT")
+    ap.add_argument("--what", nargs="+", default=None, metavar="bits|slice K|z|error")
+    ap.add_argument("--cmap", choices=["hot", "gray"], default=None)
+    ap.add_argument("--alpha", type=int, default=None, metavar="A")
+    ap.add_argument("--hi", type=_full_scale, default=None, metavar="X")
+    ap.add_argument("--csv", default=None, metavar="FILE")
     args = ap.parse_args(argv)
+    map_flags = [args.output, args.what, args.cmap, args.alpha, args.hi, args.csv]
+    if args.mode != "ratemap":
+        if any(v is not None for v in map_flags):
+            ap.error("-o, --what, --cmap, --alpha, --hi and --csv go with ratemap")
+    else:
+        if args.dst is not None or args.output is None:
+            ap.error("ratemap takes one image and -o HEAT")
+        if _is_yuv(args.src):
+            ap.error("ratemap of a Y'CbCr frame is not supported")
+        other = [args.max_bpp, args.tile, args.overlap, args.region, args.yuv, args.size, args.depth, args.chroma_site,
+                 args.ref, args.scale, args.coded_size, args.filter, args.out_size]
+        if any(v is not None for v in other) or args.level == "auto" or args.msb or args.frame != 0:
+            ap.error("ratemap goes with --level N or --roi MASK --roi-levels LO HI alone: maps of rate-constrained, "
+                     "tiled, scaled, Y'CbCr or deeper-than-8-bit coding are not supported")
+        what = args.what or ["bits"]
+        if what[0] == "slice" and len(what) == 2 and what[1].isdigit():
+            args.what = ("slice", int(what[1]))
+        elif len(what) == 1 and what[0] in ("bits", "z", "error"):
+            args.what = (what[0], None)
+        else:
+            ap.error("--what: bits, slice K, z or error expected")
+        args.cmap = args.cmap or "hot"
+        args.alpha = 256 if args.alpha is None else args.alpha
+        if not 0 <= args.alpha <= 256:
+            ap.error("--alpha: 0 to 256 expected")
     scaling = args.scale is not None or args.coded_size is not None
     frame_file = args.mode != "info" and _is_yuv(args.src if args.mode == "encode" else (args.dst or ""))
     if frame_file:
@@ -464,7 +510,7 @@ def parse_args(argv=None):
         ap.error("--tile-batch must be positive")
     if args.region is not None and args.mode != "decode":
         ap.error("--region goes with decode")
-    if args.mode != "info" and args.dst is None:
+    if args.mode in ("encode", "decode") and args.dst is None:
         ap.error(f"{args.mode} needs a destination file")
     if args.mode != "info" and args.checkpoint is None and args.synthetic is None:
         ap.error("one of the arguments --checkpoint --synthetic is required")
@@ -473,7 +519,7 @@ def parse_args(argv=None):
     if (args.roi is None) != (args.roi_levels is None):
         ap.error("--roi and --roi-levels go together")
     if args.roi is not None:
-        if args.mode != "encode":
+        if args.mode not in ("encode", "ratemap"):
             ap.error("--roi goes with encode (a decode reads the map from the file)")
         if args.max_bpp is not None or args.level is not None:
             ap.error("--roi goes with --roi-levels alone, not with --level or --max-bpp")
@@ -492,9 +538,61 @@ def _map_lines(lv) -> str:
     return "\n".join("  " + " ".join(f"{int(v):x}" for v in row) for row in lv)
 
 
+def _ratemap(args):
+    """ratemap IMAGE -o HEAT: codec.rate_map of the image, one plane of it through codec.heat_u8."""
+    import torch
+    from mlic_amd import codec
+    img, depth = load_image(args.src, deep=True)
+    if depth != 8:
+        raise SystemExit(f"{args.src}: ratemap of an image deeper than 8 bits is not supported")
+    H, W = img.shape[:2]
+    roi = None
+    if args.roi is not None:
+        roi = np.ascontiguousarray(load_image(args.roi)[:, :, 0])
+        if roi.shape != (H, W):
+            raise SystemExit(f"{args.roi}: the mask is {roi.shape[0]} x {roi.shape[1]}, the image {H} x {W}")
+    net = load_model(args)
+    dev_img = torch.from_numpy(img).to(net.device)
+    try:
+        r = codec.rate_map(net, dev_img, level=args.level, layout="hwc", roi=roi,
+                           roi_levels=None if roi is None else tuple(args.roi_levels))[0]
+    except ValueError as e:
+        raise SystemExit(f"{args.src}: {e}") from None
+    kind, k = args.what
+    if kind == "bits":
+        plane, cell, name = r["cell_bits"], 16, "bits per 16 x 16 cell"
+    elif kind == "slice":
+        if k >= r["y_map"].size(0):
+            raise SystemExit(f"--what slice {k}: the model has {r['y_map'].size(0)} slices")
+        plane, cell, name = r["y_map"][k], 16, f"bits of slice {k} per 16 x 16 cell"
+    elif kind == "z":
+        plane, cell, name = r["z_map"], 64, "bits of z per 64 x 64 cell"
+    else:
+        dec = codec.egress_u8(r["x_hat"].unsqueeze(0), H, W, "hwc")
+        plane, cell, name = codec.sq_err_blocks(dev_img, dec, block=16, layout="hwc")[0].double(), 16, \
+            "squared error per 16 x 16 block"
+    plane = plane[:-(-H // cell), :-(-W // cell)].contiguous()  # the cells that show in the image
+    heat = codec.heat_u8(plane, H, W, cell, 0.0, args.hi, args.cmap, under=dev_img if args.alpha < 256 else None,
+                         alpha=args.alpha, layout="hwc")
+    save_image(args.output, heat[0].cpu().numpy())
+    sb = r["slice_bits"].cpu().tolist()
+    if args.csv is not None:
+        with open(args.csv, "w") as f:
+            f.write("slice_bits," + ",".join(repr(v) for v in sb[:-1]) + "\n")
+            f.write("z_bits," + repr(sb[-1]) + "\n")
+            f.write(f"plane,{kind if k is None else f'{kind} {k}'},cell,{cell}\n")
+            for row in plane.cpu().tolist():
+                f.write(",".join(repr(v) for v in row) + "\n")
+    print(f"{args.src}: {H} x {W}, {r['bits']:.1f} bits, {r['bpp']:.4f} bpp (y slices " +
+          " ".join(f"{v:.0f}" for v in sb[:-1]) + f", z {sb[-1]:.0f}); {name}, maximum {float(plane.max()):.3f} -> "
+          f"{args.output}")
+
+
 def main(argv=None):
     args = parse_args(argv)
     from mlic_amd import codec
+    if args.mode == "ratemap":
+        return _ratemap(args)
     if args.mode == "info":
         from mlic_amd import spec
         with open(args.src, "rb") as f:
