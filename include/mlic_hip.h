@@ -86,6 +86,26 @@ int mlic_decompress_v(mlic_model* m, void* stream, const uint8_t* const* y, cons
                       const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz, float* x_hat,
                       const float* vbr_scales);
 
+/* ---- Progressive coding (DESIGN.md §5 "Progressive coding") ----
+ * The entropy model is causal over the S channel slices, so the first K slices of any file decode exactly and the
+ * rest can be filled with what the decoder knows without bits.
+ * mlic_layer_streams: image b of the last compress as S rANS strings, one per slice (string k = the coder inputs
+ * of phases 2 k and 2 k + 1, the lists the single string codes).  ptrs / lens: cap entries each, or NULL to query
+ * *n = S; the pointers stay valid until the model's next compress.  Refused after mlic_compress_g.
+ * mlic_decompress_prefix: y holds B * strings_per_image strings, image-major.  strings_per_image = 1: today's
+ * single string (the decoder reads forward, so a prefix of its phases needs nothing new in the file);
+ * >= slices: one string per slice, of which the first `slices` are read.  slices in [0, S] are entropy-decoded.
+ * fill 0 (mean): the remaining slices run through the slice loop as if all their symbols were 0 (y_hat = 0.0f +
+ * mean, LRP as in a decode), with no index kernel, copy, host decode or synchronisation; fill 1 (zero): the loop
+ * stops after slice `slices` - 1 and the remaining channels of y_hat are cleared.  slices = S with fill 0 issues
+ * exactly the launches of mlic_decompress_v.  Refused before any GPU call, each with its own message: slices
+ * outside [0, S]; fill not 0 or 1; strings_per_image < 1, or > 1 and below slices; a null string among those
+ * that are read. */
+int mlic_layer_streams(mlic_model* m, int b, const uint8_t** ptrs, size_t* lens, int cap, int* n);
+int mlic_decompress_prefix(mlic_model* m, void* stream, const uint8_t* const* y, const size_t* y_len,
+                           int strings_per_image, const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz,
+                           int slices, int fill, const float* vbr_scales, float* x_hat);
+
 /* ---- ROI coding on *_VBR models (DESIGN.md §5 "ROI coding") ----
  * The VBR gain is a quantisation step: y_hat = round((y - mu) * g) / g + mu, the table index from sigma * g, the
  * likelihood at (y, sigma, mu) * g.  The _g forms of forward / compress / decompress take it per latent pixel:
@@ -368,6 +388,11 @@ typedef struct mlic_quant_desc {
 int mlic_quant_phase_run(void* stream, const mlic_quant_desc* d);
 int mlic_phase_indexes_run(void* stream, const mlic_quant_desc* d);
 int mlic_phase_dequant_run(void* stream, const mlic_quant_desc* d);
+/* progressive decode, a slice that is not entropy-decoded: mlic_phase_dequant_run on all-zero symbols without the
+ * symbols.  yh = 0.0f + m at the phase's pixels (phase 0: +0 at the other parity; phase 1: the anchor pixels are
+ * left as they are); for every finite rs > 0 that is mlic_phase_dequant_run's result bit for bit (m = -0 gives +0
+ * in both).  Reads params, phase and the geometry only: sym, sym16, idx8 and the gains may be null. */
+int mlic_phase_fill_run(void* stream, const mlic_quant_desc* d);
 /* r[i] = 1 / g[i], the correctly rounded fp32 quotient, i < n (the reciprocal of a gain plane); 1 <= n <= 2^31 */
 int mlic_recip_plane_run(void* stream, const float* g, float* r, int64_t n);
 /* EntropyBottleneck (eval) on z [B][C][H][W]: r = rint(z - med[c]), z_hat = r + med[c], sym = (int32) r, lik =
@@ -688,6 +713,30 @@ int mlic_container_write_scaled(uint32_t H, uint32_t W, int vbr, int filter, con
                                 uint8_t* out, size_t cap, size_t* len);
 int mlic_container_parse_scaled(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
                                 mlic_container_scaled_info* info);
+/* The layered file (progressive coding), big-endian:
+ *     "MLL1" | u8 version 0 | u8 flags (bit 0: a VBR level word follows the size) | u8 S | u8 reserved 0
+ *     u32 H, W | (flag bit 0) u32 level | u32 h_z, w_z | u32 z_len, z bytes | S x ( u32 len, bytes )
+ * Layer k is mlic_layer_streams' string k.  bytes / write: level < 0 = no level word; the *len / out / cap protocol
+ * of mlic_container_write.  parse: validating, never reads outside data[0, n).  Refused, each with its own message:
+ * bad magic, version, flags or reserved byte; S == 0 or S > 32; what mlic_container_parse refuses about sizes,
+ * grids and levels; a cut inside the header or inside z; a length running past the end; bytes left over after the
+ * last layer.  allow_truncated != 0: a file cut at any byte after the complete z string is accepted,
+ * layers_present counts the whole layer strings, and a partial trailing length word or string is ignored; without
+ * it layers_present < S is refused.  That S is the model's is the caller's check.
+ * mlic_container_parse keeps refusing a layered file (the magic read as H is about 1.3e9). */
+typedef struct mlic_container_layered_info {
+  uint32_t H, W, hz, wz;
+  int32_t level; /* -1: none */
+  uint32_t S, layers_present;
+  uint64_t z_off, z_len;
+  uint64_t layer_off[32], layer_len[32]; /* [0, layers_present) */
+} mlic_container_layered_info;
+int mlic_container_layered_bytes(size_t z_len, const size_t* layer_lens, int S, int vbr, size_t* bytes);
+int mlic_container_write_layered(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_t wz, const uint8_t* z,
+                                 size_t z_len, const uint8_t* const* layers, const size_t* layer_lens, int S,
+                                 uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_layered(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels, int allow_truncated,
+                                 mlic_container_layered_info* info);
 /* mlic_encode_image_u8 at reduced (or raised) resolution: the H x W image is resampled to coded_H x coded_W on
  * the way in, coded as mlic_encode_image_u8 codes an image of that size, and wrapped in the scaled file with H, W
  * as the display size.  The out == NULL / rgb_dev == NULL protocol is that of mlic_encode_image_u8. */

@@ -45,6 +45,13 @@ class ContainerScaledInfo(C.Structure):
                 ("inner_off", C.c_uint64), ("inner_len", C.c_uint64), ("inner", ContainerInfo)]
 
 
+class ContainerLayeredInfo(C.Structure):
+    """mlic_container_layered_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("hz", C.c_uint32), ("wz", C.c_uint32), ("level", C.c_int32),
+                ("S", C.c_uint32), ("layers_present", C.c_uint32), ("z_off", C.c_uint64), ("z_len", C.c_uint64),
+                ("layer_off", C.c_uint64 * 32), ("layer_len", C.c_uint64 * 32)]
+
+
 class YuvDesc(C.Structure):
     """mlic_yuv_desc (include/mlic_hip.h)."""
     _fields_ = [("sub_x", C.c_int32), ("sub_y", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
@@ -116,6 +123,13 @@ def _sig(lib):
         "mlic_quant_phase_run": [p, P(QuantDesc)],
         "mlic_phase_indexes_run": [p, P(QuantDesc)],
         "mlic_phase_dequant_run": [p, P(QuantDesc)],
+        "mlic_phase_fill_run": [p, P(QuantDesc)],
+        "mlic_layer_streams": [p, i, P(p), P(sz), i, P(i)],
+        "mlic_decompress_prefix": [p, p, P(p), P(sz), i, P(p), P(sz), i, i, i, i, i, p, p],
+        "mlic_container_layered_bytes": [sz, P(sz), i, i, P(sz)],
+        "mlic_container_write_layered": [C.c_uint32, C.c_uint32, i, C.c_uint32, C.c_uint32, p, sz, P(p), P(sz), i, p,
+                                         sz, P(sz)],
+        "mlic_container_parse_layered": [p, sz, i, C.c_uint64, i, P(ContainerLayeredInfo)],
         "mlic_recip_plane_run": [p, p, p, i64],
         "mlic_eb_forward_run": [p] * 20 + [i, i, i, i],
         "mlic_eb_dequant_run": [p, p, p, p, i, i, i, i],

@@ -100,7 +100,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
                dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, yuv=None, rate_map: bool = False,
-               **kw) -> Dict:
+               progressive: bool = False, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -128,9 +128,20 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     likelihoods) and "z_bits" (the same for z), codec.rate_maps' slice_bits of one extra forward() of the padded
     image with the coder's arguments (s=, or the ROI gain plane).  Not together with tile=, yuv=, max_bpp= (the loop
     codes a filtered image), scale= / coded_size= or depth=; off by default, and the file bytes are the same either
-    way."""
+    way.
+    progressive=True: the file is the layered file (codec.write_container_layered of compress(layered=True): one
+    rANS string per channel slice), decoded from its layers, and the record also holds "layer_bytes" (S ints: the
+    exact coded bytes per slice) and "prefix_psnr" (S + 1 floats: PSNR of the mean-fill decode of the first K
+    layers, K = 0..S).  Not together with tile=, roi=, max_bpp=, scale= / coded_size= or batch_stream; off by
+    default."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
+    if progressive:
+        given = {"tile": tile, "roi": roi, "roi_levels": roi_levels, "max_bpp": max_bpp, "scale": kw.get("scale"),
+                 "coded_size": kw.get("coded_size"), "batch_stream": kw.get("batch_stream") or None}
+        for k, v in given.items():
+            if v is not None:
+                raise ValueError(f"code_image: progressive=True together with {k}= is not supported")
     if rate_map:
         given = {"tile": tile, "yuv": yuv, "max_bpp": max_bpp, "scale": kw.get("scale"),
                  "coded_size": kw.get("coded_size"), "depth": kw.get("depth")}
@@ -198,6 +209,23 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
         dec = net.decompress([[data[c.y_off:c.y_off + c.y_len]], [data[c.z_off:c.z_off + c.z_len]]], (c.hz, c.wz),
                              gain_map=codec.gain_plane(net, torch.from_numpy(fmap)))
         dect = time.time() - t0
+    elif progressive:
+        from . import codec
+        lv = level[0] if isinstance(level, (list, tuple)) else level
+        t0 = time.time()
+        out = net.compress(x, layered=True, **kw)
+        enc = time.time() - t0
+        data = codec.write_container_layered(H, W, out["shape"], out["strings"][1][0], out["layers"][0], lv)
+        nbytes = len(data)
+        c = codec.parse_container_layered(data, getattr(net, "levels", None))
+        layers, zstr = codec._layers(data, c), data[c.z_off:c.z_off + c.z_len]
+        t0 = time.time()
+        dec = net.decompress_layers([layers], [zstr], (c.hz, c.wz), **kw)
+        dect = time.time() - t0
+        prefix_psnr = []  # K = 0 .. S - 1 (K = S is the decode above)
+        for k in range(len(layers)):
+            part = net.decompress_layers([layers[:k]], [zstr], (c.hz, c.wz), **kw)["x_hat"]
+            prefix_psnr.append(psnr_u8(img, part[:, :, :H, :W]))
     elif max_bpp is None:
         t0 = time.time()
         out = net.compress(x, **kw)
@@ -211,7 +239,7 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
         files, ps, _ = codec.rate_loop(net, x.contiguous().float(), H, W, level, max_bpp, max_passes)
         enc = time.time() - t0
         nbytes, passes = buf.write(files[0]), ps[0]
-    if roi is None:
+    if roi is None and not progressive:
         buf.seek(0)
         hdr, strings, shape = read_stream(buf, vbr=level is not None)
         t0 = time.time()
@@ -222,6 +250,9 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
          "enc_s": enc, "dec_s": dect, "x_hat": x_hat}
     if passes is not None:
         r["passes"], r["met"] = passes, r["bpp"] <= max_bpp
+    if progressive:
+        r["layer_bytes"] = [len(l) for l in layers]
+        r["prefix_psnr"] = prefix_psnr + [r["psnr"]]
     if roi is not None:
         p = codec.psnr_roi(to_u8(img), to_u8(x_hat), mask, layout="chw")[0]
         r["psnr_roi"], r["psnr_bg"], r["roi_levels"] = p["psnr_roi"], p["psnr_bg"], fmap

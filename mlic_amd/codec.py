@@ -41,6 +41,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import struct
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -420,8 +421,14 @@ def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pix
     tile, overlap, grid (ny, nx), vbr, level, bytes, bpp, "tiles": per tile index, y0, x0, H, W, level, bytes,
     bpp}.  A scaled file (is_scaled_file; its flags say whether the inner file has a level word) gives {"scaled":
     True, H, W (the display size), "coded" (h, w), "filter", vbr, level, shape, Hp, Wp (of the coded image), y_len,
-    z_len, bytes, bpp (the whole file over the display pixels)}."""
+    z_len, bytes, bpp (the whole file over the display pixels)}.  A layered file (is_layered_file; whole or
+    truncated; its flags say whether it has a level word) gives {"layered": True, H, W, level, vbr, shape, Hp, Wp,
+    "slices" (S), "layers_present", "layer_bytes" (the whole layers' lengths: exact coded bytes per slice), z_len,
+    "header_bytes" (everything before the z string), bytes, bpp}: a whole file's bytes are header_bytes + z_len +
+    sum(layer_bytes) + 4 per layer."""
     data = bytes(data)
+    if is_layered_file(data):
+        return _peek_layered(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
     if is_tiled_file(data):
         return _peek_tiled(data, n_levels, MAX_IMAGE_PIXELS if max_pixels is None else max_pixels)
     if is_scaled_file(data):
@@ -479,6 +486,123 @@ def parse_container_roi(data: bytes, n_levels: int = 16, max_pixels: int = MAX_P
 
 def _strings(data: bytes, c: _lib.ContainerInfo):
     return data[c.y_off:c.y_off + c.y_len], data[c.z_off:c.z_off + c.z_len]
+
+
+# ------------------------------------------------------------------------------- progressive coding
+LAYERED_MAGIC = b"MLL1"
+MAX_LAYERS = 32  # the file's S byte
+
+
+def is_layered_file(data: bytes) -> bool:
+    """Whether the bytes begin with the layered file's magic (DESIGN.md §5 "Progressive coding")."""
+    return bytes(data[:4]) == LAYERED_MAGIC
+
+
+def container_layered_bytes(z_len: int, layer_lens, vbr: bool = False) -> int:
+    lens = [int(n) for n in layer_lens]
+    n = C.c_size_t()
+    _lib.call("mlic_container_layered_bytes", int(z_len), (C.c_size_t * max(1, len(lens)))(*lens), len(lens), int(vbr),
+              C.byref(n))
+    return n.value
+
+
+def write_container_layered(H: int, W: int, shape, z: bytes, layers: Sequence[bytes],
+                            level: Optional[int] = None) -> bytes:
+    """One image's layered file: "MLL1", version, flags, S, a reserved byte, H, W, the level word of a VBR file,
+    the z grid, the z string, then S length-prefixed layer strings (one rANS string per channel slice,
+    compress(layered=True)["layers"][b]).  Pure Python, byte-identical to mlic_container_write_layered."""
+    layers = [bytes(l) for l in layers]
+    if not 1 <= len(layers) <= MAX_LAYERS:
+        raise ValueError(f"write_container_layered: 1..{MAX_LAYERS} layers expected, got {len(layers)}")
+    if level is not None and int(level) < 0:
+        raise ValueError("write_container_layered: negative level")
+    out = [LAYERED_MAGIC, struct.pack(">BBBB", 0, 0 if level is None else 1, len(layers), 0),
+           struct.pack(">II", H, W)]
+    if level is not None:
+        out.append(struct.pack(">I", int(level)))
+    out += [struct.pack(">II", int(shape[0]), int(shape[1])), struct.pack(">I", len(z)), bytes(z)]
+    for l in layers:
+        out += [struct.pack(">I", len(l)), l]
+    return b"".join(out)
+
+
+def _write_container_layered_c(H: int, W: int, shape, z: bytes, layers: Sequence[bytes],
+                               level: Optional[int] = None) -> bytes:
+    """write_container_layered through the library's writer (the test of the two against each other)."""
+    layers = [bytes(l) for l in layers]
+    S = len(layers)
+    bufs = [C.create_string_buffer(l, max(1, len(l))) for l in layers]
+    ptrs = (C.c_void_p * max(1, S))(*[C.cast(b, C.c_void_p) for b in bufs])
+    lens = (C.c_size_t * max(1, S))(*[len(l) for l in layers])
+    lv = -1 if level is None else int(level)
+    n = C.c_size_t()
+    _lib.call("mlic_container_write_layered", H, W, lv, int(shape[0]), int(shape[1]), z, len(z), ptrs, lens, S, None, 0,
+              C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_layered", H, W, lv, int(shape[0]), int(shape[1]), z, len(z), ptrs, lens, S, buf,
+              len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_layered(data: bytes, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS,
+                            allow_truncated: bool = False) -> _lib.ContainerLayeredInfo:
+    """The validating parser of a layered file (mlic_container_parse_layered): raises _lib.MlicError on any
+    malformed input.  allow_truncated: a file cut at any byte after its complete z string is accepted, and
+    layers_present counts its whole layers.  The file's flags say whether it has a level word (level = -1
+    without one); n_levels bounds it (None: any level).  That S is the model's is the caller's check."""
+    data = bytes(data)
+    info = _lib.ContainerLayeredInfo()
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call("mlic_container_parse_layered", data, len(data), nl, int(max_pixels), int(bool(allow_truncated)),
+              C.byref(info))
+    return info
+
+
+def _layers(data: bytes, c: _lib.ContainerLayeredInfo) -> List[bytes]:
+    return [data[c.layer_off[k]:c.layer_off[k] + c.layer_len[k]] for k in range(c.layers_present)]
+
+
+def truncate_layered(data: bytes, K: int) -> bytes:
+    """The first bytes of a layered file up to the end of layer K - 1 (K = 0: up to the end of z): the
+    shortest file whose first K layers decode."""
+    data = bytes(data)
+    c = parse_container_layered(data, None, MAX_IMAGE_PIXELS, allow_truncated=True)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 0 <= K <= c.layers_present:
+        raise ValueError(f"truncate_layered: K must be in [0, {c.layers_present}] (the layers present), got {K!r}")
+    if K == 0:
+        return data[:c.z_off + c.z_len]
+    return data[:c.layer_off[K - 1] + c.layer_len[K - 1]]
+
+
+def _peek_layered(data: bytes, n_levels, max_pixels) -> Dict:
+    c = parse_container_layered(data, n_levels, max_pixels, allow_truncated=True)
+    lb = [int(c.layer_len[k]) for k in range(c.layers_present)]
+    return {"layered": True, "H": c.H, "W": c.W, "level": None if c.level < 0 else c.level, "vbr": c.level >= 0,
+            "shape": (c.hz, c.wz), "Hp": 64 * c.hz, "Wp": 64 * c.wz, "slices": c.S, "layers_present": c.layers_present,
+            "layer_bytes": lb, "z_len": int(c.z_len), "header_bytes": int(c.z_off), "bytes": len(data),
+            "bpp": 8.0 * len(data) / (c.H * c.W)}
+
+
+def _check_prefix(net, slices, fill, what: str):
+    """slices= / fill= of a decode, refused before any library call."""
+    if fill not in ("mean", "zero"):
+        raise ValueError(f"{what}: fill must be 'mean' or 'zero', got {fill!r}")
+    if slices is None:
+        return None
+    S = int(net.slice_num)
+    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= slices <= S:
+        raise ValueError(f"{what}: slices must be an integer in [0, {S}], got {slices!r}")
+    return int(slices)
+
+
+def _refuse_layered(what: str, **given):
+    """layered= composes with none of these: each is refused by name."""
+    why = {"roi": "ROI coding has no layered form", "max_bpp": "the rate loop codes plain files",
+           "level='auto'": "the level choice runs inside the rate loop", "scale": "scaled coding has no layered form",
+           "coded_size": "scaled coding has no layered form", "tiles": "tiled coding has no layered form"}
+    for name, v in given.items():
+        if v:
+            raise ValueError(f"{what}: layered=True together with {name} is not supported ({why[name]})")
 
 
 # ------------------------------------------------------------------------------------ scaled coding
@@ -1189,7 +1313,7 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
 @torch.no_grad()
 def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
                   max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None, depth: Optional[int] = None,
-                  msb: bool = False, coded_size=None, scale=None, filter: str = "lanczos3"):
+                  msb: bool = False, coded_size=None, scale=None, filter: str = "lanczos3", layered: bool = False):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
@@ -1211,7 +1335,16 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     launch, the model codes that image exactly as it codes any h x w image, and the file is the scaled file
     (write_container_scaled: the display size H x W and the filter around the coded image's file).  level and
     max_bpp act on the coded image; bpp, in the budget and in info, is the whole file over the display pixels;
-    info[b] gains "coded" and "filter".  Refused together with roi= and depth=."""
+    info[b] gains "coded" and "filter".  Refused together with roi= and depth=.
+    layered=True: progressive coding (DESIGN.md §5 "Progressive coding").  The network pass is unchanged; the y
+    symbols are coded as one rANS string per channel slice and the file is the layered file
+    (write_container_layered), which decode_images decodes whole or cut after any layer.  info[b] gains
+    "layer_bytes".  depth= composes (the file does not know its depth).  Refused, each by name, together with roi=,
+    max_bpp=, level="auto", scale= and coded_size=."""
+    if layered:
+        _refuse_layered("encode_images", roi=roi is not None or roi_levels is not None, max_bpp=max_bpp is not None,
+                        scale=scale is not None, coded_size=coded_size is not None,
+                        **{"level='auto'": isinstance(level, str)})
     scaled = coded_size is not None or scale is not None
     if scaled:
         if coded_size is not None and scale is not None:
@@ -1260,7 +1393,14 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         x = ingest_u8_scaled(img, (h, w), filter, layout)
     else:
         x = ingest(img, layout)
-    if max_bpp is None:
+    if layered:
+        lv, kw = _levels(net, level, B)
+        out = net.compress(x, layered=True, **kw)
+        zs = out["strings"][1]
+        files = [write_container_layered(h, w, out["shape"], zs[b], out["layers"][b], None if lv is None else lv[b])
+                 for b in range(B)]
+        passes = [0] * B
+    elif max_bpp is None:
         lv, kw = _levels(net, level, B)
         out = net.compress(x, **kw)
         ys, zs = out["strings"]
@@ -1281,12 +1421,15 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
                      "met": max_bpp is None or bpp <= max_bpp})
         if scaled:
             info[-1].update(coded=(h, w), filter=filter)
+        if layered:
+            info[-1]["layer_bytes"] = [len(l) for l in out["layers"][b]]
     return files, info
 
 
 @torch.no_grad()
 def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS, depth: Optional[int] = None,
-                  msb: bool = False, out_size=None, filter: Optional[str] = None):
+                  msb: bool = False, out_size=None, filter: Optional[str] = None, slices: Optional[int] = None,
+                  fill: str = "mean"):
     """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
     (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
     image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
@@ -1301,15 +1444,33 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     overrides the output size of every file, plain, VBR or scaled (the thumbnail decode; a plain file is resampled
     with lanczos3); filter= overrides the filter.  ref, sq_err and psnr are at the output size; info[b] then holds
     the output size as H, W, and "display", "coded" and "filter"; bpp stays the file over its display pixels.
-    Refused together with depth= and for ROI files."""
+    Refused together with depth= and for ROI files.
+    slices=K with fill= ("mean" / "zero"): the progressive decode (DESIGN.md §5 "Progressive coding") of plain, VBR
+    and layered files -- the first K channel slices are entropy-decoded and the rest filled as
+    net.decompress_layers says.  A layered file (encode_images(layered=True)) may be truncated (cut anywhere after
+    its z string); for it slices=None means every layer present.  Files are decoded in groups of one (kind, K), and
+    info[b] gains "slices" (and "layers_present" for a layered file).  Refused for ROI, tiled and scaled files and
+    together with out_size=."""
     if depth is not None:
         depth, msb = _check_depth(depth, "decode_images"), _check_msb(msb, "decode_images")
+    slices = _check_prefix(net, slices, fill, "decode_images")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
     if any(is_tiled_file(f) for f in files):
+        if slices is not None:
+            raise ValueError("decode_images: slices= on a tiled file is not supported (tiles have no layered form)")
         raise ValueError("decode_images: a tiled file (MLT1) is decoded by decode_tiled, whole or by region")
     vbr = hasattr(net, "levels")
+    prefix = slices is not None or any(is_layered_file(f) for f in files)
+    if prefix and out_size is not None:
+        raise ValueError("decode_images: slices= / layered files together with out_size= are not supported")
+    if prefix and any(is_scaled_file(f) for f in files):
+        raise ValueError("decode_images: slices= on a scaled file is not supported (scaled coding has no layered form)")
+    if prefix and filter is not None:
+        raise ValueError("decode_images: filter= goes with scaled files and out_size=, not with slices= / layered files")
+    if fill != "mean" and not prefix:
+        raise ValueError("decode_images: fill= goes with slices= or layered files")
     if out_size is not None:
         out_size = _check_size(out_size, "decode_images out_size")
     if filter is not None:
@@ -1321,7 +1482,10 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     if filter is not None:
         raise ValueError("decode_images: filter= given, but no file is scaled and there is no out_size=")
     maps = [None] * len(files)
-    if vbr and any(is_roi_file(f) for f in files):
+    ks = None  # progressive decode: the slices to entropy-decode, per file
+    if prefix:
+        cs, ks = _parse_prefix(net, files, slices, max_pixels)
+    elif vbr and any(is_roi_file(f) for f in files):
         # ROI files carry a level map; a plain VBR file beside them decodes through a constant map of its level
         cs = []
         for b, f in enumerate(files):
@@ -1333,12 +1497,15 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
         raise ValueError(f"decode_images: the files must share one padded size, got z grids "
                          f"{sorted({(c.hz, c.wz) for c in cs})}")
     B = len(files)
-    pairs = [_strings(f, c) for f, c in zip(files, cs)]
-    kw = {"s": [c.level for c in cs]} if vbr else {}
-    if any(m is not None for m in maps):
-        lmap = np.stack([np.full((c.hz, c.wz), c.level, np.uint8) if m is None else m for c, m in zip(cs, maps)])
-        kw = {"gain_map": gain_plane(net, torch.from_numpy(lmap))}
-    x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
+    if ks is not None:
+        x_hat = _decompress_prefix(net, files, cs, ks, fill)
+    else:
+        pairs = [_strings(f, c) for f, c in zip(files, cs)]
+        kw = {"s": [c.level for c in cs]} if vbr else {}
+        if any(m is not None for m in maps):
+            lmap = np.stack([np.full((c.hz, c.wz), c.level, np.uint8) if m is None else m for c, m in zip(cs, maps)])
+            kw = {"gain_map": gain_plane(net, torch.from_numpy(lmap))}
+        x_hat = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), **kw)["x_hat"]
     H, W = max(c.H for c in cs), max(c.W for c in cs)
     if ref is not None:
         ref, _ = (_u8_batch if depth is None else _u16_batch)(ref, "hwc", "decode_images ref")
@@ -1371,11 +1538,100 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
              "bpp": 8.0 * len(files[b]) / (c.H * c.W)}
         if maps[b] is not None:
             d["roi_levels"] = maps[b]
+        if ks is not None:
+            d["slices"] = ks[b]
+            if isinstance(c, _lib.ContainerLayeredInfo):
+                d["layers_present"] = int(c.layers_present)
         if sq is not None:
             d["sq_err"] = int(sq[b])
             d["psnr"] = psnr_from_sq_err(d["sq_err"], 3 * c.H * c.W, 255 if depth is None else (1 << depth) - 1)
         info.append(d)
     return img, info
+
+
+def _parse_prefix(net, files, slices, max_pixels):
+    """The progressive decode's files, each through its validating parser -> (infos, K per file).  A layered
+    file may be truncated; slices=None then means every layer it still has."""
+    vbr = hasattr(net, "levels")
+    n_levels = net.levels if vbr else None
+    S = int(net.slice_num)
+    cs, ks = [], []
+    for f in files:
+        if is_layered_file(f):
+            c = parse_container_layered(f, n_levels, max_pixels, allow_truncated=True)
+            if (c.level >= 0) != vbr:
+                raise ValueError(f"decode_images: the layered file {'carries a' if c.level >= 0 else 'has no'} level "
+                                 f"word, the model is {'variable' if vbr else 'fixed'}-rate")
+            if c.S != S:
+                raise ValueError(f"decode_images: the layered file has {c.S} layers, the model has {S} slices")
+            k = int(c.layers_present) if slices is None else slices
+            if k > c.layers_present:
+                raise ValueError(f"decode_images: slices={k}, but the file holds {c.layers_present} whole layers")
+        else:
+            if vbr and is_roi_file(f):
+                raise ValueError("decode_images: slices= on an ROI file is not supported (ROI coding has no layered "
+                                 "form)")
+            c = parse_container(f, vbr, n_levels, max_pixels)
+            k = slices
+        cs.append(c)
+        ks.append(k)
+    return cs, ks
+
+
+def _decompress_prefix(net, files, cs, ks, fill):
+    """One net.decompress / net.decompress_layers per group of files of one (z grid, kind, K), in input order."""
+    vbr = hasattr(net, "levels")
+    groups: Dict = {}
+    for b, (c, k) in enumerate(zip(cs, ks)):
+        groups.setdefault(((c.hz, c.wz), isinstance(c, _lib.ContainerLayeredInfo), k), []).append(b)
+    outs = [None] * len(files)
+    for (shape, lay, k), ids in groups.items():
+        kw = {"s": [cs[b].level for b in ids]} if vbr else {}
+        if lay:
+            out = net.decompress_layers([_layers(files[b], cs[b])[:k] for b in ids],
+                                        [files[b][cs[b].z_off:cs[b].z_off + cs[b].z_len] for b in ids], shape,
+                                        slices=k, fill=fill, **kw)["x_hat"]
+        else:
+            pairs = [_strings(files[b], cs[b]) for b in ids]
+            out = net.decompress([[p[0] for p in pairs], [p[1] for p in pairs]], shape, slices=k, fill=fill,
+                                 **kw)["x_hat"]
+        if len(groups) == 1:
+            return out
+        for j, b in enumerate(ids):
+            outs[b] = out[j:j + 1]
+    return torch.cat(outs, 0)
+
+
+@torch.no_grad()
+def decode_progressive(net, data: bytes, steps=None, fill: str = "mean", ref=None, max_pixels: int = MAX_PIXELS):
+    """One file (plain, VBR or layered, whole or truncated) decoded at a rising number of slices: steps, default
+    (1, 2, 4, S), each in [0, S] and strictly increasing; for a truncated layered file the steps beyond its layers
+    are left out.  -> a list of {"slices", "image" (uint8 [H,W,3] on the model's device), "bytes" (a layered
+    file's length up to that layer; None for a plain file, whose single string does not say) and, with ref
+    (uint8 [H,W,3]), "sq_err" and "psnr"}.  One independent decode per step: each is decode_images(slices=K)."""
+    _check_prefix(net, None, fill, "decode_progressive")
+    S = int(net.slice_num)
+    steps = tuple(sorted({min(k, S) for k in (1, 2, 4, S)})) if steps is None else tuple(steps)
+    if not steps or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k <= S for k in steps) \
+            or any(a >= b for a, b in zip(steps, steps[1:])):
+        raise ValueError(f"decode_progressive: steps must be strictly increasing integers in [0, {S}], got {steps!r}")
+    data = bytes(data)
+    lay = is_layered_file(data)
+    if lay:
+        have = parse_container_layered(data, net.levels if hasattr(net, "levels") else None, max_pixels, True)
+        steps = tuple(k for k in steps if k <= have.layers_present)
+        if not steps:
+            raise ValueError(f"decode_progressive: the file holds {have.layers_present} whole layers, below every step")
+    if ref is not None:
+        ref, _ = _u8_batch(ref, "hwc", "decode_progressive ref")
+    out = []
+    for k in steps:
+        img, info = decode_images(net, [data], ref=ref, max_pixels=max_pixels, slices=int(k), fill=fill)
+        d = {"slices": int(k), "image": img[0], "bytes": len(truncate_layered(data, int(k))) if lay else None}
+        if ref is not None:
+            d.update(sq_err=info[0]["sq_err"], psnr=info[0]["psnr"])
+        out.append(d)
+    return out
 
 
 def _decode_scaled(net, files, ref, max_pixels, out_size, filter):
@@ -1691,7 +1947,7 @@ def _refuse_deep_tiles(what: str, depth):
 @torch.no_grad()
 def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, layout: Optional[str] = None,
                  tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None, depth=None,
-                 coded_size=None, scale=None):
+                 coded_size=None, scale=None, layered: bool = False):
     """One uint8 image ([H,W,3] / [3,H,W], tensor or numpy array) -> one tiled file (DESIGN.md §5 "Tiled coding"):
     the image is cut into the tiles of tile_grid(H, W, tile, overlap), each tile is coded by itself and its file
     is byte for byte encode_images of that crop, and the tiled container holds them row-major with an index.
@@ -1702,6 +1958,7 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
     refused, and so is any depth= (uint16 words: the blend kernel writes bytes).  return_info=True: (file, info) with info =
     {"H", "W", "tile", "overlap", "grid", "bytes", "bpp", "level", "tile_bytes"}."""
     _refuse_with_tiles("encode_tiled", max_bpp, level, roi, roi_levels)
+    _refuse_layered("encode_tiled", tiles=layered)
     _refuse_deep_tiles("encode_tiled", depth)
     _refuse_scaled("encode_tiled", "tiles", coded_size, scale)
     img, layout = _u8_batch(img_u8, layout, "encode_tiled")
@@ -1749,7 +2006,7 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
 
 @torch.no_grad()
 def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, max_pixels: int = MAX_IMAGE_PIXELS,
-                 depth=None, out_size=None):
+                 depth=None, out_size=None, slices=None):
     """A tiled file -> (uint8 [h,w,3] on the model's device, info): the region (y0, x0, h, w) of the image (None:
     all of it).  Only the tiles that intersect the region are entropy-decoded and synthesised (per shape group,
     in chunks of at most tile_batch tiles); their fp32 x_hat is kept (12 bytes per pixel of the decoded tiles, on top of the arena of
@@ -1758,6 +2015,8 @@ def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, m
     ref (uint8 [h,w,3], the region's crop of the original), the exact sq_err and psnr."""
     _refuse_deep_tiles("decode_tiled", depth)
     _refuse_scaled("decode_tiled", "tiles", out_size)
+    if slices is not None:
+        raise ValueError("decode_tiled: slices= on a tiled file is not supported (tiles have no layered form)")
     data = bytes(data)
     if is_scaled_file(data):
         raise ValueError("decode_tiled: a scaled file (MLS1): scaled coding together with tiles is not supported; "
@@ -2232,12 +2491,13 @@ def psnr_yuv_from_sq_err(sq_err, H: int, W: int, fmt: YuvFormat) -> Dict:
 
 @torch.no_grad()
 def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[float] = None, max_passes: int = 8,
-               return_info: bool = False, roi=None, roi_levels=None, tile=None, coded_size=None, scale=None):
+               return_info: bool = False, roi=None, roi_levels=None, tile=None, coded_size=None, scale=None,
+               layered: bool = False):
     """encode_images with the Y'CbCr ingest: a frame batch (ingest_yuv's planes; host arrays cross to the device as
     bytes) -> one file per frame.  The files are plain per-image files: nothing of fmt is written, decode_images
     decodes them to RGB and decode_yuv(fmt) to planes.  level, max_bpp, max_passes and return_info as in
     encode_images (the rate loop works on the float image, so a budget and level="auto" work unchanged).  roi= and
-    tile= are refused: ROI and tiled coding together with Y'CbCr frames are out of scope.  The planes follow the
+    tile= are refused: ROI and tiled coding together with Y'CbCr frames are out of scope, and so is layered=.  The planes follow the
     format's depth: uint8 at depth 8, uint16 words above (a P010 frame: YuvFormat(depth=10, msb=True))."""
     fmt = _check_fmt(fmt, "encode_yuv")
     if roi is not None or roi_levels is not None:
@@ -2245,6 +2505,9 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
     if tile is not None:
         raise ValueError("encode_yuv: tiles together with Y'CbCr frames are not supported")
     _refuse_scaled("encode_yuv", "Y'CbCr frames", coded_size, scale)
+    if layered:
+        raise ValueError("encode_yuv: layered=True together with Y'CbCr frames is not supported (encode_images writes "
+                         "layered files)")
     y, cb, cr = _yuv_planes(y, cb, cr, fmt, "encode_yuv")
     _check_budget(max_bpp, max_passes)
     if isinstance(level, str) and max_bpp is None:
@@ -2270,17 +2533,22 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
 
 
 @torch.no_grad()
-def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS, out_size=None):
+def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS, out_size=None,
+               slices=None):
     """Files of one H x W -> ((y, cb, cr) on the model's device, info): decode_images with the Y'CbCr egress.
     info[b] holds H, W, level, bytes and bpp and, with ref=(y, cb, cr) of the originals, sq_err (three ints: Y, Cb,
     Cr), psnr_y, psnr_u, psnr_v and psnr_yuv = (6 Y + U + V) / 8 (peak 2^depth - 1).  The planes are uint8 for a
-    format of depth 8 and uint16 words above; the file does not know its depth.  ROI and tiled files are refused."""
+    format of depth 8 and uint16 words above; the file does not know its depth.  ROI, tiled and layered files and
+    slices= are refused."""
     fmt = _check_fmt(fmt, "decode_yuv")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_yuv: no files")
     if any(is_tiled_file(f) for f in files):
         raise ValueError("decode_yuv: tiled files together with Y'CbCr frames are not supported")
+    if slices is not None or any(is_layered_file(f) for f in files):
+        raise ValueError("decode_yuv: slices= / layered files together with Y'CbCr frames are not supported "
+                         "(decode_images decodes them)")
     _refuse_scaled("decode_yuv", "Y'CbCr frames", out_size, True if any(is_scaled_file(f) for f in files) else None)
     vbr = hasattr(net, "levels")
     if vbr and any(is_roi_file(f) for f in files):

@@ -217,6 +217,51 @@ int mlic_decompress_batch_stream(mlic_model* m, void* stream, const uint8_t* y, 
   });
 }
 
+int mlic_layer_streams(mlic_model* m, int b, const uint8_t** ptrs, size_t* lens, int cap, int* n) {
+  return guard([&] {
+    MLIC_CHECK(m && n, "bad arguments");
+    const std::vector<std::string>& l = impl(m).layer_streams(b);
+    *n = (int)l.size();
+    if (ptrs || lens) {
+      MLIC_CHECK(ptrs && lens && cap >= (int)l.size(), "layer_streams: ptrs and lens of at least S entries");
+      for (size_t k = 0; k < l.size(); ++k) {
+        ptrs[k] = reinterpret_cast<const uint8_t*>(l[k].data());
+        lens[k] = l[k].size();
+      }
+    }
+  });
+}
+
+int mlic_decompress_prefix(mlic_model* m, void* stream, const uint8_t* const* y, const size_t* y_len,
+                           int strings_per_image, const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz,
+                           int slices, int fill, const float* vbr_scales, float* x_hat) {
+  return guard([&] {
+    MLIC_CHECK(m && y && y_len && z && z_len && x_hat && B > 0 && hz > 0 && wz > 0, "bad arguments");
+    Model& mod = impl(m);
+    const int S = mod.cfg().S;
+    if (slices < 0 || slices > S)
+      throw Error("mlic: decompress_prefix: slices must be in [0, " + std::to_string(S) + "], got " +
+                  std::to_string(slices));
+    if (fill != 0 && fill != 1) throw Error("mlic: decompress_prefix: fill must be 0 (mean) or 1 (zero)");
+    if (strings_per_image < 1) throw Error("mlic: decompress_prefix: strings_per_image must be at least 1");
+    if (strings_per_image > 1 && strings_per_image < slices)
+      throw Error("mlic: decompress_prefix: " + std::to_string(strings_per_image) + " layer strings per image, " +
+                  std::to_string(slices) + " slices asked for");
+    const int used = strings_per_image == 1 ? (slices > 0 ? 1 : 0) : slices;
+    for (int b = 0; b < B; ++b) {
+      for (int k = 0; k < used; ++k)
+        if (y[(size_t)b * strings_per_image + k] == nullptr)
+          throw Error("mlic: decompress_prefix: a null y string among those that are read");
+      if (z[b] == nullptr) throw Error("mlic: decompress_prefix: a null z string");
+    }
+    Prefix p;
+    p.slices = slices;
+    p.fill = fill;
+    p.strings = strings_per_image;
+    mod.decompress(y, y_len, z, z_len, B, hz, wz, x_hat, vbr_scales, (hipStream_t)stream, false, nullptr, p);
+  });
+}
+
 int mlic_decompress(mlic_model* m, void* stream, const uint8_t* const* y, const size_t* y_len,
                     const uint8_t* const* z, const size_t* z_len, int B, int hz, int wz, float* x_hat,
                     float vbr_scale) {
@@ -870,6 +915,17 @@ int mlic_phase_dequant_run(void* stream, const mlic_quant_desc* d) {
   });
 }
 
+int mlic_phase_fill_run(void* stream, const mlic_quant_desc* d) {
+  return guard([&] {
+    const QuantParams Q = quant_params(d);
+    const int64_t n = (int64_t)Q.C * Q.H * Q.W;
+    MLIC_CHECK(Q.yh, "null tensor");
+    MLIC_CHECK(Q.yh_bs >= n, "yh_bs smaller than [C][H][W]");
+    phase_fill(Q, (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
 int mlic_recip_plane_run(void* stream, const float* g, float* r, int64_t n) {
   return guard([&] {
     MLIC_CHECK(g && r, "null tensor");
@@ -1150,6 +1206,46 @@ int mlic_container_parse(const uint8_t* data, size_t n, int vbr, int n_levels, u
     ContainerInfo c;
     container_ok(container_parse(data, n, vbr != 0, (uint32_t)std::max(n_levels, 0), max_pixels, &c));
     to_abi(c, info);
+  });
+}
+
+int mlic_container_layered_bytes(size_t z_len, const size_t* layer_lens, int S, int vbr, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr && layer_lens != nullptr, "container_layered_bytes: null argument");
+    MLIC_CHECK(S >= 1 && S <= (int)LAYERED_MAX_S, "container_layered_bytes: S must be in 1..32");
+    *bytes = container_layered_bytes(z_len, layer_lens, (uint32_t)S, vbr != 0);
+    MLIC_CHECK(*bytes != 0, "container_layered_bytes: the file does not fit size_t");
+  });
+}
+
+int mlic_container_write_layered(uint32_t H, uint32_t W, int level, uint32_t hz, uint32_t wz, const uint8_t* z,
+                                 size_t z_len, const uint8_t* const* layers, const size_t* layer_lens, int S,
+                                 uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    MLIC_CHECK(S >= 1 && S <= (int)LAYERED_MAX_S, "container_write_layered: S must be in 1..32");
+    container_ok(container_write_layered(H, W, level, hz, wz, z, z_len, layers, layer_lens, (uint32_t)S, out, cap, len));
+  });
+}
+
+int mlic_container_parse_layered(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels, int allow_truncated,
+                                 mlic_container_layered_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_layered: null info");
+    LayeredInfo c;
+    container_ok(container_parse_layered(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, allow_truncated != 0, &c));
+    info->H = c.H;
+    info->W = c.W;
+    info->hz = c.hz;
+    info->wz = c.wz;
+    info->level = c.level;
+    info->S = c.S;
+    info->layers_present = c.layers_present;
+    info->z_off = c.z_off;
+    info->z_len = c.z_len;
+    for (uint32_t k = 0; k < LAYERED_MAX_S; ++k) {
+      info->layer_off[k] = k < c.layers_present ? c.layer_off[k] : 0;
+      info->layer_len[k] = k < c.layers_present ? c.layer_len[k] : 0;
+    }
   });
 }
 

@@ -361,6 +361,118 @@ const char* container_parse_scaled(const uint8_t* data, size_t n, uint32_t n_lev
   return nullptr;
 }
 
+// ---------------------------------------------------------------------------------------- layered
+namespace {
+constexpr size_t LAYERED_FIXED = 16;  // magic, version, flags, S, reserved, H, W
+}
+
+size_t container_layered_bytes(size_t z_len, const size_t* layer_lens, uint32_t S, bool vbr) {
+  if (S == 0 || S > LAYERED_MAX_S || layer_lens == nullptr) return 0;
+  size_t total = LAYERED_FIXED + (vbr ? 4 : 0) + 8 + 4 + 4 * (size_t)S;
+  if (z_len > SIZE_MAX - total) return 0;
+  total += z_len;
+  for (uint32_t k = 0; k < S; ++k) {
+    if (layer_lens[k] > SIZE_MAX - total) return 0;
+    total += layer_lens[k];
+  }
+  return total;
+}
+
+const char* container_write_layered(uint32_t H, uint32_t W, int32_t level, uint32_t hz, uint32_t wz, const uint8_t* z,
+                                    size_t z_len, const uint8_t* const* layers, const size_t* layer_lens, uint32_t S,
+                                    uint8_t* out, size_t cap, size_t* len) {
+  if (len == nullptr) return "container_write_layered: null len";
+  if (S == 0 || S > LAYERED_MAX_S) return "container_write_layered: S must be in 1..32";
+  if (layer_lens == nullptr) return "container_write_layered: null layer lengths";
+  if (z_len > 0xffffffffu) return "container_write_layered: a string longer than a 32-bit length";
+  for (uint32_t k = 0; k < S; ++k)
+    if (layer_lens[k] > 0xffffffffu) return "container_write_layered: a string longer than a 32-bit length";
+  const bool vbr = level >= 0;
+  const size_t total = container_layered_bytes(z_len, layer_lens, S, vbr);
+  if (total == 0) return "container_write_layered: the file does not fit size_t";
+  *len = total;
+  if (out == nullptr) return nullptr;
+  if (cap < total) return "container_write_layered: buffer too small";
+  if (z_len && z == nullptr) return "container_write_layered: null string";
+  if (layers == nullptr) return "container_write_layered: null layers";
+  for (uint32_t k = 0; k < S; ++k)
+    if (layer_lens[k] && layers[k] == nullptr) return "container_write_layered: null string";
+  uint8_t* p = out;
+  std::memcpy(p, "MLL1", 4);
+  p[4] = 0;
+  p[5] = vbr ? 1 : 0;
+  p[6] = (uint8_t)S;
+  p[7] = 0;
+  put32(p + 8, H);
+  put32(p + 12, W);
+  p += LAYERED_FIXED;
+  if (vbr) {
+    put32(p, (uint32_t)level);
+    p += 4;
+  }
+  put32(p, hz);
+  put32(p + 4, wz);
+  put32(p + 8, (uint32_t)z_len);
+  p += 12;
+  if (z_len) std::memcpy(p, z, z_len);
+  p += z_len;
+  for (uint32_t k = 0; k < S; ++k) {
+    put32(p, (uint32_t)layer_lens[k]);
+    p += 4;
+    if (layer_lens[k]) std::memcpy(p, layers[k], layer_lens[k]);
+    p += layer_lens[k];
+  }
+  return nullptr;
+}
+
+const char* container_parse_layered(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                    bool allow_truncated, LayeredInfo* info) {
+  if (info == nullptr) return "container_parse_layered: null info";
+  if (data == nullptr && n != 0) return "container_parse_layered: null data";
+  if (n < LAYERED_FIXED) return "container_parse_layered: truncated header";
+  if (std::memcmp(data, "MLL1", 4) != 0) return "container_parse_layered: bad magic (not a layered file)";
+  if (data[4] != 0) return "container_parse_layered: unknown version";
+  if (data[5] & ~1u) return "container_parse_layered: unknown flags";
+  if (data[6] == 0 || data[6] > LAYERED_MAX_S) return "container_parse_layered: S is not in 1..32";
+  if (data[7] != 0) return "container_parse_layered: the reserved byte is not 0";
+  const bool vbr = (data[5] & 1u) != 0;
+  Reader r{data, n, 8};
+  LayeredInfo c{};
+  c.S = data[6];
+  uint32_t level = 0, ln = 0;
+  r.u32(&c.H);  // n >= LAYERED_FIXED: these two reads succeed
+  r.u32(&c.W);
+  if (vbr && !r.u32(&level)) return "container_parse_layered: truncated header (level)";
+  if (!r.u32(&c.hz) || !r.u32(&c.wz)) return "container_parse_layered: truncated header (h_z, w_z)";
+  if (c.H == 0 || c.W == 0) return "container_parse_layered: H or W is zero";
+  if (vbr && level >= n_levels) return "container_parse_layered: level is not below n_levels";
+  c.level = vbr ? (int32_t)level : -1;
+  if ((uint64_t)c.hz != ((uint64_t)c.H + 63) / 64 || (uint64_t)c.wz != ((uint64_t)c.W + 63) / 64)
+    return "container_parse_layered: h_z, w_z are not ceil(H / 64), ceil(W / 64)";
+  if ((uint64_t)c.hz * 64 > max_pixels / ((uint64_t)c.wz * 64))
+    return "container_parse_layered: padded image exceeds max_pixels";
+  if (!r.u32(&ln)) return "container_parse_layered: truncated before the z length";
+  if (ln > r.n - r.pos) return "container_parse_layered: the z length runs past the end";
+  c.z_off = r.pos;
+  c.z_len = ln;
+  r.pos += ln;
+  for (uint32_t k = 0; k < c.S; ++k) {
+    const bool word = r.u32(&ln);
+    if (!word || ln > r.n - r.pos) {
+      if (allow_truncated) break;  // a partial trailing length word or string is ignored
+      return word ? "container_parse_layered: a layer length runs past the end"
+                  : "container_parse_layered: truncated before a layer length";
+    }
+    c.layer_off[k] = r.pos;
+    c.layer_len[k] = ln;
+    r.pos += ln;
+    c.layers_present = k + 1;
+  }
+  if (c.layers_present == c.S && r.pos != r.n) return "container_parse_layered: bytes left over after the last layer";
+  *info = c;
+  return nullptr;
+}
+
 void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels) {
   for (uint64_t k = 0; k < cells; ++k) {
     const uint8_t byte = map[1 + (size_t)(k >> 1)];

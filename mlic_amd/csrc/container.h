@@ -133,5 +133,39 @@ const char* container_write_scaled(uint32_t H, uint32_t W, bool vbr, uint32_t fi
 const char* container_parse_scaled(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                    ScaledInfo* info);
 
+// ---- Progressive coding (DESIGN.md section 5 "Progressive coding").  The layered file, all integers big-endian:
+//     4 bytes "MLL1" | >B version 0 | >B flags (bit 0: a VBR level word follows the size) | >B S | >B reserved 0
+//     >II H, W | (flag bit 0) >I level | >II h_z, w_z | >I z_len, z bytes | S x ( >I len, bytes )
+// Layer k is the rANS string of channel slice k alone (phases 2 k and 2 k + 1), so a file cut after any layer
+// still decodes: z first, then the layers in the order the decoder needs them.  As H, "MLL1" exceeds every
+// max_pixels, so container_parse refuses a layered file as it refuses a tiled or a scaled one.
+constexpr uint32_t LAYERED_MAX_S = 32;
+struct LayeredInfo {
+  uint32_t H, W;    // unpadded image
+  uint32_t hz, wz;  // z grid
+  int32_t level;    // VBR level, -1 when the file has none
+  uint32_t S;       // layers the whole file has
+  uint32_t layers_present;  // whole layer strings in these n bytes (== S unless the file is truncated)
+  size_t z_off, z_len;
+  size_t layer_off[LAYERED_MAX_S], layer_len[LAYERED_MAX_S];  // [0, layers_present)
+};
+inline bool is_layered_file(const uint8_t* data, size_t n) {
+  return n >= 4 && data[0] == 'M' && data[1] == 'L' && data[2] == 'L' && data[3] == '1';
+}
+// header + z + S length words + the layers; 0 when S is outside 1..32 or the sum does not fit size_t
+size_t container_layered_bytes(size_t z_len, const size_t* layer_lens, uint32_t S, bool vbr);
+// level < 0: no level word.  layers: S pointers (one may be null when its length is 0).  The *len / out / cap
+// protocol of container_write (layers and z may be null for a size query).
+const char* container_write_layered(uint32_t H, uint32_t W, int32_t level, uint32_t hz, uint32_t wz, const uint8_t* z,
+                                    size_t z_len, const uint8_t* const* layers, const size_t* layer_lens, uint32_t S,
+                                    uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: bad magic, version, flags or reserved byte, S == 0 or S > 32, what
+// container_parse refuses about sizes, grids and levels, a cut inside the header or inside z, a length running
+// past the end, bytes left over after the last layer.  allow_truncated: a file cut at any byte after the
+// complete z string is accepted; layers_present counts the whole layer strings and a partial trailing length
+// word or string is ignored.  Without it layers_present < S is refused.
+const char* container_parse_layered(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                    bool allow_truncated, LayeredInfo* info);
+
 }  // namespace mlic
 #endif

@@ -227,6 +227,9 @@ void recip_plane(const float* g, float* r, int64_t n, hipStream_t st);
 void quant_phase(const QuantParams& P, hipStream_t st);
 void phase_indexes(const QuantParams& P, hipStream_t st);
 void phase_dequant(const QuantParams& P, hipStream_t st);
+// progressive decode: phase_dequant on all-zero symbols (yh = 0.0f + m at the phase's pixels; the anchor phase
+// zeroes the others) that reads neither sym, sym16, idx8 nor the gains
+void phase_fill(const QuantParams& P, hipStream_t st);
 
 struct EbParams {
   const float* z;

@@ -900,6 +900,33 @@ void phase_dequant(const QuantParams& P, hipStream_t st) {
   HIP_OK(hipGetLastError());
 }
 
+// progressive decode, a slice that is not entropy-decoded: phase_dequant on all-zero symbols without the
+// symbols.  For a finite rs > 0 the product 0 * rs is +0, so yh = 0.0f + m whatever the gain (m = -0 gives +0 in
+// both, a NaN keeps its payload); neither sym, sym16, idx8 nor the gains are read.  The index mapping is
+// phase_dequant_kernel's: one thread per element, a wave reads and writes 64 consecutive floats.
+__global__ void phase_fill_kernel(QuantParams P) {
+  const int HW = P.H * P.W;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = blockIdx.y;
+  if (i >= (int64_t)P.C * HW) return;
+  const int c = (int)(i / HW), p = (int)(i % HW);
+  const int h = p / P.W, w = p % P.W;
+  const bool mine = (P.phase == 0) == is_anchor(h, w);
+  float* yh = P.yh + (int64_t)b * P.yh_bs + i;
+  if (!mine) {
+    if (P.phase == 0) *yh = 0.0f;
+    return;
+  }
+  const float m = P.params[(int64_t)b * P.params_bs + (int64_t)(c + P.C) * HW + p];
+  *yh = 0.0f + m;
+}
+
+void phase_fill(const QuantParams& P, hipStream_t st) {
+  const int64_t n = (int64_t)P.C * P.H * P.W;
+  hipLaunchKernelGGL(phase_fill_kernel, dim3((unsigned)((n + 255) / 256), P.B), dim3(256), 0, st, P);
+  HIP_OK(hipGetLastError());
+}
+
 // the reciprocal plane of a gain plane, once per call: the correctly rounded fp32 1 / g (hipcc's default for
 // fp32 division, as the ingest kernel's / 255), the host's `1.0f / scale` bit for bit
 __global__ void recip_plane_kernel(const float* __restrict__ g, float* __restrict__ r, int64_t n) {

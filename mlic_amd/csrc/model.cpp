@@ -1273,16 +1273,26 @@ class PhaseDecoder {
   // single: y[0] holds every image's symbols, phase-major then image-minor (the reference's batched
   // stream); one decoder then walks the images of each phase in order
   PhaseDecoder(int B, const uint8_t* const* y, const size_t* ylen, const CdfTables* t, int32_t* h_sym,
-               int16_t* h_sym16, uint8_t* h_idx8, HostStats* hs, HostPool* pool, bool single = false)
+               int16_t* h_sym16, uint8_t* h_idx8, HostStats* hs, HostPool* pool, bool single = false, int strings = 1)
       : t_(t), h_sym_(h_sym), h_sym16_(h_sym16), h_idx8_(h_idx8), hs_(hs), pool_(pool), B_(B),
-        nlim_(opt(OPT_NARROW_LIMIT)) {  // read here, in the lane thread: the pool's workers run under no snapshot
+        nlim_(opt(OPT_NARROW_LIMIT)),  // read here, in the lane thread: the pool's workers run under no snapshot
+        y_(y), ylen_(ylen), strings_(strings) {
     dec_.resize(single ? 1 : B);
-    for (size_t b = 0; b < dec_.size(); ++b) dec_[b].set_stream(y[b], ylen[b]);
+    // layered (strings > 1): y[b * strings + k] is image b's slice k, opened at that slice's first phase
+    // (a prefix decode of no slice at all may come without a string)
+    static const uint8_t none = 0;
+    if (strings_ == 1)
+      for (size_t b = 0; b < dec_.size(); ++b) dec_[b].set_stream(y[b] ? y[b] : &none, y[b] ? ylen[b] : 0);
   }
   // one phase: uint8 indexes D2H, host rANS decode, symbols H2D as int16 -- or as int32 when one of
   // the phase's symbols does not fit (returns false: cb->sym then holds them, not cb->sym16)
-  bool run(int64_t n_per, hipStream_t st, const CoderBufs& cb) {
+  bool run(int64_t n_per, hipStream_t st, const CoderBufs& cb, int phase_id) {
     const int B = B_;
+    if (strings_ > 1 && phase_id % 2 == 0)
+      for (int b = 0; b < B; ++b) {
+        const size_t k = (size_t)b * strings_ + phase_id / 2;
+        dec_[b].set_stream(y_[k], ylen_[k]);
+      }
     HIP_OK(hipMemcpyAsync(h_idx8_, cb.idx8, (size_t)n_per * B, hipMemcpyDeviceToHost, st));
     {
       HostStats::Scope w{hs_->wait_ns};
@@ -1320,12 +1330,16 @@ class PhaseDecoder {
   HostStats* hs_;
   HostPool* pool_;
   int B_, nlim_;
+  const uint8_t* const* y_;
+  const size_t* ylen_;
+  int strings_;
 };
 
 // mlicpp.py:107-176 (forward), 220-277 (compress), 309-366 (decompress)
 void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& yhat, float* y_lik, const CoderBufs* cb,
-                       PhaseDecoder* dec) {
+                       PhaseDecoder* dec, int n_dec, int fill) {
   const int S = cfg_.S, C = cfg_.C, hM = cfg_.hM();
+  if (n_dec < 0 || mode != Mode::Decode) n_dec = S;
   const int H = hyper.H, W = hyper.W, HW = H * W;
   const int64_t n_per = (int64_t)C * H * (W / 2);
   const View hyper_means = hyper.ch(hM, hM);
@@ -1350,6 +1364,14 @@ void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& 
       HIP_OK(hipMemcpyAsync(vbr_dev, L().vbr_host.data(), sizeof(float) * 2 * L().B, hipMemcpyHostToDevice, L().st));
   }
   for (int idx = 0; idx < S; ++idx) {
+    if (idx >= n_dec && fill == 1) {
+      // zero fill: the loop ends here and the slices that were not decoded are cleared for g_s
+      // (one image's tail channels are contiguous: B rows of them, a batch stride apart)
+      if (!L().dry)
+        HIP_OK(hipMemset2DAsync(yhat.p + (int64_t)idx * C * HW, sizeof(float) * yhat.bs, 0,
+                                sizeof(float) * (cfg_.M - idx * C) * HW, L().B, L().st));
+      break;
+    }
     const size_t m = L().arena.mark();
     View ysl = yhat.ch(idx * C, C);
     View inter, chan, pa;
@@ -1392,12 +1414,15 @@ void Model::slice_loop(Mode mode, const View& hyper, const View* y, const View& 
       Q.params = par.p;
       Q.params_bs = par.bs;
       const int phase_id = 2 * idx + ph;
-      if (mode == Mode::Decode) {
+      if (mode == Mode::Decode && idx >= n_dec) {
+        // mean fill: the slice as if every symbol were 0 -- no indexes, no host round trip, no synchronisation
+        if (!L().dry) phase_fill(Q, L().st);
+      } else if (mode == Mode::Decode) {
         Q.idx8 = cb->idx8;
         Q.sym = cb->sym;
         if (!L().dry) {
           phase_indexes(Q, L().st);
-          Q.sym16 = dec->run(n_per, L().st, *cb) ? cb->sym16 : nullptr;
+          Q.sym16 = dec->run(n_per, L().st, *cb, phase_id) ? cb->sym16 : nullptr;
           phase_dequant(Q, L().st);
         }
       } else {
@@ -1764,6 +1789,7 @@ void Model::compress(const float* x, int B, int H, int W, const float* vbr_scale
   MLIC_CHECK(H % 64 == 0 && W % 64 == 0, "H and W must be multiples of 64");
   MLIC_CHECK(!gc_.empty() && !eb_.empty(), "entropy tables not set: call update() first");
   enc_all_.assign(B, EncodedImage{});
+  layers_.clear();
   enc_plane_ = gain_plane != nullptr;
   const int64_t img = (int64_t)3 * H * W, gp = (int64_t)(H / 16) * (W / 16);
   over_lanes(B, st, [&](Lane& l, int first, int cnt) {
@@ -1879,14 +1905,22 @@ HostPool& Model::host_pool() {
 
 void Model::decompress(const uint8_t* const* y, const size_t* ylen, const uint8_t* const* z, const size_t* zlen,
                        int B, int hz, int wz, float* x_hat, const float* vbr_scales, hipStream_t st, bool batch_stream,
-                       const float* gain_plane) {
+                       const float* gain_plane, const Prefix& prefix) {
   MLIC_CHECK(!gc_.empty() && !eb_.empty(), "entropy tables not set: call update() first");
   MLIC_CHECK(!(batch_stream && gain_plane), "a gain plane goes with per-image strings only");
+  const bool whole = prefix.slices < 0 && prefix.fill == 0 && prefix.strings == 1;
+  const int n_dec = prefix.slices < 0 ? cfg_.S : prefix.slices;
+  MLIC_CHECK(n_dec <= cfg_.S, "prefix decode: slices outside [0, S]");
+  MLIC_CHECK(prefix.fill == 0 || prefix.fill == 1, "prefix decode: fill must be 0 (mean) or 1 (zero)");
+  MLIC_CHECK(prefix.strings >= 1 && (prefix.strings == 1 || prefix.strings >= n_dec),
+             "prefix decode: fewer layer strings than slices");
+  MLIC_CHECK(whole || (!batch_stream && !gain_plane), "prefix decode: per-image strings without a gain plane only");
+  const int ns = prefix.strings;
   const int64_t img = (int64_t)3 * 64 * hz * 64 * wz, gp = (int64_t)16 * hz * wz;
   over_lanes(B, st, [&](Lane& l, int first, int cnt) {
     set_vbr(vbr_scales ? vbr_scales + first : nullptr, cnt, gain_plane ? gain_plane + first * gp : nullptr);
-    decompress_lane(batch_stream ? y : y + first, batch_stream ? ylen : ylen + first, z + first, zlen + first, cnt, hz,
-                    wz, x_hat + first * img, batch_stream);
+    decompress_lane(batch_stream ? y : y + first * ns, batch_stream ? ylen : ylen + first * ns, z + first,
+                    zlen + first, cnt, hz, wz, x_hat + first * img, batch_stream, prefix);
   }, batch_stream ? 1 : 16);
 }
 
@@ -1906,10 +1940,29 @@ std::string Model::batch_stream(int first, int count) const {
   return enc.flush();
 }
 
+const std::vector<std::string>& Model::layer_streams(int b) {
+  MLIC_CHECK(b >= 0 && b < (int)enc_all_.size(), "layer_streams: image index");
+  MLIC_CHECK(!enc_plane_, "layer_streams: the last compress coded with a gain plane (no layered form)");
+  if (layers_.size() != enc_all_.size()) layers_.assign(enc_all_.size(), {});
+  std::vector<std::string>& out = layers_[b];
+  const CoderView& v = enc_all_[b].y_in;
+  if (out.empty() && v.nph > 0) {
+    out.resize(v.nph / 2);
+    for (int k = 0; k < v.nph / 2; ++k) {  // coded LIFO: the slice's non-anchor phase goes in first
+      RansEncoder enc(2 * v.n_per);
+      v.put_phase(enc, 2 * k + 1, gc_);
+      v.put_phase(enc, 2 * k, gc_);
+      out[k] = enc.flush();
+    }
+  }
+  return out;
+}
+
 // mlicpp.py:292-378 for the lane's images: z decoded on the host, then 20 phases of
 // (network -> indexes D2H -> per-image host rANS decode -> symbols H2D -> dequantise)
 void Model::decompress_lane(const uint8_t* const* y, const size_t* ylen, const uint8_t* const* z,
-                            const size_t* zlen, int B, int hz, int wz, float* x_hat, bool batch_stream) {
+                            const size_t* zlen, int B, int hz, int wz, float* x_hat, bool batch_stream,
+                            const Prefix& prefix) {
   Lane& l = L();
   const int h = hz * 4, w = wz * 4;
   const int64_t n_per = (int64_t)cfg_.C * h * (w / 2);
@@ -1925,7 +1978,8 @@ void Model::decompress_lane(const uint8_t* const* y, const size_t* ylen, const u
       dz.decode(zi.data(), zper, eb_, l.h_sym + b * zper);
     }, HostPool::DECODE);
   }
-  PhaseDecoder dec(B, y, ylen, &gc_, l.h_sym, l.h_sym16, l.h_idx8, &hstats_, &host_pool(), batch_stream);
+  PhaseDecoder dec(B, y, ylen, &gc_, l.h_sym, l.h_sym16, l.h_idx8, &hstats_, &host_pool(), batch_stream,
+                   prefix.strings);
   const int32_t* hz_sym = l.h_sym;
   range_clear(l);
   View yhat;
@@ -1944,7 +1998,7 @@ void Model::decompress_lane(const uint8_t* const* y, const size_t* ylen, const u
     }
     View hyper = h_s(zh);
     yhat = alloc(cfg_.M, h, w);
-    slice_loop(Mode::Decode, hyper, nullptr, yhat, nullptr, &cb, &dec);
+    slice_loop(Mode::Decode, hyper, nullptr, yhat, nullptr, &cb, &dec, prefix.slices, prefix.fill);
     // the entropy model (h_s + slice loop) must match the encoder's arithmetic: no fallback there
     if (!l.dry && prec() != PREC_F32 && range_hit(l)) throw Error(kRangeMsg);
     g_s(yhat, out);

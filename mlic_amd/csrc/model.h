@@ -123,6 +123,17 @@ struct CoderBufs {
   int* ovf = nullptr;
 };
 
+// progressive decode (DESIGN.md section 5 "Progressive coding"): the first `slices` channel slices are
+// entropy-decoded (< 0: all), the rest filled (fill 0: mean fill, the slice loop runs on with all-zero symbols;
+// 1: zero fill, the loop stops and the tail channels of y_hat are cleared); strings = y strings per image
+// (1: the single string, whose prefix of phases the forward-reading decoder needs nothing new for; > 1: one
+// string per slice, y[b * strings + k])
+struct Prefix {
+  int slices = -1;
+  int fill = 0;
+  int strings = 1;
+};
+
 struct EncodedImage {
   std::string y;  // one rANS stream for all slices/phases
   std::string z;  // z stream (EntropyBottleneck)
@@ -211,11 +222,14 @@ class Model {
   // 279-281: phase-major, image-minor); decoded on one lane (the stream is sequential)
   void decompress(const uint8_t* const* y, const size_t* ylen, const uint8_t* const* z, const size_t* zlen, int B,
                   int hz, int wz, float* x_hat, const float* vbr_scales, hipStream_t st, bool batch_stream = false,
-                  const float* gain_plane = nullptr);
+                  const float* gain_plane = nullptr, const Prefix& prefix = Prefix{});
   // the last compress()'s images [first, first + count) coded into ONE y stream in the reference's
   // batched order (mlicpp.py:215, 279-281): byte-identical to what the reference's compress() emits for
   // that batch when it codes the same symbols
   std::string batch_stream(int first, int count) const;
+  // image b of the last compress() as S strings, one per channel slice: string k = rans_encode of phases 2 k and
+  // 2 k + 1 (the symbol and index lists of the single string); kept until the next compress()
+  const std::vector<std::string>& layer_streams(int b);
   void set_tables(const CdfTables& gc, const CdfTables& eb) {
     gc_ = gc;
     eb_ = eb;
@@ -302,7 +316,7 @@ class Model {
   void over_lanes(int B, hipStream_t caller, F&& fn, int max_lanes = 16);
   void compress_lane(const float* x, int B, int H, int W);
   void decompress_lane(const uint8_t* const* y, const size_t* ylen, const uint8_t* const* z, const size_t* zlen,
-                       int B, int hz, int wz, float* x_hat, bool batch_stream);
+                       int B, int hz, int wz, float* x_hat, bool batch_stream, const Prefix& prefix);
 
   // -- weights
   const ConvW& cw(const std::string& k) const;
@@ -354,8 +368,9 @@ class Model {
                           const View* hoisted = nullptr, bool phase_only = false);
   void lrp(const std::vector<View>& ins, const std::string& kind, int i, const View& yh_slice, bool anchor);
   View qkv_branch(const View& x, const std::string& p);
+  // n_dec / fill (Mode::Decode only): slices [n_dec, S) are not entropy-decoded (struct Prefix)
   void slice_loop(Mode mode, const View& hyper, const View* y, const View& yhat, float* y_lik, const CoderBufs* cb,
-                  class PhaseDecoder* dec);
+                  class PhaseDecoder* dec, int n_dec = -1, int fill = 0);
   void eb(const View& z, const View& z_hat, float* z_lik, int32_t* z_sym);
 
   template <class F>
@@ -365,6 +380,7 @@ class Model {
   static int phase_d2h_mode();
   void set_vbr(const float* scales, int B, const float* gain_plane = nullptr);
   bool enc_plane_ = false;  // the last compress() coded with a gain plane (batch_stream() refuses it)
+  std::vector<std::vector<std::string>> layers_;  // layer_streams(): [image][slice], emptied by compress()
 };
 
 }  // namespace mlic

@@ -308,14 +308,20 @@ class MLICPlusPlus(nn.Module):
         self._tables_pushed = h
 
     @torch.no_grad()
-    def compress(self, x: torch.Tensor, batch_stream: bool = False, **kw):
+    def compress(self, x: torch.Tensor, batch_stream: bool = False, layered: bool = False, **kw):
         """mlicpp.py:199-290.  strings = [[y_stream per image], [z_stream per image]] (B = 1: exactly
         the reference's layout; for B > 1 each image gets its own y stream, which the host codes in
         parallel).  batch_stream=True: the reference's B > 1 layout instead, ONE y stream for the batch
         (mlicpp.py:215, 279-281; phase-major, image-minor).  decompress() accepts both.
+        layered=True adds "layers": per image a list of slice_num bytes, one rANS string per channel slice
+        (progressive coding; decompress_layers reads any prefix of them); "strings" is unchanged.
         cost_time brackets the call with the caller's stream synchronised (the reference synchronises the
         whole device, mlicpp.py:200, 282; a stream keeps concurrent callers on other streams apart)."""
         B, _, H, W = x.shape
+        if layered and batch_stream:
+            raise ValueError("layered=True is not supported with batch_stream=True (layers are per-image strings)")
+        if layered and kw.get("gain_map") is not None:
+            raise ValueError("layered=True is not supported with gain_map (ROI coding has no layered form)")
         g = self._gain_plane(kw.pop("gain_map", None), B, H // 16, W // 16, x.device)
         if g is not None and batch_stream:
             raise ValueError("batch_stream=True is not supported with gain_map (ROI coding writes per-image strings)")
@@ -346,18 +352,102 @@ class MLICPlusPlus(nn.Module):
             buf = C.create_string_buffer(max(1, n.value))
             _lib.call("mlic_batch_stream", h, 0, B, buf, n.value, C.byref(n))
             ys = [C.string_at(buf, n.value)]
+        out = {"strings": [ys, zs], "shape": torch.Size([H // 64, W // 64])}
+        if layered:
+            out["layers"] = [self.layer_streams(b) for b in range(B)]
         torch.cuda.current_stream(x.device).synchronize()
-        return {"strings": [ys, zs], "shape": torch.Size([H // 64, W // 64]), "cost_time": time.time() - t0}
+        out["cost_time"] = time.time() - t0
+        return out
+
+    def layer_streams(self, b: int = 0):
+        """Image b of the last compress() as slice_num rANS strings, one per channel slice: string k codes the
+        symbols of phases 2 k and 2 k + 1 (the lists encoded_streams returns, cut per slice)."""
+        S = self.slice_num
+        ptrs, lens, n = (C.c_void_p * S)(), (C.c_size_t * S)(), C.c_int()
+        _lib.call("mlic_layer_streams", self._handle, b, ptrs, lens, S, C.byref(n))
+        return [C.string_at(ptrs[k], lens[k]) if lens[k] else b"" for k in range(n.value)]
+
+    def _prefix_args(self, slices, fill):
+        """(K, fill code) of a prefix decode, refused here before anything touches the device."""
+        S = self.slice_num
+        if fill not in ("mean", "zero"):
+            raise ValueError(f"fill must be 'mean' or 'zero', got {fill!r}")
+        if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)):
+            raise ValueError(f"slices must be an integer in [0, {S}], got {slices!r}")
+        if not 0 <= int(slices) <= S:
+            raise ValueError(f"slices must be in [0, {S}], got {slices}")
+        return int(slices), 0 if fill == "mean" else 1
+
+    def _decompress_prefix(self, ys, spi, zs, shape, K, fill, kw):
+        dev = self.device
+        B = len(zs)
+        hz, wz = int(shape[0]), int(shape[1])
+        torch.cuda.current_stream(dev).synchronize()
+        t0 = time.time()
+        h = self._ensure_handle(dev)
+        self._push_tables(h)
+        x_hat = self._out((B, 3, hz * 64, wz * 64), dev)
+        ybufs = [C.create_string_buffer(s, max(1, len(s))) for s in ys]  # (a layer may be empty)
+        zbufs = [C.create_string_buffer(s, len(s)) for s in zs]
+        yp = (C.c_void_p * len(ys))(*[C.cast(b, C.c_void_p) for b in ybufs])
+        zp = (C.c_void_p * B)(*[C.cast(b, C.c_void_p) for b in zbufs])
+        yl = (C.c_size_t * len(ys))(*[len(s) for s in ys])
+        zl = (C.c_size_t * B)(*[len(s) for s in zs])
+        sc = self._vbr_scales(B, **kw)
+        _lib.call("mlic_decompress_prefix", h, self._stream(), yp, yl, spi, zp, zl, B, hz, wz, K, fill,
+                  sc.ctypes.data, x_hat.data_ptr())
+        torch.cuda.current_stream(dev).synchronize()
+        return {"x_hat": x_hat, "cost_time": time.time() - t0, "slices": K}
 
     @torch.no_grad()
-    def decompress(self, strings, shape, **kw):
-        """mlicpp.py:292-378."""
+    def decompress_layers(self, layers, z_strings, shape, slices=None, fill: str = "mean", **kw):
+        """Progressive decode of layered strings (compress(layered=True)["layers"], or any prefix of each
+        image's list): the first `slices` channel slices are entropy-decoded (None: every layer given), the rest
+        are filled -- fill="mean": as if all their symbols were 0 (predicted mean + latent residual
+        prediction), "zero": y_hat channels cleared and the slice loop cut short.  Every image brings the same
+        number of layers, at least `slices`."""
+        layers = [list(l) for l in layers]
+        zs = list(z_strings)
+        if len(layers) != len(zs) or not zs:
+            raise ValueError("expected one list of layers and one z string per image")
+        n = len(layers[0])
+        if any(len(l) != n for l in layers):
+            raise ValueError("every image must bring the same number of layers (one K per call)")
+        if n > self.slice_num:
+            raise ValueError(f"{n} layers given, the model has {self.slice_num} slices")
+        K, f = self._prefix_args(n if slices is None else slices, fill)
+        if K > n:
+            raise ValueError(f"slices={K} but only {n} layers given")
+        if kw.get("gain_map") is not None:
+            raise ValueError("slices= / layers are not supported with gain_map (ROI coding)")
+        kw.pop("gain_map", None)
+        if n == 0:  # nothing to read: one empty string per image
+            return self._decompress_prefix([b""] * len(zs), 1, zs, shape, 0, f, kw)
+        if n == 1:  # one layer per image reads as a single string whose first slice is decoded
+            return self._decompress_prefix([l[0] for l in layers], 1, zs, shape, K, f, kw)
+        return self._decompress_prefix([s for l in layers for s in l], n, zs, shape, K, f, kw)
+
+    @torch.no_grad()
+    def decompress(self, strings, shape, slices=None, fill: str = "mean", **kw):
+        """mlicpp.py:292-378.  slices=K: a prefix decode of today's strings, the first K channel slices
+        entropy-decoded and the rest filled (decompress_layers says how); K = slice_num with fill="mean" is
+        the plain decode bit for bit."""
         dev = self.device
         ys, zs = list(strings[0]), list(strings[1])
         B = len(zs)
         single = len(ys) == 1 and B > 1  # the reference's batched layout (mlicpp.py:306-307)
         if len(ys) != B and not single:
             raise ValueError("expected one y stream per image, or one stream for the whole batch")
+        if slices is not None:
+            K, f = self._prefix_args(slices, fill)
+            if single:
+                raise ValueError("slices= is not supported with the batch-stream layout (one y stream for the batch)")
+            if kw.get("gain_map") is not None:
+                raise ValueError("slices= is not supported with gain_map (ROI coding)")
+            kw.pop("gain_map", None)
+            return self._decompress_prefix(ys, 1, zs, shape, K, f, kw)
+        if fill != "mean":
+            raise ValueError("fill= goes with slices=")
         hz, wz = int(shape[0]), int(shape[1])
         g = self._gain_plane(kw.pop("gain_map", None), B, 4 * hz, 4 * wz, dev)
         if g is not None and single:
@@ -464,13 +554,20 @@ class MLICPlusPlusVbr(MLICPlusPlus):
     def forward(self, x, stage: int = 2, s=1, inputscale=0, gain_map=None):
         return super().forward(x, stage=stage, s=s, inputscale=inputscale, gain_map=gain_map)
 
-    def compress(self, x, stage: int = 2, s=1, inputscale=0, batch_stream: bool = False, gain_map=None):
-        return super().compress(x, batch_stream=batch_stream, stage=stage, s=s, inputscale=inputscale, coder=True,
-                                gain_map=gain_map)
+    def compress(self, x, stage: int = 2, s=1, inputscale=0, batch_stream: bool = False, gain_map=None,
+                 layered: bool = False):
+        return super().compress(x, batch_stream=batch_stream, layered=layered, stage=stage, s=s,
+                                inputscale=inputscale, coder=True, gain_map=gain_map)
 
-    def decompress(self, strings, shape, stage: int = 2, s=1, inputscale=0, gain_map=None):
-        return super().decompress(strings, shape, stage=stage, s=s, inputscale=inputscale, coder=True,
-                                  gain_map=gain_map)
+    def decompress(self, strings, shape, stage: int = 2, s=1, inputscale=0, gain_map=None, slices=None,
+                   fill: str = "mean"):
+        return super().decompress(strings, shape, slices=slices, fill=fill, stage=stage, s=s, inputscale=inputscale,
+                                  coder=True, gain_map=gain_map)
+
+    def decompress_layers(self, layers, z_strings, shape, slices=None, fill: str = "mean", stage: int = 2, s=1,
+                          inputscale=0):
+        return super().decompress_layers(layers, z_strings, shape, slices=slices, fill=fill, stage=stage, s=s,
+                                         inputscale=inputscale, coder=True)
 
 
 class MLICPlusPlusSDVbr(MLICPlusPlusVbr):

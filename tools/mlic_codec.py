@@ -43,6 +43,17 @@
         (0..256, default 256): blend the map over the image, 256 = the map alone.  --csv FILE: the per-slice bit
         totals and the plane, as text.  An 8-bit RGB image; not together with any other coding option
 
+    ... --layered (encode): progressive coding.  The y symbols are coded as one rANS string per channel slice and
+        the file is the layered file, which still decodes when it is cut after any layer.  Goes with --level N; not
+        with --max-bpp, --level auto, --roi, --tile, --scale / --coded-size or frame files
+    ... --slices K [--fill mean|zero] (decode): entropy-decode the first K channel slices only, of a plain, VBR or
+        layered file.  mean (default): the other slices take their predicted mean (and the latent residual
+        prediction); zero: they are cleared and the slice loop stops after slice K - 1 (the cheap preview).  A
+        layered file, whole or truncated, is recognised by its magic; without --slices every layer it holds is
+        decoded.  Not with --out-size, --region or frame files
+    python tools/mlic_codec.py truncate IN.bit -k K -o OUT.bit     the first bytes of a layered file up to the end
+        of layer K - 1 (K = 0: the header and z alone); needs no model
+
     ... samples deeper than 8 bits (codec.encode_images(depth=) / YuvFormat(depth=); the bitstream does not know
         its depth).  A binary PPM of maxval 2^d - 1, d from 9 to 16 (16-bit big-endian samples), is encoded at depth d;
         decode IN.bit OUT.ppm --depth D writes one.  .y4m: C420pN / C422pN / C444pN for N in 9, 10, 12, 14, 16
@@ -388,7 +399,7 @@ def _full_scale(v: str) -> float:
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["encode", "decode", "info", "ratemap"])
+    ap.add_argument("mode", choices=["encode", "decode", "info", "ratemap", "truncate"])
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("--model", default="MLICPP_L")
@@ -423,7 +434,36 @@ def parse_args(argv=None):
     ap.add_argument("--alpha", type=int, default=None, metavar="A")
     ap.add_argument("--hi", type=_full_scale, default=None, metavar="X")
     ap.add_argument("--csv", default=None, metavar="FILE")
+    ap.add_argument("--layered", action="store_true")
+    ap.add_argument("--slices", type=int, default=None, metavar="K")
+    ap.add_argument("--fill", choices=["mean", "zero"], default=None)
+    ap.add_argument("-k", "--keep", type=int, default=None, metavar="K")
     args = ap.parse_args(argv)
+    if args.mode == "truncate":
+        if args.dst is not None or args.output is None or args.keep is None or args.keep < 0:
+            ap.error("truncate takes one layered file, -k K (the layers to keep, not negative) and -o OUT")
+        given = {k: v for k, v in vars(args).items() if k not in ("mode", "src", "dst", "output", "keep", "model")}
+        defaults = {k: ap.get_default(k) for k in given}
+        if given != defaults:
+            ap.error("truncate goes with -k and -o alone (it needs no model)")
+        args.frame_file = False
+        return args
+    if args.keep is not None:
+        ap.error("-k goes with truncate")
+    if args.layered:
+        if args.mode != "encode":
+            ap.error("--layered goes with encode (a layered file is recognised by its magic)")
+        if args.max_bpp is not None or args.level == "auto" or args.roi is not None or args.roi_levels is not None or \
+                args.tile is not None or args.scale is not None or args.coded_size is not None or _is_yuv(args.src):
+            ap.error("--layered goes with --level N alone, not with --max-bpp, --level auto, --roi, --tile, --scale, "
+                     "--coded-size or Y'CbCr frames")
+    if args.slices is not None or args.fill is not None:
+        if args.mode != "decode":
+            ap.error("--slices and --fill go with decode")
+        if args.slices is not None and args.slices < 0:
+            ap.error("--slices must not be negative")
+        if args.out_size is not None or args.region is not None or _is_yuv(args.dst or ""):
+            ap.error("--slices / --fill together with --out-size, --region or Y'CbCr frames are not supported")
     map_flags = [args.output, args.what, args.cmap, args.alpha, args.hi, args.csv]
     if args.mode != "ratemap":
         if any(v is not None for v in map_flags):
@@ -593,6 +633,19 @@ def main(argv=None):
     from mlic_amd import codec
     if args.mode == "ratemap":
         return _ratemap(args)
+    if args.mode == "truncate":
+        with open(args.src, "rb") as f:
+            data = f.read()
+        if not codec.is_layered_file(data):
+            raise SystemExit(f"{args.src}: not a layered file (no MLL1 magic): encode --layered writes one")
+        try:
+            cut = codec.truncate_layered(data, args.keep)
+        except ValueError as e:
+            raise SystemExit(f"{args.src}: {e}") from None
+        with open(args.output, "wb") as f:
+            f.write(cut)
+        print(f"{args.src}: {len(data)} bytes -> {args.output}: {len(cut)} bytes, {args.keep} layers")
+        return
     if args.mode == "info":
         from mlic_amd import spec
         with open(args.src, "rb") as f:
@@ -604,6 +657,18 @@ def main(argv=None):
                 raise SystemExit(f"{args.src}: the tiles {'carry a' if flag else 'have no'} level word, "
                                  f"{args.model} is {'variable' if vbr else 'fixed'}-rate")
         d = codec.peek(data, vbr=vbr, n_levels=len(spec.vbr_lambdas(args.model)) if vbr else None)
+        if d.get("layered"):
+            if d["vbr"] != vbr:
+                raise SystemExit(f"{args.src}: the file {'carries a' if d['vbr'] else 'has no'} level word, "
+                                 f"{args.model} is {'variable' if vbr else 'fixed'}-rate")
+            print(f"{args.src}: {d['H']} x {d['W']}, layered: {d['layers_present']} of {d['slices']} layers"
+                  f"{'' if d['layers_present'] == d['slices'] else ' (truncated)'}, level {d['level']}, z grid "
+                  f"{d['shape'][0]} x {d['shape'][1]}, z {d['z_len']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
+            at = d["header_bytes"] + d["z_len"]
+            for k, n in enumerate(d["layer_bytes"]):
+                at += 4 + n
+                print(f"  layer {k}: {n} B, file up to here {at} B, {8.0 * at / (d['H'] * d['W']):.4f} bpp")
+            return
         if d.get("tiled"):
             print(f"{args.src}: {d['H']} x {d['W']}, tiled: tile {d['tile']}, overlap {d['overlap']}, grid "
                   f"{d['grid'][0]} x {d['grid'][1]}, level {d['level']}, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
@@ -688,7 +753,8 @@ def main(argv=None):
         try:
             files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
                                               max_passes=args.max_passes, return_info=True, roi=roi,
-                                              roi_levels=None if roi is None else tuple(args.roi_levels), **deep, **scaled)
+                                              roi_levels=None if roi is None else tuple(args.roi_levels), **deep, **scaled,
+                                              **({"layered": True} if args.layered else {}))
         except ValueError as e:
             if not scaled:
                 raise
@@ -702,6 +768,8 @@ def main(argv=None):
             line += f", depth {depth}"
         if scaled:
             line += f", coded at {info[0]['coded'][0]} x {info[0]['coded'][1]} ({info[0]['filter']})"
+        if args.layered:
+            line += ", layered: " + " ".join(str(n) for n in info[0]["layer_bytes"]) + " B per slice"
         if args.max_bpp is not None:
             line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
                      f"{'met' if info[0]['met'] else 'not met'}")
@@ -713,6 +781,8 @@ def main(argv=None):
             data = f.read()
         net = load_model(args)
         if codec.is_tiled_file(data):
+            if args.slices is not None or args.fill is not None:
+                raise SystemExit(f"{args.src}: --slices / --fill on a tiled file are not supported")
             img, info = codec.decode_tiled(net, data, region=args.region, tile_batch=args.tile_batch)
             save_image(args.dst, img.cpu().numpy())
             y0, x0, h, w = info["region"]
@@ -728,10 +798,15 @@ def main(argv=None):
             kw["out_size"] = (args.out_size[1], args.out_size[0])
         if args.filter is not None:
             kw["filter"] = args.filter
+        if args.slices is not None:
+            kw["slices"] = args.slices
+        if args.fill is not None:
+            kw["fill"] = args.fill
         try:
             img, info = codec.decode_images(net, [data], **kw)
         except ValueError as e:
-            if not (args.out_size or args.filter or codec.is_scaled_file(data)):
+            if not (args.out_size or args.filter or codec.is_scaled_file(data) or args.slices is not None or
+                    args.fill is not None or codec.is_layered_file(data)):
                 raise
             raise SystemExit(f"{args.src}: {e}") from None
         save_image(args.dst, img[0].cpu().numpy(), depth)
@@ -739,6 +814,8 @@ def main(argv=None):
         if "coded" in info[0]:
             line += (f", display {info[0]['display'][0]} x {info[0]['display'][1]}, coded at {info[0]['coded'][0]} x "
                      f"{info[0]['coded'][1]} ({info[0]['filter']})")
+        if "slices" in info[0]:
+            line += f", {info[0]['slices']} slices decoded ({args.fill or 'mean'} fill)"
         print(line)
 
 
