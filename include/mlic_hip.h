@@ -737,6 +737,73 @@ int mlic_container_write_layered(uint32_t H, uint32_t W, int level, uint32_t hz,
                                  uint8_t* out, size_t cap, size_t* len);
 int mlic_container_parse_layered(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels, int allow_truncated,
                                  mlic_container_layered_info* info);
+/* ---- Residual coding: near-lossless and lossless files (DESIGN.md section 5 "Residual coding") ----
+ *
+ * Integer definitions (csrc/residual.h).  Samples are 8-bit RGB in the canonical order i = (c H + y) W + x.  base is
+ * the byte image the inner file decodes to, tau in 0..127, step = 2 tau + 1:
+ *     r = x - base;  q = sign(r) floor((|r| + tau) / step);  rec = clamp(base + q step, 0, 255)
+ * so |x - rec| <= tau, rec = x at tau = 0, |q| <= 255.  Context = 8 c + class; a = max - min of channel c of base
+ * over the 3 x 3 neighbourhood (coordinates clamped into the image); class 0 for a < 2, else floor(log2 a).
+ * Histogram bin q + 63 for |q| <= 63, bin 127 (the escape) otherwise.  Digest of base: the sum over i of
+ * (base_i + 1) ((i + 1) 0x9E3779B97F4A7C15) mod 2^64.
+ *
+ * mlic_image_residual_front_u8: base, and optionally x, through element strides {image, row, column, channel}.
+ * Always written: ctx u8 [B][3][H][W] (dense, canonical order), ctx_count u32 [B][24], digest u64 [B].  With x also
+ * sym int16 [B][3][H][W], hist u32 [B][24][128] and max_err u32 [B], the largest |x - rec| of each image.  The call
+ * zeroes ctx_count, digest, hist and max_err itself, on the stream.  One launch, asynchronous on `stream`.
+ * Refused before any HIP call, each with its own message: null base; null base strides; B < 1; H or W < 1; tau
+ * outside 0..127; a zero column or channel stride of base; null ctx; null ctx_count; null digest; ctx_count not
+ * 4-byte or digest not 8-byte aligned; x without strides; a zero column or channel stride of x; x without all of
+ * sym, hist and max_err; sym not 2-byte or hist / max_err not 4-byte aligned; sym, hist or max_err without x; a
+ * batch too large for one launch. */
+int mlic_image_residual_front_u8(void* stream, const uint8_t* base, const int64_t* base_strides, const uint8_t* x,
+                                 const int64_t* x_strides, int B, int H, int W, int tau, uint8_t* ctx,
+                                 uint32_t* ctx_count, uint64_t* digest, int16_t* sym, uint32_t* hist, uint32_t* max_err);
+/* mlic_image_residual_apply_u8: out = rec of (base, sym), written through out_strides; only the image's bytes are
+ * written.  With ref (its own strides): sq_err u64 [B], the exact sum of squared differences out - ref, and max_err
+ * u32 [B], the largest |out - ref|; the call zeroes both on the stream.  One launch, asynchronous on `stream`.
+ * Refused before any HIP call, each with its own message: null base; null base strides; null sym; null out or out
+ * strides; B < 1; H or W < 1; tau outside 0..127; a zero column or channel stride of base, of out; sym not 2-byte
+ * aligned; ref without sq_err; ref without max_err; sq_err or max_err without ref; ref without strides or with a
+ * zero column or channel stride; sq_err not 8-byte or max_err not 4-byte aligned; a batch too large. */
+int mlic_image_residual_apply_u8(void* stream, const uint8_t* base, const int64_t* base_strides, const int16_t* sym,
+                                 int B, int H, int W, int tau, uint8_t* out, const int64_t* out_strides,
+                                 const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err);
+/* One image's tables from its histograms hist[24][128].  Per context with a nonzero count: m = the largest |q| <= 63
+ * seen (0 if none); the symbols -m..m and, last, the escape go through mlic_pmf_to_quantized_cdf at precision 16 on
+ * (float)count / (float)total, which keeps every frequency >= 1.  m[24]: 0..63, or 0xFF for a context with count 0.
+ * freq (optional) [24][128]: the 2 m + 2 frequencies of each table, zero behind them.  cdf [24][129], cdf_len [24]
+ * (2 m + 3; 0 = absent) and offset [24] (-m) (optional, all three or none) are mlic_rans_encode's tables with
+ * stride 129; the escape of that coder carries |q| > m.  Host only. */
+int mlic_residual_tables(const uint32_t* hist, uint8_t* m, uint16_t* freq, int32_t* cdf, int32_t* cdf_len,
+                         int32_t* offset);
+/* The residual file, big-endian:
+ *     "MLR1" | u8 version 0 | u8 flags (bit 0: the inner file has a VBR level word) | u8 tau | u8 n_ctx = 24
+ *     u32 H, W | u64 digest
+ *     24 x ( u8 m (0..63, or 0xFF = absent) | unless absent: (2 m + 2) x u16 frequencies, each >= 1, sum 65536 )
+ *     u32 inner_len, inner file (exactly mlic_container_write's file for the image) | u32 res_len, residual bytes
+ * write: the *len / out / cap protocol of mlic_container_write; m is 24 bytes and freq mlic_residual_tables' rows.
+ * parse: validating, never reads outside data[0, n).  Refused, each with its own message: a truncated header, table
+ * or string; bad magic, version, flags or n_ctx; tau > 127; H or W zero; H * W > max_pixels; an m in 64..254; a
+ * zero frequency; a wrong sum; inner_len or res_len past the end; an empty inner file; trailing bytes; whatever
+ * mlic_container_parse refuses in the inner file; an inner H x W different from the outer.  info->inner's offsets
+ * are relative to the inner file.  mlic_container_parse and the ROI, tiled, scaled and layered parsers keep
+ * refusing a residual file. */
+typedef struct mlic_container_residual_info {
+  uint32_t H, W;
+  int32_t tau;
+  int32_t vbr; /* flags bit 0 */
+  uint64_t digest;
+  uint8_t m[24];
+  uint64_t freq_off[24]; /* table k's frequencies: data + freq_off[k], 2 m[k] + 2 big-endian u16 */
+  uint64_t inner_off, inner_len, res_off, res_len;
+  mlic_container_info inner;
+} mlic_container_residual_info;
+int mlic_container_write_residual(uint32_t H, uint32_t W, int vbr, int tau, uint64_t digest, const uint8_t* m,
+                                  const uint16_t* freq, const uint8_t* inner, size_t inner_len, const uint8_t* res,
+                                  size_t res_len, uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_residual(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                  mlic_container_residual_info* info);
 /* mlic_encode_image_u8 at reduced (or raised) resolution: the H x W image is resampled to coded_H x coded_W on
  * the way in, coded as mlic_encode_image_u8 codes an image of that size, and wrapped in the scaled file with H, W
  * as the display size.  The out == NULL / rgb_dev == NULL protocol is that of mlic_encode_image_u8. */

@@ -45,6 +45,13 @@ class ContainerScaledInfo(C.Structure):
                 ("inner_off", C.c_uint64), ("inner_len", C.c_uint64), ("inner", ContainerInfo)]
 
 
+class ContainerResidualInfo(C.Structure):
+    """mlic_container_residual_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("tau", C.c_int32), ("vbr", C.c_int32), ("digest", C.c_uint64),
+                ("m", C.c_uint8 * 24), ("freq_off", C.c_uint64 * 24), ("inner_off", C.c_uint64),
+                ("inner_len", C.c_uint64), ("res_off", C.c_uint64), ("res_len", C.c_uint64), ("inner", ContainerInfo)]
+
+
 class ContainerLayeredInfo(C.Structure):
     """mlic_container_layered_info (include/mlic_hip.h)."""
     _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("hz", C.c_uint32), ("wz", C.c_uint32), ("level", C.c_int32),
@@ -182,6 +189,11 @@ def _sig(lib):
         "mlic_container_write_scaled": [C.c_uint32, C.c_uint32, i, i, p, sz, p, sz, P(sz)],
         "mlic_container_parse_scaled": [p, sz, i, C.c_uint64, P(ContainerScaledInfo)],
         "mlic_encode_image_u8_scaled": [p, p, p, P(i64), i, i, i, i, i, f, i, p, sz, P(sz)],
+        "mlic_image_residual_front_u8": [p, p, P(i64), p, P(i64), i, i, i, i, p, p, p, p, p, p],
+        "mlic_image_residual_apply_u8": [p, p, P(i64), p, i, i, i, i, p, P(i64), p, P(i64), p, p],
+        "mlic_residual_tables": [p, p, p, p, p, p],
+        "mlic_container_write_residual": [C.c_uint32, C.c_uint32, i, i, C.c_uint64, p, p, p, sz, p, sz, p, sz, P(sz)],
+        "mlic_container_parse_residual": [p, sz, i, C.c_uint64, P(ContainerResidualInfo)],
         "mlic_decode_image_u8_sized": [p, p, p, sz, i, C.c_uint64, p, i, i, i, p, P(i64), sz, P(i), P(i), P(i), P(i),
                                        P(i)],
         "mlic_image_ingest_yuv8": [p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, p, i, i],

@@ -100,7 +100,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
                dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, yuv=None, rate_map: bool = False,
-               progressive: bool = False, **kw) -> Dict:
+               progressive: bool = False, max_error=None, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -133,9 +133,21 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     rANS string per channel slice), decoded from its layers, and the record also holds "layer_bytes" (S ints: the
     exact coded bytes per slice) and "prefix_psnr" (S + 1 floats: PSNR of the mean-fill decode of the first K
     layers, K = 0..S).  Not together with tile=, roi=, max_bpp=, scale= / coded_size= or batch_stream; off by
-    default."""
+    default.
+    max_error=tau: the record also holds "residual_bytes" (the residual string that brings every sample of to_u8(img)
+    within tau of the decode; codec.encode_images(max_error=tau) of to_u8(img), decoded again) and "max_abs_err"
+    (the largest error of that decode, measured: <= tau).  bytes, bpp, psnr and x_hat stay those of the base file.
+    Not together with tile=, roi=, max_bpp=, progressive=, yuv=, scale= / coded_size=, depth= or batch_stream; off
+    by default."""
     assert img.dim() == 4 and img.size(0) == 1
     H, W = img.shape[-2:]
+    if max_error is not None:
+        given = {"tile": tile, "roi": roi, "roi_levels": roi_levels, "max_bpp": max_bpp, "yuv": yuv,
+                 "progressive": progressive or None, "scale": kw.get("scale"), "coded_size": kw.get("coded_size"),
+                 "depth": kw.get("depth"), "batch_stream": kw.get("batch_stream") or None}
+        for k, v in given.items():
+            if v is not None:
+                raise ValueError(f"code_image: max_error= together with {k}= is not supported")
     if progressive:
         given = {"tile": tile, "roi": roi, "roi_levels": roi_levels, "max_bpp": max_bpp, "scale": kw.get("scale"),
                  "coded_size": kw.get("coded_size"), "batch_stream": kw.get("batch_stream") or None}
@@ -262,6 +274,12 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
             {k: v for k, v in kw.items() if k != "batch_stream"}
         sb = net.rate_map(x.contiguous().float(), **fkw)["slice_bits"][0].cpu().tolist()
         r["slice_bits"], r["z_bits"] = sb[:-1], sb[-1]
+    if max_error is not None:
+        from . import codec
+        u8 = to_u8(img[0]).permute(1, 2, 0).contiguous()
+        files, einfo = codec.encode_images(net, u8, level=level, layout="hwc", max_error=max_error, return_info=True)
+        _, dinfo = codec.decode_images(net, files, ref=u8.unsqueeze(0))
+        r["residual_bytes"], r["max_abs_err"] = einfo[0]["residual_bytes"], dinfo[0]["max_abs_err"]
     if yuv is not None:
         from . import codec
         src = codec.egress_yuv(img.float().contiguous(), H, W, yuv)

@@ -34,6 +34,13 @@ latent pixel and slice the sum of -log2 of forward()'s likelihoods, the per-cell
 per-slice totals; `sq_err_blocks` is the matching error map (squared uint8 error per block) and `heat_u8` draws either
 as a heat map, optionally blended over the image.
 
+`encode_images(max_error=tau)` adds a second layer that bounds the error of every sample (DESIGN.md §5 "Residual
+coding", csrc/residual.hip): the image is coded as before, its own strings are decoded to the base image, and
+`residual_front` gives the quantised difference with a context per sample that reads the base image alone, the
+histograms the tables are built from and a digest of the base image; the residual file wraps the unchanged plain
+file.  `decode_images` checks the digest, decodes the residual string and `residual_apply` adds it back: no sample
+is off by more than tau, and at tau = 0 the decode is the original.  `strip_residual` returns the plain file.
+
 CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
 """
@@ -47,7 +54,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, bitstream
+from . import _lib, bitstream, entropy
 
 MAX_PIXELS = 1 << 28  # default bound on a file's padded Hp * Wp (a 16384 x 16384 image)
 _NO_LEVEL_LIMIT = 0x7FFFFFFF
@@ -425,8 +432,13 @@ def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pix
     truncated; its flags say whether it has a level word) gives {"layered": True, H, W, level, vbr, shape, Hp, Wp,
     "slices" (S), "layers_present", "layer_bytes" (the whole layers' lengths: exact coded bytes per slice), z_len,
     "header_bytes" (everything before the z string), bytes, bpp}: a whole file's bytes are header_bytes + z_len +
-    sum(layer_bytes) + 4 per layer."""
+    sum(layer_bytes) + 4 per layer.  A residual file (is_residual_file; its flags say whether the inner file has a
+    level word) gives {"residual": True, H, W, "max_error" (tau), vbr, level, shape, Hp, Wp, y_len, z_len, "digest",
+    "base_bytes" (the inner file), "residual_bytes" (the residual string), "header_bytes" (the rest: header, tables
+    and the two length words), bytes, bpp}."""
     data = bytes(data)
+    if is_residual_file(data):
+        return _peek_residual(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
     if is_layered_file(data):
         return _peek_layered(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
     if is_tiled_file(data):
@@ -799,6 +811,403 @@ def _peek_scaled(data: bytes, n_levels, max_pixels) -> Dict:
             "y_len": c.y_len, "z_len": c.z_len, "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
 
 
+# ---------------------------------------------------------------------------------- residual coding
+RESIDUAL_MAGIC = b"MLR1"
+MAX_TAU = 127
+RES_CTX, RES_BINS, RES_MAX_M, RES_ABSENT, RES_CDF_STRIDE = 24, 128, 63, 0xFF, 129
+_DIGEST_K = 0x9E3779B97F4A7C15
+_CLASS_OF = np.array([0 if a < 2 else a.bit_length() - 1 for a in range(256)], np.uint8)  # class of a = max - min
+
+
+def _check_tau(tau, what: str) -> int:
+    if isinstance(tau, bool) or not isinstance(tau, (int, np.integer)) or not 0 <= tau <= MAX_TAU:
+        raise ValueError(f"{what}: max_error must be an integer in [0, {MAX_TAU}], got {tau!r}")
+    return int(tau)
+
+
+def _quantise_np(x: np.ndarray, base: np.ndarray, tau: int):
+    """(q, rec) of integer arrays: r = x - base, q = sign(r) floor((|r| + tau) / (2 tau + 1)), rec = clamp(base +
+    q (2 tau + 1), 0, 255)."""
+    step = 2 * tau + 1
+    r = x - base
+    q = np.sign(r) * ((np.abs(r) + tau) // step)
+    return q, np.clip(base + q * step, 0, 255)
+
+
+def _residual_images(base, x, layout, x_layout, what: str):
+    base, layout = _u8_batch(base, layout, f"{what} base")
+    if x is not None:
+        x, x_layout = _u8_batch(x, layout if x_layout is None else x_layout, f"{what} x")
+        if x.size(0) != base.size(0) or _hw(x, x_layout) != _hw(base, layout):
+            raise ValueError(f"{what}: x {tuple(x.shape)} ({x_layout}) does not match base {tuple(base.shape)} ({layout})")
+        if x.device != base.device:
+            raise ValueError(f"{what}: base and x are on different devices")
+    return base, layout, x, x_layout
+
+
+def _residual_front_cpu(base, x=None, tau: int = 0, layout: Optional[str] = None, x_layout: Optional[str] = None) -> Dict:
+    """residual_front in NumPy integers: the definition written out (csrc/residual.h).  Samples in the canonical
+    order i = (c H + y) W + x.  Context 8 c + class from a = max - min of channel c of base over the 3 x 3
+    neighbourhood (edge replication); class 0 for a < 2, else floor(log2 a).  Digest = the sum over i of
+    (base_i + 1) ((i + 1) K) mod 2^64.  With x: r = x - base, q = sign(r) floor((|r| + tau) / (2 tau + 1)), rec =
+    clamp(base + q (2 tau + 1), 0, 255), bin q + 63 for |q| <= 63, else the escape bin 127."""
+    tau = _check_tau(tau, "residual_front")
+    base, layout, x, x_layout = _residual_images(base, x, layout, x_layout, "residual_front")
+    b = _nchw(base.cpu(), layout).numpy().astype(np.int64)
+    B, _, H, W = b.shape
+    p = np.pad(b, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge")
+    win = [p[:, :, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)]
+    a = np.maximum.reduce(win) - np.minimum.reduce(win)
+    ctx = (_CLASS_OF[a] + 8 * np.arange(3, dtype=np.uint8).reshape(1, 3, 1, 1)).astype(np.uint8)
+    count = np.stack([np.bincount(ctx[i].reshape(-1), minlength=RES_CTX) for i in range(B)])
+    with np.errstate(over="ignore"):
+        w = np.arange(1, 3 * H * W + 1, dtype=np.uint64) * np.uint64(_DIGEST_K)
+        digest = ((b.reshape(B, -1) + 1).astype(np.uint64) * w).sum(1, dtype=np.uint64)
+    out = {"ctx": torch.from_numpy(ctx), "ctx_count": torch.from_numpy(count.astype(np.int64)),
+           "digest": torch.from_numpy(digest.view(np.int64).copy())}
+    if x is not None:
+        xv = _nchw(x.cpu(), x_layout).numpy().astype(np.int64)
+        q, rec = _quantise_np(xv, b, tau)
+        bins = np.where(np.abs(q) <= RES_MAX_M, q + RES_MAX_M, RES_BINS - 1)
+        key = ctx.astype(np.int64) * RES_BINS + bins
+        hist = np.stack([np.bincount(key[i].reshape(-1), minlength=RES_CTX * RES_BINS) for i in range(B)])
+        out.update(sym=torch.from_numpy(q.astype(np.int16)),
+                   hist=torch.from_numpy(hist.reshape(B, RES_CTX, RES_BINS).astype(np.int64)),
+                   max_err=torch.from_numpy(np.abs(xv - rec).reshape(B, -1).max(1).astype(np.int64)))
+    return out
+
+
+def _residual_apply_cpu(base, sym, tau: int, layout: Optional[str] = None, ref=None, out=None):
+    """residual_apply in NumPy integers: out = clamp(base + sym (2 tau + 1), 0, 255); with ref also the exact squared
+    error and the largest absolute error against it, per image."""
+    tau = _check_tau(tau, "residual_apply")
+    base, layout = _u8_batch(base, layout, "residual_apply base")
+    b = _nchw(base.cpu(), layout).numpy().astype(np.int64)
+    q = np.asarray(sym.cpu() if torch.is_tensor(sym) else sym).astype(np.int64).reshape(b.shape)
+    rec = np.clip(b + q * (2 * tau + 1), 0, 255)
+    img = torch.from_numpy(rec.astype(np.uint8))
+    img = img.permute(0, 2, 3, 1).contiguous() if layout == "hwc" else img
+    if out is not None:
+        out.copy_(img)
+        img = out
+    if ref is None:
+        return img
+    ref, _ = _u8_batch(ref, layout, "residual_apply ref")
+    d = rec - _nchw(ref.cpu(), layout).numpy().astype(np.int64)
+    B = b.shape[0]
+    return img, torch.from_numpy((d * d).reshape(B, -1).sum(1)), torch.from_numpy(np.abs(d).reshape(B, -1).max(1))
+
+
+def residual_front(base, x=None, tau: int = 0, layout: Optional[str] = None, x_layout: Optional[str] = None) -> Dict:
+    """The encoder's and the decoder's first pass over the base image (csrc/residual.hip, one launch; DESIGN.md §5
+    "Residual coding").  base: uint8 [B,H,W,3] / [B,3,H,W] (or one image), any strides; x: the original, the same
+    size, in x_layout (default: base's layout).  Returns {"ctx" uint8 [B,3,H,W] (the context of every sample, in
+    the canonical order), "ctx_count" int64 [B,24], "digest" int64 [B] (the uint64's bits)} and, with x, {"sym"
+    int16 [B,3,H,W] (the quantised residual), "hist" int64 [B,24,128], "max_err" int64 [B] (the largest |x - rec|)}.
+    CPU tensors take the NumPy restatement."""
+    tau = _check_tau(tau, "residual_front")
+    base, layout, x, x_layout = _residual_images(base, x, layout, x_layout, "residual_front")
+    if not base.is_cuda:
+        return _residual_front_cpu(base, x, tau, layout, x_layout)
+    B = base.size(0)
+    H, W = _hw(base, layout)
+    base = _in_place(base, layout)
+    dev = base.device
+    with torch.cuda.device(dev):
+        ctx = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev)
+        count = torch.empty(B, RES_CTX, dtype=torch.int32, device=dev)
+        digest = torch.empty(B, dtype=torch.int64, device=dev)
+        sym = hist = merr = None
+        if x is not None:
+            x = _in_place(x, x_layout)
+            sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
+            hist = torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev)
+            merr = torch.empty(B, dtype=torch.int32, device=dev)
+        if _lib.poison():  # what the kernel does not write shows
+            ctx.fill_(0xEE)
+            for t in (count, digest, hist, merr):
+                if t is not None:
+                    t.fill_(-1)
+            if sym is not None:
+                sym.fill_(-0x1112)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.call("mlic_image_residual_front_u8", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)), ptr(x),
+                  None if x is None else (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, tau, ptr(ctx), ptr(count),
+                  ptr(digest), ptr(sym), ptr(hist), ptr(merr))
+        out = {"ctx": ctx, "ctx_count": count.to(torch.int64), "digest": digest}
+        if x is not None:
+            out.update(sym=sym, hist=hist.to(torch.int64), max_err=merr.to(torch.int64))
+    return out
+
+
+def residual_apply(base, sym, tau: int, layout: Optional[str] = None, ref=None, out: Optional[torch.Tensor] = None):
+    """The decoder's last pass (csrc/residual.hip, one launch): out = clamp(base + sym (2 tau + 1), 0, 255) in base's
+    layout.  sym: int16 [B,3,H,W], dense, on base's device.  out: an optional uint8 tensor of base's shape with any
+    strides.  ref (uint8, base's shape, any strides): returns (out, sq_err int64 [B], max_abs_err int64 [B]), exact,
+    on egress_u8's terms.  CPU tensors take the NumPy restatement."""
+    tau = _check_tau(tau, "residual_apply")
+    base, layout = _u8_batch(base, layout, "residual_apply base")
+    B = base.size(0)
+    H, W = _hw(base, layout)
+    if not torch.is_tensor(sym) or sym.dtype != torch.int16 or tuple(sym.shape) != (B, 3, H, W):
+        raise ValueError(f"residual_apply: sym must be an int16 tensor {(B, 3, H, W)}")
+    if sym.device != base.device:
+        raise ValueError("residual_apply: base and sym are on different devices")
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != tuple(base.shape) or out.device != base.device):
+        raise ValueError(f"residual_apply: out must be uint8 {tuple(base.shape)} on {base.device}")
+    if ref is not None:
+        ref, _ = _u8_batch(ref, layout, "residual_apply ref")
+        if tuple(ref.shape) != tuple(base.shape):
+            raise ValueError(f"residual_apply: ref must have shape {tuple(base.shape)}, got {tuple(ref.shape)}")
+        ref = ref.to(base.device)
+    if not base.is_cuda:
+        return _residual_apply_cpu(base, sym, tau, layout, ref, out)
+    base = _in_place(base, layout)
+    sym = sym.contiguous()
+    dev = base.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(tuple(base.shape), dtype=torch.uint8, device=dev)
+        elif 0 in _strides(out, layout)[2:]:
+            raise ValueError("residual_apply: out has a zero column or channel stride")
+        sq = merr = None
+        if ref is not None:
+            ref = _in_place(ref, layout)
+            sq = torch.full((B,), -1, dtype=torch.int64, device=dev)
+            merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.call("mlic_image_residual_apply_u8", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
+                  ptr(sym), B, H, W, tau, ptr(out), (C.c_int64 * 4)(*_strides(out, layout)), ptr(ref),
+                  None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)), ptr(sq), ptr(merr))
+    return out if ref is None else (out, sq, merr.to(torch.int64))
+
+
+def residual_tables(hist) -> Dict:
+    """One image's tables from its histograms [24,128] (mlic_residual_tables): per context with a nonzero count,
+    m = the largest |q| <= 63 seen, and the symbols -m..m plus the escape through pmf_to_quantized_cdf at precision
+    16 on float32 count / total.  -> {"m" uint8 [24] (0xFF = no table), "freq" uint16 [24,128] (the file's 2 m + 2
+    frequencies per table), "cdf" int32 [24,129], "length" int32 [24], "offset" int32 [24]} (the rANS tables)."""
+    h = np.asarray(hist.cpu() if torch.is_tensor(hist) else hist)
+    if h.shape != (RES_CTX, RES_BINS) or h.min() < 0 or h.max() > 0xFFFFFFFF:
+        raise ValueError(f"residual_tables: a [{RES_CTX}, {RES_BINS}] histogram of counts expected")
+    h = np.ascontiguousarray(h, dtype=np.uint32)
+    m = np.zeros(RES_CTX, np.uint8)
+    freq = np.zeros((RES_CTX, RES_BINS), np.uint16)
+    cdf = np.zeros((RES_CTX, RES_CDF_STRIDE), np.int32)
+    length, offset = np.zeros(RES_CTX, np.int32), np.zeros(RES_CTX, np.int32)
+    _lib.call("mlic_residual_tables", h.ctypes.data, m.ctypes.data, freq.ctypes.data, cdf.ctypes.data, length.ctypes.data,
+              offset.ctypes.data)
+    return {"m": m, "freq": freq, "cdf": cdf, "length": length, "offset": offset}
+
+
+def _tables_of_freq(m, freqs) -> Dict:
+    """The rANS tables of a file's frequencies: integer sums, nothing rebuilt from floats."""
+    cdf = np.zeros((RES_CTX, RES_CDF_STRIDE), np.int32)
+    length, offset = np.zeros(RES_CTX, np.int32), np.zeros(RES_CTX, np.int32)
+    for k in range(RES_CTX):
+        if m[k] == RES_ABSENT:
+            continue
+        n = 2 * int(m[k]) + 2
+        cdf[k, 1:n + 1] = np.cumsum(np.asarray(freqs[k][:n], np.int64))
+        length[k], offset[k] = n + 1, -int(m[k])
+    return {"m": np.asarray(m, np.uint8), "cdf": cdf, "length": length, "offset": offset}
+
+
+def _coder_tables(t: Dict):
+    """(cdf, length, offset) as the rANS coder takes them: it wants every table well-formed, so a context without a
+    table gets a two-symbol placeholder that no symbol is coded with (the callers check that no sample has it)."""
+    cdf, length, offset = t["cdf"].copy(), t["length"].copy(), t["offset"].copy()
+    for k in np.flatnonzero(length == 0):
+        cdf[k, :3], length[k], offset[k] = (0, 32768, 65536), 3, 0
+    return cdf, length, offset
+
+
+def is_residual_file(data: bytes) -> bool:
+    return bytes(data[:4]) == RESIDUAL_MAGIC
+
+
+def write_container_residual(H: int, W: int, inner: bytes, res: bytes, tau: int, digest: int, m, freq,
+                             vbr: bool = False) -> bytes:
+    """The residual file (mlic_container_write_residual): "MLR1", version, flags (bit 0: vbr), tau, n_ctx, H, W, the
+    digest of the base image, the 24 tables (m and 2 m + 2 frequencies each, or 0xFF), then `inner`, the image's
+    plain or VBR file, unchanged, and `res`, the residual string, each behind its length."""
+    inner, res = bytes(inner), bytes(res)
+    m = np.ascontiguousarray(m, dtype=np.uint8)
+    freq = np.ascontiguousarray(freq, dtype=np.uint16)
+    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
+        raise ValueError(f"write_container_residual: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
+    n = C.c_size_t()
+    args = (H, W, int(bool(vbr)), int(tau), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data, freq.ctypes.data, inner,
+            len(inner), res, len(res))
+    _lib.call("mlic_container_write_residual", *args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_residual", *args, buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_residual(data: bytes, n_levels: Optional[int] = None,
+                             max_pixels: int = MAX_PIXELS) -> _lib.ContainerResidualInfo:
+    """The validating parser of a residual file (mlic_container_parse_residual): raises _lib.MlicError on any
+    malformed input.  The flags say whether the inner file has a level word; n_levels bounds it (None: any level).
+    info.inner is the inner file's ContainerInfo, its offsets relative to data[info.inner_off:]."""
+    data = bytes(data)
+    info = _lib.ContainerResidualInfo()
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call("mlic_container_parse_residual", data, len(data), nl, int(max_pixels), C.byref(info))
+    return info
+
+
+def _file_tables(data: bytes, s: _lib.ContainerResidualInfo) -> Dict:
+    freqs = []
+    for k in range(RES_CTX):
+        n = 0 if s.m[k] == RES_ABSENT else 2 * s.m[k] + 2
+        freqs.append(np.frombuffer(data, ">u2", n, s.freq_off[k]))
+    return _tables_of_freq(list(s.m), freqs)
+
+
+def strip_residual(data: bytes, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> bytes:
+    """The inner file of a residual file: byte for byte what encode_images writes without max_error=."""
+    data = bytes(data)
+    s = parse_container_residual(data, n_levels, max_pixels)
+    return data[s.inner_off:s.inner_off + s.inner_len]
+
+
+def _peek_residual(data: bytes, n_levels, max_pixels) -> Dict:
+    s = parse_container_residual(data, n_levels, max_pixels)
+    c = s.inner
+    return {"residual": True, "H": s.H, "W": s.W, "max_error": s.tau, "vbr": bool(s.vbr),
+            "level": c.level if s.vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz, "Wp": 64 * c.wz,
+            "y_len": c.y_len, "z_len": c.z_len, "digest": int(s.digest), "base_bytes": int(s.inner_len),
+            "residual_bytes": int(s.res_len), "header_bytes": len(data) - int(s.inner_len) - int(s.res_len),
+            "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
+
+
+def _refuse_residual(what: str, **given):
+    """max_error= composes with nothing but level=: each other feature is refused by name."""
+    for name, on in given.items():
+        if on:
+            raise ValueError(f"{what}: max_error= (residual coding) together with {name} is not supported")
+
+
+def _base_x_hat(net, strings, shape, kw, B):
+    """x_hat of the strings just made, as a decoder of each file alone will have it.  The fp16 range guard re-runs
+    g_s in fp32 for a whole lane when any image of it overflows, so after a batch decode that took that path each
+    image is decoded alone."""
+    counters = getattr(net, "range_fallbacks", None)
+    before = counters()["decompress_gs"] if counters else 0
+    x_hat = net.decompress(strings, shape, **kw)["x_hat"]
+    if B > 1 and counters and counters()["decompress_gs"] != before:
+        one = [net.decompress([[strings[0][b]], [strings[1][b]]], shape, **{k: [v[b]] for k, v in kw.items()})["x_hat"]
+               for b in range(B)]
+        x_hat = torch.cat(one, 0)
+    return x_hat
+
+
+def _encode_residual(net, img, layout, files, strings, shape, lv, tau):
+    """encode_images' second layer: the residual files of `files` (the images' plain or VBR files) and the info."""
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    kw = {} if lv is None else {"s": list(lv)}
+    base = egress_u8(_base_x_hat(net, strings, shape, kw, B), H, W, "hwc")
+    front = residual_front(base, img, tau, "hwc", layout)
+    worst = int(front["max_err"].max())  # computed on the device, beside the symbols
+    if worst > tau:
+        raise RuntimeError(f"encode_images: the residual layer leaves an error of {worst} > max_error {tau}")
+    sym = front["sym"].cpu().numpy().reshape(B, -1)
+    ctx = front["ctx"].cpu().numpy().reshape(B, -1)
+    hist = front["hist"].cpu().numpy()
+    digest = front["digest"].cpu().tolist()
+    out, extra = [], []
+    for b in range(B):
+        t = residual_tables(hist[b])
+        res = entropy.rans_encode(sym[b].astype(np.int32), ctx[b].astype(np.int32), *_coder_tables(t))
+        out.append(write_container_residual(H, W, files[b], res, tau, digest[b], t["m"], t["freq"], vbr=lv is not None))
+        extra.append({"max_error": tau, "base_bytes": len(files[b]), "residual_bytes": len(res)})
+    return out, extra
+
+
+def _digest_error(b: int, want: int, got: int, net) -> RuntimeError:
+    return RuntimeError(
+        f"decode_images: file {b}: the digest of the decoded base image is {got & 0xFFFFFFFFFFFFFFFF:#018x}, the file "
+        f"says {want:#018x}: this decoder's base image is not the encoder's, so the residual cannot be applied and no "
+        f"error bound holds.  The base image depends on the synthesis arithmetic: decode with the encoder's "
+        f"set_synthesis_precision and precision mode (here set_synthesis_precision "
+        f"{getattr(net, '_synth_precision', '?')}, precision mode {getattr(net, '_precision', '?')}), or decode the "
+        f"base image alone with enhance=False")
+
+
+def _decode_residual(net, files, ref, max_pixels, enhance):
+    """decode_images for residual files: the inner files as decode_images decodes them, then the residual layer."""
+    vbr = hasattr(net, "levels")
+    n_levels = net.levels if vbr else None
+    ss = [parse_container_residual(f, n_levels, max_pixels) for f in files]
+    for s in ss:
+        if bool(s.vbr) != vbr:
+            raise ValueError(f"decode_images: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
+                             f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+    inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
+    extra = [{"max_error": int(s.tau), "residual_bytes": int(s.res_len), "base_bytes": int(s.inner_len),
+              "bytes": len(f), "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
+    if not enhance:
+        img, info = decode_images(net, inner, ref=ref, max_pixels=max_pixels)
+        for d, e in zip(info, extra):
+            d.update(e, enhanced=False)
+        return img, info
+    base, info = decode_images(net, inner, max_pixels=max_pixels)
+    B, H, W = len(files), base.size(1), base.size(2)
+    if ref is not None:
+        ref, _ = _u8_batch(ref, "hwc", "decode_images ref")
+        if tuple(ref.shape) != (B, H, W, 3):
+            raise ValueError(f"decode_images: ref must be uint8 {(B, H, W, 3)}, got {tuple(ref.shape)}")
+        ref = ref.to(base.device)
+    same = all((s.H, s.W) == (H, W) for s in ss)
+    groups = [list(range(B))] if same and len({s.tau for s in ss}) == 1 else [[b] for b in range(B)]
+    img = torch.empty_like(base) if same else torch.zeros_like(base)
+    for g in groups:
+        s0 = ss[g[0]]
+        h, w, tau = s0.H, s0.W, int(s0.tau)
+        view = base[g[0]:g[-1] + 1, :h, :w]
+        front = residual_front(view, None, tau, "hwc")
+        digest = front["digest"].cpu().tolist()
+        for j, b in enumerate(g):
+            if (digest[j] & 0xFFFFFFFFFFFFFFFF) == ss[b].digest:
+                continue
+            # the batch's base image may differ from the file's own (the range guard's fp32 re-run takes a whole
+            # lane): the base is defined as the decode of the file alone
+            alone, _ = decode_images(net, [inner[b]], max_pixels=max_pixels)
+            again = int(residual_front(alone, None, tau, "hwc")["digest"].cpu()[0])
+            if (again & 0xFFFFFFFFFFFFFFFF) != ss[b].digest:
+                raise _digest_error(b, int(ss[b].digest), again, net)
+            base[b:b + 1, :h, :w] = alone
+            front = None
+        if front is None:
+            front = residual_front(view, None, tau, "hwc")
+        ctx = front["ctx"].cpu().numpy().reshape(len(g), -1)
+        count = front["ctx_count"].cpu().numpy()
+        sym = np.empty((len(g), 3 * h * w), np.int16)
+        for j, b in enumerate(g):
+            t = _file_tables(files[b], ss[b])
+            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and t["m"][k] == RES_ABSENT]
+            if missing:
+                raise ValueError(f"decode_images: file {b}: contexts {missing} occur in the base image but the file "
+                                 f"has no table for them")
+            res = files[b][ss[b].res_off:ss[b].res_off + ss[b].res_len]
+            q = entropy.rans_decode(res, ctx[j].astype(np.int32), *_coder_tables(t))
+            if q.size and (q.min() < -255 or q.max() > 255):
+                raise ValueError(f"decode_images: file {b}: the residual string holds a symbol outside [-255, 255]")
+            sym[j] = q
+        sym_d = torch.from_numpy(sym.reshape(len(g), 3, h, w)).to(base.device)
+        out = img[g[0]:g[-1] + 1, :h, :w]
+        r = residual_apply(view, sym_d, tau, "hwc", ref=None if ref is None else ref[g[0]:g[-1] + 1, :h, :w], out=out)
+        if ref is not None:
+            sq, me = r[1].cpu().tolist(), r[2].cpu().tolist()
+            for j, b in enumerate(g):
+                extra[b].update(sq_err=int(sq[j]), psnr=psnr_from_sq_err(int(sq[j]), 3 * h * w), max_abs_err=int(me[j]))
+    for d, e in zip(info, extra):
+        d.update(e)
+    return img, info
+
+
 # ---------------------------------------------------------------------------------------------- ROI
 def _mask_batch(mask, what: str) -> torch.Tensor:
     """-> 3-dim uint8 tensor [B,H,W] (a bool mask is viewed as bytes; one mask gains the batch dimension)."""
@@ -1168,7 +1577,7 @@ def heat_u8(plane, H: int, W: int, cell: int, lo: float = 0.0, hi: Optional[floa
 _RATE_MAP_REFUSED = {"tile": "tiled coding", "overlap": "tiled coding", "scale": "scaled coding",
                      "coded_size": "scaled coding", "filter": "scaled coding", "depth": "samples deeper than 8 bits",
                      "msb": "samples deeper than 8 bits", "yuv": "Y'CbCr frames", "fmt": "Y'CbCr frames",
-                     "max_bpp": "the rate loop", "max_passes": "the rate loop"}
+                     "max_bpp": "the rate loop", "max_passes": "the rate loop", "max_error": "residual coding"}
 
 
 def _refuse_rate_map(what: str, names):
@@ -1313,7 +1722,8 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
 @torch.no_grad()
 def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
                   max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None, depth: Optional[int] = None,
-                  msb: bool = False, coded_size=None, scale=None, filter: str = "lanczos3", layered: bool = False):
+                  msb: bool = False, coded_size=None, scale=None, filter: str = "lanczos3", layered: bool = False,
+                  max_error: Optional[int] = None):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
@@ -1340,7 +1750,21 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     symbols are coded as one rANS string per channel slice and the file is the layered file
     (write_container_layered), which decode_images decodes whole or cut after any layer.  info[b] gains
     "layer_bytes".  depth= composes (the file does not know its depth).  Refused, each by name, together with roi=,
-    max_bpp=, level="auto", scale= and coded_size=."""
+    max_bpp=, level="auto", scale= and coded_size=.
+    max_error=tau (0..127; None = off, 0 = lossless): residual coding (DESIGN.md §5 "Residual coding").  The image
+    is coded as without it; then net.decompress runs on the strings just made (what a decoder will run),
+    egress_u8 gives the base image, residual_front the quantised residual with its contexts and histograms, and the
+    file is the residual file (write_container_residual) around the unchanged plain or VBR file: decode_images
+    returns an image in which no sample is off by more than tau.  The bound is checked on the device before
+    anything is written.  info[b] gains "max_error", "base_bytes" and "residual_bytes"; bytes and bpp are the
+    whole file.  Refused, each by name, together with roi=, max_bpp=, level="auto", depth=, scale=, coded_size= and
+    layered=."""
+    if max_error is not None:
+        max_error = _check_tau(max_error, "encode_images")
+        _refuse_residual("encode_images", **{"roi=": roi is not None or roi_levels is not None,
+                                             "max_bpp=": max_bpp is not None, "level='auto'": isinstance(level, str),
+                                             "depth=": depth is not None, "scale=": scale is not None,
+                                             "coded_size=": coded_size is not None, "layered=": bool(layered)})
     if layered:
         _refuse_layered("encode_images", roi=roi is not None or roi_levels is not None, max_bpp=max_bpp is not None,
                         scale=scale is not None, coded_size=coded_size is not None,
@@ -1412,6 +1836,9 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         files, passes, lv = rate_loop(net, x, H, W, level, max_bpp, max_passes)
     if scaled:
         files = [write_container_scaled(H, W, f, filter, vbr=lv is not None) for f in files]
+    residual = None
+    if max_error is not None:
+        files, residual = _encode_residual(net, img, layout, files, out["strings"], out["shape"], lv, max_error)
     if not return_info:
         return files
     info = []
@@ -1419,6 +1846,8 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         bpp = 8.0 * len(f) / (H * W)
         info.append({"bytes": len(f), "bpp": bpp, "passes": passes[b], "level": None if lv is None else lv[b],
                      "met": max_bpp is None or bpp <= max_bpp})
+        if residual is not None:
+            info[-1].update(residual[b])
         if scaled:
             info[-1].update(coded=(h, w), filter=filter)
         if layered:
@@ -1429,7 +1858,7 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
 @torch.no_grad()
 def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS, depth: Optional[int] = None,
                   msb: bool = False, out_size=None, filter: Optional[str] = None, slices: Optional[int] = None,
-                  fill: str = "mean"):
+                  fill: str = "mean", enhance: bool = True):
     """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
     (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
     image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
@@ -1450,13 +1879,31 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     net.decompress_layers says.  A layered file (encode_images(layered=True)) may be truncated (cut anywhere after
     its z string); for it slices=None means every layer present.  Files are decoded in groups of one (kind, K), and
     info[b] gains "slices" (and "layers_present" for a layered file).  Refused for ROI, tiled and scaled files and
-    together with out_size=."""
-    if depth is not None:
-        depth, msb = _check_depth(depth, "decode_images"), _check_msb(msb, "decode_images")
-    slices = _check_prefix(net, slices, fill, "decode_images")
+    together with out_size=.
+    Residual files (encode_images(max_error=tau)): the inner files are decoded as above; then residual_front gives
+    the contexts and the digest of that base image, the digest is compared with the file's (on a mismatch the file
+    is decoded alone and compared once more, then an error is raised: a picture whose bound cannot be vouched for is
+    never returned), the residual string is rANS-decoded with the file's tables and residual_apply adds it back.
+    info[b] gains "max_error" (the file's tau), "residual_bytes", "base_bytes" and, with ref, "max_abs_err".
+    enhance=False returns the base picture, byte for byte decode_images(strip_residual(f)).  Refused, each by name:
+    slices=, out_size=, filter= and depth= on residual files, and a call mixing residual files with others."""
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
+    if any(is_residual_file(f) for f in files):
+        for name, given in (("slices=", slices is not None), ("out_size=", out_size is not None),
+                            ("filter=", filter is not None), ("depth=", depth is not None)):
+            if given:
+                raise ValueError(f"decode_images: {name} on a residual file (MLR1) is not supported")
+        if fill != "mean":
+            raise ValueError("decode_images: fill= goes with slices= or layered files")
+        if not all(is_residual_file(f) for f in files):
+            raise ValueError("decode_images: residual files (MLR1) and other files in one call are not supported: "
+                             "decode them in separate calls")
+        return _decode_residual(net, files, ref, max_pixels, bool(enhance))
+    if depth is not None:
+        depth, msb = _check_depth(depth, "decode_images"), _check_msb(msb, "decode_images")
+    slices = _check_prefix(net, slices, fill, "decode_images")
     if any(is_tiled_file(f) for f in files):
         if slices is not None:
             raise ValueError("decode_images: slices= on a tiled file is not supported (tiles have no layered form)")
@@ -1947,7 +2394,7 @@ def _refuse_deep_tiles(what: str, depth):
 @torch.no_grad()
 def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, layout: Optional[str] = None,
                  tile_batch: int = 8, return_info: bool = False, max_bpp=None, roi=None, roi_levels=None, depth=None,
-                 coded_size=None, scale=None, layered: bool = False):
+                 coded_size=None, scale=None, layered: bool = False, max_error=None):
     """One uint8 image ([H,W,3] / [3,H,W], tensor or numpy array) -> one tiled file (DESIGN.md §5 "Tiled coding"):
     the image is cut into the tiles of tile_grid(H, W, tile, overlap), each tile is coded by itself and its file
     is byte for byte encode_images of that crop, and the tiled container holds them row-major with an index.
@@ -1961,6 +2408,7 @@ def encode_tiled(net, img_u8, tile: int = 1024, overlap: int = 32, level=None, l
     _refuse_layered("encode_tiled", tiles=layered)
     _refuse_deep_tiles("encode_tiled", depth)
     _refuse_scaled("encode_tiled", "tiles", coded_size, scale)
+    _refuse_residual("encode_tiled", tiles=max_error is not None)
     img, layout = _u8_batch(img_u8, layout, "encode_tiled")
     if img.size(0) != 1:
         raise ValueError(f"encode_tiled takes one image, got a batch of {img.size(0)}")
@@ -2018,6 +2466,9 @@ def decode_tiled(net, data: bytes, region=None, ref=None, tile_batch: int = 8, m
     if slices is not None:
         raise ValueError("decode_tiled: slices= on a tiled file is not supported (tiles have no layered form)")
     data = bytes(data)
+    if is_residual_file(data):
+        raise ValueError("decode_tiled: a residual file (MLR1): residual coding together with tiles is not supported; "
+                         "decode_images decodes it")
     if is_scaled_file(data):
         raise ValueError("decode_tiled: a scaled file (MLS1): scaled coding together with tiles is not supported; "
                          "decode_images reads it")
@@ -2492,7 +2943,7 @@ def psnr_yuv_from_sq_err(sq_err, H: int, W: int, fmt: YuvFormat) -> Dict:
 @torch.no_grad()
 def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[float] = None, max_passes: int = 8,
                return_info: bool = False, roi=None, roi_levels=None, tile=None, coded_size=None, scale=None,
-               layered: bool = False):
+               layered: bool = False, max_error=None):
     """encode_images with the Y'CbCr ingest: a frame batch (ingest_yuv's planes; host arrays cross to the device as
     bytes) -> one file per frame.  The files are plain per-image files: nothing of fmt is written, decode_images
     decodes them to RGB and decode_yuv(fmt) to planes.  level, max_bpp, max_passes and return_info as in
@@ -2505,6 +2956,7 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
     if tile is not None:
         raise ValueError("encode_yuv: tiles together with Y'CbCr frames are not supported")
     _refuse_scaled("encode_yuv", "Y'CbCr frames", coded_size, scale)
+    _refuse_residual("encode_yuv", **{"Y'CbCr frames": max_error is not None})
     if layered:
         raise ValueError("encode_yuv: layered=True together with Y'CbCr frames is not supported (encode_images writes "
                          "layered files)")

@@ -11,6 +11,7 @@
 #include "model.h"
 #include "options.h"
 #include "resample_table.h"
+#include "residual.h"
 
 using namespace mlic;
 
@@ -1501,6 +1502,102 @@ int mlic_container_parse_scaled(const uint8_t* data, size_t n, int n_levels, uin
     info->vbr = s.vbr ? 1 : 0;
     info->inner_off = s.inner_off;
     info->inner_len = s.inner_len;
+    to_abi(s.inner, &info->inner);
+  });
+}
+
+// ---- residual coding (DESIGN.md section 5 "Residual coding")
+int mlic_image_residual_front_u8(void* stream, const uint8_t* base, const int64_t* base_strides, const uint8_t* x,
+                                 const int64_t* x_strides, int B, int H, int W, int tau, uint8_t* ctx,
+                                 uint32_t* ctx_count, uint64_t* digest, int16_t* sym, uint32_t* hist, uint32_t* max_err) {
+  return guard([&] {
+    image_residual_front_u8(base, base_strides, x, x_strides, B, H, W, tau, ctx, ctx_count, digest, sym, hist, max_err,
+                            (hipStream_t)stream);
+  });
+}
+
+int mlic_image_residual_apply_u8(void* stream, const uint8_t* base, const int64_t* base_strides, const int16_t* sym,
+                                 int B, int H, int W, int tau, uint8_t* out, const int64_t* out_strides,
+                                 const uint8_t* ref, const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err) {
+  return guard([&] {
+    image_residual_apply_u8(base, base_strides, sym, B, H, W, tau, out, out_strides, ref, ref_strides, sq_err, max_err,
+                            (hipStream_t)stream);
+  });
+}
+
+int mlic_residual_tables(const uint32_t* hist, uint8_t* m, uint16_t* freq, int32_t* cdf, int32_t* cdf_len,
+                         int32_t* offset) {
+  return guard([&] {
+    MLIC_CHECK(hist != nullptr, "residual_tables: null hist");
+    MLIC_CHECK(m != nullptr, "residual_tables: null m");
+    MLIC_CHECK((cdf != nullptr) == (cdf_len != nullptr) && (cdf != nullptr) == (offset != nullptr),
+               "residual_tables: cdf, cdf_len and offset go together");
+    for (int k = 0; k < RES_CTX; ++k) {
+      const uint32_t* h = hist + (size_t)k * RES_BINS;
+      uint64_t total = 0;
+      int mk = 0;
+      for (int j = 0; j < RES_BINS; ++j) {
+        total += h[j];
+        if (j != RES_ESCAPE_BIN && h[j]) mk = std::max(mk, std::abs(j - RES_MAX_M));
+      }
+      if (cdf) {
+        std::fill(cdf + (size_t)k * RES_CDF_STRIDE, cdf + (size_t)(k + 1) * RES_CDF_STRIDE, 0);
+        cdf_len[k] = 0;
+        offset[k] = 0;
+      }
+      if (freq) std::fill(freq + (size_t)k * RES_BINS, freq + (size_t)(k + 1) * RES_BINS, (uint16_t)0);
+      if (total == 0) {
+        m[k] = RES_ABSENT;
+        continue;
+      }
+      m[k] = (uint8_t)mk;
+      std::vector<float> pmf((size_t)2 * mk + 2);
+      for (int j = -mk; j <= mk; ++j) pmf[(size_t)(j + mk)] = (float)h[j + RES_MAX_M] / (float)total;
+      pmf[(size_t)2 * mk + 1] = (float)h[RES_ESCAPE_BIN] / (float)total;
+      const auto c = pmf_to_quantized_cdf(pmf.data(), (int)pmf.size(), 16);
+      MLIC_CHECK(c.size() == pmf.size() + 1 && c.front() == 0 && c.back() == 65536, "residual_tables: bad CDF");
+      for (size_t j = 0; j + 1 < c.size(); ++j) {
+        MLIC_CHECK(c[j + 1] > c[j], "residual_tables: a zero frequency");
+        if (freq) freq[(size_t)k * RES_BINS + j] = (uint16_t)(c[j + 1] - c[j]);
+      }
+      if (cdf) {
+        for (size_t j = 0; j < c.size(); ++j) cdf[(size_t)k * RES_CDF_STRIDE + j] = (int32_t)c[j];
+        cdf_len[k] = (int32_t)c.size();
+        offset[k] = -mk;
+      }
+    }
+  });
+}
+
+int mlic_container_write_residual(uint32_t H, uint32_t W, int vbr, int tau, uint64_t digest, const uint8_t* m,
+                                  const uint16_t* freq, const uint8_t* inner, size_t inner_len, const uint8_t* res,
+                                  size_t res_len, uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    MLIC_CHECK(tau >= 0, "container_write_residual: negative tau");
+    container_ok(container_write_residual(H, W, vbr != 0, (uint32_t)tau, digest, m, freq, inner, inner_len, res, res_len,
+                                          out, cap, len));
+  });
+}
+
+int mlic_container_parse_residual(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                  mlic_container_residual_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_residual: null info");
+    ResidualInfo s;
+    container_ok(container_parse_residual(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &s));
+    info->H = s.H;
+    info->W = s.W;
+    info->tau = (int32_t)s.tau;
+    info->vbr = s.vbr ? 1 : 0;
+    info->digest = s.digest;
+    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+      info->m[k] = s.m[k];
+      info->freq_off[k] = s.freq_off[k];
+    }
+    info->inner_off = s.inner_off;
+    info->inner_len = s.inner_len;
+    info->res_off = s.res_off;
+    info->res_len = s.res_len;
     to_abi(s.inner, &info->inner);
   });
 }

@@ -473,6 +473,124 @@ const char* container_parse_layered(const uint8_t* data, size_t n, uint32_t n_le
   return nullptr;
 }
 
+// --------------------------------------------------------------------------------------- residual
+const char* container_write_residual(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint64_t digest, const uint8_t* m,
+                                     const uint16_t* freq, const uint8_t* inner, size_t inner_len, const uint8_t* res,
+                                     size_t res_len, uint8_t* out, size_t cap, size_t* len) {
+  if (len == nullptr) return "container_write_residual: null len";
+  if (H == 0 || W == 0) return "container_write_residual: H or W is zero";
+  if (tau > 127) return "container_write_residual: tau above 127";
+  if (m == nullptr) return "container_write_residual: null m";
+  if (inner_len == 0) return "container_write_residual: an empty inner file";
+  if (inner_len > 0xffffffffu || res_len > 0xffffffffu)
+    return "container_write_residual: a string longer than a 32-bit length";
+  size_t total = RESIDUAL_HEADER + 8;
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    if (m[k] != RESIDUAL_ABSENT && m[k] > RESIDUAL_MAX_M) return "container_write_residual: an m outside 0..63";
+    total += 1 + (m[k] == RESIDUAL_ABSENT ? 0 : 2 * (2 * (size_t)m[k] + 2));
+  }
+  if (inner_len > SIZE_MAX - total || res_len > SIZE_MAX - total - inner_len)
+    return "container_write_residual: the file does not fit size_t";
+  total += inner_len + res_len;
+  *len = total;
+  if (out == nullptr) return nullptr;
+  if (cap < total) return "container_write_residual: buffer too small";
+  if (freq == nullptr) return "container_write_residual: null frequencies";
+  if (inner == nullptr || (res_len && res == nullptr)) return "container_write_residual: null string";
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    if (m[k] == RESIDUAL_ABSENT) continue;
+    uint32_t sum = 0;
+    for (uint32_t j = 0; j < 2 * (uint32_t)m[k] + 2; ++j) {
+      if (freq[k * 128 + j] == 0) return "container_write_residual: a zero frequency";
+      sum += freq[k * 128 + j];
+    }
+    if (sum != 65536) return "container_write_residual: frequencies do not sum to 65536";
+  }
+  std::memcpy(out, "MLR1", 4);
+  out[4] = 0;
+  out[5] = vbr ? 1 : 0;
+  out[6] = (uint8_t)tau;
+  out[7] = (uint8_t)RESIDUAL_CTX;
+  put32(out + 8, H);
+  put32(out + 12, W);
+  put32(out + 16, (uint32_t)(digest >> 32));
+  put32(out + 20, (uint32_t)digest);
+  uint8_t* p = out + RESIDUAL_HEADER;
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    *p++ = m[k];
+    if (m[k] == RESIDUAL_ABSENT) continue;
+    for (uint32_t j = 0; j < 2 * (uint32_t)m[k] + 2; ++j) {
+      *p++ = (uint8_t)(freq[k * 128 + j] >> 8);
+      *p++ = (uint8_t)freq[k * 128 + j];
+    }
+  }
+  put32(p, (uint32_t)inner_len);
+  std::memcpy(p + 4, inner, inner_len);
+  p += 4 + inner_len;
+  put32(p, (uint32_t)res_len);
+  if (res_len) std::memcpy(p + 4, res, res_len);
+  return nullptr;
+}
+
+const char* container_parse_residual(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                     ResidualInfo* info) {
+  if (info == nullptr) return "container_parse_residual: null info";
+  if (data == nullptr && n != 0) return "container_parse_residual: null data";
+  if (n < RESIDUAL_HEADER) return "container_parse_residual: truncated header";
+  if (std::memcmp(data, "MLR1", 4) != 0) return "container_parse_residual: bad magic (not a residual file)";
+  if (data[4] != 0) return "container_parse_residual: unknown version";
+  if (data[5] & ~1u) return "container_parse_residual: unknown flags";
+  if (data[6] > 127) return "container_parse_residual: tau above 127";
+  if (data[7] != RESIDUAL_CTX) return "container_parse_residual: n_ctx is not 24";
+  Reader r{data, n, 8};
+  ResidualInfo s{};
+  s.vbr = (data[5] & 1u) != 0;
+  s.tau = data[6];
+  uint32_t hi = 0, lo = 0;
+  r.u32(&s.H);  // n >= RESIDUAL_HEADER: the header's reads succeed
+  r.u32(&s.W);
+  r.u32(&hi);
+  r.u32(&lo);
+  s.digest = ((uint64_t)hi << 32) | lo;
+  if (s.H == 0 || s.W == 0) return "container_parse_residual: H or W is zero";
+  if ((uint64_t)s.H > max_pixels / (uint64_t)s.W) return "container_parse_residual: image exceeds max_pixels";
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    if (r.n - r.pos < 1) return "container_parse_residual: truncated before a table's m";
+    const uint8_t m = data[r.pos++];
+    s.m[k] = m;
+    s.freq_off[k] = r.pos;
+    if (m == RESIDUAL_ABSENT) continue;
+    if (m > RESIDUAL_MAX_M) return "container_parse_residual: an m outside 0..63";
+    const size_t cnt = 2 * (size_t)m + 2;
+    if (r.n - r.pos < 2 * cnt) return "container_parse_residual: truncated inside a table";
+    uint32_t sum = 0;
+    for (size_t j = 0; j < cnt; ++j) {
+      const uint32_t f = ((uint32_t)data[r.pos + 2 * j] << 8) | data[r.pos + 2 * j + 1];
+      if (f == 0) return "container_parse_residual: a zero frequency";
+      sum += f;
+    }
+    if (sum != 65536) return "container_parse_residual: a table's frequencies do not sum to 65536";
+    r.pos += 2 * cnt;
+  }
+  uint32_t ln = 0;
+  if (!r.u32(&ln)) return "container_parse_residual: truncated before the inner length";
+  if (ln > r.n - r.pos) return "container_parse_residual: the inner length runs past the end";
+  if (ln == 0) return "container_parse_residual: an empty inner file";
+  s.inner_off = r.pos;
+  s.inner_len = ln;
+  r.pos += ln;
+  if (!r.u32(&ln)) return "container_parse_residual: truncated before the residual length";
+  if (ln > r.n - r.pos) return "container_parse_residual: the residual length runs past the end";
+  s.res_off = r.pos;
+  s.res_len = ln;
+  r.pos += ln;
+  if (r.pos != r.n) return "container_parse_residual: bytes left over after the residual string";
+  if (const char* err = container_parse(data + s.inner_off, s.inner_len, s.vbr, n_levels, max_pixels, &s.inner)) return err;
+  if (s.inner.H != s.H || s.inner.W != s.W) return "container_parse_residual: the inner file's H x W is not the outer one";
+  *info = s;
+  return nullptr;
+}
+
 void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels) {
   for (uint64_t k = 0; k < cells; ++k) {
     const uint8_t byte = map[1 + (size_t)(k >> 1)];

@@ -167,5 +167,46 @@ const char* container_write_layered(uint32_t H, uint32_t W, int32_t level, uint3
 const char* container_parse_layered(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                     bool allow_truncated, LayeredInfo* info);
 
+// ---- Residual coding (DESIGN.md section 5 "Residual coding"; residual.h has the definitions).  The residual file,
+// all integers big-endian:
+//     4 bytes "MLR1" | >B version 0 | >B flags (bit 0: the inner file has a VBR level word) | >B tau | >B n_ctx = 24
+//     >II H, W | >Q digest of the base image
+//     24 x ( >B m (0..63, or 0xFF = no table) | unless absent: (2 m + 2) x >H frequencies, each >= 1, sum 65536 )
+//     >I inner_len, the inner file | >I res_len, the residual string
+// The inner file is the plain or VBR file above, unchanged.  Table k codes the symbols -m..m and, last, the escape.
+// As H, "MLR1" exceeds every max_pixels, so container_parse refuses a residual file as it refuses a scaled one.
+constexpr size_t RESIDUAL_HEADER = 24;  // up to the tables
+constexpr uint32_t RESIDUAL_CTX = 24;
+constexpr uint32_t RESIDUAL_MAX_M = 63;
+constexpr uint8_t RESIDUAL_ABSENT = 0xFF;
+struct ResidualInfo {
+  uint32_t H, W;
+  uint32_t tau;
+  bool vbr;
+  uint64_t digest;
+  uint8_t m[RESIDUAL_CTX];           // 0..63, or RESIDUAL_ABSENT
+  size_t freq_off[RESIDUAL_CTX];     // table k's 2 m + 2 big-endian u16 frequencies start at data[freq_off[k]]
+  size_t inner_off, inner_len;       // the inner file: data[inner_off, inner_off + inner_len)
+  size_t res_off, res_len;           // the residual string
+  ContainerInfo inner;               // the inner file's parse, offsets relative to the inner file
+};
+inline bool is_residual_file(const uint8_t* data, size_t n) {
+  return n >= 4 && data[0] == 'M' && data[1] == 'L' && data[2] == 'R' && data[3] == '1';
+}
+// m: 24 bytes; freq: 24 rows of 128 frequencies, the first 2 m[k] + 2 of row k are written (65536 cannot occur:
+// every frequency is >= 1 and there are at least two).  Refused: a null len, H or W zero, tau > 127, an m in
+// 64..254, a zero frequency, a row that does not sum to 65536, an empty inner file, a string longer than a 32-bit
+// length.  The *len / out / cap protocol of container_write (m, freq, inner and res may be null for a size query
+// only when out is null; the size query still needs m).
+const char* container_write_residual(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint64_t digest, const uint8_t* m,
+                                     const uint16_t* freq, const uint8_t* inner, size_t inner_len, const uint8_t* res,
+                                     size_t res_len, uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: a truncated header, table or string; bad magic, version, flags or n_ctx;
+// tau > 127; H or W zero; H * W > max_pixels; an m in 64..254; a zero frequency; frequencies that do not sum to
+// 65536; inner_len or res_len running past the end; an empty inner file; bytes left over; whatever container_parse
+// (vbr from the flags, n_levels, max_pixels) refuses in the inner file; an inner H x W that is not the outer one.
+const char* container_parse_residual(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                     ResidualInfo* info);
+
 }  // namespace mlic
 #endif

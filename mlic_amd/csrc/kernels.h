@@ -329,6 +329,18 @@ void image_ingest_u8_scaled(const uint8_t* src, const int64_t* src_strides, int 
 void image_egress_u8_scaled(const float* src, const int64_t* src_strides, int B, int h, int w, int filter, int Ho,
                             int Wo, uint8_t* dst, const int64_t* dst_strides, const uint8_t* ref,
                             const int64_t* ref_strides, uint64_t* sq_err, hipStream_t st);
+// Residual coding's passes (residual.hip; residual.h has the definitions; DESIGN.md section 5 "Residual coding").
+// Byte images through {image, row, column, channel} strides; ctx u8 and sym int16 are dense [B][3][H][W].
+// front: ctx, ctx_count [B][24] and digest [B] always; with x also sym, hist [B][24][128] and max_err [B] (all three
+// null without x).  apply: out = clamp(base + sym (2 tau + 1), 0, 255); with ref, sq_err [B] and max_err [B]
+// against it.  Both zero the sums they accumulate into on the stream, check their arguments before any HIP call
+// and throw.
+void image_residual_front_u8(const uint8_t* base, const int64_t* base_strides, const uint8_t* x,
+                             const int64_t* x_strides, int B, int H, int W, int tau, uint8_t* ctx, uint32_t* ctx_count,
+                             uint64_t* digest, int16_t* sym, uint32_t* hist, uint32_t* max_err, hipStream_t st);
+void image_residual_apply_u8(const uint8_t* base, const int64_t* base_strides, const int16_t* sym, int B, int H, int W,
+                             int tau, uint8_t* out, const int64_t* out_strides, const uint8_t* ref,
+                             const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err, hipStream_t st);
 // 8-bit Y'CbCr frame I/O (image_yuv.hip; DESIGN.md section 5 "YCbCr I/O").  The fields of mlic_yuv_desc.
 struct YuvDesc {
   int32_t sub_x, sub_y, matrix, full_range, site_x, reserved[3];

@@ -51,6 +51,12 @@
         prediction); zero: they are cleared and the slice loop stops after slice K - 1 (the cheap preview).  A
         layered file, whole or truncated, is recognised by its magic; without --slices every layer it holds is
         decoded.  Not with --out-size, --region or frame files
+    ... --max-error T / --lossless (encode): residual coding.  The image is coded as without it and a second layer
+        brings every sample of the decode within T of the original (--lossless = 0: the decode is the original);
+        the file is the residual file around the unchanged base file.  Goes with --level N; not with --max-bpp,
+        --level auto, --roi, --tile, --scale, --coded-size, --layered or Y'CbCr frames.
+    ... --base-only (decode): the base picture of a residual file alone, without the second layer.
+    python tools/mlic_codec.py strip IN.bit -o OUT.bit             the base file inside a residual file
     python tools/mlic_codec.py truncate IN.bit -k K -o OUT.bit     the first bytes of a layered file up to the end
         of layer K - 1 (K = 0: the header and z alone); needs no model
 
@@ -399,7 +405,7 @@ def _full_scale(v: str) -> float:
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["encode", "decode", "info", "ratemap", "truncate"])
+    ap.add_argument("mode", choices=["encode", "decode", "info", "ratemap", "truncate", "strip"])
     ap.add_argument("src")
     ap.add_argument("dst", nargs="?")
     ap.add_argument("--model", default="MLICPP_L")
@@ -438,7 +444,39 @@ def parse_args(argv=None):
     ap.add_argument("--slices", type=int, default=None, metavar="K")
     ap.add_argument("--fill", choices=["mean", "zero"], default=None)
     ap.add_argument("-k", "--keep", type=int, default=None, metavar="K")
+    ap.add_argument("--max-error", type=int, default=None, metavar="T")
+    ap.add_argument("--lossless", action="store_true")
+    ap.add_argument("--base-only", action="store_true")
     args = ap.parse_args(argv)
+    if args.mode == "strip":
+        if args.dst is not None or args.output is None:
+            ap.error("strip takes one residual file and -o OUT")
+        given = {k: v for k, v in vars(args).items() if k not in ("mode", "src", "dst", "output", "model")}
+        if given != {k: ap.get_default(k) for k in given}:
+            ap.error("strip goes with -o alone (it needs no model)")
+        args.frame_file = False
+        return args
+    if args.lossless:
+        if args.max_error not in (None, 0):
+            ap.error("--lossless is --max-error 0")
+        args.max_error = 0
+    if args.max_error is not None:
+        if args.mode != "encode":
+            ap.error("--max-error / --lossless go with encode (a residual file is recognised by its magic)")
+        if not 0 <= args.max_error <= 127:
+            ap.error("--max-error: 0 to 127 expected")
+        if args.max_bpp is not None or args.level == "auto" or args.roi is not None or args.roi_levels is not None or \
+                args.tile is not None or args.scale is not None or args.coded_size is not None or args.layered or \
+                _is_yuv(args.src):
+            ap.error("--max-error goes with --level N alone, not with --max-bpp, --level auto, --roi, --tile, --scale, "
+                     "--coded-size, --layered or Y'CbCr frames")
+    if args.base_only:
+        if args.mode != "decode":
+            ap.error("--base-only goes with decode")
+        if args.slices is not None or args.fill is not None or args.out_size is not None or args.filter is not None or \
+                args.region is not None or args.depth is not None or _is_yuv(args.dst or ""):
+            ap.error("--base-only goes alone: a residual file takes no --slices, --fill, --out-size, --filter, --region "
+                     "or --depth")
     if args.mode == "truncate":
         if args.dst is not None or args.output is None or args.keep is None or args.keep < 0:
             ap.error("truncate takes one layered file, -k K (the layers to keep, not negative) and -o OUT")
@@ -646,6 +684,16 @@ def main(argv=None):
             f.write(cut)
         print(f"{args.src}: {len(data)} bytes -> {args.output}: {len(cut)} bytes, {args.keep} layers")
         return
+    if args.mode == "strip":
+        with open(args.src, "rb") as f:
+            data = f.read()
+        if not codec.is_residual_file(data):
+            raise SystemExit(f"{args.src}: not a residual file (no MLR1 magic): encode --max-error T writes one")
+        inner = codec.strip_residual(data)
+        with open(args.output, "wb") as f:
+            f.write(inner)
+        print(f"{args.src}: {len(data)} bytes -> {args.output}: {len(inner)} bytes (the base file)")
+        return
     if args.mode == "info":
         from mlic_amd import spec
         with open(args.src, "rb") as f:
@@ -675,6 +723,15 @@ def main(argv=None):
             for t in d["tiles"]:
                 print(f"  tile {t['index']}: at ({t['y0']}, {t['x0']}), {t['H']} x {t['W']}, {t['bytes']} bytes, "
                       f"{t['bpp']:.4f} bpp")
+            return
+        if d.get("residual"):
+            if d["vbr"] != vbr:
+                raise SystemExit(f"{args.src}: the inner file {'carries a' if d['vbr'] else 'has no'} level word, "
+                                 f"{args.model} is {'variable' if vbr else 'fixed'}-rate")
+            print(f"{args.src}: {d['H']} x {d['W']}, residual: max error {d['max_error']}"
+                  f"{' (lossless)' if d['max_error'] == 0 else ''}, level {d['level']}, z grid {d['shape'][0]} x "
+                  f"{d['shape'][1]}, base {d['base_bytes']} B, residual {d['residual_bytes']} B, header and tables "
+                  f"{d['header_bytes']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
             return
         if d.get("scaled"):
             print(f"{args.src}: {d['H']} x {d['W']}, scaled: coded at {d['coded'][0]} x {d['coded'][1]}, filter "
@@ -754,7 +811,8 @@ def main(argv=None):
             files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
                                               max_passes=args.max_passes, return_info=True, roi=roi,
                                               roi_levels=None if roi is None else tuple(args.roi_levels), **deep, **scaled,
-                                              **({"layered": True} if args.layered else {}))
+                                              **({"layered": True} if args.layered else {}),
+                                              **({} if args.max_error is None else {"max_error": args.max_error}))
         except ValueError as e:
             if not scaled:
                 raise
@@ -770,6 +828,9 @@ def main(argv=None):
             line += f", coded at {info[0]['coded'][0]} x {info[0]['coded'][1]} ({info[0]['filter']})"
         if args.layered:
             line += ", layered: " + " ".join(str(n) for n in info[0]["layer_bytes"]) + " B per slice"
+        if args.max_error is not None:
+            line += (f", max error {args.max_error}: base {info[0]['base_bytes']} B, residual "
+                     f"{info[0]['residual_bytes']} B")
         if args.max_bpp is not None:
             line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
                      f"{'met' if info[0]['met'] else 'not met'}")
@@ -802,11 +863,15 @@ def main(argv=None):
             kw["slices"] = args.slices
         if args.fill is not None:
             kw["fill"] = args.fill
+        if args.base_only:
+            if not codec.is_residual_file(data):
+                raise SystemExit(f"{args.src}: --base-only needs a residual file (encode --max-error T)")
+            kw["enhance"] = False
         try:
             img, info = codec.decode_images(net, [data], **kw)
         except ValueError as e:
             if not (args.out_size or args.filter or codec.is_scaled_file(data) or args.slices is not None or
-                    args.fill is not None or codec.is_layered_file(data)):
+                    args.fill is not None or codec.is_layered_file(data) or codec.is_residual_file(data)):
                 raise
             raise SystemExit(f"{args.src}: {e}") from None
         save_image(args.dst, img[0].cpu().numpy(), depth)
@@ -814,6 +879,9 @@ def main(argv=None):
         if "coded" in info[0]:
             line += (f", display {info[0]['display'][0]} x {info[0]['display'][1]}, coded at {info[0]['coded'][0]} x "
                      f"{info[0]['coded'][1]} ({info[0]['filter']})")
+        if "max_error" in info[0]:
+            line += (f", max error {info[0]['max_error']}, residual {info[0]['residual_bytes']} B"
+                     f"{' (base only)' if args.base_only else ''}")
         if "slices" in info[0]:
             line += f", {info[0]['slices']} slices decoded ({args.fill or 'mean'} fill)"
         print(line)

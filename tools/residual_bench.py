@@ -1,0 +1,199 @@
+"""Time the residual layer's two kernels (csrc/residual.hip) on one batch (default 32 x 1080 x 1920, dense HWC) with
+device events, and in the same process, alternating call by call, the existing kernels that move bytes of the same
+kind: mlic_image_egress_u8 (with and without a reference) and mlic_image_sq_err_blocks_u8.  Every kernel is called
+once per round, round after round, so drift of the device's clocks falls on all of them alike; the table holds the
+median, minimum and maximum over the rounds.  Two contents: "noise" (base and x independent random bytes: every
+histogram bin is hit, runs are short) and "smooth" (a synthetic picture and a copy of it with a few grey levels of
+noise: most samples share a context and a bin, the case that contends in the LDS histogram).
+
+--rate MODEL: on synthetic images and weights, per tau in 0, 1, 2, 4, the residual string's bits per sample, the
+zeroth-order entropy of the symbols without contexts, and their cross-entropy under the file's 24 tables (escaped
+symbols counted at the escape's cost plus their bypass nibbles).  Prints one JSON line; --md PATH also writes the
+tables as markdown.
+
+Algorithmic bytes, counted from the shapes (what has to move, once), N = B*H*W*3 samples:
+    front with x: 2 N read, N (ctx) + 2 N (sym) written              front without x: N read, N written
+    apply: N + 2 N read, N written; with ref: N more read
+    egress_u8: 4 N read, N written; with ref: N more read            sq_err_blocks: 2 N read
+"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from mlic_amd import _lib, codec  # noqa: E402
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _rate(model: str, H: int, W: int, rate: int, level):
+    from mlic_amd import get_model, synthetic
+    dev = torch.device("cuda:0")
+    net = get_model(model)
+    net.load_state_dict(synthetic.synth_state_dict(model, rate=rate))
+    net = net.to(dev).eval()
+    net.update()
+    x = torch.cat([synthetic.synth_image(H, W, 70 + i) for i in range(2)])
+    imgs = (x * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().to(dev)
+    plain = codec.encode_images(net, imgs, level=level)
+    base, info = codec.decode_images(net, plain, ref=imgs)
+    rows = {}
+    for tau in (0, 1, 2, 4):
+        files, einfo = codec.encode_images(net, imgs, level=level, max_error=tau, return_info=True)
+        _, dinfo = codec.decode_images(net, files, ref=imgs)
+        f = codec.residual_front(base, imgs, tau, "hwc")
+        n = 3 * H * W
+        h0 = hc = bits = 0.0
+        for b in range(2):
+            sym = f["sym"][b].cpu().numpy().reshape(-1).astype(np.int64)
+            ctx = f["ctx"][b].cpu().numpy().reshape(-1).astype(np.int64)
+            cnt = np.bincount(sym + 255, minlength=511).astype(np.float64)
+            pr = cnt[cnt > 0] / n
+            h0 += float(-(pr * np.log2(pr)).sum())
+            t = codec.residual_tables(f["hist"][b])
+            cost = 0.0
+            for k in range(codec.RES_CTX):
+                if t["m"][k] == codec.RES_ABSENT:
+                    continue
+                m = int(t["m"][k])
+                s = sym[ctx == k]
+                fr = t["freq"][k].astype(np.float64)
+                inside = np.abs(s) <= m
+                cost += float(-np.log2(fr[s[inside] + m] / 65536.0).sum())
+                esc = np.abs(s[~inside])
+                # the escape symbol, then the bypass coder: a 4-bit count of nibbles and the value's nibbles
+                v = np.where(s[~inside] < 0, 2 * (esc - m) - 1, 2 * (esc - m - 1))
+                nib = np.ceil(np.log2(v + 1.0) / 4.0)  # 0 for v = 0
+                cost += float(esc.size * -math.log2(fr[2 * m + 1] / 65536.0) + (4.0 * (nib + 1)).sum())
+            hc += cost / n
+            bits += 8.0 * einfo[b]["residual_bytes"] / n
+        rows[str(tau)] = {"residual_bits_per_sample": bits / 2, "entropy0_bits_per_sample": h0 / 2,
+                          "cross_entropy_tables_bits_per_sample": hc / 2,
+                          "header_and_tables_bytes": [codec.peek(fl, n_levels=getattr(net, "levels", None))["header_bytes"]
+                                                      for fl in files],
+                          "base_bytes": [e["base_bytes"] for e in einfo], "residual_bytes": [e["residual_bytes"] for e in einfo],
+                          "max_abs_err": [d["max_abs_err"] for d in dinfo]}
+    return {"model": model, "synthetic_rate": rate, "level": level, "H": H, "W": W, "images": 2,
+            "base_psnr": [d["psnr"] for d in info], "base_bpp": [d["bpp"] for d in info], "rows": rows}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--tau", type=int, default=1)
+    ap.add_argument("--rate", default=None, metavar="MODEL", help="also the rate table, with this model's synthetic weights")
+    ap.add_argument("--rate-size", type=int, nargs=2, default=(512, 768), metavar=("H", "W"))
+    ap.add_argument("--synthetic-rate", type=int, default=1)
+    ap.add_argument("--level", type=int, default=None)
+    ap.add_argument("--md", default=None, help="also write the tables as markdown to this path")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("residual_bench needs a HIP device")
+    dev = torch.device("cuda:0")
+    B, H, W, tau = args.batch, args.height, args.width, args.tau
+    Hp, Wp = (H + 63) // 64 * 64, (W + 63) // 64 * 64
+    g = torch.Generator(device="cpu").manual_seed(11)
+    noise_b = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g).to(dev)
+    noise_x = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g).to(dev)
+    yy, xx = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
+    pic = (128 + 100 * torch.sin(yy / 97.0) * torch.cos(xx / 131.0)).round().clamp(0, 255).to(torch.uint8)
+    smooth_b = pic.view(1, H, W, 1).expand(B, H, W, 3).contiguous()
+    smooth_x = (smooth_b.to(torch.int16) + torch.randint(-3, 4, (B, H, W, 3), generator=g).to(dev).to(torch.int16)) \
+        .clamp(0, 255).to(torch.uint8)
+    out = torch.empty_like(noise_b)
+    ctx = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev)
+    sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
+    count = torch.empty(B, 24, dtype=torch.int32, device=dev)
+    hist = torch.empty(B, 24, 128, dtype=torch.int32, device=dev)
+    digest = torch.empty(B, dtype=torch.int64, device=dev)
+    merr = torch.empty(B, dtype=torch.int32, device=dev)
+    sq = torch.empty(B, dtype=torch.int64, device=dev)
+    x_hat = codec.ingest_u8(noise_b, "hwc")
+    blocks = torch.empty(B, (H + 15) // 16, (W + 15) // 16, dtype=torch.int64, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    s4 = (C.c_int64 * 4)(*noise_b.stride())
+    s3 = (C.c_int64 * 3)(*x_hat.stride()[:3])
+    N = B * H * W * 3
+
+    def front(b, x):
+        if x is None:
+            return lambda: _lib.call("mlic_image_residual_front_u8", stream, _p(b), s4, None, None, B, H, W, tau, _p(ctx),
+                                     _p(count), _p(digest), None, None, None)
+        return lambda: _lib.call("mlic_image_residual_front_u8", stream, _p(b), s4, _p(x), s4, B, H, W, tau, _p(ctx),
+                                 _p(count), _p(digest), _p(sym), _p(hist), _p(merr))
+
+    def apply(ref):
+        r = [_p(noise_x), s4, _p(sq), _p(merr)] if ref else [None, None, None, None]
+        return lambda: _lib.call("mlic_image_residual_apply_u8", stream, _p(noise_b), s4, _p(sym), B, H, W, tau, _p(out), s4, *r)
+
+    def egress(ref):
+        r = [_p(noise_x), s4, _p(sq)] if ref else [None, None, None]
+        return lambda: _lib.call("mlic_image_egress_u8", stream, _p(x_hat), s3, B, H, W, _p(out), s4, *r)
+
+    runs = {
+        "residual_front, x, noise": (5 * N, front(noise_b, noise_x)),
+        "residual_front, x, smooth": (5 * N, front(smooth_b, smooth_x)),
+        "residual_front, no x, noise": (2 * N, front(noise_b, None)),
+        "residual_front, no x, smooth": (2 * N, front(smooth_b, None)),
+        "residual_apply": (4 * N, apply(False)),
+        "residual_apply + ref": (5 * N, apply(True)),
+        "egress_u8 (HWC)": (5 * N, egress(False)),
+        "egress_u8 (HWC) + sq_err": (6 * N, egress(True)),
+        "sq_err_blocks_u8, block 16": (2 * N, lambda: _lib.call("mlic_image_sq_err_blocks_u8", stream, _p(noise_b), s4,
+                                                                _p(noise_x), s4, B, H, W, 16, _p(blocks))),
+    }
+    ms = {name: [] for name in runs}
+    for it in range(args.warmup + args.iters):
+        for name, (_, fn) in runs.items():  # one call of each per round
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if it >= args.warmup:
+                ms[name].append(e0.elapsed_time(e1))
+    rec = {"batch": B, "H": H, "W": W, "tau": tau, "iters": args.iters, "warmup": args.warmup, "rows": {}}
+    for name, (nbytes, _) in runs.items():
+        med = statistics.median(ms[name])
+        rec["rows"][name] = {"ms_median": med, "ms_min": min(ms[name]), "ms_max": max(ms[name]),
+                             "algorithmic_bytes": nbytes, "GBps": nbytes / med / 1e6,
+                             "fraction_of_8TBps": nbytes / med / 1e6 / 8000.0}
+    if args.rate:
+        rec["rate"] = _rate(args.rate, args.rate_size[0], args.rate_size[1], args.synthetic_rate, args.level)
+    print(json.dumps(rec))
+    if args.md:
+        lines = [f"| {B} x {H} x {W}, HWC, tau {tau} | ms (median of {args.iters}) | min | max | algorithmic MB | GB/s | "
+                 f"of 8 TB/s |", "|---|---|---|---|---|---|---|"]
+        for name, r in rec["rows"].items():
+            lines.append(f"| {name} | {r['ms_median']:.3f} | {r['ms_min']:.3f} | {r['ms_max']:.3f} | "
+                         f"{r['algorithmic_bytes'] / 1e6:.1f} | {r['GBps']:.0f} | {100 * r['fraction_of_8TBps']:.1f} % |")
+        if args.rate:
+            q = rec["rate"]
+            lines += ["", f"| {q['model']} (synthetic weights, rate {q['synthetic_rate']}), 2 x {q['H']} x {q['W']} | residual "
+                      f"bits / sample | entropy, no contexts | cross-entropy, 24 tables | header + tables B | max abs err |",
+                      "|---|---|---|---|---|---|"]
+            for t, r in q["rows"].items():
+                lines.append(f"| tau {t} | {r['residual_bits_per_sample']:.4f} | {r['entropy0_bits_per_sample']:.4f} | "
+                             f"{r['cross_entropy_tables_bits_per_sample']:.4f} | {r['header_and_tables_bytes']} | "
+                             f"{r['max_abs_err']} |")
+        os.makedirs(os.path.dirname(os.path.abspath(args.md)), exist_ok=True)
+        with open(args.md, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
