@@ -239,7 +239,10 @@ int mlic_set_poison(mlic_model* m, int on);
  * $MLIC_INTRA_HALF or 0 = the copies and the whole grid; 2 = as 1, and mlic_run_module("intra") takes the half
  * tail too: only its non-anchor pixels are then defined); "gdn_skip" = g_a's first 1x1 stride-2 skip conv
  * (3 -> N) computed inside the GDN launch that adds it, where "pw3" serves that launch (-1 default =
- * $MLIC_GDN_SKIP or on; 0 = its own launch; the same bits) */
+ * $MLIC_GDN_SKIP or on; 0 = its own launch; the same bits); "x4_epi" = the conv_x4 kernel's lean epilogue for
+ * blocks whose whole tile is stored (-1 default = $MLIC_X4_EPI or 1 = for the tile classes that measured
+ * faster with it: 3 x 3 convs, 1 x 1 convs on 128- / 256-row tiles; 2 = every tile class; 0 = the generic
+ * epilogue for every block; the same bits) */
 int mlic_set_kernel_option(const char* name, int value);
 /* the effective value of a mlic_set_kernel_option name as the next call would see it, after the
  * option's own rule: what was set, else the environment, else the default ("x4_halo": 0 off, 1 = the

@@ -302,6 +302,52 @@ __device__ __forceinline__ void conv_store_shuf4(const ConvParams& P, int b, int
   *reinterpret_cast<float4*>(P.out + (int64_t)b * P.out_bs + off) = make_float4(a[0], a[1], a[2], a[3]);
 }
 
+// gelu_epi on a pair (conv_epi4): gelu_erf2 gives gelu_erf's bits element for element
+__device__ __forceinline__ mlic_float2 gelu_epi2(mlic_float2 x) {
+#ifndef MLIC_GELU_EPI_ERFF
+  return gelu_erf2(x);
+#else
+  return mlic_float2{gelu_erff(x.x), gelu_erff(x.y)};
+#endif
+}
+
+// conv_store4 / conv_store_shuf4 without their addressing: the per-element operations, in their order, on
+// four raw sums whose bias, GDN operand and residual the caller has already fetched (conv_x4's lean
+// epilogue).  Elements 0, 2 take bias b0 and elements 1, 3 take b1 (one row: b0 == b1; under the pixel
+// shuffle the two interleaved channels).  par = oh + ow of element 0, elements at consecutive pixels (the
+// masks, which never combine with the shuffle).  With a compile-time epi every test folds away.
+__device__ __forceinline__ float4 conv_epi4(float4 v, float b0, float b1, int wexp, int epi, float4 x, int par,
+                                            float4 r) {
+  float a[4] = {v.x, v.y, v.z, v.w};
+  a[0] = ldexpf(a[0], -wexp) + b0; a[1] = ldexpf(a[1], -wexp) + b1;
+  a[2] = ldexpf(a[2], -wexp) + b0; a[3] = ldexpf(a[3], -wexp) + b1;
+  if (epi & EPI_GELU) {
+    const mlic_float2 g0 = gelu_epi2(mlic_float2{a[0], a[1]}), g1 = gelu_epi2(mlic_float2{a[2], a[3]});
+    a[0] = g0.x; a[1] = g0.y; a[2] = g1.x; a[3] = g1.y;
+  }
+  if (epi & (EPI_GDN | EPI_IGDN)) {
+    const float xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = gdn_apply(xs[e], a[e], (epi & EPI_GDN) == 0);
+  }
+  if (epi & EPI_TANH_HALF) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = 0.5f * tanhf(a[e]);
+  }
+  if (epi & (EPI_MASK_ANCHOR | EPI_MASK_NONANCHOR)) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool anc = ((par + e) & 1) == 1;
+      if ((epi & EPI_MASK_ANCHOR) && !anc) a[e] = 0.0f;
+      if ((epi & EPI_MASK_NONANCHOR) && anc) a[e] = 0.0f;
+    }
+  }
+  if (epi & EPI_RES) {
+    a[0] = r.x + a[0]; a[1] = r.y + a[1]; a[2] = r.z + a[2]; a[3] = r.w + a[3];
+  }
+  return make_float4(a[0], a[1], a[2], a[3]);
+}
+
 // CU count of the CURRENT device (grid sizing of the persistent-style kernels), cached per device id:
 // lane threads of several models may launch on different devices concurrently, so the cache is an
 // array of atomics keyed by hipGetDevice(), not one function static (a racing first store writes the

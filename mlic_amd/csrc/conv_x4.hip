@@ -596,6 +596,15 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
   // col = pixel; per 16-row group the wave transposes to rows of WN pixels and stores each Cout row
   // as 128-byte runs.  Every acc index stays compile-time (a runtime-indexed acc goes to scratch).
   constexpr int EP = WN + 4;  // row pitch (floats): the 4 row groups of a write land on distinct banks
+  const int co_w = ct * BM + wm * WR;
+  // the lean epilogue's bias (below): the wave's WR values in one coalesced load, in flight across the barrier
+  constexpr int NBV = (WR + 63) / 64;
+  float bv[NBV];
+#pragma unroll
+  for (int q = 0; q < NBV; ++q) {
+    const int r = q * 64 + lane;
+    bv[q] = (RS && P.bias && r < WR && co_w + r < P.Cout) ? P.bias[co_w + r] : 0.0f;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (abl & 4) {
@@ -606,9 +615,127 @@ __global__ __launch_bounds__(X4T) void conv_x4_kernel(ConvParams P, const _Float
     return;
   }
   float* ep = reinterpret_cast<float*>(sm) + wave * 16 * EP;
-  const int co_w = ct * BM + wm * WR;
   const bool shuf = (P.epi & EPI_SHUFFLE) != 0;
   const bool vec = conv_vec_ok(P) && !(shuf && (P.epi & (EPI_GDN | EPI_IGDN | EPI_MASK_ANCHOR | EPI_MASK_NONANCHOR)));
+  // The lean epilogue, for blocks whose whole tile is stored with 16-byte stores: every pixel of the 8 x 32
+  // tile inside the image (K = 1: inside the folded pixel row), every row of the BM tile below Cout, aligned
+  // operands (vec).  The same operations on each element in the same order as conv_store4 / conv_store_shuf4
+  // (conv_epi4: bit-identical output), without their per-store work: the bias comes from a wave-private LDS
+  // strip filled once per tile, (oy, ox), the shuffled offset and the anchor parity are per-lane constants
+  // (a lane's pixels are the same in every iteration), the per-lane base pointers are hoisted and an
+  // iteration adds a wave-uniform offset, the flags are compile-time for the forms the model's hot layers
+  // use (EC >= 0; EC = -1 reads P.epi once: GDN / IGDN, 0.5 tanh, the masks, with or without residual),
+  // GELU runs on pairs, and the iterations are taken two at a time with the next pair's LDS reads and
+  // residual / GDN-operand loads issued before this pair's stores.  Ragged edge tiles, partial Cout tiles,
+  // unaligned tensors, the shuffle on a folded grid or with a residual, and abl bit 16 ($MLIC_X4_EPI=0) take
+  // the generic path below.  (The LDS-DMA form, an A/B arm, has the generic path only.)
+  if constexpr (RS) {
+    constexpr int EPB = 8 * 16 * EP, BSP = 128;  // bias strips: behind the 8 waves' transpose strips
+    static_assert((EPB + 8 * BSP) * 4 <= LDS && WR <= BSP && (WN == 32 || WN == 64 || WN == 128), "x4 lean epilogue");
+    const bool full = oy0 + TR <= H && ox0 + TC <= W && (K > 1 || (oy0 + TR) * TC <= npix) && (ct + 1) * BM <= P.Cout;
+    const int ef = P.epi & ~(EPI_SQUARE_IN | EPI_RELU_IN);
+    if (full && vec && !(abl & 16) && !(shuf && (K == 1 || (ef & ~(EPI_SHUFFLE | EPI_GELU))))) {
+      float* bs = reinterpret_cast<float*>(sm) + EPB + wave * BSP;
+#pragma unroll
+      for (int q = 0; q < NBV; ++q)
+        if (q * 64 + lane < WR) bs[q * 64 + lane] = bv[q];
+      auto lean = [&](auto shuf_c, auto epi_c) __attribute__((always_inline)) {
+        constexpr bool SH = decltype(shuf_c)::value;
+        constexpr int EC = decltype(epi_c)::value;
+        const int epi = EC >= 0 ? EC : (ef & ~EPI_SHUFFLE);
+        // a 64-lane iteration covers GPK row groups of the strip: a group is one Cout row in runs of 4
+        // pixels, or under the shuffle the row pair (2 g, 2 g + 1) = channel pair (oc, dy) in runs of 2
+        constexpr int PX = SH ? 2 : 4, LPG = WN / PX, GPK = 64 / LPG, RG = SH ? 2 : 1;
+        constexpr int NK = 16 / (RG * GPK);
+        static_assert(NK == WN / 16 && NK % 2 == 0, "x4 lean epilogue: iterations in pairs");
+        // (an opaque copy of the lane id: nothing of the per-lane addressing below is computed, and kept in
+        // registers, ahead of the K loop)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int lg = ln / LPG, n = PX * (ln % LPG);
+        const int nn = wn * WN + n;
+        const int oy = oy0 + nn / TC, ox = ox0 + nn % TC;  // (compile-time shifts)
+        const int p = oy * W + ox;
+        int par = oy + ox;  // anchor parity of the lane's first pixel (K = 1: of the unfolded pixel)
+        if (K == 1 && (epi & (EPI_MASK_ANCHOR | EPI_MASK_NONANCHOR))) {
+          const int oh = p / P.Wo;
+          par = oh + (p - oh * P.Wo);
+        }
+        // per-lane offsets of iteration (i, k) = these + a wave-uniform part (uoff, xoff)
+        const int64_t loff = SH ? (int64_t)((co_w >> 2) + (lg >> 1)) * P.out_cs + (int64_t)(2 * oy + (lg & 1)) * (2 * W) + 2 * ox
+                                : (int64_t)(co_w + lg) * P.out_cs + p;
+        float* const out_l = P.out + (int64_t)b * P.out_bs + loff;
+        const float* const res_l = (epi & EPI_RES) ? P.res + (int64_t)b * P.res_bs + loff : nullptr;
+        const float* const aux_l =
+            (epi & (EPI_GDN | EPI_IGDN)) ? P.aux + (int64_t)b * P.aux_bs + (int64_t)(co_w + lg) * npix + p : nullptr;
+        const float* const ep_l = ep + RG * lg * EP + n;
+        const float* const bs_l = bs + RG * lg;
+        auto uoff = [&](int i, int k) __attribute__((always_inline)) {
+          const int g = k * GPK;  // first row group of the iteration
+          return SH ? (int64_t)(4 * i + (g >> 1)) * P.out_cs + (int64_t)((g & 1) * 2 * W)
+                    : (int64_t)(16 * i + g) * P.out_cs;
+        };
+        auto xoff = [&](int i, int k) __attribute__((always_inline)) { return (int64_t)(16 * i + k * GPK) * npix; };
+        auto rd = [&](int k) __attribute__((always_inline)) {
+          const float* q = ep_l + k * (RG * GPK) * EP;
+          if constexpr (SH) {
+            const float2 c0 = *reinterpret_cast<const float2*>(q), c1 = *reinterpret_cast<const float2*>(q + EP);
+            return make_float4(c0.x, c1.x, c0.y, c1.y);
+          } else {
+            return *reinterpret_cast<const float4*>(q);
+          }
+        };
+        // (no `c ? *p : zero`: a select between two objects in memory becomes a load from a selected address)
+        auto ldr = [&](int i, int k) __attribute__((always_inline)) {
+          float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (epi & EPI_RES) r = *reinterpret_cast<const float4*>(res_l + uoff(i, k));
+          return r;
+        };
+        auto ldx = [&](int i, int k) __attribute__((always_inline)) {
+          float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (epi & (EPI_GDN | EPI_IGDN)) x = *reinterpret_cast<const float4*>(aux_l + xoff(i, k));
+          return x;
+        };
+        auto fin = [&](int i, int k, float4 v, float4 x, float4 r) __attribute__((always_inline)) {
+          const int row = 16 * i + k * (RG * GPK);
+          const float b0 = bs_l[row], b1 = SH ? bs_l[row + 1] : b0;
+          return conv_epi4(v, b0, b1, P.wexp, epi, x, par, r);
+        };
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ep[(4 * G + e) * EP + j * 16 + l16] = acc[i][j][e];
+          float4 vn = rd(0), xn = ldx(i, 0), rn = ldr(i, 0);
+#pragma unroll 1
+          for (int k = 0; k < NK; k += 2) {
+            const float4 va = vn, xa = xn, ra = rn;
+            const float4 vb = rd(k + 1), xb = ldx(i, k + 1), rb = ldr(i, k + 1);
+            const float4 oa = fin(i, k, va, xa, ra);
+            if (k + 2 < NK) {  // the next pair's first iteration: reads and loads ahead of this pair's stores
+              vn = rd(k + 2);
+              xn = ldx(i, k + 2);
+              rn = ldr(i, k + 2);
+            }
+            const float4 ob = fin(i, k + 1, vb, xb, rb);
+            *reinterpret_cast<float4*>(out_l + uoff(i, k)) = oa;
+            *reinterpret_cast<float4*>(out_l + uoff(i, k + 1)) = ob;
+          }
+        }
+      };
+      using std::integral_constant;
+      if (shuf) {
+        if (ef & EPI_GELU) lean(integral_constant<bool, true>{}, integral_constant<int, EPI_GELU>{});
+        else lean(integral_constant<bool, true>{}, integral_constant<int, 0>{});
+      } else if (ef == EPI_NONE) lean(integral_constant<bool, false>{}, integral_constant<int, 0>{});
+      else if (ef == EPI_GELU) lean(integral_constant<bool, false>{}, integral_constant<int, EPI_GELU>{});
+      else if (ef == EPI_RES) lean(integral_constant<bool, false>{}, integral_constant<int, EPI_RES>{});
+      else if (ef == (EPI_GELU | EPI_RES)) lean(integral_constant<bool, false>{}, integral_constant<int, EPI_GELU | EPI_RES>{});
+      else lean(integral_constant<bool, false>{}, integral_constant<int, -1>{});
+      return;
+    }
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -1014,7 +1141,17 @@ static void launch_x4(const ConvParams& P, const _Float16* act, const _Float16* 
   x4_tgrid(P, H, W);
   const int ntx = (W + TC - 1) / TC, nty = (H + TR - 1) / TR;
   dim3 grid((P.Cout + BM - 1) / BM, ntx * nty, P.B * nsplit);
-  const int abl = opt(OPT_X4_ABL);  // diagnostics: 1 = no DMA in the loop, 2 = no MFMA
+  // The lean epilogue (conv_x4_kernel), $MLIC_X4_EPI / mlic_set_kernel_option("x4_epi"): 0 = off; 1 (the
+  // default) = the tile classes whose launches measured faster with it, every run (profiles/r18/x4_epilogue.md:
+  // 3 x 3 at BM 256, -2 to -5 %, and 1 x 1 at BM 128, -1 %; taken to hold for 3 x 3 at every tile height and
+  // for the 1 x 1 BM 256 tile, whose waves own 64 rows like BM 128's) -- not 1 x 1 at BM 224 and BM 64 nor
+  // 5 x 5 at BM 96, which measured equal, nor their untimed neighbours (5 x 5, 1 x 1 at BM 96 / 192); 2 = every
+  // class (tests, A/B)
+  const int es = opt(OPT_X4_EPI);
+  const bool lean = es >= 2 || (es == 1 && (K == 3 || (K == 1 && (BM == 128 || BM == 256))));
+  // diagnostics: 1 = no DMA in the loop, 2 = no MFMA, 4 = no epilogue, 8 = no K loop; bit 16 (not of the
+  // diagnostics switch) = every block takes the generic epilogue
+  const int abl = (opt(OPT_X4_ABL) & 15) | (lean ? 0 : 16);
   if (K == 1 && !act)
     hipLaunchKernelGGL((conv_x4_kernel<K, BM, true, false, K == 1>), grid, dim3(X4T), 0, st, P, act, wx, nchunk, H, W,
                        abl, nsplit);

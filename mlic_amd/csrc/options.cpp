@@ -45,6 +45,8 @@ const Row kRows[] = {
     {"lrp_half", "MLIC_LRP_HALF", 0, flag},
     {"intra_half", "MLIC_INTRA_HALF", 0, raw},  // 2 = on, and the module-level test entry takes the half form too
     {"gdn_skip", "MLIC_GDN_SKIP", 1, flag},
+    // conv_x4's lean epilogue: 0 = off, 1 = the tile classes that measured faster, 2 = every class (launch_x4)
+    {"x4_epi", "MLIC_X4_EPI", 1, raw},
     // frozen, in the enum's order.  MLIC_HOIST: -1 = auto (Model::hoist_on); MLIC_HOST_THREADS and mlic_create's
     // MLIC_LANES, MLIC_PRECISION, MLIC_SYNTH_FP16, MLIC_POISON apply only when set (opt_str)
     {nullptr, "MLIC_X4", 1, flag},           {nullptr, "MLIC_X4_K", 0, str},

@@ -15,7 +15,7 @@ namespace mlic {
 enum Opt : int {
   // settable (mlic_set_kernel_option), in the table's order
   OPT_X4_HALO, OPT_X4_SPLITK, OPT_LINATT_FUSED, OPT_DW_STRIP, OPT_EP_HALF, OPT_CHAIN_NJ, OPT_DWPW2, OPT_PW3,
-  OPT_NARROW_LIMIT, OPT_IMAGE_IO_PATH, OPT_LRP_HALF, OPT_INTRA_HALF, OPT_GDN_SKIP,
+  OPT_NARROW_LIMIT, OPT_IMAGE_IO_PATH, OPT_LRP_HALF, OPT_INTRA_HALF, OPT_GDN_SKIP, OPT_X4_EPI,
   OPT_SETTABLE,
   // frozen
   OPT_X4 = OPT_SETTABLE, OPT_X4_K, OPT_X4_BM_FOR, OPT_X4_BM96, OPT_X4_BM224, OPT_X4_RS, OPT_X4_DIRECT, OPT_X4_ABL,

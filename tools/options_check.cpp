@@ -21,7 +21,7 @@ using namespace mlic;
 
 static const char* kNames[OPT_SETTABLE] = {"x4_halo", "x4_splitk", "linatt_fused", "dw_strip",     "ep_half",
                                            "chain_nj", "dwpw2",    "pw3",          "narrow_limit", "image_io_path",
-                                           "lrp_half", "intra_half",   "gdn_skip"};
+                                           "lrp_half", "intra_half",   "gdn_skip",     "x4_epi"};
 
 #define REQUIRE(cond)                                                      \
   do {                                                                     \
@@ -89,7 +89,7 @@ int main() {
   for (auto& t : writers) t.join();
   REQUIRE(changes.load() > 0);
   for (int o = 0; o < OPT_SETTABLE; ++o) opt_set(kNames[o], o == OPT_NARROW_LIMIT ? 0 : -1);
-  const int dflt[OPT_SETTABLE] = {1, 0, 1, 1, 1, 1, 2, 1, 32767, -1, 0, 0, 1};  // with no MLIC_* variable set
+  const int dflt[OPT_SETTABLE] = {1, 0, 1, 1, 1, 1, 2, 1, 32767, -1, 0, 0, 1, 1};  // with no MLIC_* variable set
   bool env = false;
   for (int o = 0; o < OPT_COUNT; ++o) env = env || opt_str((Opt)o) != nullptr;
   for (int o = 0; o < OPT_SETTABLE && !env; ++o) REQUIRE(opt_get(kNames[o]) == dflt[o]);
