@@ -807,6 +807,80 @@ int mlic_container_write_residual(uint32_t H, uint32_t W, int vbr, int tau, uint
                                   size_t res_len, uint8_t* out, size_t cap, size_t* len);
 int mlic_container_parse_residual(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
                                   mlic_container_residual_info* info);
+/* ---- Segmented residual strings: the residual layer's device entropy coder ("Segments") ----
+ *
+ * The N = 3 H W samples of an image, in the canonical order, are cut into n_seg = ceil(N / seg_len) segments of
+ * seg_len samples (256..65536; the last may be shorter).  A segment's bytes are exactly mlic_rans_encode of its
+ * symbols and contexts under the image's tables, so segments code and decode independently, and a decoder that has
+ * decoded a whole segment has consumed exactly its words and holds the state 2^31 again: both decoders check that.
+ * A segment of n samples is at most 4 (n + 4) bytes (csrc/residual_seg.h derives n + 2 words).
+ * Common arguments: sym int16 [B][N] and ctx u8 [B][N], dense; m u8 [B][24] and freq u16 [B][24][128], host memory,
+ * the file's form of the tables (mlic_residual_tables); seg_bytes u32 [B][n_seg]; image b's bytes start at
+ * out + b cap (data + b data_stride); len / data_len u64 [B], host memory.
+ * Every entry refuses, before it does anything else (the device entries: before any HIP call), each with its own
+ * message: null pointers; B < 1; H or W < 1; more than 2^29 samples; seg_len outside 256..65536; n_seg that is not
+ * ceil(N / seg_len); an m in 64..254, a zero frequency or a wrong sum.  encode also: a cap that is not a multiple of
+ * 4 or is below 8 n_seg.  decode also: a segment length that is not a multiple of 4, is below 8 or is above the
+ * bound; lengths that do not sum to data_len[b]; data_len[b] above data_stride; a data_stride that is not a
+ * multiple of 4.
+ *
+ * Device entries (sym, ctx, out / data and seg_bytes of encode in device memory; scratch: device memory of
+ * mlic_residual_segments_scratch_bytes, 16-byte aligned).  They upload the tables, run on `stream`, wait for it and
+ * return an error that names the image, the first bad segment and the reason when a kernel refused something.
+ * encode: a counting pass, a scan of the lengths and a writing pass, no host round trip between them; an image
+ * whose bytes exceed cap is refused ("the bytes do not fit the capacity") with nothing written past cap.
+ * decode: seg_bytes is host memory (the file's lengths); the offsets are summed on the host and uploaded.  The
+ * kernel never reads outside a segment's bytes and refuses a bypass length above 3, a symbol index above max_value,
+ * a q outside +-255, a final state that is not 2^31 and a word count that is not the segment's.
+ * status (optional, host, u32 [B]): 0xFFFFFFFF for a clean image, else (segment << 4) | reason. */
+int mlic_residual_segments_scratch_bytes(int B, int64_t n_seg, size_t* bytes);
+int mlic_residual_encode_segments(void* stream, const int16_t* sym, const uint8_t* ctx, int B, int H, int W,
+                                  const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                                  size_t cap, uint32_t* seg_bytes, uint64_t* len, void* scratch, size_t scratch_bytes,
+                                  uint32_t* status);
+int mlic_residual_decode_segments(void* stream, const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                  const uint32_t* seg_bytes, const uint8_t* ctx, int B, int H, int W, const uint8_t* m,
+                                  const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym, void* scratch,
+                                  size_t scratch_bytes, uint32_t* status);
+/* The same contract on host memory: a loop over segments on the host rANS coder; oracle, CPU path and fallback.
+ * encode: out == NULL asks for len and seg_bytes only; an image whose bytes exceed cap is an error. */
+int mlic_residual_encode_segments_host(const int16_t* sym, const uint8_t* ctx, int B, int H, int W, const uint8_t* m,
+                                       const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
+                                       uint32_t* seg_bytes, uint64_t* len);
+int mlic_residual_decode_segments_host(const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                       const uint32_t* seg_bytes, const uint8_t* ctx, int B, int H, int W,
+                                       const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg,
+                                       int16_t* sym);
+/* The segmented residual file, big-endian:
+ *     "MLR2" | u8 version 0 | u8 flags (bit 0: VBR level word inside) | u8 tau | u8 n_ctx = 24 | u32 H, W | u64 digest
+ *     the 24 tables, exactly as in "MLR1"
+ *     u32 seg_len | u32 n_seg | u32 inner_len, inner file
+ *     u32 res_len = 4 n_seg + the sum of the lengths | n_seg x u32 segment byte lengths | the segments
+ * write: the *len / out / cap protocol of mlic_container_write; seg_bytes: n_seg host lengths, segs their bytes.
+ * parse: validating, never reads outside data[0, n).  Refused, each with its own message: everything
+ * mlic_container_parse_residual refuses; seg_len outside 256..65536; n_seg that is not ceil(3 H W / seg_len); a
+ * segment length that is not a multiple of 4, is below 8 or is above the capacity bound of its samples; res_len
+ * that is not 4 n_seg + the sum of the lengths; truncation anywhere; trailing bytes.  Every other parser refuses an
+ * "MLR2" file, and this one refuses every other file. */
+typedef struct mlic_container_residual_seg_info {
+  uint32_t H, W;
+  int32_t tau;
+  int32_t vbr;
+  uint64_t digest;
+  uint8_t m[24];
+  uint64_t freq_off[24];
+  uint32_t seg_len, n_seg;
+  uint64_t inner_off, inner_len, res_off, res_len;
+  uint64_t index_off;          /* n_seg big-endian u32 lengths */
+  uint64_t data_off, data_len; /* the concatenated segments */
+  mlic_container_info inner;
+} mlic_container_residual_seg_info;
+int mlic_container_write_residual_seg(uint32_t H, uint32_t W, int vbr, int tau, uint64_t digest, const uint8_t* m,
+                                      const uint16_t* freq, uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
+                                      const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
+                                      uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_residual_seg(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                      mlic_container_residual_seg_info* info);
 /* mlic_encode_image_u8 at reduced (or raised) resolution: the H x W image is resampled to coded_H x coded_W on
  * the way in, coded as mlic_encode_image_u8 codes an image of that size, and wrapped in the scaled file with H, W
  * as the display size.  The out == NULL / rgb_dev == NULL protocol is that of mlic_encode_image_u8. */

@@ -10,6 +10,8 @@ from .codec import (coded_size, egress_u8_scaled, ingest_u8_scaled, is_scaled_fi
                     resample_table, write_container_scaled)
 from .codec import (is_residual_file, parse_container_residual, residual_apply, residual_front,  # noqa: F401
                     residual_tables, strip_residual, write_container_residual)
+from .codec import (is_residual_seg_file, parse_container_residual_seg, residual_decode_segments,  # noqa: F401
+                    residual_encode_segments, write_container_residual_seg)
 from .codec import blend_tiles, decode_tiled, encode_tiled, tile_grid  # noqa: F401
 from .codec import YuvFormat, decode_yuv, egress_yuv, encode_yuv, ingest_yuv, split_yuv  # noqa: F401
 from .codec import egress_u16, ingest_u16  # noqa: F401
@@ -22,4 +24,5 @@ __all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusV
            "resample_table", "ingest_u8_scaled", "egress_u8_scaled", "write_container_scaled", "parse_container_scaled",
            "is_scaled_file", "coded_size", "rate_maps", "rate_map", "sq_err_blocks", "heat_u8",
            "residual_front", "residual_apply", "residual_tables", "write_container_residual", "parse_container_residual",
-           "is_residual_file", "strip_residual"]
+           "is_residual_file", "strip_residual", "is_residual_seg_file", "parse_container_residual_seg",
+           "write_container_residual_seg", "residual_encode_segments", "residual_decode_segments"]

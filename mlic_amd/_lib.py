@@ -52,6 +52,14 @@ class ContainerResidualInfo(C.Structure):
                 ("inner_len", C.c_uint64), ("res_off", C.c_uint64), ("res_len", C.c_uint64), ("inner", ContainerInfo)]
 
 
+class ContainerResidualSegInfo(C.Structure):
+    """mlic_container_residual_seg_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("tau", C.c_int32), ("vbr", C.c_int32), ("digest", C.c_uint64),
+                ("m", C.c_uint8 * 24), ("freq_off", C.c_uint64 * 24), ("seg_len", C.c_uint32), ("n_seg", C.c_uint32),
+                ("inner_off", C.c_uint64), ("inner_len", C.c_uint64), ("res_off", C.c_uint64), ("res_len", C.c_uint64),
+                ("index_off", C.c_uint64), ("data_off", C.c_uint64), ("data_len", C.c_uint64), ("inner", ContainerInfo)]
+
+
 class ContainerLayeredInfo(C.Structure):
     """mlic_container_layered_info (include/mlic_hip.h)."""
     _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("hz", C.c_uint32), ("wz", C.c_uint32), ("level", C.c_int32),
@@ -194,6 +202,14 @@ def _sig(lib):
         "mlic_residual_tables": [p, p, p, p, p, p],
         "mlic_container_write_residual": [C.c_uint32, C.c_uint32, i, i, C.c_uint64, p, p, p, sz, p, sz, p, sz, P(sz)],
         "mlic_container_parse_residual": [p, sz, i, C.c_uint64, P(ContainerResidualInfo)],
+        "mlic_residual_segments_scratch_bytes": [i, i64, P(sz)],
+        "mlic_residual_encode_segments": [p, p, p, i, i, i, p, p, i, i64, p, sz, p, p, p, sz, p],
+        "mlic_residual_decode_segments": [p, p, sz, p, p, p, i, i, i, p, p, i, i64, p, p, sz, p],
+        "mlic_residual_encode_segments_host": [p, p, i, i, i, p, p, i, i64, p, sz, p, p],
+        "mlic_residual_decode_segments_host": [p, sz, p, p, p, i, i, i, p, p, i, i64, p],
+        "mlic_container_write_residual_seg": [C.c_uint32, C.c_uint32, i, i, C.c_uint64, p, p, C.c_uint32, C.c_uint32, p,
+                                              p, sz, p, sz, p, sz, P(sz)],
+        "mlic_container_parse_residual_seg": [p, sz, i, C.c_uint64, P(ContainerResidualSegInfo)],
         "mlic_decode_image_u8_sized": [p, p, p, sz, i, C.c_uint64, p, i, i, i, p, P(i64), sz, P(i), P(i), P(i), P(i),
                                        P(i)],
         "mlic_image_ingest_yuv8": [p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, p, i, i],

@@ -100,7 +100,7 @@ def psnr_u8(a: torch.Tensor, b: torch.Tensor) -> float:
 @torch.no_grad()
 def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_passes: int = 8, lpips=None,
                dists=None, roi=None, roi_levels=None, tile=None, overlap: int = 32, yuv=None, rate_map: bool = False,
-               progressive: bool = False, max_error=None, **kw) -> Dict:
+               progressive: bool = False, max_error=None, residual_segment=None, **kw) -> Dict:
     """One image [1,3,H,W] in [0,1] through pad -> compress -> file bytes -> decompress -> crop.
     ms_ssim=True adds "ms_ssim" (metrics.ms_ssim_u8 of img against the cropped x_hat, utils/testing.py:397-421;
     None when the image is too small for the five levels).
@@ -138,8 +138,11 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     within tau of the decode; codec.encode_images(max_error=tau) of to_u8(img), decoded again) and "max_abs_err"
     (the largest error of that decode, measured: <= tau).  bytes, bpp, psnr and x_hat stay those of the base file.
     Not together with tile=, roi=, max_bpp=, progressive=, yuv=, scale= / coded_size=, depth= or batch_stream; off
-    by default."""
+    by default.  residual_segment=L (with max_error=) passes through to encode_images: the file is the segmented
+    residual file, and the record's "residual_kind" says which was written ("MLR1" or "MLR2")."""
     assert img.dim() == 4 and img.size(0) == 1
+    if residual_segment is not None and max_error is None:
+        raise ValueError("code_image: residual_segment= needs max_error=")
     H, W = img.shape[-2:]
     if max_error is not None:
         given = {"tile": tile, "roi": roi, "roi_levels": roi_levels, "max_bpp": max_bpp, "yuv": yuv,
@@ -277,9 +280,13 @@ def code_image(net, img: torch.Tensor, ms_ssim: bool = False, max_bpp=None, max_
     if max_error is not None:
         from . import codec
         u8 = to_u8(img[0]).permute(1, 2, 0).contiguous()
-        files, einfo = codec.encode_images(net, u8, level=level, layout="hwc", max_error=max_error, return_info=True)
+        files, einfo = codec.encode_images(net, u8, level=level, layout="hwc", max_error=max_error, return_info=True,
+                                           residual_segment=residual_segment)
         _, dinfo = codec.decode_images(net, files, ref=u8.unsqueeze(0))
         r["residual_bytes"], r["max_abs_err"] = einfo[0]["residual_bytes"], dinfo[0]["max_abs_err"]
+        r["residual_kind"] = files[0][:4].decode()
+        if residual_segment is not None:
+            r["residual_segment"], r["segments"] = einfo[0]["residual_segment"], einfo[0]["segments"]
     if yuv is not None:
         from . import codec
         src = codec.egress_yuv(img.float().contiguous(), H, W, yuv)

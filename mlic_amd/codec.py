@@ -40,6 +40,8 @@ coding", csrc/residual.hip): the image is coded as before, its own strings are d
 histograms the tables are built from and a digest of the base image; the residual file wraps the unchanged plain
 file.  `decode_images` checks the digest, decodes the residual string and `residual_apply` adds it back: no sample
 is off by more than tau, and at tau = 0 the decode is the original.  `strip_residual` returns the plain file.
+With `residual_segment=L` the residual string is cut into independently coded segments ("MLR2" file; DESIGN.md §5
+"Segments", csrc/residual_coder.hip) that `residual_encode_segments` / `residual_decode_segments` code on the device.
 
 CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
@@ -48,6 +50,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import re
 import struct
 from typing import Dict, List, Optional, Sequence
 
@@ -435,7 +438,8 @@ def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pix
     sum(layer_bytes) + 4 per layer.  A residual file (is_residual_file; its flags say whether the inner file has a
     level word) gives {"residual": True, H, W, "max_error" (tau), vbr, level, shape, Hp, Wp, y_len, z_len, "digest",
     "base_bytes" (the inner file), "residual_bytes" (the residual string), "header_bytes" (the rest: header, tables
-    and the two length words), bytes, bpp}."""
+    and the two length words), bytes, bpp}; a segmented one ("MLR2") also "residual_segment" and "segments", and its
+    "residual_bytes" are the index and the segments."""
     data = bytes(data)
     if is_residual_file(data):
         return _peek_residual(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
@@ -813,6 +817,9 @@ def _peek_scaled(data: bytes, n_levels, max_pixels) -> Dict:
 
 # ---------------------------------------------------------------------------------- residual coding
 RESIDUAL_MAGIC = b"MLR1"
+RESIDUAL_SEG_MAGIC = b"MLR2"  # the segmented residual file (DESIGN.md §5 "Residual coding", "Segments")
+RES_SEG_MIN, RES_SEG_MAX, RES_SEG_SLACK = 256, 65536, 4
+DEFAULT_RESIDUAL_SEGMENT = 4096
 MAX_TAU = 127
 RES_CTX, RES_BINS, RES_MAX_M, RES_ABSENT, RES_CDF_STRIDE = 24, 128, 63, 0xFF, 129
 _DIGEST_K = 0x9E3779B97F4A7C15
@@ -1010,7 +1017,11 @@ def _tables_of_freq(m, freqs) -> Dict:
         n = 2 * int(m[k]) + 2
         cdf[k, 1:n + 1] = np.cumsum(np.asarray(freqs[k][:n], np.int64))
         length[k], offset[k] = n + 1, -int(m[k])
-    return {"m": np.asarray(m, np.uint8), "cdf": cdf, "length": length, "offset": offset}
+    freq = np.zeros((RES_CTX, RES_BINS), np.uint16)
+    for k in range(RES_CTX):
+        if m[k] != RES_ABSENT:
+            freq[k, :2 * int(m[k]) + 2] = freqs[k][:2 * int(m[k]) + 2]
+    return {"m": np.asarray(m, np.uint8), "freq": freq, "cdf": cdf, "length": length, "offset": offset}
 
 
 def _coder_tables(t: Dict):
@@ -1023,7 +1034,12 @@ def _coder_tables(t: Dict):
 
 
 def is_residual_file(data: bytes) -> bool:
-    return bytes(data[:4]) == RESIDUAL_MAGIC
+    """A residual file of either kind: "MLR1" (one serial string) or "MLR2" (segments)."""
+    return bytes(data[:4]) in (RESIDUAL_MAGIC, RESIDUAL_SEG_MAGIC)
+
+
+def is_residual_seg_file(data: bytes) -> bool:
+    return bytes(data[:4]) == RESIDUAL_SEG_MAGIC
 
 
 def write_container_residual(H: int, W: int, inner: bytes, res: bytes, tau: int, digest: int, m, freq,
@@ -1068,18 +1084,243 @@ def _file_tables(data: bytes, s: _lib.ContainerResidualInfo) -> Dict:
 def strip_residual(data: bytes, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> bytes:
     """The inner file of a residual file: byte for byte what encode_images writes without max_error=."""
     data = bytes(data)
-    s = parse_container_residual(data, n_levels, max_pixels)
+    s = _parse_residual_any(data, n_levels, max_pixels)
     return data[s.inner_off:s.inner_off + s.inner_len]
 
 
+def _parse_residual_any(data: bytes, n_levels, max_pixels):
+    """The parse of a residual file of either kind (told apart by the magic)."""
+    if is_residual_seg_file(data):
+        return parse_container_residual_seg(data, n_levels, max_pixels)
+    return parse_container_residual(data, n_levels, max_pixels)
+
+
 def _peek_residual(data: bytes, n_levels, max_pixels) -> Dict:
-    s = parse_container_residual(data, n_levels, max_pixels)
+    s = _parse_residual_any(data, n_levels, max_pixels)
     c = s.inner
-    return {"residual": True, "H": s.H, "W": s.W, "max_error": s.tau, "vbr": bool(s.vbr),
-            "level": c.level if s.vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz, "Wp": 64 * c.wz,
-            "y_len": c.y_len, "z_len": c.z_len, "digest": int(s.digest), "base_bytes": int(s.inner_len),
-            "residual_bytes": int(s.res_len), "header_bytes": len(data) - int(s.inner_len) - int(s.res_len),
-            "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
+    out = {"residual": True, "H": s.H, "W": s.W, "max_error": s.tau, "vbr": bool(s.vbr),
+           "level": c.level if s.vbr else None, "shape": (c.hz, c.wz), "Hp": 64 * c.hz, "Wp": 64 * c.wz,
+           "y_len": c.y_len, "z_len": c.z_len, "digest": int(s.digest), "base_bytes": int(s.inner_len),
+           "residual_bytes": int(s.res_len), "header_bytes": len(data) - int(s.inner_len) - int(s.res_len),
+           "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
+    if is_residual_seg_file(data):
+        out.update(residual_segment=int(s.seg_len), segments=int(s.n_seg))
+    return out
+
+
+# ---- segmented residual strings (csrc/residual_seg.h, csrc/residual_coder.hip)
+class ResidualSegmentError(ValueError):
+    """A coder refused a segment: .image (index in the call's batch), .segment, .reason."""
+
+    def __init__(self, what: str, image: int, segment: int, reason: str):
+        super().__init__(f"{what}: image {image}, segment {segment}: {reason}")
+        self.image, self.segment, self.reason = image, segment, reason
+
+
+def _check_segment(segment, what: str) -> int:
+    if isinstance(segment, bool) or not isinstance(segment, (int, np.integer)) or not RES_SEG_MIN <= segment <= RES_SEG_MAX:
+        raise ValueError(f"{what}: residual_segment must be an integer in [{RES_SEG_MIN}, {RES_SEG_MAX}], got {segment!r}")
+    return int(segment)
+
+
+def _check_coder(coder, what: str) -> str:
+    if coder not in ("device", "host"):
+        raise ValueError(f"{what}: residual_coder must be 'device' or 'host', got {coder!r}")
+    return coder
+
+
+def _seg_tables(tables, B: int, what: str):
+    """(m uint8 [B,24], freq uint16 [B,24,128]) of B table dicts (residual_tables' or a file's); one dict serves all."""
+    tables = [tables] * B if isinstance(tables, dict) else list(tables)
+    if len(tables) != B:
+        raise ValueError(f"{what}: {B} images but {len(tables)} table sets")
+    m = np.ascontiguousarray(np.stack([np.asarray(t["m"], np.uint8) for t in tables]))
+    freq = np.ascontiguousarray(np.stack([np.asarray(t["freq"], np.uint16) for t in tables]))
+    if m.shape != (B, RES_CTX) or freq.shape != (B, RES_CTX, RES_BINS):
+        raise ValueError(f"{what}: tables with m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
+    return m, freq
+
+
+def _seg_call(name: str, what: str, *args):
+    """_lib.call, with a coder's refusal of a segment turned into ResidualSegmentError."""
+    try:
+        _lib.call(name, *args)
+    except _lib.MlicError as e:
+        hit = re.search(r"image (\d+), segment (\d+): (.*)$", str(e))
+        if hit is None:
+            raise
+        raise ResidualSegmentError(what, int(hit.group(1)), int(hit.group(2)), hit.group(3)) from None
+
+
+def _seg_scratch(B: int, n_seg: int, dev) -> torch.Tensor:
+    n = C.c_size_t()
+    _lib.call("mlic_residual_segments_scratch_bytes", B, n_seg, C.byref(n))
+    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+
+def residual_segment_cap(H: int, W: int, segment: int) -> int:
+    """Bytes that the segments of one H x W image cannot exceed: 4 (n + 4) per segment of n samples."""
+    N = 3 * H * W
+    return 4 * (N + RES_SEG_SLACK * -(-N // segment))
+
+
+def _seg_images(sym, ctx, what: str):
+    ok = lambda t, dt: torch.is_tensor(t) and t.dtype == dt and t.dim() == 4 and t.size(1) == 3  # noqa: E731
+    if sym is not None and not ok(sym, torch.int16):
+        raise ValueError(f"{what}: sym must be an int16 tensor [B,3,H,W]")
+    if not ok(ctx, torch.uint8):
+        raise ValueError(f"{what}: ctx must be a uint8 tensor [B,3,H,W]")
+    if sym is not None and (tuple(sym.shape) != tuple(ctx.shape) or sym.device != ctx.device):
+        raise ValueError(f"{what}: sym {tuple(sym.shape)} and ctx {tuple(ctx.shape)} must match, on one device")
+    return ctx.size(0), ctx.size(2), ctx.size(3)
+
+
+def residual_encode_segments(sym, ctx, tables, segment: int, coder: str = "device", cap: Optional[int] = None,
+                             out: Optional[torch.Tensor] = None):
+    """The segmented residual strings of B images (csrc/residual_coder.hip; mlic_residual_encode_segments): sym int16
+    and ctx uint8 [B,3,H,W] (residual_front's), tables: B dicts with "m" and "freq" (residual_tables'), segment: the
+    samples per segment.  -> [(bytes, seg_bytes uint32 [n_seg])] per image; bytes is the concatenation of the
+    segments, each exactly entropy.rans_encode of its slice.  CUDA tensors with coder="device" run the kernels (a
+    counting pass, a scan, a writing pass; only the bytes and their lengths come back); CPU tensors or coder="host"
+    take the host entry, which gives the same bytes.  cap: the bytes allowed per image (default: the bound
+    residual_segment_cap); out: an optional uint8 device buffer of at least B cap bytes to code into."""
+    what = "residual_encode_segments"
+    B, H, W = _seg_images(sym, ctx, what)
+    L, coder = _check_segment(segment, what), _check_coder(coder, what)
+    N = 3 * H * W
+    n_seg = -(-N // L)
+    m, freq = _seg_tables(tables, B, what)
+    cap = residual_segment_cap(H, W, L) if cap is None else int(cap)
+    lens = (C.c_uint64 * B)()
+    if sym.is_cuda and coder == "device":
+        sym, ctx = sym.contiguous(), ctx.contiguous()
+        dev = sym.device
+        with torch.cuda.device(dev):
+            if out is None:
+                out = torch.empty(B * cap, dtype=torch.uint8, device=dev)
+            elif out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous() or out.numel() < B * cap:
+                raise ValueError(f"{what}: out must be a contiguous uint8 tensor of at least {B * cap} bytes on {dev}")
+            segb = torch.empty(B, n_seg, dtype=torch.int32, device=dev)
+            scratch = _seg_scratch(B, n_seg, dev)
+            _seg_call("mlic_residual_encode_segments", what, _stream(), C.c_void_p(sym.data_ptr()),
+                      C.c_void_p(ctx.data_ptr()), B, H, W, m.ctypes.data, freq.ctypes.data, L, n_seg,
+                      C.c_void_p(out.data_ptr()), cap, C.c_void_p(segb.data_ptr()), lens, C.c_void_p(scratch.data_ptr()),
+                      scratch.numel(), None)
+            top = max(lens)
+            data = out[:B * cap].view(B, cap)[:, :top].cpu().numpy()
+            segb = segb.cpu().numpy().view(np.uint32)
+    else:
+        s = np.ascontiguousarray(sym.cpu().numpy())
+        c = np.ascontiguousarray(ctx.cpu().numpy())
+        data = np.empty((B, cap), np.uint8)
+        segb = np.empty((B, n_seg), np.uint32)
+        _seg_call("mlic_residual_encode_segments_host", what, s.ctypes.data, c.ctypes.data, B, H, W, m.ctypes.data,
+                  freq.ctypes.data, L, n_seg, data.ctypes.data, cap, segb.ctypes.data, lens)
+    return [(data[b, :lens[b]].tobytes(), segb[b].copy()) for b in range(B)]
+
+
+def residual_decode_segments(data, seg_bytes, ctx, tables, segment: int, coder: str = "device",
+                             out: Optional[torch.Tensor] = None):
+    """The symbols of B images' segmented residual strings (mlic_residual_decode_segments): data: B byte strings,
+    seg_bytes: B arrays of n_seg lengths, ctx uint8 [B,3,H,W], tables: B dicts with "m" and "freq".  -> int16
+    [B,3,H,W] on ctx's device, straight into the buffer residual_apply reads: on the device path no symbol and no
+    context crosses to the host.  Every segment must consume exactly its words and end at the state 2^31; a segment
+    that does not, or that holds what a well-formed one cannot, raises ResidualSegmentError.  out: an optional
+    contiguous int16 device tensor of at least B 3 H W elements to decode into (the result is a view of it)."""
+    what = "residual_decode_segments"
+    B, H, W = _seg_images(None, ctx, what)
+    L, coder = _check_segment(segment, what), _check_coder(coder, what)
+    N = 3 * H * W
+    n_seg = -(-N // L)
+    m, freq = _seg_tables(tables, B, what)
+    data = [bytes(d) for d in data]
+    if len(data) != B or len(seg_bytes) != B:
+        raise ValueError(f"{what}: {B} images but {len(data)} strings and {len(seg_bytes)} length arrays")
+    segb = np.ascontiguousarray(np.stack([np.asarray(v, np.int64).reshape(-1) for v in seg_bytes]))
+    if segb.shape != (B, n_seg) or segb.min() < 0 or segb.max() > 0xFFFFFFFF:
+        raise ValueError(f"{what}: {n_seg} segment lengths per image expected")
+    segb = segb.astype(np.uint32)
+    stride = (max(len(d) for d in data) + 3) // 4 * 4
+    buf = np.zeros((B, max(stride, 4)), np.uint8)
+    for b, d in enumerate(data):
+        buf[b, :len(d)] = np.frombuffer(d, np.uint8)
+    lens = (C.c_uint64 * B)(*[len(d) for d in data])
+    if ctx.is_cuda and coder == "device":
+        ctx = ctx.contiguous()
+        dev = ctx.device
+        with torch.cuda.device(dev):
+            if out is None:
+                sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
+                if _lib.poison():
+                    sym.fill_(-0x1112)
+            elif out.dtype != torch.int16 or out.device != dev or not out.is_contiguous() or out.numel() < B * N:
+                raise ValueError(f"{what}: out must be a contiguous int16 tensor of at least {B * N} elements on {dev}")
+            else:
+                sym = out.view(-1)[:B * N].view(B, 3, H, W)
+            scratch = _seg_scratch(B, n_seg, dev)
+            d_dev = torch.from_numpy(buf).to(dev)
+            _seg_call("mlic_residual_decode_segments", what, _stream(), C.c_void_p(d_dev.data_ptr()), buf.shape[1], lens,
+                      segb.ctypes.data, C.c_void_p(ctx.data_ptr()), B, H, W, m.ctypes.data, freq.ctypes.data, L, n_seg,
+                      C.c_void_p(sym.data_ptr()), C.c_void_p(scratch.data_ptr()), scratch.numel(), None)
+        return sym
+    c = np.ascontiguousarray(ctx.cpu().numpy())
+    q = np.empty((B, 3, H, W), np.int16)
+    _seg_call("mlic_residual_decode_segments_host", what, buf.ctypes.data, buf.shape[1], lens, segb.ctypes.data,
+              c.ctypes.data, B, H, W, m.ctypes.data, freq.ctypes.data, L, n_seg, q.ctypes.data)
+    return torch.from_numpy(q).to(ctx.device)
+
+
+def write_container_residual_seg(H: int, W: int, inner: bytes, segs: bytes, seg_bytes, segment: int, tau: int,
+                                 digest: int, m, freq, vbr: bool = False) -> bytes:
+    """The segmented residual file (mlic_container_write_residual_seg): "MLR2", then the header and the tables of
+    the "MLR1" file, seg_len, n_seg, `inner` behind its length, and behind res_len the n_seg segment byte lengths
+    and `segs`, the concatenated segments."""
+    inner, segs = bytes(inner), bytes(segs)
+    m = np.ascontiguousarray(m, dtype=np.uint8)
+    freq = np.ascontiguousarray(freq, dtype=np.uint16)
+    sb = np.ascontiguousarray(np.asarray(seg_bytes, np.int64).reshape(-1))
+    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
+        raise ValueError(f"write_container_residual_seg: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
+    if sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF)):
+        raise ValueError("write_container_residual_seg: segment lengths must fit 32 bits")
+    sb = sb.astype(np.uint32)
+    n = C.c_size_t()
+    args = (H, W, int(bool(vbr)), int(tau), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data, freq.ctypes.data,
+            int(segment) & 0xFFFFFFFF, sb.size, sb.ctypes.data, inner, len(inner), segs, len(segs))
+    _lib.call("mlic_container_write_residual_seg", *args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_residual_seg", *args, buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_residual_seg(data: bytes, n_levels: Optional[int] = None,
+                                 max_pixels: int = MAX_PIXELS) -> _lib.ContainerResidualSegInfo:
+    """The validating parser of a segmented residual file (mlic_container_parse_residual_seg): raises _lib.MlicError
+    on any malformed input.  info.index_off: the n_seg big-endian u32 lengths; info.data_off / data_len: the
+    segments."""
+    data = bytes(data)
+    info = _lib.ContainerResidualSegInfo()
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call("mlic_container_parse_residual_seg", data, len(data), nl, int(max_pixels), C.byref(info))
+    return info
+
+
+def _seg_cap_of_hist(hist, t, n_seg: int) -> int:
+    """An upper bound of one image's segment bytes from its histograms and tables: a symbol of frequency f grows the
+    coder's state by less than 16 - log2 f + 2^-14 bits and an escape by 16 more (csrc/residual_seg.h), and a
+    segment adds its flush and less than a word of rounding.  Far below one word per sample on real pictures."""
+    bits = 0.0
+    for k in range(RES_CTX):
+        if t["m"][k] == RES_ABSENT:
+            continue
+        cnt = 2 * int(t["m"][k]) + 2
+        h = np.zeros(cnt, np.float64)
+        mk = int(t["m"][k])
+        h[:cnt - 1] = hist[k, RES_MAX_M - mk:RES_MAX_M + mk + 1]
+        h[cnt - 1] = hist[k, RES_BINS - 1]
+        bits += float((h * (16.0 + 2.0 ** -14 - np.log2(t["freq"][k, :cnt].astype(np.float64)))).sum())
+        bits += (16.0 + 4 * 2.0 ** -14) * float(h[cnt - 1])
+    return (int(bits / 8.0) + 16 * n_seg + 64) // 4 * 4
 
 
 def _refuse_residual(what: str, **given):
@@ -1103,8 +1344,11 @@ def _base_x_hat(net, strings, shape, kw, B):
     return x_hat
 
 
-def _encode_residual(net, img, layout, files, strings, shape, lv, tau):
-    """encode_images' second layer: the residual files of `files` (the images' plain or VBR files) and the info."""
+def _encode_residual(net, img, layout, files, strings, shape, lv, tau, segment=None, coder="device"):
+    """encode_images' second layer: the residual files of `files` (the images' plain or VBR files) and the info.
+    segment=None: one serial string per image, coded on the host ("MLR1").  segment=L: the segmented file ("MLR2");
+    with coder="device" sym and ctx stay on the device, the histograms alone go to the host for the tables, and the
+    kernels code; coder="host" (and a CPU model) takes the host entry.  Both give the same bytes."""
     B = img.size(0)
     H, W = _hw(img, layout)
     kw = {} if lv is None else {"s": list(lv)}
@@ -1113,11 +1357,23 @@ def _encode_residual(net, img, layout, files, strings, shape, lv, tau):
     worst = int(front["max_err"].max())  # computed on the device, beside the symbols
     if worst > tau:
         raise RuntimeError(f"encode_images: the residual layer leaves an error of {worst} > max_error {tau}")
-    sym = front["sym"].cpu().numpy().reshape(B, -1)
-    ctx = front["ctx"].cpu().numpy().reshape(B, -1)
     hist = front["hist"].cpu().numpy()
     digest = front["digest"].cpu().tolist()
     out, extra = [], []
+    if segment is not None:
+        n_seg = -(-3 * H * W // segment)
+        tabs = [residual_tables(hist[b]) for b in range(B)]
+        cap = min(max(_seg_cap_of_hist(hist[b], tabs[b], n_seg) for b in range(B)), residual_segment_cap(H, W, segment))
+        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, segment, coder, cap=cap)
+        for b, (segs, seg_bytes) in enumerate(coded):
+            t = tabs[b]
+            out.append(write_container_residual_seg(H, W, files[b], segs, seg_bytes, segment, tau, digest[b], t["m"],
+                                                    t["freq"], vbr=lv is not None))
+            extra.append({"max_error": tau, "base_bytes": len(files[b]), "residual_bytes": len(segs) + 4 * n_seg,
+                          "residual_segment": segment, "segments": n_seg})
+        return out, extra
+    sym = front["sym"].cpu().numpy().reshape(B, -1)
+    ctx = front["ctx"].cpu().numpy().reshape(B, -1)
     for b in range(B):
         t = residual_tables(hist[b])
         res = entropy.rans_encode(sym[b].astype(np.int32), ctx[b].astype(np.int32), *_coder_tables(t))
@@ -1136,11 +1392,14 @@ def _digest_error(b: int, want: int, got: int, net) -> RuntimeError:
         f"base image alone with enhance=False")
 
 
-def _decode_residual(net, files, ref, max_pixels, enhance):
-    """decode_images for residual files: the inner files as decode_images decodes them, then the residual layer."""
+def _decode_residual(net, files, ref, max_pixels, enhance, coder="device"):
+    """decode_images for residual files: the inner files as decode_images decodes them, then the residual layer.
+    "MLR1" files decode their string on the host; "MLR2" files go through residual_decode_segments (coder="device":
+    the kernel, on a GPU model; "host": the host entry), whose int16 output residual_apply reads in place."""
     vbr = hasattr(net, "levels")
     n_levels = net.levels if vbr else None
-    ss = [parse_container_residual(f, n_levels, max_pixels) for f in files]
+    ss = [_parse_residual_any(f, n_levels, max_pixels) for f in files]
+    seg = [int(s.seg_len) if is_residual_seg_file(f) else 0 for f, s in zip(files, ss)]  # 0: the serial kind
     for s in ss:
         if bool(s.vbr) != vbr:
             raise ValueError(f"decode_images: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
@@ -1148,6 +1407,9 @@ def _decode_residual(net, files, ref, max_pixels, enhance):
     inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
     extra = [{"max_error": int(s.tau), "residual_bytes": int(s.res_len), "base_bytes": int(s.inner_len),
               "bytes": len(f), "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
+    for e, s, L in zip(extra, ss, seg):
+        if L:
+            e.update(residual_segment=L, segments=int(s.n_seg))
     if not enhance:
         img, info = decode_images(net, inner, ref=ref, max_pixels=max_pixels)
         for d, e in zip(info, extra):
@@ -1161,7 +1423,8 @@ def _decode_residual(net, files, ref, max_pixels, enhance):
             raise ValueError(f"decode_images: ref must be uint8 {(B, H, W, 3)}, got {tuple(ref.shape)}")
         ref = ref.to(base.device)
     same = all((s.H, s.W) == (H, W) for s in ss)
-    groups = [list(range(B))] if same and len({s.tau for s in ss}) == 1 else [[b] for b in range(B)]
+    one = same and len({(s.tau, L) for s, L in zip(ss, seg)}) == 1  # one size, tau, kind and segment length
+    groups = [list(range(B))] if one else [[b] for b in range(B)]
     img = torch.empty_like(base) if same else torch.zeros_like(base)
     for g in groups:
         s0 = ss[g[0]]
@@ -1182,21 +1445,32 @@ def _decode_residual(net, files, ref, max_pixels, enhance):
             front = None
         if front is None:
             front = residual_front(view, None, tau, "hwc")
-        ctx = front["ctx"].cpu().numpy().reshape(len(g), -1)
         count = front["ctx_count"].cpu().numpy()
-        sym = np.empty((len(g), 3 * h * w), np.int16)
+        tabs = [_file_tables(files[b], ss[b]) for b in g]
         for j, b in enumerate(g):
-            t = _file_tables(files[b], ss[b])
-            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and t["m"][k] == RES_ABSENT]
+            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and tabs[j]["m"][k] == RES_ABSENT]
             if missing:
                 raise ValueError(f"decode_images: file {b}: contexts {missing} occur in the base image but the file "
                                  f"has no table for them")
-            res = files[b][ss[b].res_off:ss[b].res_off + ss[b].res_len]
-            q = entropy.rans_decode(res, ctx[j].astype(np.int32), *_coder_tables(t))
-            if q.size and (q.min() < -255 or q.max() > 255):
-                raise ValueError(f"decode_images: file {b}: the residual string holds a symbol outside [-255, 255]")
-            sym[j] = q
-        sym_d = torch.from_numpy(sym.reshape(len(g), 3, h, w)).to(base.device)
+        if seg[g[0]]:  # segments: no symbol and no context crosses to the host on the device path
+            try:
+                sym_d = residual_decode_segments(
+                    [files[b][ss[b].data_off:ss[b].data_off + ss[b].data_len] for b in g],
+                    [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g],
+                    front["ctx"], tabs, seg[g[0]], coder)
+            except ResidualSegmentError as e:
+                raise ValueError(f"decode_images: file {g[e.image]}: segment {e.segment} of the residual string is "
+                                 f"corrupt: {e.reason}") from None
+        else:
+            ctx = front["ctx"].cpu().numpy().reshape(len(g), -1)
+            sym = np.empty((len(g), 3 * h * w), np.int16)
+            for j, b in enumerate(g):
+                res = files[b][ss[b].res_off:ss[b].res_off + ss[b].res_len]
+                q = entropy.rans_decode(res, ctx[j].astype(np.int32), *_coder_tables(tabs[j]))
+                if q.size and (q.min() < -255 or q.max() > 255):
+                    raise ValueError(f"decode_images: file {b}: the residual string holds a symbol outside [-255, 255]")
+                sym[j] = q
+            sym_d = torch.from_numpy(sym.reshape(len(g), 3, h, w)).to(base.device)
         out = img[g[0]:g[-1] + 1, :h, :w]
         r = residual_apply(view, sym_d, tau, "hwc", ref=None if ref is None else ref[g[0]:g[-1] + 1, :h, :w], out=out)
         if ref is not None:
@@ -1723,7 +1997,8 @@ def rate_loop(net, x: torch.Tensor, H: int, W: int, level, max_bpp: float, max_p
 def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bpp: Optional[float] = None,
                   max_passes: int = 8, return_info: bool = False, roi=None, roi_levels=None, depth: Optional[int] = None,
                   msb: bool = False, coded_size=None, scale=None, filter: str = "lanczos3", layered: bool = False,
-                  max_error: Optional[int] = None):
+                  max_error: Optional[int] = None, residual_segment: Optional[int] = None,
+                  residual_coder: str = "device"):
     """uint8 images ([B,H,W,3] / [B,3,H,W] tensor or numpy array, or one image; layout=None tells them apart by
     the dimension of size 3) -> one file per image.  A host array crosses to the device as uint8; then one
     ingest launch, one net.compress over the batch, B containers.  level: the VBR level (one for the batch or
@@ -1758,7 +2033,19 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     returns an image in which no sample is off by more than tau.  The bound is checked on the device before
     anything is written.  info[b] gains "max_error", "base_bytes" and "residual_bytes"; bytes and bpp are the
     whole file.  Refused, each by name, together with roi=, max_bpp=, level="auto", depth=, scale=, coded_size= and
-    layered=."""
+    layered=.
+    residual_segment=L (256..65536; needs max_error=): the segmented residual file "MLR2" (DESIGN.md §5 "Residual
+    coding", "Segments") instead of "MLR1": the residual string is cut into segments of L samples that code
+    independently, so residual_coder="device" (the default; a CPU model takes the host entry) codes them with
+    residual_encode_segments_kernel while sym and ctx stay on the device, and decode_images decodes them there.
+    residual_coder="host" builds the same bytes on the host.  None: the "MLR1" file, unchanged.  info[b] gains
+    "residual_segment" and "segments"."""
+    residual_coder = _check_coder(residual_coder, "encode_images")
+    if residual_segment is not None:
+        if max_error is None:
+            raise ValueError("encode_images: residual_segment= needs max_error= (it cuts the residual string of "
+                             "residual coding into segments)")
+        residual_segment = _check_segment(residual_segment, "encode_images")
     if max_error is not None:
         max_error = _check_tau(max_error, "encode_images")
         _refuse_residual("encode_images", **{"roi=": roi is not None or roi_levels is not None,
@@ -1838,7 +2125,8 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
         files = [write_container_scaled(H, W, f, filter, vbr=lv is not None) for f in files]
     residual = None
     if max_error is not None:
-        files, residual = _encode_residual(net, img, layout, files, out["strings"], out["shape"], lv, max_error)
+        files, residual = _encode_residual(net, img, layout, files, out["strings"], out["shape"], lv, max_error,
+                                           residual_segment, residual_coder)
     if not return_info:
         return files
     info = []
@@ -1858,7 +2146,7 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
 @torch.no_grad()
 def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_PIXELS, depth: Optional[int] = None,
                   msb: bool = False, out_size=None, filter: Optional[str] = None, slices: Optional[int] = None,
-                  fill: str = "mean", enhance: bool = True):
+                  fill: str = "mean", enhance: bool = True, residual_coder: str = "device"):
     """Files of one padded size -> (uint8 [B,H,W,3] on the model's device, info).  info[b] holds H, W, level
     (None for a fixed-rate model), bytes, bpp and, with ref (uint8 [B,H,W,3]), the exact sq_err and psnr of
     image b.  Files whose H x W differ within the padded size come back in the top-left of a zeroed
@@ -1886,7 +2174,14 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     never returned), the residual string is rANS-decoded with the file's tables and residual_apply adds it back.
     info[b] gains "max_error" (the file's tau), "residual_bytes", "base_bytes" and, with ref, "max_abs_err".
     enhance=False returns the base picture, byte for byte decode_images(strip_residual(f)).  Refused, each by name:
-    slices=, out_size=, filter= and depth= on residual files, and a call mixing residual files with others."""
+    slices=, out_size=, filter= and depth= on residual files, and a call mixing residual files with others.
+    Segmented residual files ("MLR2", encode_images(residual_segment=L)) are told apart by their magic: after the
+    same digest and table checks residual_decode_segments decodes the segments (residual_coder="device": the kernel,
+    its int16 output read in place by residual_apply; "host": the host entry) and checks per segment that exactly
+    its words were consumed and the state is back at 2^31; an error names the file and the segment.  "MLR1" and
+    "MLR2" files, sizes and tau may mix in one call: they decode in groups.  info[b] gains "residual_segment" and
+    "segments"."""
+    residual_coder = _check_coder(residual_coder, "decode_images")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
@@ -1894,13 +2189,14 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
         for name, given in (("slices=", slices is not None), ("out_size=", out_size is not None),
                             ("filter=", filter is not None), ("depth=", depth is not None)):
             if given:
-                raise ValueError(f"decode_images: {name} on a residual file (MLR1) is not supported")
+                kind = "MLR2" if all(is_residual_seg_file(f) for f in files if is_residual_file(f)) else "MLR1"
+                raise ValueError(f"decode_images: {name} on a residual file ({kind}) is not supported")
         if fill != "mean":
             raise ValueError("decode_images: fill= goes with slices= or layered files")
         if not all(is_residual_file(f) for f in files):
             raise ValueError("decode_images: residual files (MLR1) and other files in one call are not supported: "
                              "decode them in separate calls")
-        return _decode_residual(net, files, ref, max_pixels, bool(enhance))
+        return _decode_residual(net, files, ref, max_pixels, bool(enhance), residual_coder)
     if depth is not None:
         depth, msb = _check_depth(depth, "decode_images"), _check_msb(msb, "decode_images")
     slices = _check_prefix(net, slices, fill, "decode_images")

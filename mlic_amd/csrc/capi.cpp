@@ -12,6 +12,7 @@
 #include "options.h"
 #include "resample_table.h"
 #include "residual.h"
+#include "residual_seg.h"
 
 using namespace mlic;
 
@@ -1598,6 +1599,205 @@ int mlic_container_parse_residual(const uint8_t* data, size_t n, int n_levels, u
     info->inner_len = s.inner_len;
     info->res_off = s.res_off;
     info->res_len = s.res_len;
+    to_abi(s.inner, &info->inner);
+  });
+}
+
+// ---- segmented residual strings (residual_seg.h; DESIGN.md section 5 "Residual coding", "Segments")
+namespace {
+struct SegScratch {  // the device entries' scratch: tables | seg_off | seg_bytes | total | status
+  size_t tabs, off, bytes, total, status, size;
+  SegScratch(int B, int64_t n_seg) {
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    tabs = 0;
+    off = up((size_t)B * std::max(sizeof(ResSegEncTable), sizeof(ResSegDecTable)));
+    bytes = up(off + sizeof(uint32_t) * (size_t)B * n_seg);
+    total = up(bytes + sizeof(uint32_t) * (size_t)B * n_seg);
+    status = up(total + sizeof(uint64_t) * (size_t)B);
+    size = up(status + sizeof(uint32_t) * (size_t)B);
+  }
+};
+
+void seg_status_throw(const char* what, const std::vector<uint32_t>& st) {
+  for (size_t b = 0; b < st.size(); ++b)
+    if (st[b] != RES_SEG_CLEAN)
+      throw Error(std::string("mlic: ") + what + ": image " + std::to_string(b) + ", segment " +
+                  std::to_string(st[b] >> 4) + ": " + residual_seg_reason(st[b] & 15u));
+}
+
+void seg_common_check(const char* what, int B, int H, int W, const uint8_t* m, const uint16_t* freq, int seg_len,
+                      int64_t n_seg) {
+  residual_seg_check(what, B, H, W, seg_len, n_seg);
+  residual_seg_tables_check(what, m, freq, B);
+}
+bool aligned_to(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+}  // namespace
+
+int mlic_residual_segments_scratch_bytes(int B, int64_t n_seg, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr, "residual_segments_scratch_bytes: null bytes");
+    MLIC_CHECK(B >= 1 && n_seg >= 1 && n_seg <= RES_SEG_MAX_N / RES_SEG_MIN,
+               "residual_segments_scratch_bytes: B >= 1 and 1 <= n_seg <= 2^21 expected");
+    *bytes = SegScratch(B, n_seg).size;
+  });
+}
+
+int mlic_residual_encode_segments(void* stream, const int16_t* sym, const uint8_t* ctx, int B, int H, int W,
+                                  const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                                  size_t cap, uint32_t* seg_bytes, uint64_t* len, void* scratch, size_t scratch_bytes,
+                                  uint32_t* status) {
+  return guard([&] {
+    const char* what = "residual_encode_segments";
+    MLIC_CHECK(sym != nullptr, "residual_encode_segments: null sym");
+    MLIC_CHECK(ctx != nullptr, "residual_encode_segments: null ctx");
+    MLIC_CHECK(out != nullptr, "residual_encode_segments: null out");
+    MLIC_CHECK(seg_bytes != nullptr, "residual_encode_segments: null seg_bytes");
+    MLIC_CHECK(len != nullptr, "residual_encode_segments: null len");
+    MLIC_CHECK(scratch != nullptr, "residual_encode_segments: null scratch");
+    seg_common_check(what, B, H, W, m, freq, seg_len, n_seg);
+    MLIC_CHECK(cap % 4 == 0, "residual_encode_segments: the capacity must be a multiple of 4");
+    MLIC_CHECK(cap >= (size_t)RES_SEG_MIN_BYTES * (size_t)n_seg,
+               "residual_encode_segments: the capacity is too small (below 8 bytes a segment)");
+    MLIC_CHECK(cap <= 0xffffffffu, "residual_encode_segments: the capacity must fit 32 bits");
+    const SegScratch sc(B, n_seg);
+    MLIC_CHECK(scratch_bytes >= sc.size, "residual_encode_segments: scratch too small");
+    MLIC_CHECK(aligned_to(sym, 2) && aligned_to(out, 4) && aligned_to(seg_bytes, 4) && aligned_to(scratch, 16),
+               "residual_encode_segments: sym must be 2-byte, out and seg_bytes 4-byte, scratch 16-byte aligned");
+    std::vector<ResSegEncTable> tabs((size_t)B);
+    for (int b = 0; b < B; ++b)
+      residual_seg_enc_table(m + (size_t)b * RES_CTX, freq + (size_t)b * RES_CTX * RES_BINS, &tabs[(size_t)b]);
+    auto st = (hipStream_t)stream;
+    auto* base = static_cast<uint8_t*>(scratch);
+    auto* d_tabs = reinterpret_cast<ResSegEncTable*>(base + sc.tabs);
+    auto* d_status = reinterpret_cast<uint32_t*>(base + sc.status);
+    auto* d_total = reinterpret_cast<uint64_t*>(base + sc.total);
+    HIP_OK(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(ResSegEncTable) * (size_t)B, hipMemcpyHostToDevice, st));
+    residual_encode_segments(sym, ctx, B, 3 * (int64_t)H * W, seg_len, n_seg, d_tabs, out, cap,
+                             reinterpret_cast<uint32_t*>(base + sc.off), seg_bytes, d_total, d_status, st);
+    std::vector<uint32_t> hs((size_t)B);
+    HIP_OK(hipMemcpyAsync(hs.data(), d_status, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(len, d_total, sizeof(uint64_t) * (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (status) std::copy(hs.begin(), hs.end(), status);
+    seg_status_throw(what, hs);
+  });
+}
+
+int mlic_residual_decode_segments(void* stream, const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                  const uint32_t* seg_bytes, const uint8_t* ctx, int B, int H, int W, const uint8_t* m,
+                                  const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym, void* scratch,
+                                  size_t scratch_bytes, uint32_t* status) {
+  return guard([&] {
+    const char* what = "residual_decode_segments";
+    MLIC_CHECK(data != nullptr, "residual_decode_segments: null data");
+    MLIC_CHECK(ctx != nullptr, "residual_decode_segments: null ctx");
+    MLIC_CHECK(sym != nullptr, "residual_decode_segments: null sym");
+    MLIC_CHECK(scratch != nullptr, "residual_decode_segments: null scratch");
+    seg_common_check(what, B, H, W, m, freq, seg_len, n_seg);
+    const int64_t N = 3 * (int64_t)H * W;
+    MLIC_CHECK(data_stride % 4 == 0, "residual_decode_segments: the data stride must be a multiple of 4");
+    residual_seg_lengths_check(what, seg_bytes, data_len, data_stride, B, N, seg_len, n_seg);
+    const SegScratch sc(B, n_seg);
+    MLIC_CHECK(scratch_bytes >= sc.size, "residual_decode_segments: scratch too small");
+    MLIC_CHECK(aligned_to(sym, 2) && aligned_to(data, 4) && aligned_to(scratch, 16),
+               "residual_decode_segments: sym must be 2-byte, data 4-byte, scratch 16-byte aligned");
+    std::vector<ResSegDecTable> tabs((size_t)B);
+    std::vector<uint32_t> offs((size_t)B * n_seg);
+    for (int b = 0; b < B; ++b) {
+      residual_seg_dec_table(m + (size_t)b * RES_CTX, freq + (size_t)b * RES_CTX * RES_BINS, &tabs[(size_t)b]);
+      uint32_t o = 0;
+      for (int64_t k = 0; k < n_seg; ++k) {
+        offs[(size_t)b * n_seg + k] = o;
+        o += seg_bytes[(size_t)b * n_seg + k];
+      }
+    }
+    auto st = (hipStream_t)stream;
+    auto* base = static_cast<uint8_t*>(scratch);
+    auto* d_tabs = reinterpret_cast<ResSegDecTable*>(base + sc.tabs);
+    auto* d_off = reinterpret_cast<uint32_t*>(base + sc.off);
+    auto* d_bytes = reinterpret_cast<uint32_t*>(base + sc.bytes);
+    auto* d_status = reinterpret_cast<uint32_t*>(base + sc.status);
+    HIP_OK(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(ResSegDecTable) * (size_t)B, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_off, offs.data(), sizeof(uint32_t) * offs.size(), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_bytes, seg_bytes, sizeof(uint32_t) * offs.size(), hipMemcpyHostToDevice, st));
+    residual_decode_segments(data, data_stride, d_off, d_bytes, ctx, B, N, seg_len, n_seg, d_tabs, sym, d_status, st);
+    std::vector<uint32_t> hs((size_t)B);
+    HIP_OK(hipMemcpyAsync(hs.data(), d_status, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (status) std::copy(hs.begin(), hs.end(), status);
+    seg_status_throw(what, hs);
+  });
+}
+
+int mlic_residual_encode_segments_host(const int16_t* sym, const uint8_t* ctx, int B, int H, int W, const uint8_t* m,
+                                       const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
+                                       uint32_t* seg_bytes, uint64_t* len) {
+  return guard([&] {
+    MLIC_CHECK(sym != nullptr, "residual_encode_segments_host: null sym");
+    MLIC_CHECK(ctx != nullptr, "residual_encode_segments_host: null ctx");
+    MLIC_CHECK(seg_bytes != nullptr, "residual_encode_segments_host: null seg_bytes");
+    MLIC_CHECK(len != nullptr, "residual_encode_segments_host: null len");
+    seg_common_check("residual_encode_segments_host", B, H, W, m, freq, seg_len, n_seg);
+    if (out != nullptr) {
+      MLIC_CHECK(cap % 4 == 0, "residual_encode_segments_host: the capacity must be a multiple of 4");
+      MLIC_CHECK(cap >= (size_t)RES_SEG_MIN_BYTES * (size_t)n_seg,
+                 "residual_encode_segments_host: the capacity is too small (below 8 bytes a segment)");
+    }
+    residual_seg_encode_host(sym, ctx, B, H, W, m, freq, seg_len, n_seg, out, cap, seg_bytes, len);
+  });
+}
+
+int mlic_residual_decode_segments_host(const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                       const uint32_t* seg_bytes, const uint8_t* ctx, int B, int H, int W,
+                                       const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg,
+                                       int16_t* sym) {
+  return guard([&] {
+    const char* what = "residual_decode_segments_host";
+    MLIC_CHECK(data != nullptr, "residual_decode_segments_host: null data");
+    MLIC_CHECK(ctx != nullptr, "residual_decode_segments_host: null ctx");
+    MLIC_CHECK(sym != nullptr, "residual_decode_segments_host: null sym");
+    seg_common_check(what, B, H, W, m, freq, seg_len, n_seg);
+    MLIC_CHECK(data_stride % 4 == 0, "residual_decode_segments_host: the data stride must be a multiple of 4");
+    residual_seg_lengths_check(what, seg_bytes, data_len, data_stride, B, 3 * (int64_t)H * W, seg_len, n_seg);
+    residual_seg_decode_host(data, data_stride, data_len, seg_bytes, ctx, B, H, W, m, freq, seg_len, n_seg, sym);
+  });
+}
+
+int mlic_container_write_residual_seg(uint32_t H, uint32_t W, int vbr, int tau, uint64_t digest, const uint8_t* m,
+                                      const uint16_t* freq, uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
+                                      const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
+                                      uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    MLIC_CHECK(tau >= 0, "container_write_residual_seg: negative tau");
+    container_ok(container_write_residual_seg(H, W, vbr != 0, (uint32_t)tau, digest, m, freq, seg_len, n_seg, seg_bytes,
+                                              inner, inner_len, segs, segs_len, out, cap, len));
+  });
+}
+
+int mlic_container_parse_residual_seg(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                      mlic_container_residual_seg_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_residual_seg: null info");
+    ResidualSegInfo s;
+    container_ok(container_parse_residual_seg(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &s));
+    info->H = s.H;
+    info->W = s.W;
+    info->tau = (int32_t)s.tau;
+    info->vbr = s.vbr ? 1 : 0;
+    info->digest = s.digest;
+    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+      info->m[k] = s.m[k];
+      info->freq_off[k] = s.freq_off[k];
+    }
+    info->seg_len = s.seg_len;
+    info->n_seg = s.n_seg;
+    info->inner_off = s.inner_off;
+    info->inner_len = s.inner_len;
+    info->res_off = s.res_off;
+    info->res_len = s.res_len;
+    info->index_off = s.index_off;
+    info->data_off = s.data_off;
+    info->data_len = s.data_len;
     to_abi(s.inner, &info->inner);
   });
 }

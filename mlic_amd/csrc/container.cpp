@@ -591,6 +591,175 @@ const char* container_parse_residual(const uint8_t* data, size_t n, uint32_t n_l
   return nullptr;
 }
 
+// ------------------------------------------------------------------------------ residual, segmented
+namespace {
+uint64_t residual_seg_count(uint32_t H, uint32_t W, uint32_t seg_len) {
+  return (3 * (uint64_t)H * W + seg_len - 1) / seg_len;
+}
+uint64_t residual_seg_bound(uint32_t H, uint32_t W, uint32_t seg_len, uint64_t k) {  // bytes segment k may take
+  const uint64_t left = 3 * (uint64_t)H * W - k * seg_len;
+  return 4 * ((left < seg_len ? left : seg_len) + RESIDUAL_SEG_SLACK);
+}
+}  // namespace
+
+const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint64_t digest,
+                                         const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                         const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                         const uint8_t* segs, size_t segs_len, uint8_t* out, size_t cap, size_t* len) {
+  if (len == nullptr) return "container_write_residual_seg: null len";
+  if (H == 0 || W == 0) return "container_write_residual_seg: H or W is zero";
+  if (tau > 127) return "container_write_residual_seg: tau above 127";
+  if (m == nullptr) return "container_write_residual_seg: null m";
+  if (seg_len < RESIDUAL_SEG_MIN || seg_len > RESIDUAL_SEG_MAX)
+    return "container_write_residual_seg: seg_len outside 256..65536";
+  if ((uint64_t)n_seg != residual_seg_count(H, W, seg_len))
+    return "container_write_residual_seg: n_seg is not ceil(3 H W / seg_len)";
+  if (inner_len == 0) return "container_write_residual_seg: an empty inner file";
+  if (inner_len > 0xffffffffu || segs_len > 0xffffffffu - 4 * (uint64_t)n_seg)
+    return "container_write_residual_seg: a string longer than a 32-bit length";
+  size_t total = RESIDUAL_HEADER + 16;
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    if (m[k] != RESIDUAL_ABSENT && m[k] > RESIDUAL_MAX_M) return "container_write_residual_seg: an m outside 0..63";
+    total += 1 + (m[k] == RESIDUAL_ABSENT ? 0 : 2 * (2 * (size_t)m[k] + 2));
+  }
+  const size_t res_len = 4 * (size_t)n_seg + segs_len;
+  if (inner_len > SIZE_MAX - total || res_len > SIZE_MAX - total - inner_len)
+    return "container_write_residual_seg: the file does not fit size_t";
+  total += inner_len + res_len;
+  *len = total;
+  if (out == nullptr) return nullptr;
+  if (cap < total) return "container_write_residual_seg: buffer too small";
+  if (freq == nullptr) return "container_write_residual_seg: null frequencies";
+  if (inner == nullptr || seg_bytes == nullptr || segs == nullptr) return "container_write_residual_seg: null string";
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    if (m[k] == RESIDUAL_ABSENT) continue;
+    uint32_t sum = 0;
+    for (uint32_t j = 0; j < 2 * (uint32_t)m[k] + 2; ++j) {
+      if (freq[k * 128 + j] == 0) return "container_write_residual_seg: a zero frequency";
+      sum += freq[k * 128 + j];
+    }
+    if (sum != 65536) return "container_write_residual_seg: frequencies do not sum to 65536";
+  }
+  uint64_t sum = 0;
+  for (uint32_t k = 0; k < n_seg; ++k) {
+    if (seg_bytes[k] % 4) return "container_write_residual_seg: a segment length that is not a multiple of 4";
+    if (seg_bytes[k] < 8) return "container_write_residual_seg: a segment length below 8";
+    if (seg_bytes[k] > residual_seg_bound(H, W, seg_len, k))
+      return "container_write_residual_seg: a segment length above the capacity bound";
+    sum += seg_bytes[k];
+  }
+  if (sum != segs_len) return "container_write_residual_seg: the segment lengths do not sum to the data length";
+  std::memcpy(out, "MLR2", 4);
+  out[4] = 0;
+  out[5] = vbr ? 1 : 0;
+  out[6] = (uint8_t)tau;
+  out[7] = (uint8_t)RESIDUAL_CTX;
+  put32(out + 8, H);
+  put32(out + 12, W);
+  put32(out + 16, (uint32_t)(digest >> 32));
+  put32(out + 20, (uint32_t)digest);
+  uint8_t* p = out + RESIDUAL_HEADER;
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    *p++ = m[k];
+    if (m[k] == RESIDUAL_ABSENT) continue;
+    for (uint32_t j = 0; j < 2 * (uint32_t)m[k] + 2; ++j) {
+      *p++ = (uint8_t)(freq[k * 128 + j] >> 8);
+      *p++ = (uint8_t)freq[k * 128 + j];
+    }
+  }
+  put32(p, seg_len);
+  put32(p + 4, n_seg);
+  put32(p + 8, (uint32_t)inner_len);
+  std::memcpy(p + 12, inner, inner_len);
+  p += 12 + inner_len;
+  put32(p, (uint32_t)res_len);
+  p += 4;
+  for (uint32_t k = 0; k < n_seg; ++k, p += 4) put32(p, seg_bytes[k]);
+  std::memcpy(p, segs, segs_len);
+  return nullptr;
+}
+
+const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                         ResidualSegInfo* info) {
+  if (info == nullptr) return "container_parse_residual_seg: null info";
+  if (data == nullptr && n != 0) return "container_parse_residual_seg: null data";
+  if (n < RESIDUAL_HEADER) return "container_parse_residual_seg: truncated header";
+  if (std::memcmp(data, "MLR2", 4) != 0)
+    return "container_parse_residual_seg: bad magic (not a segmented residual file)";
+  if (data[4] != 0) return "container_parse_residual_seg: unknown version";
+  if (data[5] & ~1u) return "container_parse_residual_seg: unknown flags";
+  if (data[6] > 127) return "container_parse_residual_seg: tau above 127";
+  if (data[7] != RESIDUAL_CTX) return "container_parse_residual_seg: n_ctx is not 24";
+  Reader r{data, n, 8};
+  ResidualSegInfo s{};
+  s.vbr = (data[5] & 1u) != 0;
+  s.tau = data[6];
+  uint32_t hi = 0, lo = 0;
+  r.u32(&s.H);  // n >= RESIDUAL_HEADER: the header's reads succeed
+  r.u32(&s.W);
+  r.u32(&hi);
+  r.u32(&lo);
+  s.digest = ((uint64_t)hi << 32) | lo;
+  if (s.H == 0 || s.W == 0) return "container_parse_residual_seg: H or W is zero";
+  if ((uint64_t)s.H > max_pixels / (uint64_t)s.W) return "container_parse_residual_seg: image exceeds max_pixels";
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    if (r.n - r.pos < 1) return "container_parse_residual_seg: truncated before a table's m";
+    const uint8_t m = data[r.pos++];
+    s.m[k] = m;
+    s.freq_off[k] = r.pos;
+    if (m == RESIDUAL_ABSENT) continue;
+    if (m > RESIDUAL_MAX_M) return "container_parse_residual_seg: an m outside 0..63";
+    const size_t cnt = 2 * (size_t)m + 2;
+    if (r.n - r.pos < 2 * cnt) return "container_parse_residual_seg: truncated inside a table";
+    uint32_t sum = 0;
+    for (size_t j = 0; j < cnt; ++j) {
+      const uint32_t f = ((uint32_t)data[r.pos + 2 * j] << 8) | data[r.pos + 2 * j + 1];
+      if (f == 0) return "container_parse_residual_seg: a zero frequency";
+      sum += f;
+    }
+    if (sum != 65536) return "container_parse_residual_seg: a table's frequencies do not sum to 65536";
+    r.pos += 2 * cnt;
+  }
+  if (!r.u32(&s.seg_len) || !r.u32(&s.n_seg)) return "container_parse_residual_seg: truncated before seg_len, n_seg";
+  if (s.seg_len < RESIDUAL_SEG_MIN || s.seg_len > RESIDUAL_SEG_MAX)
+    return "container_parse_residual_seg: seg_len outside 256..65536";
+  if ((uint64_t)s.n_seg != residual_seg_count(s.H, s.W, s.seg_len))
+    return "container_parse_residual_seg: n_seg is not ceil(3 H W / seg_len)";
+  uint32_t ln = 0;
+  if (!r.u32(&ln)) return "container_parse_residual_seg: truncated before the inner length";
+  if (ln > r.n - r.pos) return "container_parse_residual_seg: the inner length runs past the end";
+  if (ln == 0) return "container_parse_residual_seg: an empty inner file";
+  s.inner_off = r.pos;
+  s.inner_len = ln;
+  r.pos += ln;
+  if (!r.u32(&ln)) return "container_parse_residual_seg: truncated before the residual length";
+  if (ln > r.n - r.pos) return "container_parse_residual_seg: the residual length runs past the end";
+  s.res_off = r.pos;
+  s.res_len = ln;
+  if ((uint64_t)ln < 4 * (uint64_t)s.n_seg) return "container_parse_residual_seg: the residual length is below its index";
+  s.index_off = r.pos;
+  uint64_t sum = 4 * (uint64_t)s.n_seg;
+  for (uint32_t k = 0; k < s.n_seg; ++k) {
+    uint32_t v = 0;
+    r.u32(&v);  // inside the residual length, which is inside the file
+    if (v % 4) return "container_parse_residual_seg: a segment length that is not a multiple of 4";
+    if (v < 8) return "container_parse_residual_seg: a segment length below 8";
+    if (v > residual_seg_bound(s.H, s.W, s.seg_len, k))
+      return "container_parse_residual_seg: a segment length above the capacity bound";
+    sum += v;
+  }
+  if (sum != ln) return "container_parse_residual_seg: the residual length is not 4 n_seg + the segment lengths";
+  s.data_off = r.pos;
+  s.data_len = ln - 4 * (size_t)s.n_seg;
+  r.pos += s.data_len;
+  if (r.pos != r.n) return "container_parse_residual_seg: bytes left over after the segments";
+  if (const char* err = container_parse(data + s.inner_off, s.inner_len, s.vbr, n_levels, max_pixels, &s.inner)) return err;
+  if (s.inner.H != s.H || s.inner.W != s.W)
+    return "container_parse_residual_seg: the inner file's H x W is not the outer one";
+  *info = s;
+  return nullptr;
+}
+
 void container_roi_unpack(const uint8_t* map, uint64_t cells, uint8_t* levels) {
   for (uint64_t k = 0; k < cells; ++k) {
     const uint8_t byte = map[1 + (size_t)(k >> 1)];

@@ -208,5 +208,47 @@ const char* container_write_residual(uint32_t H, uint32_t W, bool vbr, uint32_t 
 const char* container_parse_residual(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                      ResidualInfo* info);
 
+// ---- The segmented residual file (DESIGN.md section 5 "Residual coding", "Segments"; residual_seg.h has the
+// definitions): the residual string cut into independently coded segments of seg_len samples of the canonical order,
+// so that a GPU codes and decodes them in parallel.  All integers big-endian:
+//     4 bytes "MLR2" | >B version 0 | >B flags (bit 0: VBR level word inside) | >B tau | >B n_ctx = 24
+//     >II H, W | >Q digest | the 24 tables, exactly as in "MLR1"
+//     >I seg_len (256..65536) | >I n_seg = ceil(3 H W / seg_len) | >I inner_len, the inner file
+//     >I res_len = 4 n_seg + the sum of the lengths | n_seg x >I segment byte lengths | the segments, concatenated
+// A segment's bytes are rans_encode of its samples: a multiple of 4, at least 8 (the flush), and at most
+// 4 (samples + RESIDUAL_SEG_SLACK) (residual_seg.h derives n + 2 words).  As H, "MLR2" exceeds every max_pixels.
+constexpr uint32_t RESIDUAL_SEG_MIN = 256, RESIDUAL_SEG_MAX = 65536, RESIDUAL_SEG_SLACK = 4;
+struct ResidualSegInfo {
+  uint32_t H, W;
+  uint32_t tau;
+  bool vbr;
+  uint64_t digest;
+  uint8_t m[RESIDUAL_CTX];
+  size_t freq_off[RESIDUAL_CTX];
+  uint32_t seg_len, n_seg;
+  size_t inner_off, inner_len;
+  size_t res_off, res_len;    // the index and the segments
+  size_t index_off;           // n_seg big-endian u32 lengths (= res_off)
+  size_t data_off, data_len;  // the concatenated segments
+  ContainerInfo inner;
+};
+inline bool is_residual_seg_file(const uint8_t* data, size_t n) {
+  return n >= 4 && data[0] == 'M' && data[1] == 'L' && data[2] == 'R' && data[3] == '2';
+}
+// m, freq, inner as container_write_residual; seg_bytes: n_seg lengths; segs: their concatenation.  Refused, each with
+// its own message: what container_write_residual refuses; seg_len outside 256..65536; n_seg not ceil(3 H W / seg_len);
+// a segment length that is not a multiple of 4, is below 8 or is above the capacity bound; lengths that do not sum to
+// segs_len.  The *len / out / cap protocol of container_write.
+const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint64_t digest,
+                                         const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                         const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                         const uint8_t* segs, size_t segs_len, uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: everything container_parse_residual refuses (with "MLR2" as the magic);
+// truncation before seg_len / n_seg; seg_len outside 256..65536; n_seg not ceil(3 H W / seg_len); a segment length
+// that is not a multiple of 4, is below 8 or is above the capacity bound of its samples; res_len below its index or
+// not 4 n_seg + the sum of the lengths; bytes left over.
+const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                         ResidualSegInfo* info);
+
 }  // namespace mlic
 #endif

@@ -341,6 +341,19 @@ void image_residual_front_u8(const uint8_t* base, const int64_t* base_strides, c
 void image_residual_apply_u8(const uint8_t* base, const int64_t* base_strides, const int16_t* sym, int B, int H, int W,
                              int tau, uint8_t* out, const int64_t* out_strides, const uint8_t* ref,
                              const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err, hipStream_t st);
+// The device rANS coder of the segmented residual strings (residual_coder.hip; residual_seg.h has the definitions).
+// sym int16 and ctx u8 are dense [B][N]; tabs, seg_off, seg_bytes [B][n_seg], total [B] and status [B] are device
+// memory.  encode: a counting pass, a scan and a writing pass on `st`; image b's bytes go to out + b cap, each store
+// checked.  decode: seg_off and seg_bytes come from the caller; q goes to sym.  Both reset status to RES_SEG_CLEAN on
+// the stream; the caller has checked the arguments (residual_seg_check and its kin).
+struct ResSegEncTable;
+struct ResSegDecTable;
+void residual_encode_segments(const int16_t* sym, const uint8_t* ctx, int B, int64_t N, int L, int64_t n_seg,
+                              const ResSegEncTable* tabs, uint8_t* out, size_t cap, uint32_t* seg_off,
+                              uint32_t* seg_bytes, uint64_t* total, uint32_t* status, hipStream_t st);
+void residual_decode_segments(const uint8_t* data, size_t stride, const uint32_t* seg_off, const uint32_t* seg_bytes,
+                              const uint8_t* ctx, int B, int64_t N, int L, int64_t n_seg, const ResSegDecTable* tabs,
+                              int16_t* sym, uint32_t* status, hipStream_t st);
 // 8-bit Y'CbCr frame I/O (image_yuv.hip; DESIGN.md section 5 "YCbCr I/O").  The fields of mlic_yuv_desc.
 struct YuvDesc {
   int32_t sub_x, sub_y, matrix, full_range, site_x, reserved[3];

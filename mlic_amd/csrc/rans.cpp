@@ -216,7 +216,7 @@ bool RansDecoderState::decode(const I* indexes, int64_t n, const CdfTables& t, S
         v = (int32_t)get_bits(BYPASS_PRECISION);
         nb += v;
       }
-      if (nb > 8) throw std::runtime_error("rans: corrupt bypass length");
+      if (nb > max_bypass_) throw std::runtime_error("rans: corrupt bypass length");
       uint32_t raw = 0;
       for (int32_t j = 0; j < nb; ++j) raw |= get_bits(BYPASS_PRECISION) << (j * BYPASS_PRECISION);
       value = (int32_t)(raw >> 1);

@@ -92,11 +92,15 @@ class RansDecoderState {
     pos_ = m.pos;
     state_ = m.state;
   }
+  // the longest bypass length decode() accepts (compressai's coder: 8 nibbles for 32-bit values); a stream whose
+  // values are known to be narrower sets its own (the residual segments: 3), and a longer one is a corrupt stream
+  void set_max_bypass(int nb) { max_bypass_ = nb; }
 
  private:
   std::vector<uint32_t> words_;
   size_t pos_ = 0;
   uint64_t state_ = 0;
+  int max_bypass_ = 8;
   uint32_t get_word();
 };
 

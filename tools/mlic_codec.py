@@ -55,6 +55,10 @@
         brings every sample of the decode within T of the original (--lossless = 0: the decode is the original);
         the file is the residual file around the unchanged base file.  Goes with --level N; not with --max-bpp,
         --level auto, --roi, --tile, --scale, --coded-size, --layered or Y'CbCr frames.
+    ... --residual-segment L (encode, with --max-error / --lossless): the segmented residual file ("MLR2"): the
+        residual string in independent segments of L samples (256..65536), coded and decoded on the GPU.
+        --residual-coder host|device (encode with --residual-segment, decode): which coder runs; the bytes and the
+        picture are the same either way.  decode, strip and info recognise the file by its magic.
     ... --base-only (decode): the base picture of a residual file alone, without the second layer.
     python tools/mlic_codec.py strip IN.bit -o OUT.bit             the base file inside a residual file
     python tools/mlic_codec.py truncate IN.bit -k K -o OUT.bit     the first bytes of a layered file up to the end
@@ -447,6 +451,8 @@ def parse_args(argv=None):
     ap.add_argument("--max-error", type=int, default=None, metavar="T")
     ap.add_argument("--lossless", action="store_true")
     ap.add_argument("--base-only", action="store_true")
+    ap.add_argument("--residual-segment", type=int, default=None, metavar="L")
+    ap.add_argument("--residual-coder", choices=["host", "device"], default=None)
     args = ap.parse_args(argv)
     if args.mode == "strip":
         if args.dst is not None or args.output is None:
@@ -460,6 +466,15 @@ def parse_args(argv=None):
         if args.max_error not in (None, 0):
             ap.error("--lossless is --max-error 0")
         args.max_error = 0
+    if args.residual_segment is not None:
+        if args.max_error is None:
+            ap.error("--residual-segment goes with encode --max-error T / --lossless")
+        if not 256 <= args.residual_segment <= 65536:
+            ap.error("--residual-segment: 256 to 65536 expected")
+    if args.residual_coder is not None and args.mode == "encode" and args.residual_segment is None:
+        ap.error("--residual-coder goes with --residual-segment L (encode) or with decode")
+    if args.residual_coder is not None and args.mode not in ("encode", "decode"):
+        ap.error("--residual-coder goes with encode and decode")
     if args.max_error is not None:
         if args.mode != "encode":
             ap.error("--max-error / --lossless go with encode (a residual file is recognised by its magic)")
@@ -688,7 +703,7 @@ def main(argv=None):
         with open(args.src, "rb") as f:
             data = f.read()
         if not codec.is_residual_file(data):
-            raise SystemExit(f"{args.src}: not a residual file (no MLR1 magic): encode --max-error T writes one")
+            raise SystemExit(f"{args.src}: not a residual file (no MLR1 / MLR2 magic): encode --max-error T writes one")
         inner = codec.strip_residual(data)
         with open(args.output, "wb") as f:
             f.write(inner)
@@ -730,8 +745,9 @@ def main(argv=None):
                                  f"{args.model} is {'variable' if vbr else 'fixed'}-rate")
             print(f"{args.src}: {d['H']} x {d['W']}, residual: max error {d['max_error']}"
                   f"{' (lossless)' if d['max_error'] == 0 else ''}, level {d['level']}, z grid {d['shape'][0]} x "
-                  f"{d['shape'][1]}, base {d['base_bytes']} B, residual {d['residual_bytes']} B, header and tables "
-                  f"{d['header_bytes']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
+                  f"{d['shape'][1]}, base {d['base_bytes']} B, residual {d['residual_bytes']} B"
+                  + (f" in {d['segments']} segments of {d['residual_segment']}" if "segments" in d else "") +
+                  f", header and tables {d['header_bytes']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
             return
         if d.get("scaled"):
             print(f"{args.src}: {d['H']} x {d['W']}, scaled: coded at {d['coded'][0]} x {d['coded'][1]}, filter "
@@ -812,7 +828,10 @@ def main(argv=None):
                                               max_passes=args.max_passes, return_info=True, roi=roi,
                                               roi_levels=None if roi is None else tuple(args.roi_levels), **deep, **scaled,
                                               **({"layered": True} if args.layered else {}),
-                                              **({} if args.max_error is None else {"max_error": args.max_error}))
+                                              **({} if args.max_error is None else {"max_error": args.max_error}),
+                                              **({} if args.residual_segment is None else
+                                                 {"residual_segment": args.residual_segment,
+                                                  "residual_coder": args.residual_coder or "device"}))
         except ValueError as e:
             if not scaled:
                 raise
@@ -831,6 +850,8 @@ def main(argv=None):
         if args.max_error is not None:
             line += (f", max error {args.max_error}: base {info[0]['base_bytes']} B, residual "
                      f"{info[0]['residual_bytes']} B")
+            if args.residual_segment is not None:
+                line += f" in {info[0]['segments']} segments of {args.residual_segment}"
         if args.max_bpp is not None:
             line += (f", {info[0]['passes']} passes, level {info[0]['level']}, budget {args.max_bpp:g} bpp "
                      f"{'met' if info[0]['met'] else 'not met'}")
@@ -867,6 +888,8 @@ def main(argv=None):
             if not codec.is_residual_file(data):
                 raise SystemExit(f"{args.src}: --base-only needs a residual file (encode --max-error T)")
             kw["enhance"] = False
+        if args.residual_coder is not None:
+            kw["residual_coder"] = args.residual_coder
         try:
             img, info = codec.decode_images(net, [data], **kw)
         except ValueError as e:

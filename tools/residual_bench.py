@@ -11,6 +11,14 @@ zeroth-order entropy of the symbols without contexts, and their cross-entropy un
 symbols counted at the escape's cost plus their bypass nibbles).  Prints one JSON line; --md PATH also writes the
 tables as markdown.
 
+--segments: the segmented residual strings (csrc/residual_coder.hip).  (a) mlic_residual_encode_segments and
+mlic_residual_decode_segments on the batch's symbols (both contents, L in 1024, 4096, 16384): the time of the whole
+entry between two device events (table upload, the launches -- count, scan, write for the encoder -- and the status
+read-back), the bytes in and out, the waves launched, and the bytes of the segments against one serial string.
+(b) With --segments-model MODEL: wall time per image of encode_images and decode_images for "MLR1", "MLR2" with the
+host coder and "MLR2" with the device coder, on the same images in the same process (--e2e-batch images of the bench
+size), and the files' sizes.
+
 Algorithmic bytes, counted from the shapes (what has to move, once), N = B*H*W*3 samples:
     front with x: 2 N read, N (ctx) + 2 N (sym) written              front without x: N read, N written
     apply: N + 2 N read, N written; with ref: N more read
@@ -87,6 +95,110 @@ def _rate(model: str, H: int, W: int, rate: int, level):
             "base_psnr": [d["psnr"] for d in info], "base_bpp": [d["bpp"] for d in info], "rows": rows}
 
 
+def _segments_kernels(contents, B, H, W, tau, iters, warmup, lengths):
+    """(a): per content and segment length, the two entries between device events."""
+    rows = {}
+    N = 3 * H * W
+    for name, (base, x) in contents.items():
+        f = codec.residual_front(base, x, tau, "hwc")
+        hist = f["hist"].cpu().numpy()
+        tabs = [codec.residual_tables(hist[b]) for b in range(B)]
+        serial = None
+        for L in lengths:
+            n_seg = -(-N // L)
+            cap = min(max(codec._seg_cap_of_hist(hist[b], tabs[b], n_seg) for b in range(B)),
+                      codec.residual_segment_cap(H, W, L))
+            buf = torch.empty(B * cap, dtype=torch.uint8, device=base.device)
+            enc, dec, coded = [], [], None
+            for it in range(warmup + iters):
+                e0, e1, d0, d1 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
+                e0.record()
+                coded = codec.residual_encode_segments(f["sym"], f["ctx"], tabs, L, "device", cap=cap, out=buf)
+                e1.record()
+                e1.synchronize()
+                data, segb = [c[0] for c in coded], [c[1] for c in coded]
+                d0.record()
+                q = codec.residual_decode_segments(data, segb, f["ctx"], tabs, L, "device")
+                d1.record()
+                d1.synchronize()
+                if it >= warmup:
+                    enc.append(e0.elapsed_time(e1))
+                    dec.append(d0.elapsed_time(d1))
+            assert torch.equal(q, f["sym"])
+            print(f"segments: {name}, L {L} done", file=sys.stderr, flush=True)
+            nbytes = sum(len(c[0]) for c in coded)
+            if serial is None:  # one serial string per image, for the size comparison (image 0 only: it is slow)
+                from mlic_amd import entropy
+                serial = len(entropy.rans_encode(f["sym"][0].reshape(-1).cpu().numpy().astype(np.int32),
+                                                 f["ctx"][0].reshape(-1).cpu().numpy().astype(np.int32),
+                                                 *codec._coder_tables(tabs[0])))
+            rows[f"{name}, L {L}"] = {
+                "segments_per_image": n_seg, "waves": B * -(-n_seg // 64), "capacity_bytes_per_image": cap,
+                "encode_ms_median": statistics.median(enc), "encode_ms_min": min(enc),
+                "decode_ms_median": statistics.median(dec), "decode_ms_min": min(dec),
+                "encode_bytes_in": 2 * 3 * B * N, "decode_bytes_in": B * N + nbytes, "decode_bytes_out": 2 * B * N,
+                "segment_bytes": nbytes, "index_bytes": 4 * n_seg * B,
+                "image0_segmented_bytes": len(coded[0][0]) + 4 * n_seg, "image0_serial_bytes": serial,
+                "image0_overhead_bytes_per_segment": (len(coded[0][0]) + 4 * n_seg - serial) / n_seg}
+    return rows
+
+
+def _segments_e2e(model, B, H, W, rate, level, tau, lengths, reps):
+    """(b): wall time per image of encode_images / decode_images per file kind, and the files' sizes."""
+    import time
+    from mlic_amd import get_model, synthetic
+    dev = torch.device("cuda:0")
+    net = get_model(model)
+    net.load_state_dict(synthetic.synth_state_dict(model, rate=rate))
+    net = net.to(dev).eval()
+    net.update()
+    x = torch.cat([synthetic.synth_image(H, W, 70 + i) for i in range(B)])
+    imgs = (x * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().to(dev)
+    kinds = {"MLR1 (host, serial)": {}}
+    for L in lengths:
+        kinds[f"MLR2 host, L {L}"] = {"residual_segment": L, "residual_coder": "host"}
+        kinds[f"MLR2 device, L {L}"] = {"residual_segment": L, "residual_coder": "device"}
+    plain = codec.encode_images(net, imgs, level=level)
+    codec.decode_images(net, plain)
+    torch.cuda.synchronize()
+    rows = {}
+    for it in range(reps + 1):  # the first round warms up
+        for name, kw in kinds.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            files = codec.encode_images(net, imgs, level=level, max_error=tau, **kw)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            out, _ = codec.decode_images(net, files, residual_coder=kw.get("residual_coder", "device"))
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            assert int((out.to(torch.int16) - imgs.to(torch.int16)).abs().max()) <= tau
+            r = rows.setdefault(name, {"encode_ms_per_image": [], "decode_ms_per_image": [],
+                                       "file_bytes": [len(f) for f in files]})
+            print(f"segments e2e: round {it}, {name} done", file=sys.stderr, flush=True)
+            if it:
+                r["encode_ms_per_image"].append(1e3 * (t1 - t0) / B)
+                r["decode_ms_per_image"].append(1e3 * (t2 - t1) / B)
+    # the same calls without the second layer: what the residual layer adds
+    base = {"encode_ms_per_image": [], "decode_ms_per_image": [], "file_bytes": [len(f) for f in plain]}
+    for it in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        codec.encode_images(net, imgs, level=level)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        codec.decode_images(net, plain)
+        torch.cuda.synchronize()
+        base["encode_ms_per_image"].append(1e3 * (t1 - t0) / B)
+        base["decode_ms_per_image"].append(1e3 * (time.perf_counter() - t1) / B)
+    rows["plain file (no residual layer)"] = base
+    for r in rows.values():
+        r["encode_ms_per_image"] = statistics.median(r["encode_ms_per_image"])
+        r["decode_ms_per_image"] = statistics.median(r["decode_ms_per_image"])
+    return {"model": model, "synthetic_rate": rate, "level": level, "images": B, "H": H, "W": W, "tau": tau,
+            "reps": reps, "rows": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -100,6 +212,11 @@ def main():
     ap.add_argument("--synthetic-rate", type=int, default=1)
     ap.add_argument("--level", type=int, default=None)
     ap.add_argument("--md", default=None, help="also write the tables as markdown to this path")
+    ap.add_argument("--segments", action="store_true", help="also the segmented coder's entries (csrc/residual_coder.hip)")
+    ap.add_argument("--segment-lengths", type=int, nargs="+", default=(1024, 4096, 16384))
+    ap.add_argument("--segments-model", default=None, metavar="MODEL", help="with --segments: the end-to-end wall times")
+    ap.add_argument("--e2e-batch", type=int, default=8)
+    ap.add_argument("--e2e-reps", type=int, default=3)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("residual_bench needs a HIP device")
@@ -174,6 +291,12 @@ def main():
                              "fraction_of_8TBps": nbytes / med / 1e6 / 8000.0}
     if args.rate:
         rec["rate"] = _rate(args.rate, args.rate_size[0], args.rate_size[1], args.synthetic_rate, args.level)
+    if args.segments:
+        rec["segments"] = _segments_kernels({"noise": (noise_b, noise_x), "smooth": (smooth_b, smooth_x)}, B, H, W, tau,
+                                            max(3, args.iters // 4), 1, args.segment_lengths)
+        if args.segments_model:
+            rec["segments_e2e"] = _segments_e2e(args.segments_model, args.e2e_batch, H, W, args.synthetic_rate, args.level,
+                                                tau, args.segment_lengths, args.e2e_reps)
     print(json.dumps(rec))
     if args.md:
         lines = [f"| {B} x {H} x {W}, HWC, tau {tau} | ms (median of {args.iters}) | min | max | algorithmic MB | GB/s | "
@@ -190,6 +313,23 @@ def main():
                 lines.append(f"| tau {t} | {r['residual_bits_per_sample']:.4f} | {r['entropy0_bits_per_sample']:.4f} | "
                              f"{r['cross_entropy_tables_bits_per_sample']:.4f} | {r['header_and_tables_bytes']} | "
                              f"{r['max_abs_err']} |")
+        if args.segments:
+            lines += ["", f"| segments, {B} x {H} x {W}, tau {tau} | segments / image | waves | encode ms (median) | min | "
+                      f"decode ms (median) | min | segment MB | image 0: segmented B | serial B | overhead B / segment |",
+                      "|---|---|---|---|---|---|---|---|---|---|---|"]
+            for name, r in rec["segments"].items():
+                lines.append(f"| {name} | {r['segments_per_image']} | {r['waves']} | {r['encode_ms_median']:.3f} | "
+                             f"{r['encode_ms_min']:.3f} | {r['decode_ms_median']:.3f} | {r['decode_ms_min']:.3f} | "
+                             f"{r['segment_bytes'] / 1e6:.1f} | {r['image0_segmented_bytes']} | {r['image0_serial_bytes']} | "
+                             f"{r['image0_overhead_bytes_per_segment']:.2f} |")
+        if args.segments and args.segments_model:
+            q = rec["segments_e2e"]
+            lines += ["", f"| {q['model']} (synthetic rate {q['synthetic_rate']}), {q['images']} x {q['H']} x {q['W']}, tau "
+                      f"{q['tau']}, wall ms per image (median of {q['reps']}) | encode_images | decode_images | file bytes "
+                      f"(mean) |", "|---|---|---|---|"]
+            for name, r in q["rows"].items():
+                lines.append(f"| {name} | {r['encode_ms_per_image']:.2f} | {r['decode_ms_per_image']:.2f} | "
+                             f"{sum(r['file_bytes']) / len(r['file_bytes']):.0f} |")
         os.makedirs(os.path.dirname(os.path.abspath(args.md)), exist_ok=True)
         with open(args.md, "w") as f:
             f.write("\n".join(lines) + "\n")
