@@ -881,6 +881,77 @@ int mlic_container_write_residual_seg(uint32_t H, uint32_t W, int vbr, int tau, 
                                       uint8_t* out, size_t cap, size_t* len);
 int mlic_container_parse_residual_seg(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
                                       mlic_container_residual_seg_info* info);
+/* ---- Residual coding of 9..16-bit samples (DESIGN.md section 5 "Residual coding", "Deep samples") ----
+ *
+ * Integer definitions (csrc/residual16.h).  Samples are d-bit RGB, d in 9..16, LSB-aligned in uint16 words, in the
+ * canonical order; maxv = 2^d - 1 and a word above maxv reads as maxv.  base is the inner file decoded alone at depth
+ * d (mlic_image_egress_u16, msb = 0), tau in 0..127, step = 2 tau + 1:
+ *     r = x - base;  q = sign(r) floor((|r| + tau) / step);  rec = clamp(base + q step, 0, maxv)
+ * so |x - rec| <= tau, rec = x at tau = 0, |q| <= maxv.  Split by the shift s in 0..d-7: hi = q >> s (arithmetic),
+ * lo = q - (hi << s) in 0..2^s-1, q = (hi << s) + lo.  hi is the symbol of the 8-bit layer: its histogram bins, the
+ * tables (mlic_residual_tables) and both segment coders (mlic_residual_encode_segments / _decode_segments) are reused
+ * unchanged, which needs |hi| <= 255, i.e. (max|q| + 2^s - 1) >> s <= 255; s = d - 7 always fits.  Context = 8 c +
+ * class(a >> (d - 8)), a = max - min of channel c of base over the clamped 3 x 3 neighbourhood.  Digest: the 8-bit
+ * formula on the words of base.
+ * Low-bit plane: row r = c H + y, group g = x / 64, G = ceil(W / 64); 64-bit word (r G + g) s + j holds bit j of
+ * lo(r, x) at bit x mod 64, bits beyond column W zero; 3 H G s words an image, none at s = 0.
+ *
+ * mlic_image_residual_front_u16: base, and optionally x, through element strides {image, row, column, channel}.
+ * Always written: ctx u8 [B][3][H][W], ctx_count u32 [B][24], digest u64 [B].  With x also sym int16 [B][3][H][W] (hi,
+ * saturated to int16: a shift that does not fit shows in max_abs_q), lo_plane u64 [B][3 H G shift] (NULL exactly when
+ * shift is 0), hist u32 [B][24][128] of hi, max_err u32 [B] (the largest |x - rec|), max_abs_q u32 [B] and sum_abs_q
+ * u64 [B].  Without x, shift is ignored.  The call zeroes what it accumulates into, on the stream.  One launch.
+ * mlic_image_residual_stats_u16: max_abs_q and sum_abs_q alone, by a statistics launch of the same kernel: the shift
+ * is chosen from them (mlic_residual_shift), so they are needed before the front pass.
+ * mlic_image_residual_apply_u16: out = rec of (base, (sym << shift) + lo), written through out_strides; with ref also
+ * sq_err u64 [B] and max_err u32 [B].  status u32 [B] (required): nonzero for an image that holds a sym outside
+ * +-255; such a sample is written as base and the caller must refuse the image.
+ * Refused before any HIP call, each with its own message: what the 8-bit entries refuse; a depth outside 9..16; a
+ * shift outside 0..depth - 7; a lo_plane that does not go with the shift; pointers that are not aligned to their
+ * element (words 2 bytes, lo_plane and sum_abs_q 8); a null status. */
+int mlic_image_residual_front_u16(void* stream, const uint16_t* base, const int64_t* base_strides, const uint16_t* x,
+                                  const int64_t* x_strides, int B, int H, int W, int depth, int tau, int shift,
+                                  uint8_t* ctx, uint32_t* ctx_count, uint64_t* digest, int16_t* sym, uint64_t* lo_plane,
+                                  uint32_t* hist, uint32_t* max_err, uint32_t* max_abs_q, uint64_t* sum_abs_q);
+int mlic_image_residual_stats_u16(void* stream, const uint16_t* base, const int64_t* base_strides, const uint16_t* x,
+                                  const int64_t* x_strides, int B, int H, int W, int depth, int tau,
+                                  uint32_t* max_abs_q, uint64_t* sum_abs_q);
+int mlic_image_residual_apply_u16(void* stream, const uint16_t* base, const int64_t* base_strides, const int16_t* sym,
+                                  const uint64_t* lo_plane, int B, int H, int W, int depth, int tau, int shift,
+                                  uint16_t* out, const int64_t* out_strides, const uint16_t* ref,
+                                  const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err, uint32_t* status);
+/* The shift rule, host only: the smallest s in 0..depth-7 with (max_abs_q + 2^s - 1) >> s <= 255 and sum_abs_q <=
+ * 8 N 2^s (N = 3 H W), or depth - 7 if there is none.  The shift travels in the file; a decoder never evaluates this. */
+int mlic_residual_shift(int depth, uint64_t N, uint32_t max_abs_q, uint64_t sum_abs_q, int* shift);
+/* The deep residual file, big-endian (the plane's 64-bit words little-endian):
+ *     "MLR3" | the "MLR2" header and tables | u8 depth (9..16) | u8 shift (0..depth - 7)
+ *     u32 seg_len | u32 n_seg | u32 inner_len, inner file | u32 res_len | the index | the segments
+ *     u32 lo_len = 8 * 3 H ceil(W / 64) shift | the low-bit plane
+ * Always segmented.  parse refuses, each with its own message: everything mlic_container_parse_residual_seg refuses; a
+ * depth or shift out of range; a wrong lo_len; truncation inside the plane; trailing bytes.  Every other parser
+ * refuses an "MLR3" file. */
+typedef struct mlic_container_residual_deep_info {
+  uint32_t H, W;
+  int32_t tau;
+  int32_t vbr;
+  uint64_t digest;
+  uint8_t m[24];
+  uint64_t freq_off[24];
+  uint32_t seg_len, n_seg;
+  uint64_t inner_off, inner_len, res_off, res_len;
+  uint64_t index_off;
+  uint64_t data_off, data_len;
+  int32_t depth, shift;
+  uint64_t lo_off, lo_len; /* the low-bit plane */
+  mlic_container_info inner;
+} mlic_container_residual_deep_info;
+int mlic_container_write_residual_deep(uint32_t H, uint32_t W, int vbr, int tau, int depth, int shift, uint64_t digest,
+                                       const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                       const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                       const uint8_t* segs, size_t segs_len, const uint8_t* lo, size_t lo_len,
+                                       uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_residual_deep(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                       mlic_container_residual_deep_info* info);
 /* mlic_encode_image_u8 at reduced (or raised) resolution: the H x W image is resampled to coded_H x coded_W on
  * the way in, coded as mlic_encode_image_u8 codes an image of that size, and wrapped in the scaled file with H, W
  * as the display size.  The out == NULL / rgb_dev == NULL protocol is that of mlic_encode_image_u8. */

@@ -12,6 +12,9 @@ from .codec import (is_residual_file, parse_container_residual, residual_apply, 
                     residual_tables, strip_residual, write_container_residual)
 from .codec import (is_residual_seg_file, parse_container_residual_seg, residual_decode_segments,  # noqa: F401
                     residual_encode_segments, write_container_residual_seg)
+from .codec import (encode_residual16, is_residual_deep_file, parse_container_residual_deep,  # noqa: F401
+                    residual_apply16, residual_front16, residual_shift, residual_stats16,
+                    write_container_residual_deep)
 from .codec import blend_tiles, decode_tiled, encode_tiled, tile_grid  # noqa: F401
 from .codec import YuvFormat, decode_yuv, egress_yuv, encode_yuv, ingest_yuv, split_yuv  # noqa: F401
 from .codec import egress_u16, ingest_u16  # noqa: F401
@@ -25,4 +28,6 @@ __all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusV
            "is_scaled_file", "coded_size", "rate_maps", "rate_map", "sq_err_blocks", "heat_u8",
            "residual_front", "residual_apply", "residual_tables", "write_container_residual", "parse_container_residual",
            "is_residual_file", "strip_residual", "is_residual_seg_file", "parse_container_residual_seg",
-           "write_container_residual_seg", "residual_encode_segments", "residual_decode_segments"]
+           "write_container_residual_seg", "residual_encode_segments", "residual_decode_segments",
+           "encode_residual16", "is_residual_deep_file", "parse_container_residual_deep", "residual_apply16",
+           "residual_front16", "residual_shift", "residual_stats16", "write_container_residual_deep"]

@@ -60,6 +60,15 @@ class ContainerResidualSegInfo(C.Structure):
                 ("index_off", C.c_uint64), ("data_off", C.c_uint64), ("data_len", C.c_uint64), ("inner", ContainerInfo)]
 
 
+class ContainerResidualDeepInfo(C.Structure):
+    """mlic_container_residual_deep_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("tau", C.c_int32), ("vbr", C.c_int32), ("digest", C.c_uint64),
+                ("m", C.c_uint8 * 24), ("freq_off", C.c_uint64 * 24), ("seg_len", C.c_uint32), ("n_seg", C.c_uint32),
+                ("inner_off", C.c_uint64), ("inner_len", C.c_uint64), ("res_off", C.c_uint64), ("res_len", C.c_uint64),
+                ("index_off", C.c_uint64), ("data_off", C.c_uint64), ("data_len", C.c_uint64), ("depth", C.c_int32),
+                ("shift", C.c_int32), ("lo_off", C.c_uint64), ("lo_len", C.c_uint64), ("inner", ContainerInfo)]
+
+
 class ContainerLayeredInfo(C.Structure):
     """mlic_container_layered_info (include/mlic_hip.h)."""
     _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("hz", C.c_uint32), ("wz", C.c_uint32), ("level", C.c_int32),
@@ -210,6 +219,13 @@ def _sig(lib):
         "mlic_container_write_residual_seg": [C.c_uint32, C.c_uint32, i, i, C.c_uint64, p, p, C.c_uint32, C.c_uint32, p,
                                               p, sz, p, sz, p, sz, P(sz)],
         "mlic_container_parse_residual_seg": [p, sz, i, C.c_uint64, P(ContainerResidualSegInfo)],
+        "mlic_image_residual_front_u16": [p, p, P(i64), p, P(i64), i, i, i, i, i, i, p, p, p, p, p, p, p, p, p],
+        "mlic_image_residual_stats_u16": [p, p, P(i64), p, P(i64), i, i, i, i, i, p, p],
+        "mlic_image_residual_apply_u16": [p, p, P(i64), p, p, i, i, i, i, i, i, p, P(i64), p, P(i64), p, p, p],
+        "mlic_residual_shift": [i, C.c_uint64, C.c_uint32, C.c_uint64, P(i)],
+        "mlic_container_write_residual_deep": [C.c_uint32, C.c_uint32, i, i, i, i, C.c_uint64, p, p, C.c_uint32,
+                                               C.c_uint32, p, p, sz, p, sz, p, sz, p, sz, P(sz)],
+        "mlic_container_parse_residual_deep": [p, sz, i, C.c_uint64, P(ContainerResidualDeepInfo)],
         "mlic_decode_image_u8_sized": [p, p, p, sz, i, C.c_uint64, p, i, i, i, p, P(i64), sz, P(i), P(i), P(i), P(i),
                                        P(i)],
         "mlic_image_ingest_yuv8": [p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, p, i, i],

@@ -439,9 +439,10 @@ def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pix
     level word) gives {"residual": True, H, W, "max_error" (tau), vbr, level, shape, Hp, Wp, y_len, z_len, "digest",
     "base_bytes" (the inner file), "residual_bytes" (the residual string), "header_bytes" (the rest: header, tables
     and the two length words), bytes, bpp}; a segmented one ("MLR2") also "residual_segment" and "segments", and its
-    "residual_bytes" are the index and the segments."""
+    "residual_bytes" are the index and the segments; a deep one ("MLR3", is_residual_deep_file) besides those
+    "depth", "shift" and "low_bytes" (the low-bit plane)."""
     data = bytes(data)
-    if is_residual_file(data):
+    if is_residual_file(data) or is_residual_deep_file(data):
         return _peek_residual(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
     if is_layered_file(data):
         return _peek_layered(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
@@ -1082,14 +1083,17 @@ def _file_tables(data: bytes, s: _lib.ContainerResidualInfo) -> Dict:
 
 
 def strip_residual(data: bytes, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> bytes:
-    """The inner file of a residual file: byte for byte what encode_images writes without max_error=."""
+    """The inner file of a residual file ("MLR1", "MLR2" or "MLR3"): byte for byte what encode_images writes without
+    max_error= (for "MLR3": what encode_images(depth=) writes)."""
     data = bytes(data)
     s = _parse_residual_any(data, n_levels, max_pixels)
     return data[s.inner_off:s.inner_off + s.inner_len]
 
 
 def _parse_residual_any(data: bytes, n_levels, max_pixels):
-    """The parse of a residual file of either kind (told apart by the magic)."""
+    """The parse of a residual file of any kind (told apart by the magic)."""
+    if is_residual_deep_file(data):
+        return parse_container_residual_deep(data, n_levels, max_pixels)
     if is_residual_seg_file(data):
         return parse_container_residual_seg(data, n_levels, max_pixels)
     return parse_container_residual(data, n_levels, max_pixels)
@@ -1103,8 +1107,11 @@ def _peek_residual(data: bytes, n_levels, max_pixels) -> Dict:
            "y_len": c.y_len, "z_len": c.z_len, "digest": int(s.digest), "base_bytes": int(s.inner_len),
            "residual_bytes": int(s.res_len), "header_bytes": len(data) - int(s.inner_len) - int(s.res_len),
            "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
-    if is_residual_seg_file(data):
+    if is_residual_seg_file(data) or is_residual_deep_file(data):
         out.update(residual_segment=int(s.seg_len), segments=int(s.n_seg))
+    if is_residual_deep_file(data):
+        out.update(depth=int(s.depth), shift=int(s.shift), low_bytes=int(s.lo_len))
+        out["header_bytes"] -= int(s.lo_len)
     return out
 
 
@@ -1479,6 +1486,497 @@ def _decode_residual(net, files, ref, max_pixels, enhance, coder="device"):
                 extra[b].update(sq_err=int(sq[j]), psnr=psnr_from_sq_err(int(sq[j]), 3 * h * w), max_abs_err=int(me[j]))
     for d, e in zip(info, extra):
         d.update(e)
+    return img, info
+
+
+# ---- residual coding of 9..16-bit samples (csrc/residual16.h, csrc/residual16.hip; DESIGN.md §5 "Deep samples")
+RESIDUAL_DEEP_MAGIC = b"MLR3"
+RES16_MIN_DEPTH, RES16_MAX_HI = 9, 255
+
+
+def is_residual_deep_file(data: bytes) -> bool:
+    return bytes(data[:4]) == RESIDUAL_DEEP_MAGIC
+
+
+def _check_shift(shift, depth: int, what: str) -> int:
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 0 <= shift <= depth - 7:
+        raise ValueError(f"{what}: shift must be an integer in [0, depth - 7 = {depth - 7}], got {shift!r}")
+    return int(shift)
+
+
+def residual_shift_fits(max_abs_q: int, shift: int) -> bool:
+    """Whether `shift` keeps every |hi| within 255 for an image whose largest |q| is max_abs_q."""
+    return (int(max_abs_q) + (1 << shift) - 1) >> shift <= RES16_MAX_HI
+
+
+def residual_min_shift(depth: int, max_abs_q: int) -> int:
+    """The smallest shift that fits (depth - 7 always does)."""
+    return next(s for s in range(depth - 6) if residual_shift_fits(max_abs_q, s))
+
+
+def residual_shift(depth: int, n: int, max_abs_q: int, sum_abs_q: int) -> int:
+    """The shift rule (mlic_residual_shift; host integers): the smallest s in 0..depth-7 with (max_abs_q + 2^s - 1)
+    >> s <= 255 and sum_abs_q <= 8 n 2^s, n = 3 H W the image's samples; depth - 7 if there is none."""
+    depth = _check_depth(depth, "residual_shift", RES16_MIN_DEPTH)
+    s = C.c_int()
+    _lib.call("mlic_residual_shift", depth, int(n), int(max_abs_q), int(sum_abs_q), C.byref(s))
+    return s.value
+
+
+def residual_plane_words(H: int, W: int, shift: int) -> int:
+    """64-bit words of one image's low-bit plane: 3 H ceil(W / 64) shift."""
+    return 3 * H * -(-W // 64) * shift
+
+
+def _residual16_images(base, x, layout, x_layout, what: str):
+    base, layout = _u16_batch(base, layout, f"{what} base")
+    if x is not None:
+        x, x_layout = _u16_batch(x, layout if x_layout is None else x_layout, f"{what} x")
+        if x.size(0) != base.size(0) or _hw(x, x_layout) != _hw(base, layout):
+            raise ValueError(f"{what}: x {tuple(x.shape)} ({x_layout}) does not match base {tuple(base.shape)} ({layout})")
+        if x.device != base.device:
+            raise ValueError(f"{what}: base and x are on different devices")
+    return base, layout, x, x_layout
+
+
+def _samples_np(t: torch.Tensor, layout: str, depth: int) -> np.ndarray:
+    """uint16 words (any device) -> int64 samples [B,3,H,W]; a word above maxv reads as maxv."""
+    return samples_of_words(_nchw(t.cpu(), layout), depth).numpy().astype(np.int64)
+
+
+def _pack_plane_np(lo: np.ndarray, shift: int) -> np.ndarray:
+    """lo int64 [B,3,H,W] in 0..2^shift-1 -> the low-bit planes, uint64 [B, 3 H G shift]: word ((c H + y) G + g) shift
+    + j holds bit j of lo(c, y, x) at bit x mod 64, zero beyond column W."""
+    B, _, H, W = lo.shape
+    G = -(-W // 64)
+    p = np.zeros((B, 3, H, 64 * G), np.uint64)
+    p[..., :W] = lo.astype(np.uint64)
+    p = p.reshape(B, 3, H, G, 64)
+    bit = np.uint64(1) << np.arange(64, dtype=np.uint64)
+    out = np.zeros((B, 3, H, G, shift), np.uint64)
+    for j in range(shift):
+        out[..., j] = (((p >> np.uint64(j)) & np.uint64(1)) * bit).sum(-1, dtype=np.uint64)
+    return out.reshape(B, -1)
+
+
+def _unpack_plane_np(plane: np.ndarray, H: int, W: int, shift: int) -> np.ndarray:
+    """The inverse of _pack_plane_np: uint64 [B, 3 H G shift] -> lo int64 [B,3,H,W]."""
+    B = plane.shape[0]
+    G = -(-W // 64)
+    if shift == 0:
+        return np.zeros((B, 3, H, W), np.int64)
+    w = plane.reshape(B, 3, H, G, shift, 1) >> np.arange(64, dtype=np.uint64).reshape(1, 1, 1, 1, 1, 64)
+    bits = (w & np.uint64(1)).astype(np.int64)  # [B,3,H,G,shift,64]
+    lo = (bits << np.arange(shift, dtype=np.int64).reshape(1, 1, 1, 1, shift, 1)).sum(4)
+    return lo.reshape(B, 3, H, 64 * G)[..., :W]
+
+
+def _residual_front16_cpu(base, x, depth: int, tau: int, shift: int, layout: str, x_layout, stats: bool = False) -> Dict:
+    """residual_front16 / residual_stats16 in NumPy integers: the definitions of csrc/residual16.h written out."""
+    b = _samples_np(base, layout, depth)
+    B, _, H, W = b.shape
+    out = {}
+    if not stats:
+        p = np.pad(b, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge")
+        win = [p[:, :, dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)]
+        a = (np.maximum.reduce(win) - np.minimum.reduce(win)) >> (depth - 8)
+        ctx = (_CLASS_OF[a] + 8 * np.arange(3, dtype=np.uint8).reshape(1, 3, 1, 1)).astype(np.uint8)
+        count = np.stack([np.bincount(ctx[i].reshape(-1), minlength=RES_CTX) for i in range(B)])
+        with np.errstate(over="ignore"):
+            w = np.arange(1, 3 * H * W + 1, dtype=np.uint64) * np.uint64(_DIGEST_K)
+            digest = ((b.reshape(B, -1) + 1).astype(np.uint64) * w).sum(1, dtype=np.uint64)
+        out = {"ctx": torch.from_numpy(ctx), "ctx_count": torch.from_numpy(count.astype(np.int64)),
+               "digest": torch.from_numpy(digest.view(np.int64).copy())}
+    if x is None:
+        return out
+    xv = _samples_np(x, x_layout, depth)
+    step, maxv = 2 * tau + 1, (1 << depth) - 1
+    r = xv - b
+    q = np.sign(r) * ((np.abs(r) + tau) // step)
+    aq = np.abs(q).reshape(B, -1)
+    out.update(max_abs_q=torch.from_numpy(aq.max(1)), sum_abs_q=torch.from_numpy(aq.sum(1)))
+    if stats:
+        return out
+    rec = np.clip(b + q * step, 0, maxv)
+    hi = q >> shift
+    lo = q - (hi << shift)
+    bins = np.where(np.abs(hi) <= RES_MAX_M, hi + RES_MAX_M, RES_BINS - 1)
+    key = ctx.astype(np.int64) * RES_BINS + bins
+    hist = np.stack([np.bincount(key[i].reshape(-1), minlength=RES_CTX * RES_BINS) for i in range(B)])
+    out.update(sym=torch.from_numpy(np.clip(hi, -32768, 32767).astype(np.int16)),
+               plane=torch.from_numpy(_pack_plane_np(lo, shift).view(np.int64).copy()),
+               hist=torch.from_numpy(hist.reshape(B, RES_CTX, RES_BINS).astype(np.int64)),
+               max_err=torch.from_numpy(np.abs(xv - rec).reshape(B, -1).max(1).astype(np.int64)))
+    return out
+
+
+def _u16_in_place(t: torch.Tensor, layout: str) -> torch.Tensor:
+    return _dense_u16(t, (2, 3) if layout == "hwc" else (3, 1))
+
+
+def residual_front16(base, x=None, depth: int = 16, tau: int = 0, shift: int = 0, layout: Optional[str] = None,
+                     x_layout: Optional[str] = None) -> Dict:
+    """residual_front for samples of `depth` bits (9..16) in uint16 words, LSB-aligned (csrc/residual16.hip, one
+    launch; DESIGN.md §5 "Residual coding", "Deep samples").  base: uint16 [B,H,W,3] / [B,3,H,W] (or one image), any
+    strides; x: the original, the same size, in x_layout.  Returns {"ctx" uint8 [B,3,H,W], "ctx_count" int64 [B,24],
+    "digest" int64 [B]} and, with x, {"sym" int16 [B,3,H,W] (hi = q >> shift, saturated to int16), "plane" int64
+    [B, 3 H ceil(W/64) shift] (the low-bit plane's 64-bit words), "hist" int64 [B,24,128] (of hi), "max_err" int64
+    [B], "max_abs_q" int64 [B], "sum_abs_q" int64 [B]}.  sym fits the 8-bit layer's tables and coders when
+    residual_shift_fits(max_abs_q, shift).  CPU tensors take the NumPy restatement (the same bits)."""
+    what = "residual_front16"
+    depth, tau = _check_depth(depth, what, RES16_MIN_DEPTH), _check_tau(tau, what)
+    shift = _check_shift(shift, depth, what)
+    base, layout, x, x_layout = _residual16_images(base, x, layout, x_layout, what)
+    if not base.is_cuda:
+        return _residual_front16_cpu(base, x, depth, tau, shift, layout, x_layout)
+    B = base.size(0)
+    H, W = _hw(base, layout)
+    base = _u16_in_place(base, layout)
+    dev = base.device
+    with torch.cuda.device(dev):
+        ctx = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev)
+        count = torch.empty(B, RES_CTX, dtype=torch.int32, device=dev)
+        digest = torch.empty(B, dtype=torch.int64, device=dev)
+        sym = plane = hist = merr = mq = sq = None
+        if x is not None:
+            x = _u16_in_place(x, x_layout)
+            sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
+            plane = torch.empty(B, residual_plane_words(H, W, shift), dtype=torch.int64, device=dev)
+            hist = torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev)
+            merr = torch.empty(B, dtype=torch.int32, device=dev)
+            mq = torch.empty(B, dtype=torch.int32, device=dev)
+            sq = torch.empty(B, dtype=torch.int64, device=dev)
+        if _lib.poison():  # what the kernel does not write shows
+            ctx.fill_(0xEE)
+            for t in (count, digest, hist, merr, mq, sq, plane):
+                if t is not None:
+                    t.fill_(-1)
+            if sym is not None:
+                sym.fill_(-0x1112)
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.call("mlic_image_residual_front_u16", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)), ptr(x),
+                  None if x is None else (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, depth, tau, shift, ptr(ctx),
+                  ptr(count), ptr(digest), ptr(sym), ptr(plane), ptr(hist), ptr(merr), ptr(mq), ptr(sq))
+        out = {"ctx": ctx, "ctx_count": count.to(torch.int64), "digest": digest}
+        if x is not None:
+            out.update(sym=sym, plane=plane, hist=hist.to(torch.int64), max_err=merr.to(torch.int64),
+                       max_abs_q=mq.to(torch.int64), sum_abs_q=sq)
+    return out
+
+
+def residual_stats16(base, x, depth: int, tau: int = 0, layout: Optional[str] = None,
+                     x_layout: Optional[str] = None) -> Dict:
+    """{"max_abs_q" int64 [B], "sum_abs_q" int64 [B]} of the quantised residual of x against base: what the shift is
+    chosen from (residual_shift), by a statistics launch of the front kernel (mlic_image_residual_stats_u16)."""
+    what = "residual_stats16"
+    depth, tau = _check_depth(depth, what, RES16_MIN_DEPTH), _check_tau(tau, what)
+    if x is None:
+        raise ValueError(f"{what}: x is needed")
+    base, layout, x, x_layout = _residual16_images(base, x, layout, x_layout, what)
+    if not base.is_cuda:
+        return _residual_front16_cpu(base, x, depth, tau, 0, layout, x_layout, stats=True)
+    B = base.size(0)
+    H, W = _hw(base, layout)
+    base, x = _u16_in_place(base, layout), _u16_in_place(x, x_layout)
+    dev = base.device
+    with torch.cuda.device(dev):
+        mq = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        sq = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        _lib.call("mlic_image_residual_stats_u16", _stream(), C.c_void_p(base.data_ptr()),
+                  (C.c_int64 * 4)(*_strides(base, layout)), C.c_void_p(x.data_ptr()),
+                  (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, depth, tau, C.c_void_p(mq.data_ptr()),
+                  C.c_void_p(sq.data_ptr()))
+    return {"max_abs_q": mq.to(torch.int64), "sum_abs_q": sq}
+
+
+def _residual_apply16_cpu(base, sym, plane, depth, tau, shift, layout, ref, out):
+    b = _samples_np(base, layout, depth)
+    B, _, H, W = b.shape
+    hi = np.asarray(sym.cpu()).astype(np.int64).reshape(b.shape)
+    bad = np.flatnonzero((np.abs(hi) > RES16_MAX_HI).reshape(B, -1).any(1))
+    if bad.size:
+        raise ValueError(f"residual_apply16: image {int(bad[0])} holds a symbol outside [-255, 255]")
+    lo = _unpack_plane_np(np.ascontiguousarray(plane.cpu().numpy()).view(np.uint64).reshape(B, -1), H, W, shift)
+    rec = np.clip(b + ((hi << shift) + lo) * (2 * tau + 1), 0, (1 << depth) - 1)
+    img = torch.from_numpy(rec.astype(np.uint16))
+    img = img.permute(0, 2, 3, 1).contiguous() if layout == "hwc" else img
+    if out is not None:
+        out.copy_(img)
+        img = out
+    if ref is None:
+        return img
+    d = rec - _samples_np(ref, layout, depth)
+    return img, torch.from_numpy((d * d).reshape(B, -1).sum(1)), torch.from_numpy(np.abs(d).reshape(B, -1).max(1))
+
+
+def residual_apply16(base, sym, plane, depth: int, tau: int, shift: int, layout: Optional[str] = None, ref=None,
+                     out: Optional[torch.Tensor] = None):
+    """The deep decoder's last pass (csrc/residual16.hip, one launch): out = clamp(base + ((sym << shift) + lo)
+    (2 tau + 1), 0, 2^depth - 1) as uint16 words in base's layout, lo read from `plane` (int64 [B, 3 H ceil(W/64)
+    shift], residual_front16's).  sym: int16 [B,3,H,W], dense, on base's device; a sym outside [-255, 255] is
+    refused (ValueError naming the image).  out: an optional uint16 tensor of base's shape with any strides.  ref
+    (uint16, base's shape): returns (out, sq_err int64 [B], max_abs_err int64 [B]), exact.  CPU tensors take the
+    NumPy restatement."""
+    what = "residual_apply16"
+    depth, tau = _check_depth(depth, what, RES16_MIN_DEPTH), _check_tau(tau, what)
+    shift = _check_shift(shift, depth, what)
+    base, layout = _u16_batch(base, layout, f"{what} base")
+    B = base.size(0)
+    H, W = _hw(base, layout)
+    if not torch.is_tensor(sym) or sym.dtype != torch.int16 or tuple(sym.shape) != (B, 3, H, W):
+        raise ValueError(f"{what}: sym must be an int16 tensor {(B, 3, H, W)}")
+    words = residual_plane_words(H, W, shift)
+    if not torch.is_tensor(plane) or plane.dtype != torch.int64 or tuple(plane.shape) != (B, words):
+        raise ValueError(f"{what}: plane must be an int64 tensor {(B, words)}")
+    if sym.device != base.device or plane.device != base.device:
+        raise ValueError(f"{what}: base, sym and plane must be on one device")
+    if out is not None and (out.dtype != torch.uint16 or tuple(out.shape) != tuple(base.shape) or out.device != base.device):
+        raise ValueError(f"{what}: out must be uint16 {tuple(base.shape)} on {base.device}")
+    if ref is not None:
+        ref, _ = _u16_batch(ref, layout, f"{what} ref")
+        if tuple(ref.shape) != tuple(base.shape):
+            raise ValueError(f"{what}: ref must have shape {tuple(base.shape)}, got {tuple(ref.shape)}")
+        ref = ref.to(base.device)
+    if not base.is_cuda:
+        return _residual_apply16_cpu(base, sym, plane, depth, tau, shift, layout, ref, out)
+    base = _u16_in_place(base, layout)
+    sym, plane = sym.contiguous(), plane.contiguous()
+    dev = base.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(tuple(base.shape), dtype=torch.int16, device=dev)
+            if _lib.poison():
+                out.fill_(-1)
+            out = out.view(torch.uint16)
+        elif 0 in _strides(out, layout)[2:]:
+            raise ValueError(f"{what}: out has a zero column or channel stride")
+        sq = merr = None
+        if ref is not None:
+            ref = _u16_in_place(ref, layout)
+            sq = torch.full((B,), -1, dtype=torch.int64, device=dev)
+            merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        status = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.call("mlic_image_residual_apply_u16", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
+                  ptr(sym), ptr(plane), B, H, W, depth, tau, shift, ptr(out), (C.c_int64 * 4)(*_strides(out, layout)),
+                  ptr(ref), None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)), ptr(sq), ptr(merr),
+                  ptr(status))
+        bad = torch.nonzero(status).flatten().cpu().tolist()
+        if ref is not None:
+            ref.record_stream(torch.cuda.current_stream())
+    if bad:
+        raise ValueError(f"{what}: image {bad[0]} holds a symbol outside [-255, 255]")
+    return out if ref is None else (out, sq, merr.to(torch.int64))
+
+
+def write_container_residual_deep(H: int, W: int, inner: bytes, segs: bytes, seg_bytes, segment: int, tau: int,
+                                  depth: int, shift: int, low: bytes, digest: int, m, freq, vbr: bool = False) -> bytes:
+    """The deep residual file (mlic_container_write_residual_deep): "MLR3", the header and the tables of the "MLR2"
+    file, depth and shift, seg_len, n_seg, `inner`, the index and `segs`, and behind lo_len the low-bit plane `low`
+    (8 * 3 H ceil(W / 64) shift bytes, little-endian 64-bit words)."""
+    inner, segs, low = bytes(inner), bytes(segs), bytes(low)
+    m = np.ascontiguousarray(m, dtype=np.uint8)
+    freq = np.ascontiguousarray(freq, dtype=np.uint16)
+    sb = np.ascontiguousarray(np.asarray(seg_bytes, np.int64).reshape(-1))
+    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
+        raise ValueError(f"write_container_residual_deep: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
+    if sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF)):
+        raise ValueError("write_container_residual_deep: segment lengths must fit 32 bits")
+    sb = sb.astype(np.uint32)
+    n = C.c_size_t()
+    args = (H, W, int(bool(vbr)), int(tau), int(depth), int(shift), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data,
+            freq.ctypes.data, int(segment) & 0xFFFFFFFF, sb.size, sb.ctypes.data, inner, len(inner), segs, len(segs),
+            low, len(low))
+    _lib.call("mlic_container_write_residual_deep", *args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_residual_deep", *args, buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_residual_deep(data: bytes, n_levels: Optional[int] = None,
+                                  max_pixels: int = MAX_PIXELS) -> _lib.ContainerResidualDeepInfo:
+    """The validating parser of a deep residual file (mlic_container_parse_residual_deep): raises _lib.MlicError on any
+    malformed input.  The fields of the "MLR2" parse, and depth, shift, lo_off / lo_len (the low-bit plane)."""
+    data = bytes(data)
+    info = _lib.ContainerResidualDeepInfo()
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call("mlic_container_parse_residual_deep", data, len(data), nl, int(max_pixels), C.byref(info))
+    return info
+
+
+@torch.no_grad()
+def encode_residual16(net, imgs_u16, depth: int, max_error: int = 0, level=None, layout: Optional[str] = None,
+                      residual_segment: int = DEFAULT_RESIDUAL_SEGMENT, residual_coder: str = "device",
+                      shift: Optional[int] = None, return_info: bool = False):
+    """Lossless (max_error=0) and near-lossless coding of uint16 images of `depth` bits (9..16, LSB-aligned; DESIGN.md
+    §5 "Residual coding", "Deep samples") -> one "MLR3" file per image.  The images are ingested and compressed
+    exactly as encode_images(depth=) does (the inner file is that file, byte for byte); the base image is the decode
+    of that file alone through egress_u16.  residual_stats16 gives max|q| and sum|q| per image, the shift rule
+    (residual_shift) or `shift` the split, residual_front16 the high parts with their contexts and histograms and the
+    low-bit plane; the bound is checked on the device, the high parts go through residual_tables and
+    residual_encode_segments (residual_coder as in encode_images), the low bits are stored raw.  An explicit shift=
+    that does not fit an image is refused, naming the smallest that fits.  return_info=True: (files, info), info[b] =
+    encode_images' fields and "max_error", "depth", "shift", "base_bytes", "residual_bytes", "low_bytes",
+    "residual_segment", "segments"."""
+    what = "encode_residual16"
+    depth, tau = _check_depth(depth, what, RES16_MIN_DEPTH), _check_tau(max_error, what)
+    L, coder = _check_segment(residual_segment, what), _check_coder(residual_coder, what)
+    if shift is not None:
+        shift = _check_shift(shift, depth, what)
+    img, layout = _u16_batch(imgs_u16, layout, what)
+    inner, info = encode_images(net, img, level=level, layout=layout, depth=depth, return_info=True)
+    vbr = hasattr(net, "levels")
+    cs = [parse_container(f, vbr, net.levels if vbr else None) for f in inner]
+    pairs = [_strings(f, c) for f, c in zip(inner, cs)]
+    B = img.size(0)
+    H, W = _hw(img, layout)
+    kw = {"s": [c.level for c in cs]} if vbr else {}
+    x_hat = _base_x_hat(net, [[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), kw, B)
+    base = egress_u16(x_hat.float(), H, W, depth, "hwc")
+    img = img.to(base.device)
+    stats = residual_stats16(base, img, depth, tau, "hwc", layout)
+    mq, sq = stats["max_abs_q"].cpu().tolist(), stats["sum_abs_q"].cpu().tolist()
+    if shift is None:
+        shifts = [residual_shift(depth, 3 * H * W, mq[b], sq[b]) for b in range(B)]
+    else:
+        for b in range(B):
+            if not residual_shift_fits(mq[b], shift):
+                raise ValueError(f"{what}: shift={shift} does not fit image {b} (its largest |q| is {mq[b]}): the "
+                                 f"smallest shift that fits is {residual_min_shift(depth, mq[b])}")
+        shifts = [shift] * B
+    n_seg = -(-3 * H * W // L)
+    files = [None] * B
+    a = 0
+    while a < B:  # runs of images with one shift: one front launch each
+        e = a + 1
+        while e < B and shifts[e] == shifts[a]:
+            e += 1
+        s = shifts[a]
+        front = residual_front16(base[a:e], img[a:e], depth, tau, s, "hwc", layout)
+        worst = int(front["max_err"].max())  # computed on the device, beside the symbols
+        if worst > tau:
+            raise RuntimeError(f"{what}: the residual layer leaves an error of {worst} > max_error {tau}")
+        hist = front["hist"].cpu().numpy()
+        digest = front["digest"].cpu().tolist()
+        plane = front["plane"].cpu().numpy()
+        tabs = [residual_tables(hist[j]) for j in range(e - a)]
+        cap = min(max(_seg_cap_of_hist(hist[j], tabs[j], n_seg) for j in range(e - a)), residual_segment_cap(H, W, L))
+        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, L, coder, cap=cap)
+        for j, (segs, seg_bytes) in enumerate(coded):
+            b, t = a + j, tabs[j]
+            low = plane[j].astype("<i8").tobytes()
+            files[b] = write_container_residual_deep(H, W, inner[b], segs, seg_bytes, L, tau, depth, s, low, digest[j],
+                                                     t["m"], t["freq"], vbr=vbr)
+            info[b].update(bytes=len(files[b]), bpp=8.0 * len(files[b]) / (H * W), max_error=tau, depth=depth, shift=s,
+                           base_bytes=len(inner[b]), residual_bytes=len(segs) + 4 * n_seg, low_bytes=len(low),
+                           residual_segment=L, segments=n_seg)
+        a = e
+    return (files, info) if return_info else files
+
+
+def _decode_residual16(net, files, ref, max_pixels, enhance, coder, depth):
+    """decode_images for "MLR3" files: the inner files decoded at the file's depth, then the deep residual layer."""
+    vbr = hasattr(net, "levels")
+    n_levels = net.levels if vbr else None
+    ss = [parse_container_residual_deep(f, n_levels, max_pixels) for f in files]
+    B = len(files)
+    for b, s in enumerate(ss):
+        if bool(s.vbr) != vbr:
+            raise ValueError(f"decode_images: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
+                             f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+        if depth is not None and depth != s.depth:
+            raise ValueError(f"decode_images: depth={depth}, but file {b} (MLR3) holds samples of depth {s.depth}")
+    if ref is not None:
+        ref, _ = _u16_batch(ref, "hwc", "decode_images ref")
+    depths = sorted({int(s.depth) for s in ss})
+    if len(depths) > 1:  # one depth at a time, pasted into one canvas
+        parts = {}
+        for d in depths:
+            idx = [b for b in range(B) if ss[b].depth == d]
+            r = None if ref is None else torch.stack([ref.cpu().view(torch.int16)[b] for b in idx]).view(torch.uint16)
+            parts[d] = (idx, _decode_residual16(net, [files[b] for b in idx], r, max_pixels, enhance, coder, None))
+        dev = next(iter(parts.values()))[1][0].device
+        Hm, Wm = max(s.H for s in ss), max(s.W for s in ss)
+        img = torch.zeros(B, Hm, Wm, 3, dtype=torch.int16, device=dev)
+        info = [None] * B
+        for idx, (im, inf) in parts.values():
+            for j, b in enumerate(idx):
+                h, w = min(im.size(1), Hm), min(im.size(2), Wm)
+                img[b, :h, :w].copy_(im[j, :h, :w].view(torch.int16))
+                info[b] = inf[j]
+        return img.view(torch.uint16), info
+    d = depths[0]
+    inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
+    extra = [{"max_error": int(s.tau), "depth": d, "shift": int(s.shift), "residual_bytes": int(s.res_len),
+              "base_bytes": int(s.inner_len), "low_bytes": int(s.lo_len), "residual_segment": int(s.seg_len),
+              "segments": int(s.n_seg), "bytes": len(f), "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
+    if not enhance:
+        img, info = decode_images(net, inner, ref=ref, max_pixels=max_pixels, depth=d)
+        for di, e in zip(info, extra):
+            di.update(e, enhanced=False)
+        return img, info
+    base, info = decode_images(net, inner, max_pixels=max_pixels, depth=d)
+    H, W = base.size(1), base.size(2)
+    if ref is not None:
+        if tuple(ref.shape) != (B, H, W, 3):
+            raise ValueError(f"decode_images: ref must be uint16 {(B, H, W, 3)}, got {tuple(ref.shape)}")
+        ref = ref.to(base.device)
+    same = all((s.H, s.W) == (H, W) for s in ss)
+    one = same and len({(s.tau, s.shift, s.seg_len) for s in ss}) == 1
+    groups = [list(range(B))] if one else [[b] for b in range(B)]
+    img = (torch.empty if same else torch.zeros)(B, H, W, 3, dtype=torch.int16, device=base.device).view(torch.uint16)
+    for g in groups:
+        s0 = ss[g[0]]
+        h, w, tau, sh, L = s0.H, s0.W, int(s0.tau), int(s0.shift), int(s0.seg_len)
+        view = base[g[0]:g[-1] + 1, :h, :w]
+        front = residual_front16(view, None, d, tau, 0, "hwc")
+        digest = front["digest"].cpu().tolist()
+        for j, b in enumerate(g):
+            if (digest[j] & 0xFFFFFFFFFFFFFFFF) == ss[b].digest:
+                continue
+            # the base is defined as the decode of the file alone (the range guard's fp32 re-run takes a whole lane)
+            alone, _ = decode_images(net, [inner[b]], max_pixels=max_pixels, depth=d)
+            again = int(residual_front16(alone, None, d, tau, 0, "hwc")["digest"].cpu()[0])
+            if (again & 0xFFFFFFFFFFFFFFFF) != ss[b].digest:
+                raise _digest_error(b, int(ss[b].digest), again, net)
+            base[b:b + 1, :h, :w].view(torch.int16).copy_(alone.view(torch.int16))
+            front = None
+        if front is None:
+            front = residual_front16(view, None, d, tau, 0, "hwc")
+        count = front["ctx_count"].cpu().numpy()
+        tabs = [_file_tables(files[b], ss[b]) for b in g]
+        planes = []
+        for j, b in enumerate(g):
+            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and tabs[j]["m"][k] == RES_ABSENT]
+            if missing:
+                raise ValueError(f"decode_images: file {b}: contexts {missing} occur in the base image but the file "
+                                 f"has no table for them")
+            pl = np.frombuffer(files[b], "<u8", residual_plane_words(h, w, sh), ss[b].lo_off)
+            if sh and w % 64 and (pl.reshape(3 * h, -(-w // 64), sh)[:, -1, :] >> np.uint64(w % 64)).any():
+                raise ValueError(f"decode_images: file {b}: the low-bit plane has bits set beyond column {w} (its "
+                                 f"padding bits must be zero)")
+            planes.append(pl.view(np.int64))
+        try:
+            sym_d = residual_decode_segments(
+                [files[b][ss[b].data_off:ss[b].data_off + ss[b].data_len] for b in g],
+                [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g], front["ctx"], tabs, L, coder)
+        except ResidualSegmentError as e:
+            raise ValueError(f"decode_images: file {g[e.image]}: segment {e.segment} of the residual string is "
+                             f"corrupt: {e.reason}") from None
+        plane_d = torch.from_numpy(np.stack(planes).reshape(len(g), -1).copy()).to(base.device)
+        out = img[g[0]:g[-1] + 1, :h, :w]
+        try:
+            r = residual_apply16(view, sym_d, plane_d, d, tau, sh, "hwc",
+                                 ref=None if ref is None else ref[g[0]:g[-1] + 1, :h, :w], out=out)
+        except ValueError as e:
+            raise ValueError(f"decode_images: files {g[0]}..{g[-1]}: {e}") from None
+        if ref is not None:
+            sq, me = r[1].cpu().tolist(), r[2].cpu().tolist()
+            for j, b in enumerate(g):
+                extra[b].update(sq_err=int(sq[j]), psnr=psnr_from_sq_err(int(sq[j]), 3 * h * w, (1 << d) - 1),
+                                max_abs_err=int(me[j]))
+    for di, e in zip(info, extra):
+        di.update(e)
     return img, info
 
 
@@ -2033,7 +2531,7 @@ def encode_images(net, imgs_u8, level=None, layout: Optional[str] = None, max_bp
     returns an image in which no sample is off by more than tau.  The bound is checked on the device before
     anything is written.  info[b] gains "max_error", "base_bytes" and "residual_bytes"; bytes and bpp are the
     whole file.  Refused, each by name, together with roi=, max_bpp=, level="auto", depth=, scale=, coded_size= and
-    layered=.
+    layered=.  Samples of 9..16 bits are coded with a bound by encode_residual16 (the "MLR3" file).
     residual_segment=L (256..65536; needs max_error=): the segmented residual file "MLR2" (DESIGN.md §5 "Residual
     coding", "Segments") instead of "MLR1": the residual string is cut into segments of L samples that code
     independently, so residual_coder="device" (the default; a CPU model takes the host entry) codes them with
@@ -2180,11 +2678,32 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     its int16 output read in place by residual_apply; "host": the host entry) and checks per segment that exactly
     its words were consumed and the state is back at 2^31; an error names the file and the segment.  "MLR1" and
     "MLR2" files, sizes and tau may mix in one call: they decode in groups.  info[b] gains "residual_segment" and
-    "segments"."""
+    "segments".
+    Deep residual files ("MLR3", encode_residual16; DESIGN.md §5 "Residual coding", "Deep samples") come back as
+    uint16 [B,H,W,3] at the file's depth: the inner files are decoded at that depth, residual_front16 gives the
+    contexts and the digest (the same decode-alone retry and the same error), residual_decode_segments the high parts,
+    the low-bit plane's padding bits are checked and residual_apply16 puts the samples together.  depth=, if given,
+    must be the file's; ref is uint16, psnr has peak 2^depth - 1; enhance=False returns the base picture at the file's
+    depth; info[b] gains "depth", "shift" and "low_bytes".  Refused by name: slices=, out_size=, filter=, msb=True,
+    and a call that mixes "MLR3" files with others.  Files that differ in tau, shift, depth, segment length or size
+    decode in groups."""
     residual_coder = _check_coder(residual_coder, "decode_images")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
+    if any(is_residual_deep_file(f) for f in files):
+        for name, given in (("slices=", slices is not None), ("out_size=", out_size is not None),
+                            ("filter=", filter is not None), ("msb=True", bool(msb))):
+            if given:
+                raise ValueError(f"decode_images: {name} on a residual file (MLR3) is not supported")
+        if fill != "mean":
+            raise ValueError("decode_images: fill= goes with slices= or layered files")
+        if not all(is_residual_deep_file(f) for f in files):
+            raise ValueError("decode_images: deep residual files (MLR3) and other files in one call are not supported: "
+                             "decode them in separate calls")
+        if depth is not None:
+            depth = _check_depth(depth, "decode_images")
+        return _decode_residual16(net, files, ref, max_pixels, bool(enhance), residual_coder, depth)
     if any(is_residual_file(f) for f in files):
         for name, given in (("slices=", slices is not None), ("out_size=", out_size is not None),
                             ("filter=", filter is not None), ("depth=", depth is not None)):

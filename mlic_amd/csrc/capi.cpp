@@ -12,6 +12,7 @@
 #include "options.h"
 #include "resample_table.h"
 #include "residual.h"
+#include "residual16.h"
 #include "residual_seg.h"
 
 using namespace mlic;
@@ -1798,6 +1799,94 @@ int mlic_container_parse_residual_seg(const uint8_t* data, size_t n, int n_level
     info->index_off = s.index_off;
     info->data_off = s.data_off;
     info->data_len = s.data_len;
+    to_abi(s.inner, &info->inner);
+  });
+}
+
+// ---- residual coding of 9..16-bit samples (residual16.h; DESIGN.md section 5 "Residual coding", "Deep samples")
+int mlic_image_residual_front_u16(void* stream, const uint16_t* base, const int64_t* base_strides, const uint16_t* x,
+                                  const int64_t* x_strides, int B, int H, int W, int depth, int tau, int shift,
+                                  uint8_t* ctx, uint32_t* ctx_count, uint64_t* digest, int16_t* sym, uint64_t* lo_plane,
+                                  uint32_t* hist, uint32_t* max_err, uint32_t* max_abs_q, uint64_t* sum_abs_q) {
+  return guard([&] {
+    image_residual_front_u16(base, base_strides, x, x_strides, B, H, W, depth, tau, shift, ctx, ctx_count, digest, sym,
+                             lo_plane, hist, max_err, max_abs_q, sum_abs_q, (hipStream_t)stream);
+  });
+}
+
+int mlic_image_residual_stats_u16(void* stream, const uint16_t* base, const int64_t* base_strides, const uint16_t* x,
+                                  const int64_t* x_strides, int B, int H, int W, int depth, int tau,
+                                  uint32_t* max_abs_q, uint64_t* sum_abs_q) {
+  return guard([&] {
+    image_residual_stats_u16(base, base_strides, x, x_strides, B, H, W, depth, tau, max_abs_q, sum_abs_q,
+                             (hipStream_t)stream);
+  });
+}
+
+int mlic_image_residual_apply_u16(void* stream, const uint16_t* base, const int64_t* base_strides, const int16_t* sym,
+                                  const uint64_t* lo_plane, int B, int H, int W, int depth, int tau, int shift,
+                                  uint16_t* out, const int64_t* out_strides, const uint16_t* ref,
+                                  const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err, uint32_t* status) {
+  return guard([&] {
+    image_residual_apply_u16(base, base_strides, sym, lo_plane, B, H, W, depth, tau, shift, out, out_strides, ref,
+                             ref_strides, sq_err, max_err, status, (hipStream_t)stream);
+  });
+}
+
+int mlic_residual_shift(int depth, uint64_t N, uint32_t max_abs_q, uint64_t sum_abs_q, int* shift) {
+  return guard([&] {
+    MLIC_CHECK(shift != nullptr, "residual_shift: null shift");
+    MLIC_CHECK(depth >= RES16_MIN_DEPTH && depth <= RES16_MAX_DEPTH, "residual_shift: depth must be in 9..16");
+    MLIC_CHECK(N >= 1 && N <= 3 * (1ull << 32), "residual_shift: N must be in 1..3 * 2^32");
+    MLIC_CHECK(max_abs_q < (1u << depth), "residual_shift: max_abs_q must be below 2^depth");
+    MLIC_CHECK(sum_abs_q <= (uint64_t)max_abs_q * N, "residual_shift: sum_abs_q above N max_abs_q");
+    *shift = residual16_shift(depth, N, max_abs_q, sum_abs_q);
+  });
+}
+
+int mlic_container_write_residual_deep(uint32_t H, uint32_t W, int vbr, int tau, int depth, int shift, uint64_t digest,
+                                       const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                       const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                       const uint8_t* segs, size_t segs_len, const uint8_t* lo, size_t lo_len,
+                                       uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    MLIC_CHECK(tau >= 0, "container_write_residual_deep: negative tau");
+    MLIC_CHECK(depth >= 0 && shift >= 0, "container_write_residual_deep: negative depth or shift");
+    container_ok(container_write_residual_deep(H, W, vbr != 0, (uint32_t)tau, (uint32_t)depth, (uint32_t)shift, digest,
+                                               m, freq, seg_len, n_seg, seg_bytes, inner, inner_len, segs, segs_len, lo,
+                                               lo_len, out, cap, len));
+  });
+}
+
+int mlic_container_parse_residual_deep(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                       mlic_container_residual_deep_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_residual_deep: null info");
+    ResidualDeepInfo d;
+    container_ok(container_parse_residual_deep(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &d));
+    const ResidualSegInfo& s = d.seg;
+    info->H = s.H;
+    info->W = s.W;
+    info->tau = (int32_t)s.tau;
+    info->vbr = s.vbr ? 1 : 0;
+    info->digest = s.digest;
+    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+      info->m[k] = s.m[k];
+      info->freq_off[k] = s.freq_off[k];
+    }
+    info->seg_len = s.seg_len;
+    info->n_seg = s.n_seg;
+    info->inner_off = s.inner_off;
+    info->inner_len = s.inner_len;
+    info->res_off = s.res_off;
+    info->res_len = s.res_len;
+    info->index_off = s.index_off;
+    info->data_off = s.data_off;
+    info->data_len = s.data_len;
+    info->depth = (int32_t)d.depth;
+    info->shift = (int32_t)d.shift;
+    info->lo_off = d.lo_off;
+    info->lo_len = d.lo_len;
     to_abi(s.inner, &info->inner);
   });
 }

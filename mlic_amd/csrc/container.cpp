@@ -600,56 +600,75 @@ uint64_t residual_seg_bound(uint32_t H, uint32_t W, uint32_t seg_len, uint64_t k
   const uint64_t left = 3 * (uint64_t)H * W - k * seg_len;
   return 4 * ((left < seg_len ? left : seg_len) + RESIDUAL_SEG_SLACK);
 }
+uint64_t residual_lo_bytes(uint32_t H, uint32_t W, uint32_t shift) {  // the low-bit plane of the "MLR3" file
+  return 8 * 3 * (uint64_t)H * (((uint64_t)W + 63) / 64) * shift;
+}
 }  // namespace
 
-const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint64_t digest,
-                                         const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
-                                         const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
-                                         const uint8_t* segs, size_t segs_len, uint8_t* out, size_t cap, size_t* len) {
-  if (len == nullptr) return "container_write_residual_seg: null len";
-  if (H == 0 || W == 0) return "container_write_residual_seg: H or W is zero";
-  if (tau > 127) return "container_write_residual_seg: tau above 127";
-  if (m == nullptr) return "container_write_residual_seg: null m";
+namespace {
+// The "MLR2" and the "MLR3" file differ by the magic, by depth and shift behind the tables and by the low-bit plane
+// behind the segments: one writer and one parser serve both, and each refusal carries the name of its entry.
+#define SEG_MSG(text) (deep ? "container_write_residual_deep: " text : "container_write_residual_seg: " text)
+const char* write_residual_seg(bool deep, uint32_t depth, uint32_t shift, const uint8_t* lo, size_t lo_len, uint32_t H,
+                               uint32_t W, bool vbr, uint32_t tau, uint64_t digest, const uint8_t* m,
+                               const uint16_t* freq, uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
+                               const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
+                               uint8_t* out, size_t cap, size_t* len) {
+  if (len == nullptr) return SEG_MSG("null len");
+  if (H == 0 || W == 0) return SEG_MSG("H or W is zero");
+  if (tau > 127) return SEG_MSG("tau above 127");
+  if (m == nullptr) return SEG_MSG("null m");
   if (seg_len < RESIDUAL_SEG_MIN || seg_len > RESIDUAL_SEG_MAX)
-    return "container_write_residual_seg: seg_len outside 256..65536";
+    return SEG_MSG("seg_len outside 256..65536");
   if ((uint64_t)n_seg != residual_seg_count(H, W, seg_len))
-    return "container_write_residual_seg: n_seg is not ceil(3 H W / seg_len)";
-  if (inner_len == 0) return "container_write_residual_seg: an empty inner file";
+    return SEG_MSG("n_seg is not ceil(3 H W / seg_len)");
+  if (deep) {
+    if (depth < 9 || depth > 16) return SEG_MSG("depth outside 9..16");
+    if (shift > depth - 7) return SEG_MSG("shift outside 0..depth - 7");
+    if ((uint64_t)lo_len != residual_lo_bytes(H, W, shift)) return SEG_MSG("lo_len is not 8 * 3 H ceil(W / 64) shift");
+    if (lo_len > 0xffffffffu) return SEG_MSG("a string longer than a 32-bit length");
+  }
+  if (inner_len == 0) return SEG_MSG("an empty inner file");
   if (inner_len > 0xffffffffu || segs_len > 0xffffffffu - 4 * (uint64_t)n_seg)
-    return "container_write_residual_seg: a string longer than a 32-bit length";
-  size_t total = RESIDUAL_HEADER + 16;
+    return SEG_MSG("a string longer than a 32-bit length");
+  size_t total = RESIDUAL_HEADER + 16 + (deep ? 6 : 0);
   for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
-    if (m[k] != RESIDUAL_ABSENT && m[k] > RESIDUAL_MAX_M) return "container_write_residual_seg: an m outside 0..63";
+    if (m[k] != RESIDUAL_ABSENT && m[k] > RESIDUAL_MAX_M) return SEG_MSG("an m outside 0..63");
     total += 1 + (m[k] == RESIDUAL_ABSENT ? 0 : 2 * (2 * (size_t)m[k] + 2));
   }
   const size_t res_len = 4 * (size_t)n_seg + segs_len;
   if (inner_len > SIZE_MAX - total || res_len > SIZE_MAX - total - inner_len)
-    return "container_write_residual_seg: the file does not fit size_t";
+    return SEG_MSG("the file does not fit size_t");
   total += inner_len + res_len;
+  if (deep) {
+    if (lo_len > SIZE_MAX - total) return SEG_MSG("the file does not fit size_t");
+    total += lo_len;
+  }
   *len = total;
   if (out == nullptr) return nullptr;
-  if (cap < total) return "container_write_residual_seg: buffer too small";
-  if (freq == nullptr) return "container_write_residual_seg: null frequencies";
-  if (inner == nullptr || seg_bytes == nullptr || segs == nullptr) return "container_write_residual_seg: null string";
+  if (cap < total) return SEG_MSG("buffer too small");
+  if (freq == nullptr) return SEG_MSG("null frequencies");
+  if (inner == nullptr || seg_bytes == nullptr || segs == nullptr || (lo_len && lo == nullptr))
+    return SEG_MSG("null string");
   for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
     if (m[k] == RESIDUAL_ABSENT) continue;
     uint32_t sum = 0;
     for (uint32_t j = 0; j < 2 * (uint32_t)m[k] + 2; ++j) {
-      if (freq[k * 128 + j] == 0) return "container_write_residual_seg: a zero frequency";
+      if (freq[k * 128 + j] == 0) return SEG_MSG("a zero frequency");
       sum += freq[k * 128 + j];
     }
-    if (sum != 65536) return "container_write_residual_seg: frequencies do not sum to 65536";
+    if (sum != 65536) return SEG_MSG("frequencies do not sum to 65536");
   }
   uint64_t sum = 0;
   for (uint32_t k = 0; k < n_seg; ++k) {
-    if (seg_bytes[k] % 4) return "container_write_residual_seg: a segment length that is not a multiple of 4";
-    if (seg_bytes[k] < 8) return "container_write_residual_seg: a segment length below 8";
+    if (seg_bytes[k] % 4) return SEG_MSG("a segment length that is not a multiple of 4");
+    if (seg_bytes[k] < 8) return SEG_MSG("a segment length below 8");
     if (seg_bytes[k] > residual_seg_bound(H, W, seg_len, k))
-      return "container_write_residual_seg: a segment length above the capacity bound";
+      return SEG_MSG("a segment length above the capacity bound");
     sum += seg_bytes[k];
   }
-  if (sum != segs_len) return "container_write_residual_seg: the segment lengths do not sum to the data length";
-  std::memcpy(out, "MLR2", 4);
+  if (sum != segs_len) return SEG_MSG("the segment lengths do not sum to the data length");
+  std::memcpy(out, deep ? "MLR3" : "MLR2", 4);
   out[4] = 0;
   out[5] = vbr ? 1 : 0;
   out[6] = (uint8_t)tau;
@@ -667,6 +686,10 @@ const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint3
       *p++ = (uint8_t)freq[k * 128 + j];
     }
   }
+  if (deep) {
+    *p++ = (uint8_t)depth;
+    *p++ = (uint8_t)shift;
+  }
   put32(p, seg_len);
   put32(p + 4, n_seg);
   put32(p + 8, (uint32_t)inner_len);
@@ -676,20 +699,47 @@ const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint3
   p += 4;
   for (uint32_t k = 0; k < n_seg; ++k, p += 4) put32(p, seg_bytes[k]);
   std::memcpy(p, segs, segs_len);
+  if (deep) {
+    p += segs_len;
+    put32(p, (uint32_t)lo_len);
+    if (lo_len) std::memcpy(p + 4, lo, lo_len);
+  }
   return nullptr;
 }
+#undef SEG_MSG
+}  // namespace
 
-const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
-                                         ResidualSegInfo* info) {
-  if (info == nullptr) return "container_parse_residual_seg: null info";
-  if (data == nullptr && n != 0) return "container_parse_residual_seg: null data";
-  if (n < RESIDUAL_HEADER) return "container_parse_residual_seg: truncated header";
-  if (std::memcmp(data, "MLR2", 4) != 0)
-    return "container_parse_residual_seg: bad magic (not a segmented residual file)";
-  if (data[4] != 0) return "container_parse_residual_seg: unknown version";
-  if (data[5] & ~1u) return "container_parse_residual_seg: unknown flags";
-  if (data[6] > 127) return "container_parse_residual_seg: tau above 127";
-  if (data[7] != RESIDUAL_CTX) return "container_parse_residual_seg: n_ctx is not 24";
+const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint64_t digest,
+                                         const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                         const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                         const uint8_t* segs, size_t segs_len, uint8_t* out, size_t cap, size_t* len) {
+  return write_residual_seg(false, 0, 0, nullptr, 0, H, W, vbr, tau, digest, m, freq, seg_len, n_seg, seg_bytes, inner,
+                            inner_len, segs, segs_len, out, cap, len);
+}
+
+const char* container_write_residual_deep(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint32_t depth,
+                                          uint32_t shift, uint64_t digest, const uint8_t* m, const uint16_t* freq,
+                                          uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
+                                          const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
+                                          const uint8_t* lo, size_t lo_len, uint8_t* out, size_t cap, size_t* len) {
+  return write_residual_seg(true, depth, shift, lo, lo_len, H, W, vbr, tau, digest, m, freq, seg_len, n_seg, seg_bytes,
+                            inner, inner_len, segs, segs_len, out, cap, len);
+}
+
+namespace {
+#define SEG_MSG(text) (deep ? "container_parse_residual_deep: " text : "container_parse_residual_seg: " text)
+const char* parse_residual_seg(bool deep, const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                               ResidualSegInfo* info, ResidualDeepInfo* more) {
+  if (info == nullptr) return SEG_MSG("null info");
+  if (data == nullptr && n != 0) return SEG_MSG("null data");
+  if (n < RESIDUAL_HEADER) return SEG_MSG("truncated header");
+  if (std::memcmp(data, deep ? "MLR3" : "MLR2", 4) != 0)
+    return deep ? "container_parse_residual_deep: bad magic (not a deep residual file)"
+                : SEG_MSG("bad magic (not a segmented residual file)");
+  if (data[4] != 0) return SEG_MSG("unknown version");
+  if (data[5] & ~1u) return SEG_MSG("unknown flags");
+  if (data[6] > 127) return SEG_MSG("tau above 127");
+  if (data[7] != RESIDUAL_CTX) return SEG_MSG("n_ctx is not 24");
   Reader r{data, n, 8};
   ResidualSegInfo s{};
   s.vbr = (data[5] & 1u) != 0;
@@ -700,63 +750,100 @@ const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t
   r.u32(&hi);
   r.u32(&lo);
   s.digest = ((uint64_t)hi << 32) | lo;
-  if (s.H == 0 || s.W == 0) return "container_parse_residual_seg: H or W is zero";
-  if ((uint64_t)s.H > max_pixels / (uint64_t)s.W) return "container_parse_residual_seg: image exceeds max_pixels";
+  if (s.H == 0 || s.W == 0) return SEG_MSG("H or W is zero");
+  if ((uint64_t)s.H > max_pixels / (uint64_t)s.W) return SEG_MSG("image exceeds max_pixels");
   for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
-    if (r.n - r.pos < 1) return "container_parse_residual_seg: truncated before a table's m";
+    if (r.n - r.pos < 1) return SEG_MSG("truncated before a table's m");
     const uint8_t m = data[r.pos++];
     s.m[k] = m;
     s.freq_off[k] = r.pos;
     if (m == RESIDUAL_ABSENT) continue;
-    if (m > RESIDUAL_MAX_M) return "container_parse_residual_seg: an m outside 0..63";
+    if (m > RESIDUAL_MAX_M) return SEG_MSG("an m outside 0..63");
     const size_t cnt = 2 * (size_t)m + 2;
-    if (r.n - r.pos < 2 * cnt) return "container_parse_residual_seg: truncated inside a table";
+    if (r.n - r.pos < 2 * cnt) return SEG_MSG("truncated inside a table");
     uint32_t sum = 0;
     for (size_t j = 0; j < cnt; ++j) {
       const uint32_t f = ((uint32_t)data[r.pos + 2 * j] << 8) | data[r.pos + 2 * j + 1];
-      if (f == 0) return "container_parse_residual_seg: a zero frequency";
+      if (f == 0) return SEG_MSG("a zero frequency");
       sum += f;
     }
-    if (sum != 65536) return "container_parse_residual_seg: a table's frequencies do not sum to 65536";
+    if (sum != 65536) return SEG_MSG("a table's frequencies do not sum to 65536");
     r.pos += 2 * cnt;
   }
-  if (!r.u32(&s.seg_len) || !r.u32(&s.n_seg)) return "container_parse_residual_seg: truncated before seg_len, n_seg";
+  uint32_t depth = 0, shift = 0;
+  if (deep) {
+    if (r.n - r.pos < 2) return SEG_MSG("truncated before depth, shift");
+    depth = data[r.pos++];
+    shift = data[r.pos++];
+    if (depth < 9 || depth > 16) return SEG_MSG("depth outside 9..16");
+    if (shift > depth - 7) return SEG_MSG("shift outside 0..depth - 7");
+  }
+  if (!r.u32(&s.seg_len) || !r.u32(&s.n_seg)) return SEG_MSG("truncated before seg_len, n_seg");
   if (s.seg_len < RESIDUAL_SEG_MIN || s.seg_len > RESIDUAL_SEG_MAX)
-    return "container_parse_residual_seg: seg_len outside 256..65536";
+    return SEG_MSG("seg_len outside 256..65536");
   if ((uint64_t)s.n_seg != residual_seg_count(s.H, s.W, s.seg_len))
-    return "container_parse_residual_seg: n_seg is not ceil(3 H W / seg_len)";
+    return SEG_MSG("n_seg is not ceil(3 H W / seg_len)");
   uint32_t ln = 0;
-  if (!r.u32(&ln)) return "container_parse_residual_seg: truncated before the inner length";
-  if (ln > r.n - r.pos) return "container_parse_residual_seg: the inner length runs past the end";
-  if (ln == 0) return "container_parse_residual_seg: an empty inner file";
+  if (!r.u32(&ln)) return SEG_MSG("truncated before the inner length");
+  if (ln > r.n - r.pos) return SEG_MSG("the inner length runs past the end");
+  if (ln == 0) return SEG_MSG("an empty inner file");
   s.inner_off = r.pos;
   s.inner_len = ln;
   r.pos += ln;
-  if (!r.u32(&ln)) return "container_parse_residual_seg: truncated before the residual length";
-  if (ln > r.n - r.pos) return "container_parse_residual_seg: the residual length runs past the end";
+  if (!r.u32(&ln)) return SEG_MSG("truncated before the residual length");
+  if (ln > r.n - r.pos) return SEG_MSG("the residual length runs past the end");
   s.res_off = r.pos;
   s.res_len = ln;
-  if ((uint64_t)ln < 4 * (uint64_t)s.n_seg) return "container_parse_residual_seg: the residual length is below its index";
+  if ((uint64_t)ln < 4 * (uint64_t)s.n_seg) return SEG_MSG("the residual length is below its index");
   s.index_off = r.pos;
   uint64_t sum = 4 * (uint64_t)s.n_seg;
   for (uint32_t k = 0; k < s.n_seg; ++k) {
     uint32_t v = 0;
     r.u32(&v);  // inside the residual length, which is inside the file
-    if (v % 4) return "container_parse_residual_seg: a segment length that is not a multiple of 4";
-    if (v < 8) return "container_parse_residual_seg: a segment length below 8";
+    if (v % 4) return SEG_MSG("a segment length that is not a multiple of 4");
+    if (v < 8) return SEG_MSG("a segment length below 8");
     if (v > residual_seg_bound(s.H, s.W, s.seg_len, k))
-      return "container_parse_residual_seg: a segment length above the capacity bound";
+      return SEG_MSG("a segment length above the capacity bound");
     sum += v;
   }
-  if (sum != ln) return "container_parse_residual_seg: the residual length is not 4 n_seg + the segment lengths";
+  if (sum != ln) return SEG_MSG("the residual length is not 4 n_seg + the segment lengths");
   s.data_off = r.pos;
   s.data_len = ln - 4 * (size_t)s.n_seg;
   r.pos += s.data_len;
-  if (r.pos != r.n) return "container_parse_residual_seg: bytes left over after the segments";
+  if (deep) {
+    uint32_t lo_len = 0;
+    if (!r.u32(&lo_len)) return SEG_MSG("truncated before the low-bit plane's length");
+    if ((uint64_t)lo_len != residual_lo_bytes(s.H, s.W, shift))
+      return SEG_MSG("lo_len is not 8 * 3 H ceil(W / 64) shift");
+    if (lo_len > r.n - r.pos) return SEG_MSG("truncated inside the low-bit plane");
+    more->depth = depth;
+    more->shift = shift;
+    more->lo_off = r.pos;
+    more->lo_len = lo_len;
+    r.pos += lo_len;
+    if (r.pos != r.n) return SEG_MSG("bytes left over after the low-bit plane");
+  }
+  if (r.pos != r.n) return SEG_MSG("bytes left over after the segments");
   if (const char* err = container_parse(data + s.inner_off, s.inner_len, s.vbr, n_levels, max_pixels, &s.inner)) return err;
   if (s.inner.H != s.H || s.inner.W != s.W)
-    return "container_parse_residual_seg: the inner file's H x W is not the outer one";
+    return SEG_MSG("the inner file's H x W is not the outer one");
   *info = s;
+  return nullptr;
+}
+#undef SEG_MSG
+}  // namespace
+
+const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                         ResidualSegInfo* info) {
+  return parse_residual_seg(false, data, n, n_levels, max_pixels, info, nullptr);
+}
+
+const char* container_parse_residual_deep(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                          ResidualDeepInfo* info) {
+  if (info == nullptr) return "container_parse_residual_deep: null info";
+  ResidualDeepInfo d{};
+  if (const char* err = parse_residual_seg(true, data, n, n_levels, max_pixels, &d.seg, &d)) return err;
+  *info = d;
   return nullptr;
 }
 

@@ -250,5 +250,34 @@ const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint3
 const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                          ResidualSegInfo* info);
 
+// ---- The deep residual file (DESIGN.md section 5 "Residual coding", "Deep samples"; residual16.h has the
+// definitions): the segmented file for 9..16-bit samples.  The segments code hi = q >> shift; the low `shift` bits of
+// every q are stored raw in the low-bit plane.  All integers big-endian, the plane's 64-bit words little-endian (as
+// the rANS words are):
+//     4 bytes "MLR3" | the rest of the "MLR2" header | the 24 tables | >B depth (9..16) | >B shift (0..depth - 7)
+//     >I seg_len | >I n_seg | >I inner_len, the inner file | >I res_len | the index | the segments
+//     >I lo_len = 8 * 3 H ceil(W / 64) shift | the low-bit plane
+// There is no serial form.  As H, "MLR3" exceeds every max_pixels.
+struct ResidualDeepInfo {
+  ResidualSegInfo seg;  // everything the "MLR2" file has
+  uint32_t depth, shift;
+  size_t lo_off, lo_len;  // the low-bit plane
+};
+inline bool is_residual_deep_file(const uint8_t* data, size_t n) {
+  return n >= 4 && data[0] == 'M' && data[1] == 'L' && data[2] == 'R' && data[3] == '3';
+}
+// As container_write_residual_seg, with depth, shift and the plane.  Refused besides, each with its own message: a
+// depth outside 9..16; a shift outside 0..depth - 7; a lo_len that is not 8 * 3 H ceil(W / 64) shift.
+const char* container_write_residual_deep(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint32_t depth,
+                                          uint32_t shift, uint64_t digest, const uint8_t* m, const uint16_t* freq,
+                                          uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
+                                          const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
+                                          const uint8_t* lo, size_t lo_len, uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: everything container_parse_residual_seg refuses (with "MLR3" as the magic);
+// truncation before depth and shift; a depth or shift out of range; truncation before lo_len; a wrong lo_len;
+// truncation inside the plane; bytes left over.
+const char* container_parse_residual_deep(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                          ResidualDeepInfo* info);
+
 }  // namespace mlic
 #endif

@@ -341,6 +341,26 @@ void image_residual_front_u8(const uint8_t* base, const int64_t* base_strides, c
 void image_residual_apply_u8(const uint8_t* base, const int64_t* base_strides, const int16_t* sym, int B, int H, int W,
                              int tau, uint8_t* out, const int64_t* out_strides, const uint8_t* ref,
                              const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err, hipStream_t st);
+// The same two passes on 9..16-bit samples in uint16 words (residual16.hip; residual16.h has the definitions; DESIGN.md
+// section 5 "Residual coding", "Deep samples").  front without x: ctx, ctx_count, digest.  With x also sym (hi = q >>
+// shift, int16), lo_plane (u64 [B][3 H ceil(W / 64) shift], null at shift 0), hist of hi, max_err, and the statistics
+// max_abs_q u32 [B] and sum_abs_q u64 [B].  stats: a launch of the front kernel that gives the statistics alone (the
+// shift is chosen from them).  apply: out = rec of (base, (sym << shift) + lo); status u32 [B] is nonzero for an image
+// that holds a sym outside +-255.  All zero what they accumulate into on the stream, check their arguments before
+// any HIP call and throw.
+void image_residual_front_u16(const uint16_t* base, const int64_t* base_strides, const uint16_t* x,
+                              const int64_t* x_strides, int B, int H, int W, int depth, int tau, int shift,
+                              uint8_t* ctx, uint32_t* ctx_count, uint64_t* digest, int16_t* sym, uint64_t* lo_plane,
+                              uint32_t* hist, uint32_t* max_err, uint32_t* max_abs_q, uint64_t* sum_abs_q,
+                              hipStream_t st);
+void image_residual_stats_u16(const uint16_t* base, const int64_t* base_strides, const uint16_t* x,
+                              const int64_t* x_strides, int B, int H, int W, int depth, int tau, uint32_t* max_abs_q,
+                              uint64_t* sum_abs_q, hipStream_t st);
+void image_residual_apply_u16(const uint16_t* base, const int64_t* base_strides, const int16_t* sym,
+                              const uint64_t* lo_plane, int B, int H, int W, int depth, int tau, int shift,
+                              uint16_t* out, const int64_t* out_strides, const uint16_t* ref,
+                              const int64_t* ref_strides, uint64_t* sq_err, uint32_t* max_err, uint32_t* status,
+                              hipStream_t st);
 // The device rANS coder of the segmented residual strings (residual_coder.hip; residual_seg.h has the definitions).
 // sym int16 and ctx u8 are dense [B][N]; tabs, seg_off, seg_bytes [B][n_seg], total [B] and status [B] are device
 // memory.  encode: a counting pass, a scan and a writing pass on `st`; image b's bytes go to out + b cap, each store

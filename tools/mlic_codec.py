@@ -59,6 +59,10 @@
         residual string in independent segments of L samples (256..65536), coded and decoded on the GPU.
         --residual-coder host|device (encode with --residual-segment, decode): which coder runs; the bytes and the
         picture are the same either way.  decode, strip and info recognise the file by its magic.
+        An image deeper than 8 bits (a 16-bit PPM) gets the deep residual file ("MLR3"): always segmented
+        (--residual-segment defaults to the codec's 4096), the low bits of every residual stored raw;
+        --residual-shift S fixes how many (0..depth - 7; default: the codec's shift rule).  decode writes the 16-bit
+        PPM at the file's depth.
     ... --base-only (decode): the base picture of a residual file alone, without the second layer.
     python tools/mlic_codec.py strip IN.bit -o OUT.bit             the base file inside a residual file
     python tools/mlic_codec.py truncate IN.bit -k K -o OUT.bit     the first bytes of a layered file up to the end
@@ -453,6 +457,7 @@ def parse_args(argv=None):
     ap.add_argument("--base-only", action="store_true")
     ap.add_argument("--residual-segment", type=int, default=None, metavar="L")
     ap.add_argument("--residual-coder", choices=["host", "device"], default=None)
+    ap.add_argument("--residual-shift", type=int, default=None, metavar="S")
     args = ap.parse_args(argv)
     if args.mode == "strip":
         if args.dst is not None or args.output is None:
@@ -475,6 +480,11 @@ def parse_args(argv=None):
         ap.error("--residual-coder goes with --residual-segment L (encode) or with decode")
     if args.residual_coder is not None and args.mode not in ("encode", "decode"):
         ap.error("--residual-coder goes with encode and decode")
+    if args.residual_shift is not None:
+        if args.mode != "encode" or args.max_error is None:
+            ap.error("--residual-shift goes with encode --max-error T / --lossless of an image deeper than 8 bits")
+        if not 0 <= args.residual_shift <= 9:
+            ap.error("--residual-shift: 0 to depth - 7 expected")
     if args.max_error is not None:
         if args.mode != "encode":
             ap.error("--max-error / --lossless go with encode (a residual file is recognised by its magic)")
@@ -702,7 +712,7 @@ def main(argv=None):
     if args.mode == "strip":
         with open(args.src, "rb") as f:
             data = f.read()
-        if not codec.is_residual_file(data):
+        if not (codec.is_residual_file(data) or codec.is_residual_deep_file(data)):
             raise SystemExit(f"{args.src}: not a residual file (no MLR1 / MLR2 magic): encode --max-error T writes one")
         inner = codec.strip_residual(data)
         with open(args.output, "wb") as f:
@@ -747,6 +757,7 @@ def main(argv=None):
                   f"{' (lossless)' if d['max_error'] == 0 else ''}, level {d['level']}, z grid {d['shape'][0]} x "
                   f"{d['shape'][1]}, base {d['base_bytes']} B, residual {d['residual_bytes']} B"
                   + (f" in {d['segments']} segments of {d['residual_segment']}" if "segments" in d else "") +
+                  (f", depth {d['depth']}, low bits {d['low_bytes']} B (shift {d['shift']})" if "shift" in d else "") +
                   f", header and tables {d['header_bytes']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
             return
         if d.get("scaled"):
@@ -823,6 +834,23 @@ def main(argv=None):
                 raise SystemExit(f"{args.src}: scaled coding of an image deeper than 8 bits is not supported")
             scaled = {"scale": args.scale, "filter": args.filter or "lanczos3",
                       "coded_size": None if args.coded_size is None else (args.coded_size[1], args.coded_size[0])}
+        if args.residual_shift is not None and depth == 8:
+            raise SystemExit(f"{args.src}: --residual-shift goes with an image deeper than 8 bits")
+        if args.max_error is not None and depth != 8:  # samples of 9..16 bits: the "MLR3" file, always segmented
+            try:
+                files, info = codec.encode_residual16(
+                    net, img, depth, max_error=args.max_error, level=args.level, layout="hwc",
+                    residual_segment=args.residual_segment or codec.DEFAULT_RESIDUAL_SEGMENT,
+                    residual_coder=args.residual_coder or "device", shift=args.residual_shift, return_info=True)
+            except ValueError as e:
+                raise SystemExit(f"{args.src}: {e}") from None
+            with open(args.dst, "wb") as f:
+                f.write(files[0])
+            d = info[0]
+            print(f"{args.src}: {img.shape[0]} x {img.shape[1]} -> {d['bytes']} bytes, {d['bpp']:.4f} bpp, depth {depth}, "
+                  f"max error {args.max_error}: base {d['base_bytes']} B, residual {d['residual_bytes']} B in "
+                  f"{d['segments']} segments of {d['residual_segment']}, low bits {d['low_bytes']} B (shift {d['shift']})")
+            return
         try:
             files, info = codec.encode_images(net, img, level=args.level, layout="hwc", max_bpp=args.max_bpp,
                                               max_passes=args.max_passes, return_info=True, roi=roi,
@@ -875,7 +903,11 @@ def main(argv=None):
         if args.region is not None:
             raise SystemExit(f"{args.src}: --region needs a tiled file (encode --tile T)")
         depth = args.depth or 8
-        kw = {} if depth == 8 else {"depth": depth}
+        if codec.is_residual_deep_file(data):  # the file knows its depth
+            depth = codec.peek(data, n_levels=getattr(net, "levels", None))["depth"]
+            if args.depth not in (None, depth):
+                raise SystemExit(f"{args.src}: --depth {args.depth}, but the file holds samples of depth {depth}")
+        kw = {} if depth == 8 or codec.is_residual_deep_file(data) else {"depth": depth}
         if args.out_size is not None:
             kw["out_size"] = (args.out_size[1], args.out_size[0])
         if args.filter is not None:
@@ -885,7 +917,7 @@ def main(argv=None):
         if args.fill is not None:
             kw["fill"] = args.fill
         if args.base_only:
-            if not codec.is_residual_file(data):
+            if not (codec.is_residual_file(data) or codec.is_residual_deep_file(data)):
                 raise SystemExit(f"{args.src}: --base-only needs a residual file (encode --max-error T)")
             kw["enhance"] = False
         if args.residual_coder is not None:
@@ -894,7 +926,8 @@ def main(argv=None):
             img, info = codec.decode_images(net, [data], **kw)
         except ValueError as e:
             if not (args.out_size or args.filter or codec.is_scaled_file(data) or args.slices is not None or
-                    args.fill is not None or codec.is_layered_file(data) or codec.is_residual_file(data)):
+                    args.fill is not None or codec.is_layered_file(data) or codec.is_residual_file(data) or
+                    codec.is_residual_deep_file(data)):
                 raise
             raise SystemExit(f"{args.src}: {e}") from None
         save_image(args.dst, img[0].cpu().numpy(), depth)
@@ -905,6 +938,8 @@ def main(argv=None):
         if "max_error" in info[0]:
             line += (f", max error {info[0]['max_error']}, residual {info[0]['residual_bytes']} B"
                      f"{' (base only)' if args.base_only else ''}")
+            if "shift" in info[0]:
+                line += f", depth {info[0]['depth']}, low bits {info[0]['low_bytes']} B (shift {info[0]['shift']})"
         if "slices" in info[0]:
             line += f", {info[0]['slices']} slices decoded ({args.fill or 'mean'} fill)"
         print(line)
