@@ -851,6 +851,26 @@ int mlic_residual_decode_segments_host(const uint8_t* data, size_t data_stride, 
                                        const uint32_t* seg_bytes, const uint8_t* ctx, int B, int H, int W,
                                        const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg,
                                        int16_t* sym);
+/* The same five for a string of N samples that is not an RGB image's 3 H W (a Y'CbCr frame's N = H W + 2 hc wc:
+ * mlic_residual_yuv_samples): int64_t N stands in place of int H, int W; scratch_bytes_n takes N and seg_len and
+ * works out n_seg.  Refused, each with its own message: N < 1; N above 2^29; n_seg that is not ceil(N / seg_len);
+ * everything else as the entries above.  At N = 3 H W they give the entries' above results byte for byte. */
+int mlic_residual_segments_scratch_bytes_n(int B, int64_t N, int seg_len, size_t* bytes);
+int mlic_residual_encode_segments_n(void* stream, const int16_t* sym, const uint8_t* ctx, int B, int64_t N,
+                                    const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                                    size_t cap, uint32_t* seg_bytes, uint64_t* len, void* scratch,
+                                    size_t scratch_bytes, uint32_t* status);
+int mlic_residual_decode_segments_n(void* stream, const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                    const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N, const uint8_t* m,
+                                    const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym, void* scratch,
+                                    size_t scratch_bytes, uint32_t* status);
+int mlic_residual_encode_segments_host_n(const int16_t* sym, const uint8_t* ctx, int B, int64_t N, const uint8_t* m,
+                                         const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
+                                         uint32_t* seg_bytes, uint64_t* len);
+int mlic_residual_decode_segments_host_n(const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                         const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N,
+                                         const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg,
+                                         int16_t* sym);
 /* The segmented residual file, big-endian:
  *     "MLR2" | u8 version 0 | u8 flags (bit 0: VBR level word inside) | u8 tau | u8 n_ctx = 24 | u32 H, W | u64 digest
  *     the 24 tables, exactly as in "MLR1"
@@ -1103,6 +1123,122 @@ int mlic_decode_image_yuv16(mlic_model* m, void* stream, const uint8_t* file, si
                             uint16_t* y_dev, const int64_t* y_strides, size_t y_cap, uint16_t* cb_dev,
                             const int64_t* cb_strides, size_t cb_cap, uint16_t* cr_dev, const int64_t* cr_strides,
                             size_t cr_cap, int* H, int* W, int* level);
+/* ---- Residual coding of Y'CbCr frames (DESIGN.md section 5 "Residual coding", "Y'CbCr frames") ----
+ *
+ * Integer definitions (csrc/residual_yuv.h).  A frame is three planes, p = 0 Y' of H x W, p = 1 Cb and p = 2 Cr of
+ * hc x wc = ceil(H / sub_y) x ceil(W / sub_x); samples of depth d in 8..16, maxv = 2^d - 1: bytes at d = 8, uint16
+ * words above, LSB-aligned (sample = min(word, maxv)) or MSB-aligned (sample = word >> (16 - d); written words carry
+ * zero low bits).  Canonical order: i = off_p + y w_p + x, off = {0, H W, H W + hc wc}, N = H W + 2 hc wc <= 2^29.
+ * base is the three planes mlic_image_egress_yuv8 / _yuv16 writes from the inner file decoded alone; q, rec, hi, lo
+ * and the shift rule are those of the deep layer with maxv (rec clamps to [0, maxv], not to the legal range), the
+ * shift is 0 at depth 8 and in 0..d-7 above.  Context = 8 p + class(a >> (d - 8)), a = max - min of base plane p over
+ * the 3 x 3 neighbourhood clamped into that plane; bins, escape, tables and digest (over the canonical index) are the
+ * 8-bit layer's.  Low-bit plane: rows in canonical order, G_p = ceil(w_p / 64); the 64-bit word
+ * (rowbase_p + y G_p + g) s + j holds bit j of lo at bit x mod 64, zero beyond the plane's width;
+ * s (H G_0 + 2 hc G_1) words a frame.
+ *
+ * Planes come as three pointers with element strides {image, row, column} (column stride 2: the semi-planar forms).
+ * Of desc only sub_x / sub_y are used; the rest is validated as the egress validates it.
+ * front: always ctx u8 [B][N], ctx_count u32 [B][24], digest u64 [B]; with the three x planes (all NULL without x)
+ * also sym int16 [B][N] (hi, saturated), lo_plane u64, hist u32 [B][24][128], max_err, max_abs_q u32 [B] and
+ * sum_abs_q u64 [B].  stats: max_abs_q and sum_abs_q alone.  apply: the three out planes through their own strides;
+ * with the three ref planes also sq_err u64 [B][3] (per plane) and max_err u32 [B]; status u32 [B] (required) is
+ * nonzero for a frame that holds a sym outside +-255, and such a sample is written as base.  One launch each, over
+ * the three planes of all B frames; they zero what they accumulate into on the stream.
+ * Refused before any HIP call, each with its own message: a null base plane or strides; B < 1; H or W < 1 or above
+ * 2^24; more than 2^29 samples; what the egress refuses of desc; tau outside 0..127; a zero column stride; x, out
+ * or ref given as fewer than three planes; null outputs that the call needs, outputs that go with x (ref) without
+ * it; pointers not aligned to their element.  _yuv8: uint8 planes, depth 8, the shift must be 0 and lo_plane NULL.
+ * _yuv16: uint16 planes, 2-byte aligned, depth 9..16, msb 0 / 1, shift 0..depth - 7, lo_plane NULL exactly when the
+ * shift is 0. */
+int mlic_image_residual_front_yuv8(void* stream, const uint8_t* base_y, const int64_t* base_y_strides,
+                                   const uint8_t* base_cb, const int64_t* base_cb_strides, const uint8_t* base_cr,
+                                   const int64_t* base_cr_strides, const uint8_t* x_y, const int64_t* x_y_strides,
+                                   const uint8_t* x_cb, const int64_t* x_cb_strides, const uint8_t* x_cr,
+                                   const int64_t* x_cr_strides, const mlic_yuv_desc* desc, int B, int H, int W, int tau,
+                                   int shift, uint8_t* ctx, uint32_t* ctx_count, uint64_t* digest, int16_t* sym,
+                                   uint64_t* lo_plane, uint32_t* hist, uint32_t* max_err, uint32_t* max_abs_q,
+                                   uint64_t* sum_abs_q);
+int mlic_image_residual_stats_yuv8(void* stream, const uint8_t* base_y, const int64_t* base_y_strides,
+                                   const uint8_t* base_cb, const int64_t* base_cb_strides, const uint8_t* base_cr,
+                                   const int64_t* base_cr_strides, const uint8_t* x_y, const int64_t* x_y_strides,
+                                   const uint8_t* x_cb, const int64_t* x_cb_strides, const uint8_t* x_cr,
+                                   const int64_t* x_cr_strides, const mlic_yuv_desc* desc, int B, int H, int W, int tau,
+                                   uint32_t* max_abs_q, uint64_t* sum_abs_q);
+int mlic_image_residual_apply_yuv8(void* stream, const uint8_t* base_y, const int64_t* base_y_strides,
+                                   const uint8_t* base_cb, const int64_t* base_cb_strides, const uint8_t* base_cr,
+                                   const int64_t* base_cr_strides, const int16_t* sym, const uint64_t* lo_plane,
+                                   const mlic_yuv_desc* desc, int B, int H, int W, int tau, int shift, uint8_t* out_y,
+                                   const int64_t* out_y_strides, uint8_t* out_cb, const int64_t* out_cb_strides,
+                                   uint8_t* out_cr, const int64_t* out_cr_strides, const uint8_t* ref_y,
+                                   const int64_t* ref_y_strides, const uint8_t* ref_cb, const int64_t* ref_cb_strides,
+                                   const uint8_t* ref_cr, const int64_t* ref_cr_strides, uint64_t* sq_err,
+                                   uint32_t* max_err, uint32_t* status);
+int mlic_image_residual_front_yuv16(void* stream, const uint16_t* base_y, const int64_t* base_y_strides,
+                                    const uint16_t* base_cb, const int64_t* base_cb_strides, const uint16_t* base_cr,
+                                    const int64_t* base_cr_strides, const uint16_t* x_y, const int64_t* x_y_strides,
+                                    const uint16_t* x_cb, const int64_t* x_cb_strides, const uint16_t* x_cr,
+                                    const int64_t* x_cr_strides, const mlic_yuv_desc* desc, int depth, int msb, int B,
+                                    int H, int W, int tau, int shift, uint8_t* ctx, uint32_t* ctx_count,
+                                    uint64_t* digest, int16_t* sym, uint64_t* lo_plane, uint32_t* hist,
+                                    uint32_t* max_err, uint32_t* max_abs_q, uint64_t* sum_abs_q);
+int mlic_image_residual_stats_yuv16(void* stream, const uint16_t* base_y, const int64_t* base_y_strides,
+                                    const uint16_t* base_cb, const int64_t* base_cb_strides, const uint16_t* base_cr,
+                                    const int64_t* base_cr_strides, const uint16_t* x_y, const int64_t* x_y_strides,
+                                    const uint16_t* x_cb, const int64_t* x_cb_strides, const uint16_t* x_cr,
+                                    const int64_t* x_cr_strides, const mlic_yuv_desc* desc, int depth, int msb, int B,
+                                    int H, int W, int tau, uint32_t* max_abs_q, uint64_t* sum_abs_q);
+int mlic_image_residual_apply_yuv16(void* stream, const uint16_t* base_y, const int64_t* base_y_strides,
+                                    const uint16_t* base_cb, const int64_t* base_cb_strides, const uint16_t* base_cr,
+                                    const int64_t* base_cr_strides, const int16_t* sym, const uint64_t* lo_plane,
+                                    const mlic_yuv_desc* desc, int depth, int msb, int B, int H, int W, int tau,
+                                    int shift, uint16_t* out_y, const int64_t* out_y_strides, uint16_t* out_cb,
+                                    const int64_t* out_cb_strides, uint16_t* out_cr, const int64_t* out_cr_strides,
+                                    const uint16_t* ref_y, const int64_t* ref_y_strides, const uint16_t* ref_cb,
+                                    const int64_t* ref_cb_strides, const uint16_t* ref_cr,
+                                    const int64_t* ref_cr_strides, uint64_t* sq_err, uint32_t* max_err,
+                                    uint32_t* status);
+/* Host only.  *N = H W + 2 hc wc; *words = shift (H G_0 + 2 hc G_1), the 64-bit words of one frame's low-bit plane.
+ * Refused: a null result; H or W < 1 or above 2^24; a sub pair that is not {1,1}, {2,1} or {2,2}; more than 2^29
+ * samples; a shift outside 0..9.  The shift rule is mlic_residual_shift with the frame's N (depth 9..16; at depth 8
+ * the shift is 0). */
+int mlic_residual_yuv_samples(int H, int W, int sub_x, int sub_y, uint64_t* N);
+int mlic_residual_yuv_plane_words(int H, int W, int sub_x, int sub_y, int shift, uint64_t* words);
+/* The Y'CbCr residual file, big-endian (the plane's 64-bit words little-endian); H, W are the luma size:
+ *     "MLR4" | the "MLR2" header and tables
+ *     u8 depth (8..16) | u8 shift | u8 sub_x | u8 sub_y | u8 matrix | u8 flags (bit 0 full_range, bit 1 site_x left)
+ *     u32 seg_len | u32 n_seg | u32 inner_len, inner file | u32 res_len | the index | the segments
+ *     u32 lo_len = 8 shift (H G_0 + 2 hc G_1) | the low-bit plane
+ * Always segmented; the inner file is byte for byte what the Y'CbCr encode writes without a residual.  parse refuses,
+ * each with its own message: everything mlic_container_parse_residual_seg refuses, with n_seg against ceil(N /
+ * seg_len) for this frame's N; a depth outside 8..16; a shift outside 0..depth - 7, a nonzero shift at depth 8; a sub
+ * pair that is not {1,1}, {2,1} or {2,2}; a matrix outside 0..2, matrix 2 (BT.2020) at depth 8; reserved flag bits; a
+ * wrong lo_len; truncation anywhere; trailing bytes.  Every other parser refuses an "MLR4" file.  There is no
+ * single-call encode or decode of this file. */
+typedef struct mlic_container_residual_yuv_info {
+  uint32_t H, W;
+  int32_t tau;
+  int32_t vbr;
+  uint64_t digest;
+  uint8_t m[24];
+  uint64_t freq_off[24];
+  uint32_t seg_len, n_seg;
+  uint64_t inner_off, inner_len, res_off, res_len;
+  uint64_t index_off;
+  uint64_t data_off, data_len;
+  int32_t depth, shift;
+  uint64_t lo_off, lo_len; /* the low-bit plane */
+  int32_t sub_x, sub_y, matrix, full_range, site_x; /* site_x: 1 = left */
+  mlic_container_info inner;
+} mlic_container_residual_yuv_info;
+int mlic_container_write_residual_yuv(uint32_t H, uint32_t W, int vbr, int tau, int depth, int shift, int sub_x,
+                                      int sub_y, int matrix, int full_range, int site_x, uint64_t digest,
+                                      const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                      const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                      const uint8_t* segs, size_t segs_len, const uint8_t* lo, size_t lo_len,
+                                      uint8_t* out, size_t cap, size_t* len);
+int mlic_container_parse_residual_yuv(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                      mlic_container_residual_yuv_info* info);
 /* per-image sum of -log2(lik) over n_per elements (fixed reduction order); synchronous */
 int mlic_neglog2_sum(void* stream, const float* lik, int B, int64_t n_per, double* out);
 /* GaussianConditional likelihood (compressai, eval; mlicpp.py:132,168) element-wise: lik = max(Phi((0.5-|v|)/s')

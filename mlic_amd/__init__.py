@@ -15,6 +15,9 @@ from .codec import (is_residual_seg_file, parse_container_residual_seg, residual
 from .codec import (encode_residual16, is_residual_deep_file, parse_container_residual_deep,  # noqa: F401
                     residual_apply16, residual_front16, residual_shift, residual_stats16,
                     write_container_residual_deep)
+from .codec import (encode_residual_yuv, is_residual_yuv_file, parse_container_residual_yuv,  # noqa: F401
+                    residual_apply_yuv, residual_front_yuv, residual_stats_yuv, residual_yuv_format,
+                    write_container_residual_yuv)
 from .codec import blend_tiles, decode_tiled, encode_tiled, tile_grid  # noqa: F401
 from .codec import YuvFormat, decode_yuv, egress_yuv, encode_yuv, ingest_yuv, split_yuv  # noqa: F401
 from .codec import egress_u16, ingest_u16  # noqa: F401
@@ -30,4 +33,6 @@ __all__ = ["MLICPlusPlus", "MLICPlusPlusSD", "MLICPlusPlusSDVbr", "MLICPlusPlusV
            "is_residual_file", "strip_residual", "is_residual_seg_file", "parse_container_residual_seg",
            "write_container_residual_seg", "residual_encode_segments", "residual_decode_segments",
            "encode_residual16", "is_residual_deep_file", "parse_container_residual_deep", "residual_apply16",
-           "residual_front16", "residual_shift", "residual_stats16", "write_container_residual_deep"]
+           "residual_front16", "residual_shift", "residual_stats16", "write_container_residual_deep",
+           "encode_residual_yuv", "is_residual_yuv_file", "parse_container_residual_yuv", "residual_apply_yuv",
+           "residual_front_yuv", "residual_stats_yuv", "residual_yuv_format", "write_container_residual_yuv"]

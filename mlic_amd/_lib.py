@@ -69,6 +69,17 @@ class ContainerResidualDeepInfo(C.Structure):
                 ("shift", C.c_int32), ("lo_off", C.c_uint64), ("lo_len", C.c_uint64), ("inner", ContainerInfo)]
 
 
+class ContainerResidualYuvInfo(C.Structure):
+    """mlic_container_residual_yuv_info (include/mlic_hip.h)."""
+    _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("tau", C.c_int32), ("vbr", C.c_int32), ("digest", C.c_uint64),
+                ("m", C.c_uint8 * 24), ("freq_off", C.c_uint64 * 24), ("seg_len", C.c_uint32), ("n_seg", C.c_uint32),
+                ("inner_off", C.c_uint64), ("inner_len", C.c_uint64), ("res_off", C.c_uint64), ("res_len", C.c_uint64),
+                ("index_off", C.c_uint64), ("data_off", C.c_uint64), ("data_len", C.c_uint64), ("depth", C.c_int32),
+                ("shift", C.c_int32), ("lo_off", C.c_uint64), ("lo_len", C.c_uint64), ("sub_x", C.c_int32),
+                ("sub_y", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32), ("site_x", C.c_int32),
+                ("inner", ContainerInfo)]
+
+
 class ContainerLayeredInfo(C.Structure):
     """mlic_container_layered_info (include/mlic_hip.h)."""
     _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("hz", C.c_uint32), ("wz", C.c_uint32), ("level", C.c_int32),
@@ -242,6 +253,24 @@ def _sig(lib):
         "mlic_encode_image_yuv16": [p, p, p, P(i64), p, P(i64), p, P(i64), P(YuvDesc), i, i, i, i, f, i, p, sz, P(sz)],
         "mlic_decode_image_yuv16": [p, p, p, sz, i, C.c_uint64, p, P(YuvDesc), i, i, p, P(i64), sz, p, P(i64), sz, p,
                                     P(i64), sz, P(i), P(i), P(i)],
+        "mlic_residual_segments_scratch_bytes_n": [i, i64, i, P(sz)],
+        "mlic_residual_encode_segments_n": [p, p, p, i, i64, p, p, i, i64, p, sz, p, p, p, sz, p],
+        "mlic_residual_decode_segments_n": [p, p, sz, p, p, p, i, i64, p, p, i, i64, p, p, sz, p],
+        "mlic_residual_encode_segments_host_n": [p, p, i, i64, p, p, i, i64, p, sz, p, p],
+        "mlic_residual_decode_segments_host_n": [p, sz, p, p, p, i, i64, p, p, i, i64, p],
+        "mlic_image_residual_front_yuv8": [p] + [p, P(i64)] * 6 + [P(YuvDesc), i, i, i, i, i] + [p] * 9,
+        "mlic_image_residual_stats_yuv8": [p] + [p, P(i64)] * 6 + [P(YuvDesc), i, i, i, i, p, p],
+        "mlic_image_residual_apply_yuv8": [p] + [p, P(i64)] * 3 + [p, p, P(YuvDesc), i, i, i, i, i] +
+                                          [p, P(i64)] * 6 + [p, p, p],
+        "mlic_image_residual_front_yuv16": [p] + [p, P(i64)] * 6 + [P(YuvDesc), i, i, i, i, i, i, i] + [p] * 9,
+        "mlic_image_residual_stats_yuv16": [p] + [p, P(i64)] * 6 + [P(YuvDesc), i, i, i, i, i, i, p, p],
+        "mlic_image_residual_apply_yuv16": [p] + [p, P(i64)] * 3 + [p, p, P(YuvDesc), i, i, i, i, i, i, i] +
+                                           [p, P(i64)] * 6 + [p, p, p],
+        "mlic_residual_yuv_samples": [i, i, i, i, P(C.c_uint64)],
+        "mlic_residual_yuv_plane_words": [i, i, i, i, i, P(C.c_uint64)],
+        "mlic_container_write_residual_yuv": [C.c_uint32, C.c_uint32, i, i, i, i, i, i, i, i, i, C.c_uint64, p, p,
+                                              C.c_uint32, C.c_uint32, p, p, sz, p, sz, p, sz, p, sz, P(sz)],
+        "mlic_container_parse_residual_yuv": [p, sz, i, C.c_uint64, P(ContainerResidualYuvInfo)],
         "mlic_neglog2_sum": [p, p, i, i64, p],
         "mlic_gaussian_likelihood": [p, p, p, p, i64, f, p],
         "mlic_scale_indexes": [p, p, i64, p, i, p],

@@ -440,9 +440,10 @@ def peek(data: bytes, vbr: bool = False, n_levels: Optional[int] = None, max_pix
     "base_bytes" (the inner file), "residual_bytes" (the residual string), "header_bytes" (the rest: header, tables
     and the two length words), bytes, bpp}; a segmented one ("MLR2") also "residual_segment" and "segments", and its
     "residual_bytes" are the index and the segments; a deep one ("MLR3", is_residual_deep_file) besides those
-    "depth", "shift" and "low_bytes" (the low-bit plane)."""
+    "depth", "shift" and "low_bytes" (the low-bit plane); a Y'CbCr one ("MLR4", is_residual_yuv_file) besides those
+    "sub", "matrix", "full_range" and "site_x" (H, W are the luma size)."""
     data = bytes(data)
-    if is_residual_file(data) or is_residual_deep_file(data):
+    if is_residual_file(data) or is_residual_deep_file(data) or bytes(data[:4]) == b"MLR4":
         return _peek_residual(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
     if is_layered_file(data):
         return _peek_layered(data, n_levels, MAX_PIXELS if max_pixels is None else max_pixels)
@@ -820,6 +821,7 @@ def _peek_scaled(data: bytes, n_levels, max_pixels) -> Dict:
 RESIDUAL_MAGIC = b"MLR1"
 RESIDUAL_SEG_MAGIC = b"MLR2"  # the segmented residual file (DESIGN.md §5 "Residual coding", "Segments")
 RES_SEG_MIN, RES_SEG_MAX, RES_SEG_SLACK = 256, 65536, 4
+RES_SEG_MAX_N = 1 << 29  # samples of one string (csrc/residual_seg.h)
 DEFAULT_RESIDUAL_SEGMENT = 4096
 MAX_TAU = 127
 RES_CTX, RES_BINS, RES_MAX_M, RES_ABSENT, RES_CDF_STRIDE = 24, 128, 63, 0xFF, 129
@@ -1083,8 +1085,8 @@ def _file_tables(data: bytes, s: _lib.ContainerResidualInfo) -> Dict:
 
 
 def strip_residual(data: bytes, n_levels: Optional[int] = None, max_pixels: int = MAX_PIXELS) -> bytes:
-    """The inner file of a residual file ("MLR1", "MLR2" or "MLR3"): byte for byte what encode_images writes without
-    max_error= (for "MLR3": what encode_images(depth=) writes)."""
+    """The inner file of a residual file ("MLR1", "MLR2", "MLR3" or "MLR4"): byte for byte what encode_images writes
+    without max_error= (for "MLR3": what encode_images(depth=) writes; for "MLR4": what encode_yuv writes)."""
     data = bytes(data)
     s = _parse_residual_any(data, n_levels, max_pixels)
     return data[s.inner_off:s.inner_off + s.inner_len]
@@ -1092,6 +1094,8 @@ def strip_residual(data: bytes, n_levels: Optional[int] = None, max_pixels: int 
 
 def _parse_residual_any(data: bytes, n_levels, max_pixels):
     """The parse of a residual file of any kind (told apart by the magic)."""
+    if bytes(data[:4]) == b"MLR4":
+        return parse_container_residual_yuv(data, n_levels, max_pixels)
     if is_residual_deep_file(data):
         return parse_container_residual_deep(data, n_levels, max_pixels)
     if is_residual_seg_file(data):
@@ -1107,11 +1111,15 @@ def _peek_residual(data: bytes, n_levels, max_pixels) -> Dict:
            "y_len": c.y_len, "z_len": c.z_len, "digest": int(s.digest), "base_bytes": int(s.inner_len),
            "residual_bytes": int(s.res_len), "header_bytes": len(data) - int(s.inner_len) - int(s.res_len),
            "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
-    if is_residual_seg_file(data) or is_residual_deep_file(data):
+    yuv = bytes(data[:4]) == b"MLR4"
+    if is_residual_seg_file(data) or is_residual_deep_file(data) or yuv:
         out.update(residual_segment=int(s.seg_len), segments=int(s.n_seg))
-    if is_residual_deep_file(data):
+    if is_residual_deep_file(data) or yuv:
         out.update(depth=int(s.depth), shift=int(s.shift), low_bytes=int(s.lo_len))
         out["header_bytes"] -= int(s.lo_len)
+    if yuv:
+        out.update(sub=(int(s.sub_x), int(s.sub_y)), matrix={0: "bt601", 1: "bt709", 2: "bt2020"}[int(s.matrix)],
+                   full_range=bool(s.full_range), site_x="left" if s.site_x else "centre")
     return out
 
 
@@ -1172,14 +1180,21 @@ def residual_segment_cap(H: int, W: int, segment: int) -> int:
 
 
 def _seg_images(sym, ctx, what: str):
-    ok = lambda t, dt: torch.is_tensor(t) and t.dtype == dt and t.dim() == 4 and t.size(1) == 3  # noqa: E731
+    """-> (B, N, (H, W) or None): [B,3,H,W] planes of an RGB image, or [B,N] strings of N samples (a Y'CbCr frame's
+    canonical order), which take the entries with N in place of H, W."""
+    ok = lambda t, dt: torch.is_tensor(t) and t.dtype == dt and (t.dim() == 2 or (t.dim() == 4 and t.size(1) == 3))  # noqa: E731
     if sym is not None and not ok(sym, torch.int16):
-        raise ValueError(f"{what}: sym must be an int16 tensor [B,3,H,W]")
+        raise ValueError(f"{what}: sym must be an int16 tensor [B,3,H,W] (or [B,N])")
     if not ok(ctx, torch.uint8):
-        raise ValueError(f"{what}: ctx must be a uint8 tensor [B,3,H,W]")
+        raise ValueError(f"{what}: ctx must be a uint8 tensor [B,3,H,W] (or [B,N])")
     if sym is not None and (tuple(sym.shape) != tuple(ctx.shape) or sym.device != ctx.device):
         raise ValueError(f"{what}: sym {tuple(sym.shape)} and ctx {tuple(ctx.shape)} must match, on one device")
-    return ctx.size(0), ctx.size(2), ctx.size(3)
+    if ctx.dim() == 2:
+        if not 1 <= ctx.size(1) <= RES_SEG_MAX_N:
+            raise ValueError(f"{what}: N must be in [1, 2^29], got {ctx.size(1)}")
+        return ctx.size(0), ctx.size(1), None
+    return ctx.size(0), 3 * ctx.size(2) * ctx.size(3), (ctx.size(2), ctx.size(3))
+
 
 
 def residual_encode_segments(sym, ctx, tables, segment: int, coder: str = "device", cap: Optional[int] = None,
@@ -1192,12 +1207,13 @@ def residual_encode_segments(sym, ctx, tables, segment: int, coder: str = "devic
     take the host entry, which gives the same bytes.  cap: the bytes allowed per image (default: the bound
     residual_segment_cap); out: an optional uint8 device buffer of at least B cap bytes to code into."""
     what = "residual_encode_segments"
-    B, H, W = _seg_images(sym, ctx, what)
+    B, N, hw = _seg_images(sym, ctx, what)
     L, coder = _check_segment(segment, what), _check_coder(coder, what)
-    N = 3 * H * W
     n_seg = -(-N // L)
+    size = hw if hw is not None else (N,)  # H, W of an RGB image, or N alone (the _n entries)
+    sfx = "" if hw is not None else "_n"
     m, freq = _seg_tables(tables, B, what)
-    cap = residual_segment_cap(H, W, L) if cap is None else int(cap)
+    cap = 4 * (N + RES_SEG_SLACK * n_seg) if cap is None else int(cap)
     lens = (C.c_uint64 * B)()
     if sym.is_cuda and coder == "device":
         sym, ctx = sym.contiguous(), ctx.contiguous()
@@ -1209,8 +1225,8 @@ def residual_encode_segments(sym, ctx, tables, segment: int, coder: str = "devic
                 raise ValueError(f"{what}: out must be a contiguous uint8 tensor of at least {B * cap} bytes on {dev}")
             segb = torch.empty(B, n_seg, dtype=torch.int32, device=dev)
             scratch = _seg_scratch(B, n_seg, dev)
-            _seg_call("mlic_residual_encode_segments", what, _stream(), C.c_void_p(sym.data_ptr()),
-                      C.c_void_p(ctx.data_ptr()), B, H, W, m.ctypes.data, freq.ctypes.data, L, n_seg,
+            _seg_call("mlic_residual_encode_segments" + sfx, what, _stream(), C.c_void_p(sym.data_ptr()),
+                      C.c_void_p(ctx.data_ptr()), B, *size, m.ctypes.data, freq.ctypes.data, L, n_seg,
                       C.c_void_p(out.data_ptr()), cap, C.c_void_p(segb.data_ptr()), lens, C.c_void_p(scratch.data_ptr()),
                       scratch.numel(), None)
             top = max(lens)
@@ -1221,7 +1237,7 @@ def residual_encode_segments(sym, ctx, tables, segment: int, coder: str = "devic
         c = np.ascontiguousarray(ctx.cpu().numpy())
         data = np.empty((B, cap), np.uint8)
         segb = np.empty((B, n_seg), np.uint32)
-        _seg_call("mlic_residual_encode_segments_host", what, s.ctypes.data, c.ctypes.data, B, H, W, m.ctypes.data,
+        _seg_call("mlic_residual_encode_segments_host" + sfx, what, s.ctypes.data, c.ctypes.data, B, *size, m.ctypes.data,
                   freq.ctypes.data, L, n_seg, data.ctypes.data, cap, segb.ctypes.data, lens)
     return [(data[b, :lens[b]].tobytes(), segb[b].copy()) for b in range(B)]
 
@@ -1235,10 +1251,12 @@ def residual_decode_segments(data, seg_bytes, ctx, tables, segment: int, coder: 
     that does not, or that holds what a well-formed one cannot, raises ResidualSegmentError.  out: an optional
     contiguous int16 device tensor of at least B 3 H W elements to decode into (the result is a view of it)."""
     what = "residual_decode_segments"
-    B, H, W = _seg_images(None, ctx, what)
+    B, N, hw = _seg_images(None, ctx, what)
     L, coder = _check_segment(segment, what), _check_coder(coder, what)
-    N = 3 * H * W
     n_seg = -(-N // L)
+    size = hw if hw is not None else (N,)
+    sfx = "" if hw is not None else "_n"
+    shape = tuple(ctx.shape)
     m, freq = _seg_tables(tables, B, what)
     data = [bytes(d) for d in data]
     if len(data) != B or len(seg_bytes) != B:
@@ -1257,23 +1275,23 @@ def residual_decode_segments(data, seg_bytes, ctx, tables, segment: int, coder: 
         dev = ctx.device
         with torch.cuda.device(dev):
             if out is None:
-                sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
+                sym = torch.empty(shape, dtype=torch.int16, device=dev)
                 if _lib.poison():
                     sym.fill_(-0x1112)
             elif out.dtype != torch.int16 or out.device != dev or not out.is_contiguous() or out.numel() < B * N:
                 raise ValueError(f"{what}: out must be a contiguous int16 tensor of at least {B * N} elements on {dev}")
             else:
-                sym = out.view(-1)[:B * N].view(B, 3, H, W)
+                sym = out.view(-1)[:B * N].view(shape)
             scratch = _seg_scratch(B, n_seg, dev)
             d_dev = torch.from_numpy(buf).to(dev)
-            _seg_call("mlic_residual_decode_segments", what, _stream(), C.c_void_p(d_dev.data_ptr()), buf.shape[1], lens,
-                      segb.ctypes.data, C.c_void_p(ctx.data_ptr()), B, H, W, m.ctypes.data, freq.ctypes.data, L, n_seg,
+            _seg_call("mlic_residual_decode_segments" + sfx, what, _stream(), C.c_void_p(d_dev.data_ptr()), buf.shape[1],
+                      lens, segb.ctypes.data, C.c_void_p(ctx.data_ptr()), B, *size, m.ctypes.data, freq.ctypes.data, L, n_seg,
                       C.c_void_p(sym.data_ptr()), C.c_void_p(scratch.data_ptr()), scratch.numel(), None)
         return sym
     c = np.ascontiguousarray(ctx.cpu().numpy())
-    q = np.empty((B, 3, H, W), np.int16)
-    _seg_call("mlic_residual_decode_segments_host", what, buf.ctypes.data, buf.shape[1], lens, segb.ctypes.data,
-              c.ctypes.data, B, H, W, m.ctypes.data, freq.ctypes.data, L, n_seg, q.ctypes.data)
+    q = np.empty(shape, np.int16)
+    _seg_call("mlic_residual_decode_segments_host" + sfx, what, buf.ctypes.data, buf.shape[1], lens, segb.ctypes.data,
+              c.ctypes.data, B, *size, m.ctypes.data, freq.ctypes.data, L, n_seg, q.ctypes.data)
     return torch.from_numpy(q).to(ctx.device)
 
 
@@ -2691,6 +2709,8 @@ def decode_images(net, files: Sequence[bytes], ref=None, max_pixels: int = MAX_P
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_images: no files")
+    if any(bytes(f[:4]) == b"MLR4" for f in files):
+        raise ValueError("decode_images: a Y'CbCr residual file (MLR4) holds planes, not RGB: decode_yuv decodes it")
     if any(is_residual_deep_file(f) for f in files):
         for name, given in (("slices=", slices is not None), ("out_size=", out_size is not None),
                             ("filter=", filter is not None), ("msb=True", bool(msb))):
@@ -3801,16 +3821,29 @@ def encode_yuv(net, y, cb, cr, fmt: YuvFormat, level=None, max_bpp: Optional[flo
 
 @torch.no_grad()
 def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels: int = MAX_PIXELS, out_size=None,
-               slices=None):
+               slices=None, enhance: bool = True, residual_coder: str = "device"):
     """Files of one H x W -> ((y, cb, cr) on the model's device, info): decode_images with the Y'CbCr egress.
     info[b] holds H, W, level, bytes and bpp and, with ref=(y, cb, cr) of the originals, sq_err (three ints: Y, Cb,
     Cr), psnr_y, psnr_u, psnr_v and psnr_yuv = (6 Y + U + V) / 8 (peak 2^depth - 1).  The planes are uint8 for a
     format of depth 8 and uint16 words above; the file does not know its depth.  ROI, tiled and layered files and
-    slices= are refused."""
+    slices= are refused.  "MLR4" files (encode_residual_yuv's) decode through the residual layer: the planes are the
+    input samples exactly at max_error 0 and within it otherwise, info gains encode_residual_yuv's fields and, with
+    ref, "max_abs_err"; an fmt whose depth, sub, matrix, range or siting differ from the file's is refused by the
+    field's name; enhance=False gives the base planes alone; a mix of residual and plain files is refused."""
     fmt = _check_fmt(fmt, "decode_yuv")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("decode_yuv: no files")
+    res = [is_residual_yuv_file(f) for f in files]
+    if any(res):
+        if not all(res):
+            raise ValueError("decode_yuv: residual (MLR4) and plain files cannot be mixed in one call")
+        if out_size is not None or slices is not None:
+            raise ValueError("decode_yuv: out_size= / slices= together with residual (MLR4) files are not supported")
+        if not isinstance(enhance, (bool, np.bool_)):
+            raise ValueError(f"decode_yuv: enhance must be a bool, got {enhance!r}")
+        return _decode_residual_yuv(net, files, fmt, ref, max_pixels, bool(enhance),
+                                    _check_coder(residual_coder, "decode_yuv"))
     if any(is_tiled_file(f) for f in files):
         raise ValueError("decode_yuv: tiled files together with Y'CbCr frames are not supported")
     if slices is not None or any(is_layered_file(f) for f in files):
@@ -3837,6 +3870,588 @@ def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels
             d.update(psnr_yuv_from_sq_err(sq[b], H, W, fmt))
         info.append(d)
     return tuple(r[:3]), info
+
+# ---- residual coding of Y'CbCr frames (csrc/residual_yuv.h, csrc/residual_yuv.hip; DESIGN.md §5 "Y'CbCr frames")
+RESIDUAL_YUV_MAGIC = b"MLR4"
+_residual_shift_rule = residual_shift  # encode_residual_yuv has a parameter of that name
+
+
+def is_residual_yuv_file(data: bytes) -> bool:
+    return bytes(data[:4]) == RESIDUAL_YUV_MAGIC
+
+
+def _check_shift_yuv(shift, depth: int, what: str) -> int:
+    top = 0 if depth == 8 else depth - 7
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 0 <= shift <= top:
+        raise ValueError(f"{what}: shift must be an integer in [0, {top}] at depth {depth} (0 at depth 8, depth - 7 "
+                         f"above), got {shift!r}")
+    return int(shift)
+
+
+def residual_yuv_geom(H: int, W: int, sub) -> Dict:
+    """The sizes of one frame in the canonical order (csrc/residual_yuv.h): per plane "h", "w", "off" (the index of
+    its first sample), "G" (64-column groups of a row) and "rowbase" (groups before its first row); "N" samples and
+    "groups" (the low-bit plane has groups * shift 64-bit words)."""
+    sx, sy = sub
+    h = [H, -(-H // sy), -(-H // sy)]
+    w = [W, -(-W // sx), -(-W // sx)]
+    G = [-(-v // 64) for v in w]
+    off, rowbase, o, r = [], [], 0, 0
+    for p in range(3):
+        off.append(o)
+        rowbase.append(r)
+        o += h[p] * w[p]
+        r += h[p] * G[p]
+    return {"h": h, "w": w, "off": off, "G": G, "rowbase": rowbase, "N": o, "groups": r}
+
+
+def residual_yuv_samples(H: int, W: int, sub) -> int:
+    """N = H W + 2 hc wc, the samples of one frame (mlic_residual_yuv_samples)."""
+    n = C.c_uint64()
+    _lib.call("mlic_residual_yuv_samples", int(H), int(W), int(sub[0]), int(sub[1]), C.byref(n))
+    return n.value
+
+
+def residual_yuv_plane_words(H: int, W: int, sub, shift: int) -> int:
+    """64-bit words of one frame's low-bit plane: shift (H G_0 + 2 hc G_1) (mlic_residual_yuv_plane_words)."""
+    n = C.c_uint64()
+    _lib.call("mlic_residual_yuv_plane_words", int(H), int(W), int(sub[0]), int(sub[1]), int(shift), C.byref(n))
+    return n.value
+
+
+def _yuv_samples_np(planes, fmt: YuvFormat):
+    """Three planes (any device) -> three int64 sample arrays [B,h,w]."""
+    if fmt.depth == 8:
+        return [t.cpu().numpy().astype(np.int64) for t in planes]
+    return [samples_of_words(t.cpu(), fmt.depth, fmt.msb).numpy().astype(np.int64) for t in planes]
+
+
+def _pack_plane_yuv_np(lo, shift: int) -> np.ndarray:
+    """Three lo arrays int64 [B,h_p,w_p] -> the low-bit planes uint64 [B, groups * shift]: rows in canonical order,
+    word (rowbase_p + y G_p + g) shift + j holds bit j of lo at bit x mod 64, zero beyond the plane's width."""
+    B = lo[0].shape[0]
+    bit = np.uint64(1) << np.arange(64, dtype=np.uint64)
+    parts = []
+    for v in lo:
+        _, h, w = v.shape
+        G = -(-w // 64)
+        pad = np.zeros((B, h, 64 * G), np.uint64)
+        pad[..., :w] = v.astype(np.uint64)
+        pad = pad.reshape(B, h, G, 64)
+        out = np.zeros((B, h, G, shift), np.uint64)
+        for j in range(shift):
+            out[..., j] = (((pad >> np.uint64(j)) & np.uint64(1)) * bit).sum(-1, dtype=np.uint64)
+        parts.append(out.reshape(B, -1))
+    return np.concatenate(parts, 1)
+
+
+def _unpack_plane_yuv_np(plane: np.ndarray, geom: Dict, shift: int):
+    """The inverse of _pack_plane_yuv_np: uint64 [B, groups * shift] -> three lo arrays int64 [B,h_p,w_p]."""
+    B = plane.shape[0]
+    out = []
+    for p in range(3):
+        h, w, G = geom["h"][p], geom["w"][p], geom["G"][p]
+        if shift == 0:
+            out.append(np.zeros((B, h, w), np.int64))
+            continue
+        a = geom["rowbase"][p] * shift
+        words = plane[:, a:a + h * G * shift].reshape(B, h, G, shift, 1)
+        bits = ((words >> np.arange(64, dtype=np.uint64).reshape(1, 1, 1, 1, 64)) & np.uint64(1)).astype(np.int64)
+        lo = (bits << np.arange(shift, dtype=np.int64).reshape(1, 1, 1, shift, 1)).sum(3)
+        out.append(lo.reshape(B, h, 64 * G)[..., :w])
+    return out
+
+
+def _residual_front_yuv_cpu(base, x, fmt: YuvFormat, tau: int, shift: int, stats: bool = False) -> Dict:
+    """residual_front_yuv / residual_stats_yuv in NumPy integers: the definitions of csrc/residual_yuv.h written out."""
+    d = fmt.depth
+    b = _yuv_samples_np(base, fmt)
+    B = b[0].shape[0]
+    out = {}
+    ctx = None
+    if not stats:
+        ctx = []
+        for p, v in enumerate(b):
+            h, w = v.shape[1:]
+            pad = np.pad(v, ((0, 0), (1, 1), (1, 1)), mode="edge")
+            win = [pad[:, dy:dy + h, dx:dx + w] for dy in range(3) for dx in range(3)]
+            a = (np.maximum.reduce(win) - np.minimum.reduce(win)) >> (d - 8)
+            ctx.append((_CLASS_OF[a] + 8 * p).astype(np.uint8).reshape(B, -1))
+        ctx = np.concatenate(ctx, 1)
+        flat = np.concatenate([v.reshape(B, -1) for v in b], 1)
+        count = np.stack([np.bincount(ctx[i], minlength=RES_CTX) for i in range(B)])
+        with np.errstate(over="ignore"):
+            wgt = np.arange(1, flat.shape[1] + 1, dtype=np.uint64) * np.uint64(_DIGEST_K)
+            digest = ((flat + 1).astype(np.uint64) * wgt).sum(1, dtype=np.uint64)
+        out = {"ctx": torch.from_numpy(ctx), "ctx_count": torch.from_numpy(count.astype(np.int64)),
+               "digest": torch.from_numpy(digest.view(np.int64).copy())}
+    if x is None:
+        return out
+    xv = _yuv_samples_np(x, fmt)
+    step, maxv = 2 * tau + 1, fmt.maxv
+    q = [np.sign(a - c) * ((np.abs(a - c) + tau) // step) for a, c in zip(xv, b)]
+    aq = np.concatenate([np.abs(v).reshape(B, -1) for v in q], 1)
+    out.update(max_abs_q=torch.from_numpy(aq.max(1)), sum_abs_q=torch.from_numpy(aq.sum(1)))
+    if stats:
+        return out
+    rec = [np.clip(c + v * step, 0, maxv) for c, v in zip(b, q)]
+    hi = [v >> shift for v in q]
+    lo = [v - (u << shift) for v, u in zip(q, hi)]
+    hif = np.concatenate([v.reshape(B, -1) for v in hi], 1)
+    bins = np.where(np.abs(hif) <= RES_MAX_M, hif + RES_MAX_M, RES_BINS - 1)
+    key = ctx.astype(np.int64) * RES_BINS + bins
+    hist = np.stack([np.bincount(key[i], minlength=RES_CTX * RES_BINS) for i in range(B)])
+    err = np.concatenate([np.abs(a - r).reshape(B, -1) for a, r in zip(xv, rec)], 1)
+    out.update(sym=torch.from_numpy(np.clip(hif, -32768, 32767).astype(np.int16)),
+               plane=torch.from_numpy(_pack_plane_yuv_np(lo, shift).view(np.int64).copy()),
+               hist=torch.from_numpy(hist.reshape(B, RES_CTX, RES_BINS).astype(np.int64)),
+               max_err=torch.from_numpy(err.max(1).astype(np.int64)))
+    return out
+
+
+def _residual_planes(base, x, fmt: YuvFormat, what: str):
+    base = _yuv_planes(*base, fmt, f"{what} base")
+    if x is not None:
+        x = _yuv_planes(*x, fmt, f"{what} x")
+        if tuple(x[0].shape) != tuple(base[0].shape):
+            raise ValueError(f"{what}: x {tuple(x[0].shape)} does not match base {tuple(base[0].shape)}")
+        if x[0].device != base[0].device:
+            raise ValueError(f"{what}: base and x are on different devices")
+    return base, x
+
+
+def _planes_in_place(planes, fmt: YuvFormat):
+    if fmt.depth == 8:
+        return tuple(t.contiguous() if t.stride(2) == 0 else t for t in planes)
+    return tuple(_dense_u16(t, (2,)) for t in planes)
+
+
+def _yuv_entry(kind: str, fmt: YuvFormat):
+    """(the entry's name, the depth arguments the 16-bit entry takes)."""
+    return (f"mlic_image_residual_{kind}_yuv8", ()) if fmt.depth == 8 else \
+        (f"mlic_image_residual_{kind}_yuv16", (fmt.depth, int(fmt.msb)))
+
+
+def residual_front_yuv(base, x=None, fmt: Optional[YuvFormat] = None, tau: int = 0, shift: int = 0) -> Dict:
+    """residual_front16 for the planes of Y'CbCr frames (csrc/residual_yuv.hip, one launch over the three planes of
+    all frames; DESIGN.md §5 "Residual coding", "Y'CbCr frames").  base, x: (y, cb, cr) in the forms ingest_yuv
+    takes (uint8 planes at fmt.depth 8, uint16 words above, any strides: dense, semi-planar views, pitched rows).
+    Returns {"ctx" uint8 [B,N], "ctx_count" int64 [B,24], "digest" int64 [B]} in the canonical order (plane, row,
+    column; N = H W + 2 hc wc) and, with x, {"sym" int16 [B,N] (hi, saturated), "plane" int64 [B, shift (H G_0 +
+    2 hc G_1)], "hist" int64 [B,24,128], "max_err", "max_abs_q", "sum_abs_q" int64 [B]}.  The shift is 0 at depth 8.
+    CPU tensors take the NumPy restatement (the same bits)."""
+    what = "residual_front_yuv"
+    fmt, tau = _check_fmt(fmt, what), _check_tau(tau, what)
+    shift = _check_shift_yuv(shift, fmt.depth, what)
+    base, x = _residual_planes(base, x, fmt, what)
+    if not base[0].is_cuda:
+        return _residual_front_yuv_cpu(base, x, fmt, tau, shift)
+    B, H, W = base[0].shape
+    N = residual_yuv_samples(H, W, fmt.sub)
+    base = _planes_in_place(base, fmt)
+    dev = base[0].device
+    with torch.cuda.device(dev):
+        ctx = torch.empty(B, N, dtype=torch.uint8, device=dev)
+        count = torch.empty(B, RES_CTX, dtype=torch.int32, device=dev)
+        digest = torch.empty(B, dtype=torch.int64, device=dev)
+        sym = plane = hist = merr = mq = sq = None
+        if x is not None:
+            x = _planes_in_place(x, fmt)
+            sym = torch.empty(B, N, dtype=torch.int16, device=dev)
+            plane = torch.empty(B, residual_yuv_plane_words(H, W, fmt.sub, shift), dtype=torch.int64, device=dev)
+            hist = torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev)
+            merr = torch.empty(B, dtype=torch.int32, device=dev)
+            mq = torch.empty(B, dtype=torch.int32, device=dev)
+            sq = torch.empty(B, dtype=torch.int64, device=dev)
+        if _lib.poison():  # what the kernel does not write shows
+            ctx.fill_(0xEE)
+            for t in (count, digest, hist, merr, mq, sq, plane):
+                if t is not None:
+                    t.fill_(-1)
+            if sym is not None:
+                sym.fill_(-0x1112)
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        name, deep = _yuv_entry("front", fmt)
+        d = fmt.desc()
+        _lib.call(name, _stream(), *_plane_args(*base), *([None] * 6 if x is None else _plane_args(*x)), C.byref(d),
+                  *deep, B, H, W, tau, shift, ptr(ctx), ptr(count), ptr(digest), ptr(sym), ptr(plane), ptr(hist),
+                  ptr(merr), ptr(mq), ptr(sq))
+        out = {"ctx": ctx, "ctx_count": count.to(torch.int64), "digest": digest}
+        if x is not None:
+            out.update(sym=sym, plane=plane, hist=hist.to(torch.int64), max_err=merr.to(torch.int64),
+                       max_abs_q=mq.to(torch.int64), sum_abs_q=sq)
+    return out
+
+
+def residual_stats_yuv(base, x, fmt: YuvFormat, tau: int = 0) -> Dict:
+    """{"max_abs_q" int64 [B], "sum_abs_q" int64 [B]} of the quantised residual of the planes x against base: what the
+    shift is chosen from (residual_shift with the frame's N), by a statistics launch of the front kernel."""
+    what = "residual_stats_yuv"
+    fmt, tau = _check_fmt(fmt, what), _check_tau(tau, what)
+    if x is None:
+        raise ValueError(f"{what}: x is needed")
+    base, x = _residual_planes(base, x, fmt, what)
+    if not base[0].is_cuda:
+        return _residual_front_yuv_cpu(base, x, fmt, tau, 0, stats=True)
+    B, H, W = base[0].shape
+    base, x = _planes_in_place(base, fmt), _planes_in_place(x, fmt)
+    dev = base[0].device
+    with torch.cuda.device(dev):
+        mq = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        sq = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        name, deep = _yuv_entry("stats", fmt)
+        d = fmt.desc()
+        _lib.call(name, _stream(), *_plane_args(*base), *_plane_args(*x), C.byref(d), *deep, B, H, W, tau,
+                  C.c_void_p(mq.data_ptr()), C.c_void_p(sq.data_ptr()))
+    return {"max_abs_q": mq.to(torch.int64), "sum_abs_q": sq}
+
+
+def _residual_apply_yuv_cpu(base, sym, plane, fmt: YuvFormat, tau, shift, ref, out):
+    b = _yuv_samples_np(base, fmt)
+    B, H, W = b[0].shape
+    geom = residual_yuv_geom(H, W, fmt.sub)
+    hi = np.asarray(sym.cpu()).astype(np.int64).reshape(B, -1)
+    bad = np.flatnonzero((np.abs(hi) > RES16_MAX_HI).any(1))
+    if bad.size:
+        raise ValueError(f"residual_apply_yuv: frame {int(bad[0])} holds a symbol outside [-255, 255]")
+    lo = _unpack_plane_yuv_np(np.ascontiguousarray(plane.cpu().numpy()).view(np.uint64).reshape(B, -1), geom, shift)
+    rec = []
+    for p in range(3):
+        h, w, o = geom["h"][p], geom["w"][p], geom["off"][p]
+        q = (hi[:, o:o + h * w].reshape(B, h, w) << shift) + lo[p]
+        rec.append(np.clip(b[p] + q * (2 * tau + 1), 0, fmt.maxv))
+    if fmt.depth == 8:
+        planes = tuple(torch.from_numpy(v.astype(np.uint8)) for v in rec)
+    else:
+        planes = tuple(words_of_samples(torch.from_numpy(v), fmt.depth, fmt.msb) for v in rec)
+    if out is not None:
+        for o, v in zip(out, planes):
+            o.copy_(v)
+        planes = tuple(out)
+    if ref is None:
+        return planes
+    r = _yuv_samples_np(ref, fmt)
+    d = [a - c for a, c in zip(rec, r)]
+    sq = np.stack([(v * v).reshape(B, -1).sum(1) for v in d], 1)
+    me = np.stack([np.abs(v).reshape(B, -1).max(1) for v in d], 1).max(1)
+    return planes + (torch.from_numpy(sq), torch.from_numpy(me))
+
+
+def residual_apply_yuv(base, sym, plane, fmt: YuvFormat, tau: int, shift: int, ref=None, out=None):
+    """The Y'CbCr decoder's last pass (csrc/residual_yuv.hip, one launch): the three planes clamp(base + ((sym <<
+    shift) + lo) (2 tau + 1), 0, 2^depth - 1) in fmt's word type and alignment, lo read from `plane` (int64 [B, shift
+    (H G_0 + 2 hc G_1)], residual_front_yuv's).  sym: int16 [B,N], dense, on base's device; a sym outside [-255, 255]
+    is refused (ValueError naming the frame).  out: optional (y, cb, cr) of the planes' shapes with any strides:
+    only the planes' samples are written.  ref (y, cb, cr): returns (y, cb, cr, sq_err int64 [B,3], max_abs_err
+    int64 [B]), exact.  CPU tensors take the NumPy restatement."""
+    what = "residual_apply_yuv"
+    fmt, tau = _check_fmt(fmt, what), _check_tau(tau, what)
+    shift = _check_shift_yuv(shift, fmt.depth, what)
+    base = _yuv_planes(*base, fmt, f"{what} base")
+    B, H, W = base[0].shape
+    dev = base[0].device
+    N = residual_yuv_geom(H, W, fmt.sub)["N"]
+    if not torch.is_tensor(sym) or sym.dtype != torch.int16 or tuple(sym.shape) != (B, N):
+        raise ValueError(f"{what}: sym must be an int16 tensor {(B, N)}")
+    words = residual_yuv_geom(H, W, fmt.sub)["groups"] * shift
+    if not torch.is_tensor(plane) or plane.dtype != torch.int64 or tuple(plane.shape) != (B, words):
+        raise ValueError(f"{what}: plane must be an int64 tensor {(B, words)}")
+    if sym.device != dev or plane.device != dev:
+        raise ValueError(f"{what}: base, sym and plane must be on one device")
+    shapes = tuple(tuple(t.shape) for t in base)
+    if out is not None:
+        out = tuple(out)
+        if len(out) != 3 or any(not torch.is_tensor(t) or t.dtype != fmt.dtype or tuple(t.shape) != s or t.device != dev
+                                for t, s in zip(out, shapes)):
+            raise ValueError(f"{what}: out must be three {'uint8' if fmt.depth == 8 else 'uint16'} tensors {shapes} "
+                             f"on {dev}")
+    if ref is not None:
+        ref = _yuv_planes(*ref, fmt, f"{what} ref")
+        if tuple(ref[0].shape) != shapes[0]:
+            raise ValueError(f"{what}: ref must be a frame batch of {shapes[0]}, got {tuple(ref[0].shape)}")
+        ref = tuple(t.to(dev) for t in ref)
+    if not base[0].is_cuda:
+        return _residual_apply_yuv_cpu(base, sym, plane, fmt, tau, shift, ref, out)
+    base = _planes_in_place(base, fmt)
+    sym, plane = sym.contiguous(), plane.contiguous()
+    with torch.cuda.device(dev):
+        if out is None:
+            if fmt.depth == 8:
+                out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
+            else:
+                out = tuple(torch.empty(s, dtype=torch.int16, device=dev) for s in shapes)
+            if _lib.poison():
+                for t in out:
+                    t.fill_(0xFF if fmt.depth == 8 else -1)
+            if fmt.depth > 8:
+                out = tuple(t.view(torch.uint16) for t in out)
+        elif any(t.stride(2) == 0 for t in out):
+            raise ValueError(f"{what}: an out plane has a zero column stride")
+        sq = merr = None
+        if ref is not None:
+            ref = _planes_in_place(ref, fmt)
+            sq = torch.full((B, 3), -1, dtype=torch.int64, device=dev)
+            merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        status = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        name, deep = _yuv_entry("apply", fmt)
+        d = fmt.desc()
+        _lib.call(name, _stream(), *_plane_args(*base), ptr(sym), ptr(plane), C.byref(d), *deep, B, H, W, tau, shift,
+                  *_plane_args(*out), *([None] * 6 if ref is None else _plane_args(*ref)), ptr(sq), ptr(merr),
+                  ptr(status))
+        bad = torch.nonzero(status).flatten().cpu().tolist()
+        if ref is not None:
+            for t in ref:
+                t.record_stream(torch.cuda.current_stream())
+    if bad:
+        raise ValueError(f"{what}: frame {bad[0]} holds a symbol outside [-255, 255]")
+    return out if ref is None else out + (sq, merr.to(torch.int64))
+
+
+def write_container_residual_yuv(H: int, W: int, inner: bytes, segs: bytes, seg_bytes, segment: int, tau: int,
+                                 fmt: YuvFormat, shift: int, low: bytes, digest: int, m, freq, vbr: bool = False) -> bytes:
+    """The Y'CbCr residual file (mlic_container_write_residual_yuv): "MLR4", the header and the tables of the "MLR2"
+    file (H, W the luma size), depth, shift, sub_x, sub_y, matrix and the flags of `fmt`, seg_len, n_seg, `inner`,
+    the index and `segs`, and behind lo_len the low-bit plane `low` (little-endian 64-bit words).  Whether the
+    words are MSB-aligned is not written: the file holds samples."""
+    inner, segs, low = bytes(inner), bytes(segs), bytes(low)
+    fmt = _check_fmt(fmt, "write_container_residual_yuv")
+    m = np.ascontiguousarray(m, dtype=np.uint8)
+    freq = np.ascontiguousarray(freq, dtype=np.uint16)
+    sb = np.ascontiguousarray(np.asarray(seg_bytes, np.int64).reshape(-1))
+    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
+        raise ValueError(f"write_container_residual_yuv: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
+    if sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF)):
+        raise ValueError("write_container_residual_yuv: segment lengths must fit 32 bits")
+    sb = sb.astype(np.uint32)
+    n = C.c_size_t()
+    args = (H, W, int(bool(vbr)), int(tau), fmt.depth, int(shift), fmt.sub[0], fmt.sub[1], _YUV_MATRIX[fmt.matrix][0],
+            int(fmt.full_range), int(fmt.site_x == "left"), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data,
+            freq.ctypes.data, int(segment) & 0xFFFFFFFF, sb.size, sb.ctypes.data, inner, len(inner), segs, len(segs),
+            low, len(low))
+    _lib.call("mlic_container_write_residual_yuv", *args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_residual_yuv", *args, buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def parse_container_residual_yuv(data: bytes, n_levels: Optional[int] = None,
+                                 max_pixels: int = MAX_PIXELS) -> _lib.ContainerResidualYuvInfo:
+    """The validating parser of a Y'CbCr residual file (mlic_container_parse_residual_yuv): raises _lib.MlicError on
+    any malformed input.  The fields of the "MLR3" parse, and sub_x, sub_y, matrix, full_range, site_x (1: left)."""
+    data = bytes(data)
+    info = _lib.ContainerResidualYuvInfo()
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call("mlic_container_parse_residual_yuv", data, len(data), nl, int(max_pixels), C.byref(info))
+    return info
+
+
+_YUV_MATRIX_NAME = {v[0]: k for k, v in _YUV_MATRIX.items()}
+
+
+def _fmt_fields(fmt: YuvFormat) -> Dict:
+    return {"depth": fmt.depth, "sub": fmt.sub, "matrix": fmt.matrix, "full_range": fmt.full_range,
+            "site_x": fmt.site_x}
+
+
+def _file_fmt_fields(s) -> Dict:
+    return {"depth": int(s.depth), "sub": (int(s.sub_x), int(s.sub_y)), "matrix": _YUV_MATRIX_NAME[int(s.matrix)],
+            "full_range": bool(s.full_range), "site_x": "left" if s.site_x else "centre"}
+
+
+def residual_yuv_format(data: bytes, msb: bool = False, n_levels: Optional[int] = None,
+                        max_pixels: int = MAX_PIXELS) -> YuvFormat:
+    """The YuvFormat an "MLR4" file was written with; msb (the alignment of uint16 words) is the caller's."""
+    f = _file_fmt_fields(parse_container_residual_yuv(data, n_levels, max_pixels))
+    return YuvFormat(f["sub"], f["matrix"], f["full_range"], f["site_x"], f["depth"], bool(msb) and f["depth"] > 8)
+
+
+@torch.no_grad()
+def encode_residual_yuv(net, y, cb, cr, fmt: YuvFormat, max_error: int = 0, level=None,
+                        residual_segment: int = DEFAULT_RESIDUAL_SEGMENT, residual_shift: Optional[int] = None,
+                        residual_coder: str = "device", return_info: bool = False, **refused):
+    """Lossless (max_error=0) and near-lossless coding of Y'CbCr frames (DESIGN.md §5 "Residual coding", "Y'CbCr
+    frames") -> one "MLR4" file per frame.  The planes are ingested and compressed exactly as encode_yuv does (the
+    inner file is that file, byte for byte); the base planes are the decode of that file alone through egress_yuv
+    with the same format.  Above depth 8 residual_stats_yuv gives max|q| and sum|q| per frame and the shift rule
+    (residual_shift with the frame's N) or residual_shift= the split; residual_front_yuv gives the high parts with
+    their contexts and histograms and the low-bit plane; the bound is checked on the device, the high parts go
+    through residual_tables and residual_encode_segments, the low bits are stored raw.  Every sample of every plane
+    comes back within max_error, samples outside the legal range included.  max_bpp, level="auto", roi, tile,
+    scale / coded_size and layered are refused by name.  return_info=True: (files, info), info[b] as
+    encode_residual16 gives it, plus "sub" and "depth"."""
+    what = "encode_residual_yuv"
+    fmt, tau = _check_fmt(fmt, what), _check_tau(max_error, what)
+    names = {"max_bpp": "max_bpp=", "max_passes": "max_bpp=", "roi": "roi=", "roi_levels": "roi=", "tile": "tiles",
+             "coded_size": "scaled coding", "scale": "scaled coding", "layered": "layered="}
+    for k, v in refused.items():
+        if k not in names:
+            raise TypeError(f"{what}() got an unexpected keyword argument {k!r}")
+        if v is not None and v is not False:
+            raise ValueError(f"{what}: residual coding of Y'CbCr frames together with {names[k]} is not supported")
+    if isinstance(level, str):
+        raise ValueError(f"{what}: residual coding of Y'CbCr frames together with level='auto' is not supported")
+    L, coder = _check_segment(residual_segment, what), _check_coder(residual_coder, what)
+    depth = fmt.depth
+    shift = residual_shift
+    if shift is not None:
+        shift = _check_shift_yuv(shift, depth, what)
+    y, cb, cr = _yuv_planes(y, cb, cr, fmt, what)
+    inner, info = encode_yuv(net, y, cb, cr, fmt, level=level, return_info=True)
+    vbr = hasattr(net, "levels")
+    cs = [parse_container(f, vbr, net.levels if vbr else None) for f in inner]
+    pairs = [_strings(f, c) for f, c in zip(inner, cs)]
+    B, H, W = y.shape
+    kw = {"s": [c.level for c in cs]} if vbr else {}
+    x_hat = _base_x_hat(net, [[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), kw, B)
+    base = egress_yuv(x_hat.float(), H, W, fmt)
+    dev = base[0].device
+    x = tuple(t.to(dev) for t in (y, cb, cr))
+    N = residual_yuv_geom(H, W, fmt.sub)["N"]
+    if depth == 8:
+        shifts = [0] * B
+    else:
+        stats = residual_stats_yuv(base, x, fmt, tau)
+        mq, sq = stats["max_abs_q"].cpu().tolist(), stats["sum_abs_q"].cpu().tolist()
+        if shift is None:
+            shifts = [_residual_shift_rule(depth, N, mq[b], sq[b]) for b in range(B)]
+        else:
+            for b in range(B):
+                if not residual_shift_fits(mq[b], shift):
+                    raise ValueError(f"{what}: residual_shift={shift} does not fit frame {b} (its largest |q| is "
+                                     f"{mq[b]}): the smallest shift that fits is {residual_min_shift(depth, mq[b])}")
+            shifts = [shift] * B
+    n_seg = -(-N // L)
+    files = [None] * B
+    a = 0
+    while a < B:  # runs of frames with one shift: one front launch each
+        e = a + 1
+        while e < B and shifts[e] == shifts[a]:
+            e += 1
+        s = shifts[a]
+        front = residual_front_yuv(tuple(t[a:e] for t in base), tuple(t[a:e] for t in x), fmt, tau, s)
+        worst = int(front["max_err"].max())  # computed on the device, beside the symbols
+        if worst > tau:
+            raise RuntimeError(f"{what}: the residual layer leaves an error of {worst} > max_error {tau}")
+        hist = front["hist"].cpu().numpy()
+        digest = front["digest"].cpu().tolist()
+        plane = front["plane"].cpu().numpy()
+        tabs = [residual_tables(hist[j]) for j in range(e - a)]
+        cap = min(max(_seg_cap_of_hist(hist[j], tabs[j], n_seg) for j in range(e - a)), 4 * (N + RES_SEG_SLACK * n_seg))
+        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, L, coder, cap=cap)
+        for j, (segs, seg_bytes) in enumerate(coded):
+            b, t = a + j, tabs[j]
+            low = plane[j].astype("<i8").tobytes()
+            files[b] = write_container_residual_yuv(H, W, inner[b], segs, seg_bytes, L, tau, fmt, s, low, digest[j],
+                                                    t["m"], t["freq"], vbr=vbr)
+            info[b].update(bytes=len(files[b]), bpp=8.0 * len(files[b]) / (H * W), max_error=tau, depth=depth, shift=s,
+                           sub=fmt.sub, base_bytes=len(inner[b]), residual_bytes=len(segs) + 4 * n_seg,
+                           low_bytes=len(low), residual_segment=L, segments=n_seg)
+        a = e
+    return (files, info) if return_info else files
+
+
+def _decode_residual_yuv(net, files, fmt: YuvFormat, ref, max_pixels, enhance, coder):
+    """decode_yuv for "MLR4" files: the inner files decoded to base planes, then the residual layer."""
+    vbr = hasattr(net, "levels")
+    n_levels = net.levels if vbr else None
+    ss = [parse_container_residual_yuv(f, n_levels, max_pixels) for f in files]
+    B = len(files)
+    want = _fmt_fields(fmt)
+    for b, s in enumerate(ss):
+        if bool(s.vbr) != vbr:
+            raise ValueError(f"decode_yuv: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
+                             f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+        got = _file_fmt_fields(s)
+        for k in ("depth", "sub", "matrix", "full_range", "site_x"):
+            if k == "site_x" and got["sub"][0] == 1:
+                continue  # the siting of an unsubsampled frame means nothing
+            if got[k] != want[k]:
+                raise ValueError(f"decode_yuv: file {b} (MLR4) was written with {k}={got[k]!r}, fmt has "
+                                 f"{k}={want[k]!r}: the residual applies to the encoder's base planes only")
+    if len({(s.H, s.W) for s in ss}) != 1:
+        raise ValueError(f"decode_yuv: the files must share one size, got {sorted({(s.H, s.W) for s in ss})}")
+    H, W = ss[0].H, ss[0].W
+    inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
+    extra = [{"max_error": int(s.tau), "depth": int(s.depth), "shift": int(s.shift), "sub": fmt.sub,
+              "residual_bytes": int(s.res_len), "base_bytes": int(s.inner_len), "low_bytes": int(s.lo_len),
+              "residual_segment": int(s.seg_len), "segments": int(s.n_seg), "bytes": len(f),
+              "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
+    if not enhance:
+        planes, info = decode_yuv(net, inner, fmt, ref=ref, max_pixels=max_pixels)
+        for di, e in zip(info, extra):
+            di.update(e, enhanced=False)
+        return planes, info
+    base, info = decode_yuv(net, inner, fmt, max_pixels=max_pixels)
+    geom = residual_yuv_geom(H, W, fmt.sub)
+    if ref is not None:
+        ref = _yuv_planes(*ref, fmt, "decode_yuv ref")
+        if tuple(ref[0].shape) != (B, H, W):
+            raise ValueError(f"decode_yuv: ref must be a frame batch of {(B, H, W)}, got {tuple(ref[0].shape)}")
+        ref = tuple(t.to(base[0].device) for t in ref)
+    one = len({(s.tau, s.shift, s.seg_len) for s in ss}) == 1
+    groups = [list(range(B))] if one else [[b] for b in range(B)]
+    out = tuple(torch.empty(tuple(t.shape), dtype=torch.uint8 if fmt.depth == 8 else torch.int16, device=t.device)
+                for t in base)
+    if fmt.depth > 8:
+        out = tuple(t.view(torch.uint16) for t in out)
+    for g in groups:
+        s0 = ss[g[0]]
+        tau, sh, L = int(s0.tau), int(s0.shift), int(s0.seg_len)
+        sl = slice(g[0], g[-1] + 1)
+        view = tuple(t[sl] for t in base)
+        front = residual_front_yuv(view, None, fmt, tau, 0)
+        digest = front["digest"].cpu().tolist()
+        for j, b in enumerate(g):
+            if (digest[j] & 0xFFFFFFFFFFFFFFFF) == ss[b].digest:
+                continue
+            # the base is defined as the decode of the file alone (the range guard's fp32 re-run takes a whole lane)
+            alone, _ = decode_yuv(net, [inner[b]], fmt, max_pixels=max_pixels)
+            again = int(residual_front_yuv(alone, None, fmt, tau, 0)["digest"].cpu()[0])
+            if (again & 0xFFFFFFFFFFFFFFFF) != ss[b].digest:
+                raise _digest_error(b, int(ss[b].digest), again, net)
+            for t, v in zip(base, alone):
+                (t[b:b + 1] if fmt.depth == 8 else t[b:b + 1].view(torch.int16)).copy_(
+                    v if fmt.depth == 8 else v.view(torch.int16))
+            front = None
+        if front is None:
+            front = residual_front_yuv(view, None, fmt, tau, 0)
+        count = front["ctx_count"].cpu().numpy()
+        tabs = [_file_tables(files[b], ss[b]) for b in g]
+        planes = []
+        for j, b in enumerate(g):
+            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and tabs[j]["m"][k] == RES_ABSENT]
+            if missing:
+                raise ValueError(f"decode_yuv: file {b}: contexts {missing} occur in the base planes but the file has "
+                                 f"no table for them")
+            pl = np.frombuffer(files[b], "<u8", geom["groups"] * sh, ss[b].lo_off)
+            for p in range(3):
+                w, G, a = geom["w"][p], geom["G"][p], geom["rowbase"][p] * sh
+                if sh and w % 64 and (pl[a:a + geom["h"][p] * G * sh].reshape(geom["h"][p], G, sh)[:, -1, :]
+                                      >> np.uint64(w % 64)).any():
+                    raise ValueError(f"decode_yuv: file {b}: the low-bit plane has bits set beyond column {w} of plane "
+                                     f"{p} (its padding bits must be zero)")
+            planes.append(pl.view(np.int64))
+        try:
+            sym_d = residual_decode_segments(
+                [files[b][ss[b].data_off:ss[b].data_off + ss[b].data_len] for b in g],
+                [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g], front["ctx"], tabs, L, coder)
+        except ResidualSegmentError as e:
+            raise ValueError(f"decode_yuv: file {g[e.image]}: segment {e.segment} of the residual string is corrupt: "
+                             f"{e.reason}") from None
+        plane_d = torch.from_numpy(np.stack(planes).reshape(len(g), -1).copy()).to(base[0].device)
+        try:
+            r = residual_apply_yuv(view, sym_d, plane_d, fmt, tau, sh,
+                                   ref=None if ref is None else tuple(t[sl] for t in ref), out=tuple(t[sl] for t in out))
+        except ValueError as e:
+            raise ValueError(f"decode_yuv: files {g[0]}..{g[-1]}: {e}") from None
+        if ref is not None:
+            sq, me = r[3].cpu().tolist(), r[4].cpu().tolist()
+            for j, b in enumerate(g):
+                extra[b].update(psnr_yuv_from_sq_err(sq[j], H, W, fmt), max_abs_err=int(me[j]))
+    for di, e in zip(info, extra):
+        di.update(e)
+    return out, info
 
 
 def psnr_from_sq_err(sq_err: int, n: int, peak: int = 255) -> float:

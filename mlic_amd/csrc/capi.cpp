@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -14,6 +15,7 @@
 #include "residual.h"
 #include "residual16.h"
 #include "residual_seg.h"
+#include "residual_yuv.h"
 
 using namespace mlic;
 
@@ -1626,11 +1628,6 @@ void seg_status_throw(const char* what, const std::vector<uint32_t>& st) {
                   std::to_string(st[b] >> 4) + ": " + residual_seg_reason(st[b] & 15u));
 }
 
-void seg_common_check(const char* what, int B, int H, int W, const uint8_t* m, const uint16_t* freq, int seg_len,
-                      int64_t n_seg) {
-  residual_seg_check(what, B, H, W, seg_len, n_seg);
-  residual_seg_tables_check(what, m, freq, B);
-}
 bool aligned_to(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 }  // namespace
 
@@ -1643,44 +1640,131 @@ int mlic_residual_segments_scratch_bytes(int B, int64_t n_seg, size_t* bytes) {
   });
 }
 
+namespace {
+// the four entries below, for a string of N samples; `check` is residual_seg_check or residual_seg_check_n
+void seg_encode_dev(const std::string& w, const std::function<void()>& check, void* stream, const int16_t* sym, const uint8_t* ctx, int B,
+                    int64_t N, const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                    size_t cap, uint32_t* seg_bytes, uint64_t* len, void* scratch, size_t scratch_bytes,
+                    uint32_t* status) {
+  const char* what = w.c_str();
+  MLIC_CHECK(sym != nullptr, w + ": null sym");
+  MLIC_CHECK(ctx != nullptr, w + ": null ctx");
+  MLIC_CHECK(out != nullptr, w + ": null out");
+  MLIC_CHECK(seg_bytes != nullptr, w + ": null seg_bytes");
+  MLIC_CHECK(len != nullptr, w + ": null len");
+  MLIC_CHECK(scratch != nullptr, w + ": null scratch");
+  check();
+  residual_seg_tables_check(what, m, freq, B);
+  MLIC_CHECK(cap % 4 == 0, w + ": the capacity must be a multiple of 4");
+  MLIC_CHECK(cap >= (size_t)RES_SEG_MIN_BYTES * (size_t)n_seg,
+             w + ": the capacity is too small (below 8 bytes a segment)");
+  MLIC_CHECK(cap <= 0xffffffffu, w + ": the capacity must fit 32 bits");
+  const SegScratch sc(B, n_seg);
+  MLIC_CHECK(scratch_bytes >= sc.size, w + ": scratch too small");
+  MLIC_CHECK(aligned_to(sym, 2) && aligned_to(out, 4) && aligned_to(seg_bytes, 4) && aligned_to(scratch, 16),
+             w + ": sym must be 2-byte, out and seg_bytes 4-byte, scratch 16-byte aligned");
+  std::vector<ResSegEncTable> tabs((size_t)B);
+  for (int b = 0; b < B; ++b)
+    residual_seg_enc_table(m + (size_t)b * RES_CTX, freq + (size_t)b * RES_CTX * RES_BINS, &tabs[(size_t)b]);
+  auto st = (hipStream_t)stream;
+  auto* base = static_cast<uint8_t*>(scratch);
+  auto* d_tabs = reinterpret_cast<ResSegEncTable*>(base + sc.tabs);
+  auto* d_status = reinterpret_cast<uint32_t*>(base + sc.status);
+  auto* d_total = reinterpret_cast<uint64_t*>(base + sc.total);
+  HIP_OK(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(ResSegEncTable) * (size_t)B, hipMemcpyHostToDevice, st));
+  residual_encode_segments(sym, ctx, B, N, seg_len, n_seg, d_tabs, out, cap, reinterpret_cast<uint32_t*>(base + sc.off),
+                           seg_bytes, d_total, d_status, st);
+  std::vector<uint32_t> hs((size_t)B);
+  HIP_OK(hipMemcpyAsync(hs.data(), d_status, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(len, d_total, sizeof(uint64_t) * (size_t)B, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (status) std::copy(hs.begin(), hs.end(), status);
+  seg_status_throw(what, hs);
+}
+
+void seg_decode_dev(const std::string& w, const std::function<void()>& check, void* stream, const uint8_t* data, size_t data_stride,
+                    const uint64_t* data_len, const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N,
+                    const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym, void* scratch,
+                    size_t scratch_bytes, uint32_t* status) {
+  const char* what = w.c_str();
+  MLIC_CHECK(data != nullptr, w + ": null data");
+  MLIC_CHECK(ctx != nullptr, w + ": null ctx");
+  MLIC_CHECK(sym != nullptr, w + ": null sym");
+  MLIC_CHECK(scratch != nullptr, w + ": null scratch");
+  check();
+  residual_seg_tables_check(what, m, freq, B);
+  MLIC_CHECK(data_stride % 4 == 0, w + ": the data stride must be a multiple of 4");
+  residual_seg_lengths_check(what, seg_bytes, data_len, data_stride, B, N, seg_len, n_seg);
+  const SegScratch sc(B, n_seg);
+  MLIC_CHECK(scratch_bytes >= sc.size, w + ": scratch too small");
+  MLIC_CHECK(aligned_to(sym, 2) && aligned_to(data, 4) && aligned_to(scratch, 16),
+             w + ": sym must be 2-byte, data 4-byte, scratch 16-byte aligned");
+  std::vector<ResSegDecTable> tabs((size_t)B);
+  std::vector<uint32_t> offs((size_t)B * n_seg);
+  for (int b = 0; b < B; ++b) {
+    residual_seg_dec_table(m + (size_t)b * RES_CTX, freq + (size_t)b * RES_CTX * RES_BINS, &tabs[(size_t)b]);
+    uint32_t o = 0;
+    for (int64_t k = 0; k < n_seg; ++k) {
+      offs[(size_t)b * n_seg + k] = o;
+      o += seg_bytes[(size_t)b * n_seg + k];
+    }
+  }
+  auto st = (hipStream_t)stream;
+  auto* base = static_cast<uint8_t*>(scratch);
+  auto* d_tabs = reinterpret_cast<ResSegDecTable*>(base + sc.tabs);
+  auto* d_off = reinterpret_cast<uint32_t*>(base + sc.off);
+  auto* d_bytes = reinterpret_cast<uint32_t*>(base + sc.bytes);
+  auto* d_status = reinterpret_cast<uint32_t*>(base + sc.status);
+  HIP_OK(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(ResSegDecTable) * (size_t)B, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_off, offs.data(), sizeof(uint32_t) * offs.size(), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_bytes, seg_bytes, sizeof(uint32_t) * offs.size(), hipMemcpyHostToDevice, st));
+  residual_decode_segments(data, data_stride, d_off, d_bytes, ctx, B, N, seg_len, n_seg, d_tabs, sym, d_status, st);
+  std::vector<uint32_t> hs((size_t)B);
+  HIP_OK(hipMemcpyAsync(hs.data(), d_status, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (status) std::copy(hs.begin(), hs.end(), status);
+  seg_status_throw(what, hs);
+}
+
+void seg_encode_host(const std::string& w, const std::function<void()>& check, const int16_t* sym, const uint8_t* ctx, int B, int64_t N,
+                     const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
+                     uint32_t* seg_bytes, uint64_t* len) {
+  MLIC_CHECK(sym != nullptr, w + ": null sym");
+  MLIC_CHECK(ctx != nullptr, w + ": null ctx");
+  MLIC_CHECK(seg_bytes != nullptr, w + ": null seg_bytes");
+  MLIC_CHECK(len != nullptr, w + ": null len");
+  check();
+  residual_seg_tables_check(w.c_str(), m, freq, B);
+  if (out != nullptr) {
+    MLIC_CHECK(cap % 4 == 0, w + ": the capacity must be a multiple of 4");
+    MLIC_CHECK(cap >= (size_t)RES_SEG_MIN_BYTES * (size_t)n_seg,
+               w + ": the capacity is too small (below 8 bytes a segment)");
+  }
+  residual_seg_encode_host_n(w.c_str(), sym, ctx, B, N, m, freq, seg_len, n_seg, out, cap, seg_bytes, len);
+}
+
+void seg_decode_host(const std::string& w, const std::function<void()>& check, const uint8_t* data, size_t data_stride,
+                     const uint64_t* data_len, const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N,
+                     const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym) {
+  MLIC_CHECK(data != nullptr, w + ": null data");
+  MLIC_CHECK(ctx != nullptr, w + ": null ctx");
+  MLIC_CHECK(sym != nullptr, w + ": null sym");
+  check();
+  residual_seg_tables_check(w.c_str(), m, freq, B);
+  MLIC_CHECK(data_stride % 4 == 0, w + ": the data stride must be a multiple of 4");
+  residual_seg_lengths_check(w.c_str(), seg_bytes, data_len, data_stride, B, N, seg_len, n_seg);
+  residual_seg_decode_host_n(w.c_str(), data, data_stride, data_len, seg_bytes, ctx, B, N, m, freq, seg_len, n_seg, sym);
+}
+}  // namespace
+
 int mlic_residual_encode_segments(void* stream, const int16_t* sym, const uint8_t* ctx, int B, int H, int W,
                                   const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
                                   size_t cap, uint32_t* seg_bytes, uint64_t* len, void* scratch, size_t scratch_bytes,
                                   uint32_t* status) {
   return guard([&] {
-    const char* what = "residual_encode_segments";
-    MLIC_CHECK(sym != nullptr, "residual_encode_segments: null sym");
-    MLIC_CHECK(ctx != nullptr, "residual_encode_segments: null ctx");
-    MLIC_CHECK(out != nullptr, "residual_encode_segments: null out");
-    MLIC_CHECK(seg_bytes != nullptr, "residual_encode_segments: null seg_bytes");
-    MLIC_CHECK(len != nullptr, "residual_encode_segments: null len");
-    MLIC_CHECK(scratch != nullptr, "residual_encode_segments: null scratch");
-    seg_common_check(what, B, H, W, m, freq, seg_len, n_seg);
-    MLIC_CHECK(cap % 4 == 0, "residual_encode_segments: the capacity must be a multiple of 4");
-    MLIC_CHECK(cap >= (size_t)RES_SEG_MIN_BYTES * (size_t)n_seg,
-               "residual_encode_segments: the capacity is too small (below 8 bytes a segment)");
-    MLIC_CHECK(cap <= 0xffffffffu, "residual_encode_segments: the capacity must fit 32 bits");
-    const SegScratch sc(B, n_seg);
-    MLIC_CHECK(scratch_bytes >= sc.size, "residual_encode_segments: scratch too small");
-    MLIC_CHECK(aligned_to(sym, 2) && aligned_to(out, 4) && aligned_to(seg_bytes, 4) && aligned_to(scratch, 16),
-               "residual_encode_segments: sym must be 2-byte, out and seg_bytes 4-byte, scratch 16-byte aligned");
-    std::vector<ResSegEncTable> tabs((size_t)B);
-    for (int b = 0; b < B; ++b)
-      residual_seg_enc_table(m + (size_t)b * RES_CTX, freq + (size_t)b * RES_CTX * RES_BINS, &tabs[(size_t)b]);
-    auto st = (hipStream_t)stream;
-    auto* base = static_cast<uint8_t*>(scratch);
-    auto* d_tabs = reinterpret_cast<ResSegEncTable*>(base + sc.tabs);
-    auto* d_status = reinterpret_cast<uint32_t*>(base + sc.status);
-    auto* d_total = reinterpret_cast<uint64_t*>(base + sc.total);
-    HIP_OK(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(ResSegEncTable) * (size_t)B, hipMemcpyHostToDevice, st));
-    residual_encode_segments(sym, ctx, B, 3 * (int64_t)H * W, seg_len, n_seg, d_tabs, out, cap,
-                             reinterpret_cast<uint32_t*>(base + sc.off), seg_bytes, d_total, d_status, st);
-    std::vector<uint32_t> hs((size_t)B);
-    HIP_OK(hipMemcpyAsync(hs.data(), d_status, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(len, d_total, sizeof(uint64_t) * (size_t)B, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (status) std::copy(hs.begin(), hs.end(), status);
-    seg_status_throw(what, hs);
+    seg_encode_dev("residual_encode_segments", [&] { residual_seg_check("residual_encode_segments", B, H, W, seg_len, n_seg); },
+                   stream, sym, ctx, B, 3 * (int64_t)H * W, m, freq, seg_len, n_seg, out, cap, seg_bytes, len, scratch,
+                   scratch_bytes, status);
   });
 }
 
@@ -1689,44 +1773,9 @@ int mlic_residual_decode_segments(void* stream, const uint8_t* data, size_t data
                                   const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym, void* scratch,
                                   size_t scratch_bytes, uint32_t* status) {
   return guard([&] {
-    const char* what = "residual_decode_segments";
-    MLIC_CHECK(data != nullptr, "residual_decode_segments: null data");
-    MLIC_CHECK(ctx != nullptr, "residual_decode_segments: null ctx");
-    MLIC_CHECK(sym != nullptr, "residual_decode_segments: null sym");
-    MLIC_CHECK(scratch != nullptr, "residual_decode_segments: null scratch");
-    seg_common_check(what, B, H, W, m, freq, seg_len, n_seg);
-    const int64_t N = 3 * (int64_t)H * W;
-    MLIC_CHECK(data_stride % 4 == 0, "residual_decode_segments: the data stride must be a multiple of 4");
-    residual_seg_lengths_check(what, seg_bytes, data_len, data_stride, B, N, seg_len, n_seg);
-    const SegScratch sc(B, n_seg);
-    MLIC_CHECK(scratch_bytes >= sc.size, "residual_decode_segments: scratch too small");
-    MLIC_CHECK(aligned_to(sym, 2) && aligned_to(data, 4) && aligned_to(scratch, 16),
-               "residual_decode_segments: sym must be 2-byte, data 4-byte, scratch 16-byte aligned");
-    std::vector<ResSegDecTable> tabs((size_t)B);
-    std::vector<uint32_t> offs((size_t)B * n_seg);
-    for (int b = 0; b < B; ++b) {
-      residual_seg_dec_table(m + (size_t)b * RES_CTX, freq + (size_t)b * RES_CTX * RES_BINS, &tabs[(size_t)b]);
-      uint32_t o = 0;
-      for (int64_t k = 0; k < n_seg; ++k) {
-        offs[(size_t)b * n_seg + k] = o;
-        o += seg_bytes[(size_t)b * n_seg + k];
-      }
-    }
-    auto st = (hipStream_t)stream;
-    auto* base = static_cast<uint8_t*>(scratch);
-    auto* d_tabs = reinterpret_cast<ResSegDecTable*>(base + sc.tabs);
-    auto* d_off = reinterpret_cast<uint32_t*>(base + sc.off);
-    auto* d_bytes = reinterpret_cast<uint32_t*>(base + sc.bytes);
-    auto* d_status = reinterpret_cast<uint32_t*>(base + sc.status);
-    HIP_OK(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(ResSegDecTable) * (size_t)B, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_off, offs.data(), sizeof(uint32_t) * offs.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_bytes, seg_bytes, sizeof(uint32_t) * offs.size(), hipMemcpyHostToDevice, st));
-    residual_decode_segments(data, data_stride, d_off, d_bytes, ctx, B, N, seg_len, n_seg, d_tabs, sym, d_status, st);
-    std::vector<uint32_t> hs((size_t)B);
-    HIP_OK(hipMemcpyAsync(hs.data(), d_status, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (status) std::copy(hs.begin(), hs.end(), status);
-    seg_status_throw(what, hs);
+    seg_decode_dev("residual_decode_segments", [&] { residual_seg_check("residual_decode_segments", B, H, W, seg_len, n_seg); },
+                   stream, data, data_stride, data_len, seg_bytes, ctx, B, 3 * (int64_t)H * W, m, freq, seg_len, n_seg,
+                   sym, scratch, scratch_bytes, status);
   });
 }
 
@@ -1734,17 +1783,9 @@ int mlic_residual_encode_segments_host(const int16_t* sym, const uint8_t* ctx, i
                                        const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
                                        uint32_t* seg_bytes, uint64_t* len) {
   return guard([&] {
-    MLIC_CHECK(sym != nullptr, "residual_encode_segments_host: null sym");
-    MLIC_CHECK(ctx != nullptr, "residual_encode_segments_host: null ctx");
-    MLIC_CHECK(seg_bytes != nullptr, "residual_encode_segments_host: null seg_bytes");
-    MLIC_CHECK(len != nullptr, "residual_encode_segments_host: null len");
-    seg_common_check("residual_encode_segments_host", B, H, W, m, freq, seg_len, n_seg);
-    if (out != nullptr) {
-      MLIC_CHECK(cap % 4 == 0, "residual_encode_segments_host: the capacity must be a multiple of 4");
-      MLIC_CHECK(cap >= (size_t)RES_SEG_MIN_BYTES * (size_t)n_seg,
-                 "residual_encode_segments_host: the capacity is too small (below 8 bytes a segment)");
-    }
-    residual_seg_encode_host(sym, ctx, B, H, W, m, freq, seg_len, n_seg, out, cap, seg_bytes, len);
+    seg_encode_host("residual_encode_segments_host",
+                    [&] { residual_seg_check("residual_encode_segments_host", B, H, W, seg_len, n_seg); }, sym, ctx, B,
+                    3 * (int64_t)H * W, m, freq, seg_len, n_seg, out, cap, seg_bytes, len);
   });
 }
 
@@ -1753,14 +1794,63 @@ int mlic_residual_decode_segments_host(const uint8_t* data, size_t data_stride, 
                                        const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg,
                                        int16_t* sym) {
   return guard([&] {
-    const char* what = "residual_decode_segments_host";
-    MLIC_CHECK(data != nullptr, "residual_decode_segments_host: null data");
-    MLIC_CHECK(ctx != nullptr, "residual_decode_segments_host: null ctx");
-    MLIC_CHECK(sym != nullptr, "residual_decode_segments_host: null sym");
-    seg_common_check(what, B, H, W, m, freq, seg_len, n_seg);
-    MLIC_CHECK(data_stride % 4 == 0, "residual_decode_segments_host: the data stride must be a multiple of 4");
-    residual_seg_lengths_check(what, seg_bytes, data_len, data_stride, B, 3 * (int64_t)H * W, seg_len, n_seg);
-    residual_seg_decode_host(data, data_stride, data_len, seg_bytes, ctx, B, H, W, m, freq, seg_len, n_seg, sym);
+    seg_decode_host("residual_decode_segments_host",
+                    [&] { residual_seg_check("residual_decode_segments_host", B, H, W, seg_len, n_seg); }, data,
+                    data_stride, data_len, seg_bytes, ctx, B, 3 * (int64_t)H * W, m, freq, seg_len, n_seg, sym);
+  });
+}
+
+// the same four for a string of N samples (a Y'CbCr frame's N = H W + 2 hc wc: residual_yuv.h)
+int mlic_residual_segments_scratch_bytes_n(int B, int64_t N, int seg_len, size_t* bytes) {
+  return guard([&] {
+    MLIC_CHECK(bytes != nullptr, "residual_segments_scratch_bytes_n: null bytes");
+    MLIC_CHECK(seg_len >= RES_SEG_MIN && seg_len <= RES_SEG_MAX,
+               "residual_segments_scratch_bytes_n: the segment length is outside 256..65536");
+    residual_seg_check_n("residual_segments_scratch_bytes_n", B, N, seg_len, residual_n_seg(N, seg_len));
+    *bytes = SegScratch(B, residual_n_seg(N, seg_len)).size;
+  });
+}
+
+int mlic_residual_encode_segments_n(void* stream, const int16_t* sym, const uint8_t* ctx, int B, int64_t N,
+                                    const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                                    size_t cap, uint32_t* seg_bytes, uint64_t* len, void* scratch,
+                                    size_t scratch_bytes, uint32_t* status) {
+  return guard([&] {
+    seg_encode_dev("residual_encode_segments_n", [&] { residual_seg_check_n("residual_encode_segments_n", B, N, seg_len, n_seg); },
+                   stream, sym, ctx, B, N, m, freq, seg_len, n_seg, out, cap, seg_bytes, len, scratch, scratch_bytes,
+                   status);
+  });
+}
+
+int mlic_residual_decode_segments_n(void* stream, const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                    const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N, const uint8_t* m,
+                                    const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym, void* scratch,
+                                    size_t scratch_bytes, uint32_t* status) {
+  return guard([&] {
+    seg_decode_dev("residual_decode_segments_n", [&] { residual_seg_check_n("residual_decode_segments_n", B, N, seg_len, n_seg); },
+                   stream, data, data_stride, data_len, seg_bytes, ctx, B, N, m, freq, seg_len, n_seg, sym, scratch,
+                   scratch_bytes, status);
+  });
+}
+
+int mlic_residual_encode_segments_host_n(const int16_t* sym, const uint8_t* ctx, int B, int64_t N, const uint8_t* m,
+                                         const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
+                                         uint32_t* seg_bytes, uint64_t* len) {
+  return guard([&] {
+    seg_encode_host("residual_encode_segments_host_n",
+                    [&] { residual_seg_check_n("residual_encode_segments_host_n", B, N, seg_len, n_seg); }, sym, ctx, B,
+                    N, m, freq, seg_len, n_seg, out, cap, seg_bytes, len);
+  });
+}
+
+int mlic_residual_decode_segments_host_n(const uint8_t* data, size_t data_stride, const uint64_t* data_len,
+                                         const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N,
+                                         const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg,
+                                         int16_t* sym) {
+  return guard([&] {
+    seg_decode_host("residual_decode_segments_host_n",
+                    [&] { residual_seg_check_n("residual_decode_segments_host_n", B, N, seg_len, n_seg); }, data,
+                    data_stride, data_len, seg_bytes, ctx, B, N, m, freq, seg_len, n_seg, sym);
   });
 }
 
@@ -2210,6 +2300,165 @@ int mlic_decode_image_yuv16(mlic_model* m, void* stream, const uint8_t* file, si
                   r3[3] = {0, cr_strides[0], cr_strides[1]};
     image_egress_yuv16(x, s3, 1, (int)c.H, (int)c.W, &d, depth, msb, y_dev, y3, cb_dev, b3, cr_dev, r3, nullptr, nullptr,
                        nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  });
+}
+
+// ---- residual coding of Y'CbCr frames (residual_yuv.h; DESIGN.md section 5 "Residual coding", "Y'CbCr frames")
+namespace {
+struct Planes3 {  // three plane pointers and their strides, as the kernels' host entries take them
+  const void* p[3];
+  const int64_t* s[3];
+};
+struct DescArg {  // the descriptor, or null for the entries' own refusal
+  YuvDesc d;
+  const YuvDesc* ptr;
+  explicit DescArg(const mlic_yuv_desc* desc) : d{}, ptr(nullptr) {
+    if (desc) {
+      d = yuv_desc(desc);
+      ptr = &d;
+    }
+  }
+};
+}  // namespace
+
+#define MLIC_RES_YUV_ENTRIES(SFX, WORD, BYTES, DEPTH_PARAMS, DEPTH, MSB)                                              \
+  int mlic_image_residual_front_##SFX(                                                                                \
+      void* stream, const WORD* base_y, const int64_t* base_y_strides, const WORD* base_cb,                           \
+      const int64_t* base_cb_strides, const WORD* base_cr, const int64_t* base_cr_strides, const WORD* x_y,           \
+      const int64_t* x_y_strides, const WORD* x_cb, const int64_t* x_cb_strides, const WORD* x_cr,                    \
+      const int64_t* x_cr_strides, const mlic_yuv_desc* desc, DEPTH_PARAMS int B, int H, int W, int tau, int shift,   \
+      uint8_t* ctx, uint32_t* ctx_count, uint64_t* digest, int16_t* sym, uint64_t* lo_plane, uint32_t* hist,          \
+      uint32_t* max_err, uint32_t* max_abs_q, uint64_t* sum_abs_q) {                                                  \
+    return guard([&] {                                                                                                \
+      const Planes3 b{{base_y, base_cb, base_cr}, {base_y_strides, base_cb_strides, base_cr_strides}};               \
+      const Planes3 x{{x_y, x_cb, x_cr}, {x_y_strides, x_cb_strides, x_cr_strides}};                                 \
+      const DescArg d(desc);                                                                                          \
+      image_residual_front_planes("image_residual_front_" #SFX, BYTES, b.p, b.s, x.p, x.s, d.ptr, DEPTH, MSB, B, H,  \
+                                  W, tau, shift, ctx, ctx_count, digest, sym, lo_plane, hist, max_err, max_abs_q,     \
+                                  sum_abs_q, (hipStream_t)stream);                                                    \
+    });                                                                                                               \
+  }                                                                                                                   \
+  int mlic_image_residual_stats_##SFX(                                                                                \
+      void* stream, const WORD* base_y, const int64_t* base_y_strides, const WORD* base_cb,                           \
+      const int64_t* base_cb_strides, const WORD* base_cr, const int64_t* base_cr_strides, const WORD* x_y,           \
+      const int64_t* x_y_strides, const WORD* x_cb, const int64_t* x_cb_strides, const WORD* x_cr,                    \
+      const int64_t* x_cr_strides, const mlic_yuv_desc* desc, DEPTH_PARAMS int B, int H, int W, int tau,              \
+      uint32_t* max_abs_q, uint64_t* sum_abs_q) {                                                                     \
+    return guard([&] {                                                                                                \
+      const Planes3 b{{base_y, base_cb, base_cr}, {base_y_strides, base_cb_strides, base_cr_strides}};               \
+      const Planes3 x{{x_y, x_cb, x_cr}, {x_y_strides, x_cb_strides, x_cr_strides}};                                 \
+      const DescArg d(desc);                                                                                          \
+      image_residual_stats_planes("image_residual_stats_" #SFX, BYTES, b.p, b.s, x.p, x.s, d.ptr, DEPTH, MSB, B, H,  \
+                                  W, tau, max_abs_q, sum_abs_q, (hipStream_t)stream);                                 \
+    });                                                                                                               \
+  }                                                                                                                   \
+  int mlic_image_residual_apply_##SFX(                                                                                \
+      void* stream, const WORD* base_y, const int64_t* base_y_strides, const WORD* base_cb,                           \
+      const int64_t* base_cb_strides, const WORD* base_cr, const int64_t* base_cr_strides, const int16_t* sym,        \
+      const uint64_t* lo_plane, const mlic_yuv_desc* desc, DEPTH_PARAMS int B, int H, int W, int tau, int shift,      \
+      WORD* out_y, const int64_t* out_y_strides, WORD* out_cb, const int64_t* out_cb_strides, WORD* out_cr,           \
+      const int64_t* out_cr_strides, const WORD* ref_y, const int64_t* ref_y_strides, const WORD* ref_cb,             \
+      const int64_t* ref_cb_strides, const WORD* ref_cr, const int64_t* ref_cr_strides, uint64_t* sq_err,             \
+      uint32_t* max_err, uint32_t* status) {                                                                          \
+    return guard([&] {                                                                                                \
+      const Planes3 b{{base_y, base_cb, base_cr}, {base_y_strides, base_cb_strides, base_cr_strides}};               \
+      const Planes3 r{{ref_y, ref_cb, ref_cr}, {ref_y_strides, ref_cb_strides, ref_cr_strides}};                     \
+      void* const o[3] = {out_y, out_cb, out_cr};                                                                     \
+      const int64_t* const os[3] = {out_y_strides, out_cb_strides, out_cr_strides};                                   \
+      const DescArg d(desc);                                                                                          \
+      image_residual_apply_planes("image_residual_apply_" #SFX, BYTES, b.p, b.s, sym, lo_plane, d.ptr, DEPTH, MSB,   \
+                                  B, H, W, tau, shift, o, os, r.p, r.s, sq_err, max_err, status,                      \
+                                  (hipStream_t)stream);                                                               \
+    });                                                                                                               \
+  }
+#define MLIC_NO_PARAMS
+#define MLIC_DEPTH_PARAMS int depth, int msb,
+MLIC_RES_YUV_ENTRIES(yuv8, uint8_t, 1, MLIC_NO_PARAMS, 8, 0)
+MLIC_RES_YUV_ENTRIES(yuv16, uint16_t, 2, MLIC_DEPTH_PARAMS, depth, msb)
+#undef MLIC_RES_YUV_ENTRIES
+#undef MLIC_NO_PARAMS
+#undef MLIC_DEPTH_PARAMS
+
+namespace {
+void res_yuv_size_check(const std::string& w, int H, int W, int sub_x, int sub_y) {
+  MLIC_CHECK(H >= 1 && W >= 1, w + ": H and W must be positive");
+  MLIC_CHECK(H <= (1 << 24) && W <= (1 << 24), w + ": frame side above 2^24");
+  MLIC_CHECK(residual_yuv_sub_ok(sub_x, sub_y), w + ": sub_x, sub_y must be one of {1, 1}, {2, 1}, {2, 2}");
+  MLIC_CHECK(residual_yuv_geom(H, W, sub_x, sub_y).N <= RES_SEG_MAX_N, w + ": the frame has more than 2^29 samples");
+}
+}  // namespace
+
+int mlic_residual_yuv_samples(int H, int W, int sub_x, int sub_y, uint64_t* N) {
+  return guard([&] {
+    MLIC_CHECK(N != nullptr, "residual_yuv_samples: null N");
+    res_yuv_size_check("residual_yuv_samples", H, W, sub_x, sub_y);
+    *N = (uint64_t)residual_yuv_geom(H, W, sub_x, sub_y).N;
+  });
+}
+
+int mlic_residual_yuv_plane_words(int H, int W, int sub_x, int sub_y, int shift, uint64_t* words) {
+  return guard([&] {
+    MLIC_CHECK(words != nullptr, "residual_yuv_plane_words: null words");
+    res_yuv_size_check("residual_yuv_plane_words", H, W, sub_x, sub_y);
+    MLIC_CHECK(shift >= 0 && shift <= residual16_max_shift(RES16_MAX_DEPTH), "residual_yuv_plane_words: shift must be in 0..9");
+    *words = residual_yuv_plane_words((uint64_t)H, (uint64_t)W, sub_x, sub_y, shift);
+  });
+}
+
+int mlic_container_write_residual_yuv(uint32_t H, uint32_t W, int vbr, int tau, int depth, int shift, int sub_x,
+                                      int sub_y, int matrix, int full_range, int site_x, uint64_t digest,
+                                      const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
+                                      const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
+                                      const uint8_t* segs, size_t segs_len, const uint8_t* lo, size_t lo_len,
+                                      uint8_t* out, size_t cap, size_t* len) {
+  return guard([&] {
+    MLIC_CHECK(tau >= 0, "container_write_residual_yuv: negative tau");
+    MLIC_CHECK(depth >= 0 && shift >= 0, "container_write_residual_yuv: negative depth or shift");
+    MLIC_CHECK(sub_x >= 0 && sub_y >= 0 && matrix >= 0, "container_write_residual_yuv: negative sub_x, sub_y or matrix");
+    MLIC_CHECK(full_range == 0 || full_range == 1, "container_write_residual_yuv: full_range must be 0 or 1");
+    MLIC_CHECK(site_x == 0 || site_x == 1, "container_write_residual_yuv: site_x must be 0 (centre) or 1 (left)");
+    container_ok(container_write_residual_yuv(H, W, vbr != 0, (uint32_t)tau, (uint32_t)depth, (uint32_t)shift,
+                                              (uint32_t)sub_x, (uint32_t)sub_y, (uint32_t)matrix,
+                                              (uint32_t)(full_range | (site_x << 1)), digest, m, freq, seg_len, n_seg,
+                                              seg_bytes, inner, inner_len, segs, segs_len, lo, lo_len, out, cap, len));
+  });
+}
+
+int mlic_container_parse_residual_yuv(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
+                                      mlic_container_residual_yuv_info* info) {
+  return guard([&] {
+    MLIC_CHECK(info != nullptr, "container_parse_residual_yuv: null info");
+    ResidualYuvInfo y;
+    container_ok(container_parse_residual_yuv(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &y));
+    const ResidualSegInfo& s = y.deep.seg;
+    info->H = s.H;
+    info->W = s.W;
+    info->tau = (int32_t)s.tau;
+    info->vbr = s.vbr ? 1 : 0;
+    info->digest = s.digest;
+    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+      info->m[k] = s.m[k];
+      info->freq_off[k] = s.freq_off[k];
+    }
+    info->seg_len = s.seg_len;
+    info->n_seg = s.n_seg;
+    info->inner_off = s.inner_off;
+    info->inner_len = s.inner_len;
+    info->res_off = s.res_off;
+    info->res_len = s.res_len;
+    info->index_off = s.index_off;
+    info->data_off = s.data_off;
+    info->data_len = s.data_len;
+    info->depth = (int32_t)y.deep.depth;
+    info->shift = (int32_t)y.deep.shift;
+    info->lo_off = y.deep.lo_off;
+    info->lo_len = y.deep.lo_len;
+    info->sub_x = (int32_t)y.sub_x;
+    info->sub_y = (int32_t)y.sub_y;
+    info->matrix = (int32_t)y.matrix;
+    info->full_range = y.full_range ? 1 : 0;
+    info->site_x = y.site_left ? 1 : 0;
+    to_abi(s.inner, &info->inner);
   });
 }
 

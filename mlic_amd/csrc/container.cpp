@@ -593,23 +593,54 @@ const char* container_parse_residual(const uint8_t* data, size_t n, uint32_t n_l
 
 // ------------------------------------------------------------------------------ residual, segmented
 namespace {
-uint64_t residual_seg_count(uint32_t H, uint32_t W, uint32_t seg_len) {
-  return (3 * (uint64_t)H * W + seg_len - 1) / seg_len;
+enum { K_SEG = 0, K_DEEP = 1, K_YUV = 2 };  // "MLR2", "MLR3", "MLR4"
+struct YuvFields {                          // what the "MLR4" file says of its frame beyond depth and shift
+  uint32_t sub_x, sub_y, matrix, flags;
+};
+// samples of the canonical order: 3 H W of an RGB image, H W + 2 hc wc of a Y'CbCr frame
+uint64_t residual_samples(int kind, uint32_t H, uint32_t W, const YuvFields& y) {
+  if (kind != K_YUV) return 3 * (uint64_t)H * W;
+  const uint64_t hc = ((uint64_t)H + y.sub_y - 1) / y.sub_y, wc = ((uint64_t)W + y.sub_x - 1) / y.sub_x;
+  return (uint64_t)H * W + 2 * hc * wc;
 }
-uint64_t residual_seg_bound(uint32_t H, uint32_t W, uint32_t seg_len, uint64_t k) {  // bytes segment k may take
-  const uint64_t left = 3 * (uint64_t)H * W - k * seg_len;
+uint64_t residual_seg_count(uint64_t N, uint32_t seg_len) { return (N + seg_len - 1) / seg_len; }
+uint64_t residual_seg_bound(uint64_t N, uint32_t seg_len, uint64_t k) {  // bytes segment k may take
+  const uint64_t left = N - k * seg_len;
   return 4 * ((left < seg_len ? left : seg_len) + RESIDUAL_SEG_SLACK);
 }
-uint64_t residual_lo_bytes(uint32_t H, uint32_t W, uint32_t shift) {  // the low-bit plane of the "MLR3" file
-  return 8 * 3 * (uint64_t)H * (((uint64_t)W + 63) / 64) * shift;
+// the low-bit plane of the "MLR3" and the "MLR4" file
+uint64_t residual_lo_bytes(int kind, uint32_t H, uint32_t W, const YuvFields& y, uint32_t shift) {
+  if (kind != K_YUV) return 8 * 3 * (uint64_t)H * (((uint64_t)W + 63) / 64) * shift;
+  const uint64_t hc = ((uint64_t)H + y.sub_y - 1) / y.sub_y, wc = ((uint64_t)W + y.sub_x - 1) / y.sub_x;
+  return 8 * (uint64_t)shift * ((uint64_t)H * (((uint64_t)W + 63) / 64) + 2 * hc * ((wc + 63) / 64));
 }
+const char* residual_magic_of(int kind) { return kind == K_YUV ? "MLR4" : kind == K_DEEP ? "MLR3" : "MLR2"; }
 }  // namespace
 
 namespace {
-// The "MLR2" and the "MLR3" file differ by the magic, by depth and shift behind the tables and by the low-bit plane
-// behind the segments: one writer and one parser serve both, and each refusal carries the name of its entry.
-#define SEG_MSG(text) (deep ? "container_write_residual_deep: " text : "container_write_residual_seg: " text)
-const char* write_residual_seg(bool deep, uint32_t depth, uint32_t shift, const uint8_t* lo, size_t lo_len, uint32_t H,
+// depth, shift and the frame's fields of the "MLR4" file: the same refusals on both sides
+const char* residual_yuv_fields_check(bool write, uint32_t depth, uint32_t shift, const YuvFields& y) {
+#define YUV_MSG(text) (write ? "container_write_residual_yuv: " text : "container_parse_residual_yuv: " text)
+  if (depth < 8 || depth > 16) return YUV_MSG("depth outside 8..16");
+  if (depth == 8 && shift != 0) return YUV_MSG("shift must be 0 at depth 8");
+  if (depth > 8 && shift > depth - 7) return YUV_MSG("shift outside 0..depth - 7");
+  if (!((y.sub_x == 1 && y.sub_y == 1) || (y.sub_x == 2 && (y.sub_y == 1 || y.sub_y == 2))))
+    return YUV_MSG("sub_x, sub_y is not one of {1, 1}, {2, 1}, {2, 2}");
+  if (y.matrix > 2) return YUV_MSG("matrix outside 0..2");
+  if (y.matrix == 2 && depth == 8) return YUV_MSG("matrix 2 (BT.2020) at depth 8");
+  if (y.flags & ~3u) return YUV_MSG("reserved flag bits are set");
+  return nullptr;
+#undef YUV_MSG
+}
+
+// The "MLR2", the "MLR3" and the "MLR4" file differ by the magic, by depth and shift (and the frame's fields) behind
+// the tables, by the number of samples and by the low-bit plane behind the segments: one writer and one parser serve
+// all three, and each refusal carries the name of its entry.
+#define SEG_MSG(text)                                                                                              \
+  (kind == K_YUV ? "container_write_residual_yuv: " text                                                           \
+                 : kind == K_DEEP ? "container_write_residual_deep: " text : "container_write_residual_seg: " text)
+const char* write_residual_seg(int kind, const YuvFields& yf, uint32_t depth, uint32_t shift, const uint8_t* lo,
+                               size_t lo_len, uint32_t H,
                                uint32_t W, bool vbr, uint32_t tau, uint64_t digest, const uint8_t* m,
                                const uint16_t* freq, uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
                                const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
@@ -620,18 +651,27 @@ const char* write_residual_seg(bool deep, uint32_t depth, uint32_t shift, const 
   if (m == nullptr) return SEG_MSG("null m");
   if (seg_len < RESIDUAL_SEG_MIN || seg_len > RESIDUAL_SEG_MAX)
     return SEG_MSG("seg_len outside 256..65536");
-  if ((uint64_t)n_seg != residual_seg_count(H, W, seg_len))
-    return SEG_MSG("n_seg is not ceil(3 H W / seg_len)");
-  if (deep) {
+  const bool deep = kind != K_SEG;
+  if (kind == K_YUV) {
+    if (const char* err = residual_yuv_fields_check(true, depth, shift, yf)) return err;
+  }
+  const uint64_t N = residual_samples(kind, H, W, yf);
+  if ((uint64_t)n_seg != residual_seg_count(N, seg_len))
+    return kind == K_YUV ? SEG_MSG("n_seg is not ceil(N / seg_len)") : SEG_MSG("n_seg is not ceil(3 H W / seg_len)");
+  if (kind == K_DEEP) {
     if (depth < 9 || depth > 16) return SEG_MSG("depth outside 9..16");
     if (shift > depth - 7) return SEG_MSG("shift outside 0..depth - 7");
-    if ((uint64_t)lo_len != residual_lo_bytes(H, W, shift)) return SEG_MSG("lo_len is not 8 * 3 H ceil(W / 64) shift");
+  }
+  if (deep) {
+    if ((uint64_t)lo_len != residual_lo_bytes(kind, H, W, yf, shift))
+      return kind == K_YUV ? SEG_MSG("lo_len is not 8 * shift * (H G_0 + 2 hc G_1)")
+                           : SEG_MSG("lo_len is not 8 * 3 H ceil(W / 64) shift");
     if (lo_len > 0xffffffffu) return SEG_MSG("a string longer than a 32-bit length");
   }
   if (inner_len == 0) return SEG_MSG("an empty inner file");
   if (inner_len > 0xffffffffu || segs_len > 0xffffffffu - 4 * (uint64_t)n_seg)
     return SEG_MSG("a string longer than a 32-bit length");
-  size_t total = RESIDUAL_HEADER + 16 + (deep ? 6 : 0);
+  size_t total = RESIDUAL_HEADER + 16 + (deep ? 6 : 0) + (kind == K_YUV ? 4 : 0);
   for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
     if (m[k] != RESIDUAL_ABSENT && m[k] > RESIDUAL_MAX_M) return SEG_MSG("an m outside 0..63");
     total += 1 + (m[k] == RESIDUAL_ABSENT ? 0 : 2 * (2 * (size_t)m[k] + 2));
@@ -663,12 +703,12 @@ const char* write_residual_seg(bool deep, uint32_t depth, uint32_t shift, const 
   for (uint32_t k = 0; k < n_seg; ++k) {
     if (seg_bytes[k] % 4) return SEG_MSG("a segment length that is not a multiple of 4");
     if (seg_bytes[k] < 8) return SEG_MSG("a segment length below 8");
-    if (seg_bytes[k] > residual_seg_bound(H, W, seg_len, k))
+    if (seg_bytes[k] > residual_seg_bound(N, seg_len, k))
       return SEG_MSG("a segment length above the capacity bound");
     sum += seg_bytes[k];
   }
   if (sum != segs_len) return SEG_MSG("the segment lengths do not sum to the data length");
-  std::memcpy(out, deep ? "MLR3" : "MLR2", 4);
+  std::memcpy(out, residual_magic_of(kind), 4);
   out[4] = 0;
   out[5] = vbr ? 1 : 0;
   out[6] = (uint8_t)tau;
@@ -689,6 +729,12 @@ const char* write_residual_seg(bool deep, uint32_t depth, uint32_t shift, const 
   if (deep) {
     *p++ = (uint8_t)depth;
     *p++ = (uint8_t)shift;
+  }
+  if (kind == K_YUV) {
+    *p++ = (uint8_t)yf.sub_x;
+    *p++ = (uint8_t)yf.sub_y;
+    *p++ = (uint8_t)yf.matrix;
+    *p++ = (uint8_t)yf.flags;
   }
   put32(p, seg_len);
   put32(p + 4, n_seg);
@@ -713,7 +759,7 @@ const char* container_write_residual_seg(uint32_t H, uint32_t W, bool vbr, uint3
                                          const uint8_t* m, const uint16_t* freq, uint32_t seg_len, uint32_t n_seg,
                                          const uint32_t* seg_bytes, const uint8_t* inner, size_t inner_len,
                                          const uint8_t* segs, size_t segs_len, uint8_t* out, size_t cap, size_t* len) {
-  return write_residual_seg(false, 0, 0, nullptr, 0, H, W, vbr, tau, digest, m, freq, seg_len, n_seg, seg_bytes, inner,
+  return write_residual_seg(K_SEG, YuvFields{}, 0, 0, nullptr, 0, H, W, vbr, tau, digest, m, freq, seg_len, n_seg, seg_bytes, inner,
                             inner_len, segs, segs_len, out, cap, len);
 }
 
@@ -722,20 +768,34 @@ const char* container_write_residual_deep(uint32_t H, uint32_t W, bool vbr, uint
                                           uint32_t seg_len, uint32_t n_seg, const uint32_t* seg_bytes,
                                           const uint8_t* inner, size_t inner_len, const uint8_t* segs, size_t segs_len,
                                           const uint8_t* lo, size_t lo_len, uint8_t* out, size_t cap, size_t* len) {
-  return write_residual_seg(true, depth, shift, lo, lo_len, H, W, vbr, tau, digest, m, freq, seg_len, n_seg, seg_bytes,
-                            inner, inner_len, segs, segs_len, out, cap, len);
+  return write_residual_seg(K_DEEP, YuvFields{}, depth, shift, lo, lo_len, H, W, vbr, tau, digest, m, freq, seg_len,
+                            n_seg, seg_bytes, inner, inner_len, segs, segs_len, out, cap, len);
+}
+
+const char* container_write_residual_yuv(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint32_t depth, uint32_t shift,
+                                         uint32_t sub_x, uint32_t sub_y, uint32_t matrix, uint32_t flags,
+                                         uint64_t digest, const uint8_t* m, const uint16_t* freq, uint32_t seg_len,
+                                         uint32_t n_seg, const uint32_t* seg_bytes, const uint8_t* inner,
+                                         size_t inner_len, const uint8_t* segs, size_t segs_len, const uint8_t* lo,
+                                         size_t lo_len, uint8_t* out, size_t cap, size_t* len) {
+  return write_residual_seg(K_YUV, YuvFields{sub_x, sub_y, matrix, flags}, depth, shift, lo, lo_len, H, W, vbr, tau,
+                            digest, m, freq, seg_len, n_seg, seg_bytes, inner, inner_len, segs, segs_len, out, cap, len);
 }
 
 namespace {
-#define SEG_MSG(text) (deep ? "container_parse_residual_deep: " text : "container_parse_residual_seg: " text)
-const char* parse_residual_seg(bool deep, const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
-                               ResidualSegInfo* info, ResidualDeepInfo* more) {
+#define SEG_MSG(text)                                                                                              \
+  (kind == K_YUV ? "container_parse_residual_yuv: " text                                                           \
+                 : kind == K_DEEP ? "container_parse_residual_deep: " text : "container_parse_residual_seg: " text)
+const char* parse_residual_seg(int kind, const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                               ResidualSegInfo* info, ResidualDeepInfo* more, YuvFields* frame) {
+  const bool deep = kind != K_SEG;
   if (info == nullptr) return SEG_MSG("null info");
   if (data == nullptr && n != 0) return SEG_MSG("null data");
   if (n < RESIDUAL_HEADER) return SEG_MSG("truncated header");
-  if (std::memcmp(data, deep ? "MLR3" : "MLR2", 4) != 0)
-    return deep ? "container_parse_residual_deep: bad magic (not a deep residual file)"
-                : SEG_MSG("bad magic (not a segmented residual file)");
+  if (std::memcmp(data, residual_magic_of(kind), 4) != 0)
+    return kind == K_YUV    ? "container_parse_residual_yuv: bad magic (not a Y'CbCr residual file)"
+           : kind == K_DEEP ? "container_parse_residual_deep: bad magic (not a deep residual file)"
+                            : SEG_MSG("bad magic (not a segmented residual file)");
   if (data[4] != 0) return SEG_MSG("unknown version");
   if (data[5] & ~1u) return SEG_MSG("unknown flags");
   if (data[6] > 127) return SEG_MSG("tau above 127");
@@ -771,18 +831,30 @@ const char* parse_residual_seg(bool deep, const uint8_t* data, size_t n, uint32_
     r.pos += 2 * cnt;
   }
   uint32_t depth = 0, shift = 0;
-  if (deep) {
+  YuvFields yf{};
+  if (kind == K_DEEP) {
     if (r.n - r.pos < 2) return SEG_MSG("truncated before depth, shift");
     depth = data[r.pos++];
     shift = data[r.pos++];
     if (depth < 9 || depth > 16) return SEG_MSG("depth outside 9..16");
     if (shift > depth - 7) return SEG_MSG("shift outside 0..depth - 7");
   }
+  if (kind == K_YUV) {
+    if (r.n - r.pos < 6) return SEG_MSG("truncated before depth, shift and the frame's fields");
+    depth = data[r.pos++];
+    shift = data[r.pos++];
+    yf.sub_x = data[r.pos++];
+    yf.sub_y = data[r.pos++];
+    yf.matrix = data[r.pos++];
+    yf.flags = data[r.pos++];
+    if (const char* err = residual_yuv_fields_check(false, depth, shift, yf)) return err;
+  }
+  const uint64_t N = residual_samples(kind, s.H, s.W, yf);
   if (!r.u32(&s.seg_len) || !r.u32(&s.n_seg)) return SEG_MSG("truncated before seg_len, n_seg");
   if (s.seg_len < RESIDUAL_SEG_MIN || s.seg_len > RESIDUAL_SEG_MAX)
     return SEG_MSG("seg_len outside 256..65536");
-  if ((uint64_t)s.n_seg != residual_seg_count(s.H, s.W, s.seg_len))
-    return SEG_MSG("n_seg is not ceil(3 H W / seg_len)");
+  if ((uint64_t)s.n_seg != residual_seg_count(N, s.seg_len))
+    return kind == K_YUV ? SEG_MSG("n_seg is not ceil(N / seg_len)") : SEG_MSG("n_seg is not ceil(3 H W / seg_len)");
   uint32_t ln = 0;
   if (!r.u32(&ln)) return SEG_MSG("truncated before the inner length");
   if (ln > r.n - r.pos) return SEG_MSG("the inner length runs past the end");
@@ -802,7 +874,7 @@ const char* parse_residual_seg(bool deep, const uint8_t* data, size_t n, uint32_
     r.u32(&v);  // inside the residual length, which is inside the file
     if (v % 4) return SEG_MSG("a segment length that is not a multiple of 4");
     if (v < 8) return SEG_MSG("a segment length below 8");
-    if (v > residual_seg_bound(s.H, s.W, s.seg_len, k))
+    if (v > residual_seg_bound(N, s.seg_len, k))
       return SEG_MSG("a segment length above the capacity bound");
     sum += v;
   }
@@ -813,13 +885,15 @@ const char* parse_residual_seg(bool deep, const uint8_t* data, size_t n, uint32_
   if (deep) {
     uint32_t lo_len = 0;
     if (!r.u32(&lo_len)) return SEG_MSG("truncated before the low-bit plane's length");
-    if ((uint64_t)lo_len != residual_lo_bytes(s.H, s.W, shift))
-      return SEG_MSG("lo_len is not 8 * 3 H ceil(W / 64) shift");
+    if ((uint64_t)lo_len != residual_lo_bytes(kind, s.H, s.W, yf, shift))
+      return kind == K_YUV ? SEG_MSG("lo_len is not 8 * shift * (H G_0 + 2 hc G_1)")
+                           : SEG_MSG("lo_len is not 8 * 3 H ceil(W / 64) shift");
     if (lo_len > r.n - r.pos) return SEG_MSG("truncated inside the low-bit plane");
     more->depth = depth;
     more->shift = shift;
     more->lo_off = r.pos;
     more->lo_len = lo_len;
+    if (frame) *frame = yf;
     r.pos += lo_len;
     if (r.pos != r.n) return SEG_MSG("bytes left over after the low-bit plane");
   }
@@ -835,15 +909,28 @@ const char* parse_residual_seg(bool deep, const uint8_t* data, size_t n, uint32_
 
 const char* container_parse_residual_seg(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                          ResidualSegInfo* info) {
-  return parse_residual_seg(false, data, n, n_levels, max_pixels, info, nullptr);
+  return parse_residual_seg(K_SEG, data, n, n_levels, max_pixels, info, nullptr, nullptr);
 }
 
 const char* container_parse_residual_deep(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                           ResidualDeepInfo* info) {
   if (info == nullptr) return "container_parse_residual_deep: null info";
   ResidualDeepInfo d{};
-  if (const char* err = parse_residual_seg(true, data, n, n_levels, max_pixels, &d.seg, &d)) return err;
+  if (const char* err = parse_residual_seg(K_DEEP, data, n, n_levels, max_pixels, &d.seg, &d, nullptr)) return err;
   *info = d;
+  return nullptr;
+}
+
+const char* container_parse_residual_yuv(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                         ResidualYuvInfo* info) {
+  if (info == nullptr) return "container_parse_residual_yuv: null info";
+  ResidualYuvInfo y{};
+  YuvFields f{};
+  if (const char* err = parse_residual_seg(K_YUV, data, n, n_levels, max_pixels, &y.deep.seg, &y.deep, &f)) return err;
+  y.sub_x = f.sub_x, y.sub_y = f.sub_y, y.matrix = f.matrix;
+  y.full_range = (f.flags & 1u) != 0;
+  y.site_left = (f.flags & 2u) != 0;
+  *info = y;
   return nullptr;
 }
 

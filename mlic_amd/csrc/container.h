@@ -279,5 +279,38 @@ const char* container_write_residual_deep(uint32_t H, uint32_t W, bool vbr, uint
 const char* container_parse_residual_deep(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
                                           ResidualDeepInfo* info);
 
+// ---- The Y'CbCr residual file (DESIGN.md section 5 "Residual coding", "Y'CbCr frames"; residual_yuv.h has the
+// definitions): the deep file for the three planes of a frame.  H, W are the luma size, hc = ceil(H / sub_y),
+// wc = ceil(W / sub_x), N = H W + 2 hc wc samples, G_0 = ceil(W / 64), G_1 = ceil(wc / 64).  Always segmented.
+//     4 bytes "MLR4" | the rest of the "MLR2" header | the 24 tables
+//     >B depth (8..16) | >B shift (0 at depth 8, else 0..depth - 7) | >B sub_x | >B sub_y | >B matrix (0..2)
+//     >B flags (bit 0 full_range, bit 1 site_x left; the rest 0)
+//     >I seg_len | >I n_seg = ceil(N / seg_len) | >I inner_len, the inner file | >I res_len | the index | the segments
+//     >I lo_len = 8 shift (H G_0 + 2 hc G_1) | the low-bit plane (64-bit words little-endian)
+// The inner file is what the Y'CbCr encode writes without a residual.  As H, "MLR4" exceeds every max_pixels.
+struct ResidualYuvInfo {
+  ResidualDeepInfo deep;  // everything the "MLR3" file has
+  uint32_t sub_x, sub_y, matrix;
+  bool full_range, site_left;
+};
+inline bool is_residual_yuv_file(const uint8_t* data, size_t n) {
+  return n >= 4 && data[0] == 'M' && data[1] == 'L' && data[2] == 'R' && data[3] == '4';
+}
+// As container_write_residual_deep with the frame's fields; flags as in the file.  Refused besides, each with its own
+// message: a depth outside 8..16; a nonzero shift at depth 8, a shift outside 0..depth - 7 above; a sub pair that is
+// not {1, 1}, {2, 1} or {2, 2}; a matrix outside 0..2, matrix 2 at depth 8; reserved flag bits; n_seg not
+// ceil(N / seg_len); a lo_len that is not 8 shift (H G_0 + 2 hc G_1).
+const char* container_write_residual_yuv(uint32_t H, uint32_t W, bool vbr, uint32_t tau, uint32_t depth, uint32_t shift,
+                                         uint32_t sub_x, uint32_t sub_y, uint32_t matrix, uint32_t flags,
+                                         uint64_t digest, const uint8_t* m, const uint16_t* freq, uint32_t seg_len,
+                                         uint32_t n_seg, const uint32_t* seg_bytes, const uint8_t* inner,
+                                         size_t inner_len, const uint8_t* segs, size_t segs_len, const uint8_t* lo,
+                                         size_t lo_len, uint8_t* out, size_t cap, size_t* len);
+// Refused, each with its own message: everything container_parse_residual_seg refuses (with "MLR4" as the magic and
+// n_seg against this frame's N); truncation before depth, shift and the frame's fields; what the writer refuses of
+// them; truncation before lo_len; a wrong lo_len; truncation inside the plane; bytes left over.
+const char* container_parse_residual_yuv(const uint8_t* data, size_t n, uint32_t n_levels, uint64_t max_pixels,
+                                         ResidualYuvInfo* info);
+
 }  // namespace mlic
 #endif

@@ -416,6 +416,33 @@ void image_egress_yuv16(const float* src, const int64_t* src_strides, int B, int
 // that must refuse before they touch a device
 void image_yuv16_check(const YuvDesc* desc, int depth, int msb, const void* y, const void* cb, const void* cr,
                        const char* who);
+// Residual coding's two passes over the planes of Y'CbCr frames (residual_yuv.hip; residual_yuv.h has the definitions;
+// DESIGN.md section 5 "Residual coding", "Y'CbCr frames").  word_bytes 1: byte planes, depth 8, msb 0, shift 0 and a
+// null lo_plane; word_bytes 2: uint16 planes, depth 9..16, msb 0 / 1, shift 0..depth - 7.  Planes come as {y, cb, cr}
+// pointers with element strides {image, row, column}; of desc only sub_x / sub_y are used, the rest is validated as
+// the egress validates it.  ctx u8 and sym int16 are dense [B][N] in the canonical order, N = H W + 2 hc wc.
+// front: ctx, ctx_count [B][24] and digest [B] always; with the three x planes (all null without) also sym, lo_plane
+// (u64 [B][shift (H G_0 + 2 hc G_1)], null at shift 0), hist [B][24][128], max_err, max_abs_q [B] and sum_abs_q [B].
+// stats: the last two alone.  apply: the three out planes = rec of (base, (sym << shift) + lo); with the three ref
+// planes sq_err u64 [B][3] (per plane) and max_err u32 [B]; status u32 [B] is nonzero for a frame that holds a sym
+// outside +-255 (such a sample is written as base).  All zero what they accumulate into on the stream, check their
+// arguments before any HIP call and throw with `who` in front.
+void image_residual_front_planes(const char* who, int word_bytes, const void* const base[3],
+                                 const int64_t* const base_strides[3], const void* const x[3],
+                                 const int64_t* const x_strides[3], const YuvDesc* desc, int depth, int msb, int B, int H,
+                                 int W, int tau, int shift, uint8_t* ctx, uint32_t* ctx_count, uint64_t* digest,
+                                 int16_t* sym, uint64_t* lo_plane, uint32_t* hist, uint32_t* max_err,
+                                 uint32_t* max_abs_q, uint64_t* sum_abs_q, hipStream_t st);
+void image_residual_stats_planes(const char* who, int word_bytes, const void* const base[3],
+                                 const int64_t* const base_strides[3], const void* const x[3],
+                                 const int64_t* const x_strides[3], const YuvDesc* desc, int depth, int msb, int B, int H,
+                                 int W, int tau, uint32_t* max_abs_q, uint64_t* sum_abs_q, hipStream_t st);
+void image_residual_apply_planes(const char* who, int word_bytes, const void* const base[3],
+                                 const int64_t* const base_strides[3], const int16_t* sym, const uint64_t* lo_plane,
+                                 const YuvDesc* desc, int depth, int msb, int B, int H, int W, int tau, int shift,
+                                 void* const out[3], const int64_t* const out_strides[3], const void* const ref[3],
+                                 const int64_t* const ref_strides[3], uint64_t* sq_err, uint32_t* max_err,
+                                 uint32_t* status, hipStream_t st);
 // tiled decode's egress: the h x w region at (y0, x0) of the H x W image, blended from the tiles of the grid
 // (container.h: tile T, overlap V) with feathered seams, as uint8 through dst's {row, column, channel} strides.
 // tiles_dev: the device table, tile index (row-major) -> that tile's contiguous fp32 [3][pad64(ey)][pad64(ex)]

@@ -56,16 +56,29 @@ int64_t first_uncodable(const int16_t* sym, const uint8_t* ctx, int64_t n, const
 }
 }  // namespace
 
+namespace {
+void seg_len_check(const char* what, int64_t N, int seg_len, int64_t n_seg, const char* of) {
+  if (seg_len < RES_SEG_MIN || seg_len > RES_SEG_MAX)
+    fail(what, "the segment length " + std::to_string(seg_len) + " is outside 256..65536");
+  if (n_seg != residual_n_seg(N, seg_len))
+    fail(what, "n_seg " + std::to_string(n_seg) + " is not ceil(" + of + " / seg_len) = " +
+                   std::to_string(residual_n_seg(N, seg_len)));
+}
+}  // namespace
+
 void residual_seg_check(const char* what, int B, int H, int W, int seg_len, int64_t n_seg) {
   if (B < 1) fail(what, "B must be positive");
   if (H < 1 || W < 1) fail(what, "H and W must be positive");
   const int64_t N = 3 * (int64_t)H * W;
   if (N > RES_SEG_MAX_N) fail(what, "the image has more than 2^29 samples");
-  if (seg_len < RES_SEG_MIN || seg_len > RES_SEG_MAX)
-    fail(what, "the segment length " + std::to_string(seg_len) + " is outside 256..65536");
-  if (n_seg != residual_n_seg(N, seg_len))
-    fail(what, "n_seg " + std::to_string(n_seg) + " is not ceil(3 H W / seg_len) = " +
-                   std::to_string(residual_n_seg(N, seg_len)));
+  seg_len_check(what, N, seg_len, n_seg, "3 H W");
+}
+
+void residual_seg_check_n(const char* what, int B, int64_t N, int seg_len, int64_t n_seg) {
+  if (B < 1) fail(what, "B must be positive");
+  if (N < 1) fail(what, "N must be positive");
+  if (N > RES_SEG_MAX_N) fail(what, "N is above 2^29 samples");
+  seg_len_check(what, N, seg_len, n_seg, "N");
 }
 
 void residual_seg_tables_check(const char* what, const uint8_t* m, const uint16_t* freq, int B) {
@@ -143,8 +156,13 @@ void residual_seg_dec_table(const uint8_t* m, const uint16_t* freq, ResSegDecTab
 void residual_seg_encode_host(const int16_t* sym, const uint8_t* ctx, int B, int H, int W, const uint8_t* m,
                               const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out, size_t cap,
                               uint32_t* seg_bytes, uint64_t* len) {
-  const char* what = "residual_encode_segments_host";
-  const int64_t N = 3 * (int64_t)H * W;
+  residual_seg_encode_host_n("residual_encode_segments_host", sym, ctx, B, 3 * (int64_t)H * W, m, freq, seg_len, n_seg,
+                             out, cap, seg_bytes, len);
+}
+
+void residual_seg_encode_host_n(const char* what, const int16_t* sym, const uint8_t* ctx, int B, int64_t N,
+                                const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                                size_t cap, uint32_t* seg_bytes, uint64_t* len) {
   for (int b = 0; b < B; ++b) {
     const uint8_t* mb = m + (size_t)b * RES_CTX;
     const CdfTables t = coder_tables(mb, freq + (size_t)b * RES_CTX * RES_BINS);
@@ -179,8 +197,13 @@ void residual_seg_encode_host(const int16_t* sym, const uint8_t* ctx, int B, int
 void residual_seg_decode_host(const uint8_t* data, size_t stride, const uint64_t* data_len, const uint32_t* seg_bytes,
                               const uint8_t* ctx, int B, int H, int W, const uint8_t* m, const uint16_t* freq,
                               int seg_len, int64_t n_seg, int16_t* sym) {
-  const char* what = "residual_decode_segments_host";
-  const int64_t N = 3 * (int64_t)H * W;
+  residual_seg_decode_host_n("residual_decode_segments_host", data, stride, data_len, seg_bytes, ctx, B,
+                             3 * (int64_t)H * W, m, freq, seg_len, n_seg, sym);
+}
+
+void residual_seg_decode_host_n(const char* what, const uint8_t* data, size_t stride, const uint64_t* data_len,
+                                const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N, const uint8_t* m,
+                                const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym) {
   (void)data_len;
   for (int b = 0; b < B; ++b) {
     const uint8_t* mb = m + (size_t)b * RES_CTX;

@@ -91,6 +91,7 @@ struct alignas(16) ResSegDecTable {
 // Host side (residual_seg.cpp).  The checks throw std::runtime_error with a message that begins "mlic: <what>: ";
 // the device entries call them before any HIP call.  m: [B][24], freq: [B][24][128] (the file's form).
 void residual_seg_check(const char* what, int B, int H, int W, int seg_len, int64_t n_seg);
+void residual_seg_check_n(const char* what, int B, int64_t N, int seg_len, int64_t n_seg);  // 1 <= N <= RES_SEG_MAX_N
 void residual_seg_tables_check(const char* what, const uint8_t* m, const uint16_t* freq, int B);
 // each length a multiple of 4, >= 8 and within residual_seg_cap_bytes of its samples; sum = data_len[b] <= stride
 void residual_seg_lengths_check(const char* what, const uint32_t* seg_bytes, const uint64_t* data_len, size_t stride,
@@ -106,6 +107,14 @@ void residual_seg_encode_host(const int16_t* sym, const uint8_t* ctx, int B, int
 void residual_seg_decode_host(const uint8_t* data, size_t stride, const uint64_t* data_len, const uint32_t* seg_bytes,
                               const uint8_t* ctx, int B, int H, int W, const uint8_t* m, const uint16_t* freq,
                               int seg_len, int64_t n_seg, int16_t* sym);
+// The same two for a string of N samples that is not an RGB image's 3 H W (a Y'CbCr frame: residual_yuv.h), with the
+// entry's name for the messages; the two above forward here.
+void residual_seg_encode_host_n(const char* what, const int16_t* sym, const uint8_t* ctx, int B, int64_t N,
+                                const uint8_t* m, const uint16_t* freq, int seg_len, int64_t n_seg, uint8_t* out,
+                                size_t cap, uint32_t* seg_bytes, uint64_t* len);
+void residual_seg_decode_host_n(const char* what, const uint8_t* data, size_t stride, const uint64_t* data_len,
+                                const uint32_t* seg_bytes, const uint8_t* ctx, int B, int64_t N, const uint8_t* m,
+                                const uint16_t* freq, int seg_len, int64_t n_seg, int16_t* sym);
 
 }  // namespace mlic
 #endif

@@ -63,6 +63,11 @@
         (--residual-segment defaults to the codec's 4096), the low bits of every residual stored raw;
         --residual-shift S fixes how many (0..depth - 7; default: the codec's shift rule).  decode writes the 16-bit
         PPM at the file's depth.
+    ... --frame-max-error T / --frame-lossless (encode of a .y4m or .yuv frame): residual coding of the planes
+        themselves (the "MLR4" file): every sample of Y', Cb and Cr of the decode is within T of the source's, at the
+        frame's own subsampling and depth; always segmented, with --residual-segment, --residual-shift (frames deeper
+        than 8 bits) and --residual-coder as above.  decode of such a file to .y4m / .yuv takes matrix, range, siting,
+        subsampling and depth from the file.  Not with --max-bpp, --level auto, --roi, --tile, --scale or --layered.
     ... --base-only (decode): the base picture of a residual file alone, without the second layer.
     python tools/mlic_codec.py strip IN.bit -o OUT.bit             the base file inside a residual file
     python tools/mlic_codec.py truncate IN.bit -k K -o OUT.bit     the first bytes of a layered file up to the end
@@ -458,6 +463,8 @@ def parse_args(argv=None):
     ap.add_argument("--residual-segment", type=int, default=None, metavar="L")
     ap.add_argument("--residual-coder", choices=["host", "device"], default=None)
     ap.add_argument("--residual-shift", type=int, default=None, metavar="S")
+    ap.add_argument("--frame-max-error", type=int, default=None, metavar="T")
+    ap.add_argument("--frame-lossless", action="store_true")
     args = ap.parse_args(argv)
     if args.mode == "strip":
         if args.dst is not None or args.output is None:
@@ -471,17 +478,36 @@ def parse_args(argv=None):
         if args.max_error not in (None, 0):
             ap.error("--lossless is --max-error 0")
         args.max_error = 0
+    if args.frame_lossless:
+        if args.frame_max_error not in (None, 0):
+            ap.error("--frame-lossless is --frame-max-error 0")
+        args.frame_max_error = 0
+    if args.frame_max_error is not None:
+        if args.mode != "encode":
+            ap.error("--frame-max-error / --frame-lossless go with encode (a residual file is recognised by its magic)")
+        if args.max_error is not None:
+            ap.error("--frame-max-error / --frame-lossless and --max-error / --lossless do not go together")
+        if not _is_yuv(args.src):
+            ap.error("--frame-max-error / --frame-lossless go with a .y4m or .yuv source (an image file takes "
+                     "--max-error / --lossless)")
+        if not 0 <= args.frame_max_error <= 127:
+            ap.error("--frame-max-error: 0 to 127 expected")
+        if args.max_bpp is not None or args.level == "auto" or args.roi is not None or args.roi_levels is not None or \
+                args.tile is not None or args.scale is not None or args.coded_size is not None or args.layered:
+            ap.error("--frame-max-error goes with --level N alone, not with --max-bpp, --level auto, --roi, --tile, "
+                     "--scale, --coded-size or --layered")
     if args.residual_segment is not None:
-        if args.max_error is None:
+        if args.max_error is None and args.frame_max_error is None:
             ap.error("--residual-segment goes with encode --max-error T / --lossless")
         if not 256 <= args.residual_segment <= 65536:
             ap.error("--residual-segment: 256 to 65536 expected")
-    if args.residual_coder is not None and args.mode == "encode" and args.residual_segment is None:
+    if args.residual_coder is not None and args.mode == "encode" and args.residual_segment is None and \
+            args.frame_max_error is None:  # a frame's residual file is always segmented
         ap.error("--residual-coder goes with --residual-segment L (encode) or with decode")
     if args.residual_coder is not None and args.mode not in ("encode", "decode"):
         ap.error("--residual-coder goes with encode and decode")
     if args.residual_shift is not None:
-        if args.mode != "encode" or args.max_error is None:
+        if args.mode != "encode" or (args.max_error is None and args.frame_max_error is None):
             ap.error("--residual-shift goes with encode --max-error T / --lossless of an image deeper than 8 bits")
         if not 0 <= args.residual_shift <= 9:
             ap.error("--residual-shift: 0 to depth - 7 expected")
@@ -499,7 +525,7 @@ def parse_args(argv=None):
         if args.mode != "decode":
             ap.error("--base-only goes with decode")
         if args.slices is not None or args.fill is not None or args.out_size is not None or args.filter is not None or \
-                args.region is not None or args.depth is not None or _is_yuv(args.dst or ""):
+                args.region is not None or (args.depth is not None and not _is_yuv(args.dst or "")):
             ap.error("--base-only goes alone: a residual file takes no --slices, --fill, --out-size, --filter, --region "
                      "or --depth")
     if args.mode == "truncate":
@@ -712,7 +738,7 @@ def main(argv=None):
     if args.mode == "strip":
         with open(args.src, "rb") as f:
             data = f.read()
-        if not (codec.is_residual_file(data) or codec.is_residual_deep_file(data)):
+        if not (codec.is_residual_file(data) or codec.is_residual_deep_file(data) or codec.is_residual_yuv_file(data)):
             raise SystemExit(f"{args.src}: not a residual file (no MLR1 / MLR2 magic): encode --max-error T writes one")
         inner = codec.strip_residual(data)
         with open(args.output, "wb") as f:
@@ -758,6 +784,8 @@ def main(argv=None):
                   f"{d['shape'][1]}, base {d['base_bytes']} B, residual {d['residual_bytes']} B"
                   + (f" in {d['segments']} segments of {d['residual_segment']}" if "segments" in d else "") +
                   (f", depth {d['depth']}, low bits {d['low_bytes']} B (shift {d['shift']})" if "shift" in d else "") +
+                  (f", Y'CbCr frame: sub {d['sub'][0]}x{d['sub'][1]}, matrix {d['matrix']}, "
+                   f"{'full' if d['full_range'] else 'limited'} range, chroma sited {d['site_x']}" if "sub" in d else "") +
                   f", header and tables {d['header_bytes']} B, {d['bytes']} bytes, {d['bpp']:.4f} bpp")
             return
         if d.get("scaled"):
@@ -773,6 +801,25 @@ def main(argv=None):
     if args.mode == "encode" and args.frame_file:
         planes, fmt = load_yuv(args.src, args)
         net = load_model(args)
+        if args.frame_max_error is not None:  # the "MLR4" file: every sample of every plane within the bound
+            if args.residual_shift is not None and fmt.depth == 8:
+                raise SystemExit(f"{args.src}: --residual-shift goes with a frame deeper than 8 bits")
+            try:
+                files, info = codec.encode_residual_yuv(
+                    net, *planes, fmt, max_error=args.frame_max_error, level=args.level,
+                    residual_segment=args.residual_segment or codec.DEFAULT_RESIDUAL_SEGMENT,
+                    residual_shift=args.residual_shift, residual_coder=args.residual_coder or "device",
+                    return_info=True)
+            except ValueError as e:
+                raise SystemExit(f"{args.src}: {e}") from None
+            with open(args.dst, "wb") as f:
+                f.write(files[0])
+            d = info[0]
+            H, W = planes[0].shape
+            print(f"{args.src}: {H} x {W} {fmt!r} -> {len(files[0])} bytes, {d['bpp']:.4f} bpp, max error "
+                  f"{args.frame_max_error}: base {d['base_bytes']} B, residual {d['residual_bytes']} B in {d['segments']} "
+                  f"segments of {d['residual_segment']}, low bits {d['low_bytes']} B (shift {d['shift']})")
+            return
         files, info = codec.encode_yuv(net, *planes, fmt, level=args.level, max_bpp=args.max_bpp,
                                        max_passes=args.max_passes, return_info=True)
         with open(args.dst, "wb") as f:
@@ -791,17 +838,39 @@ def main(argv=None):
             raise SystemExit(f"{args.src}: a tiled file decodes to an RGB image, not to Y'CbCr planes")
         net = load_model(args)
         fmt = _yuv_format(args, codec._YUV_SUB[args.yuv], "left")
+        res_yuv = codec.is_residual_yuv_file(data)
+        if args.base_only and not res_yuv:
+            raise SystemExit(f"{args.src}: --base-only needs a residual file (encode --frame-max-error T)")
+        if res_yuv:  # the file knows its format; the alignment of a raw file's words stays the caller's
+            fmt = codec.residual_yuv_format(data, msb=args.msb)
+            if args.depth is not None and args.depth != fmt.depth:
+                raise SystemExit(f"{args.src}: --depth {args.depth}, but the file (MLR4) holds samples of depth {fmt.depth}")
+            want = codec._YUV_SUB[args.yuv]
+            if _ext(args.dst) == ".yuv" and want != fmt.sub:
+                raise SystemExit(f"{args.src}: --yuv {args.yuv} is {want[0]}x{want[1]} subsampled, the file (MLR4) holds "
+                                 f"{fmt.sub[0]}x{fmt.sub[1]}")
         if _ext(args.dst) == ".y4m" and args.msb:
             raise SystemExit(f"{args.dst}: a .y4m file holds LSB-aligned samples (--msb goes with a raw .yuv file)")
         ref = None
         if args.ref is not None:
             d = codec.peek(data, vbr=hasattr(net, "levels"))
             ref, rfmt = load_yuv(args.ref, args, size=(d["W"], d["H"]))
-            if _ext(args.ref) == ".y4m":
+            if _ext(args.ref) == ".y4m" and not res_yuv:
                 fmt = rfmt  # the source's subsampling and siting
-        planes, info = codec.decode_yuv(net, [data], fmt, ref=ref)
+        rkw = {}
+        if res_yuv:
+            rkw = {"enhance": not args.base_only, "residual_coder": args.residual_coder or "device"}
+        try:
+            planes, info = codec.decode_yuv(net, [data], fmt, ref=ref, **rkw)
+        except ValueError as e:
+            if not res_yuv:
+                raise
+            raise SystemExit(f"{args.src}: {e}") from None
         save_yuv(args.dst, [p[0].cpu().numpy() for p in planes], fmt, args)
         line = f"{args.src}: {info[0]['H']} x {info[0]['W']}, level {info[0]['level']}, {info[0]['bpp']:.4f} bpp, {fmt!r}"
+        if "max_error" in info[0]:
+            line += (f", max error {info[0]['max_error']}, residual {info[0]['residual_bytes']} B"
+                     f"{' (base only)' if args.base_only else ''}")
         if ref is not None:
             line += (f"\nPSNR Y {info[0]['psnr_y']:.4f} dB, U {info[0]['psnr_u']:.4f} dB, V {info[0]['psnr_v']:.4f} dB, "
                      f"YUV (6:1:1) {info[0]['psnr_yuv']:.4f} dB")
