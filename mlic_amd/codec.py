@@ -42,6 +42,8 @@ file.  `decode_images` checks the digest, decodes the residual string and `resid
 is off by more than tau, and at tau = 0 the decode is the original.  `strip_residual` returns the plain file.
 With `residual_segment=L` the residual string is cut into independently coded segments ("MLR2" file; DESIGN.md §5
 "Segments", csrc/residual_coder.hip) that `residual_encode_segments` / `residual_decode_segments` code on the device.
+Deep RGB (`encode_residual16`, "MLR3") and Y'CbCr frames (`encode_residual_yuv`, "MLR4") go through the same encoder
+and decoder (`_encode_residual_layer`, `_decode_residual_layer`); a `_ResidualKind` supplies what differs.
 
 CUDA tensors run the HIP kernels (csrc/image_io.hip, csrc/roi.hip) on the current stream; CPU tensors run a torch
 restatement, so everything but the model also works without a GPU (as metrics.py does).
@@ -52,7 +54,7 @@ import ctypes as C
 import math
 import re
 import struct
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -908,6 +910,72 @@ def _residual_apply_cpu(base, sym, tau: int, layout: Optional[str] = None, ref=N
     return img, torch.from_numpy((d * d).reshape(B, -1).sum(1)), torch.from_numpy(np.abs(d).reshape(B, -1).max(1))
 
 
+def _ptr(t):
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+
+def _front_buffers(dev, shape, with_x: bool, plane_words: Optional[int] = None) -> Dict:
+    """What a front launch writes, on `dev`: ctx (of `shape`, B first), count and digest; with x also sym, hist and
+    merr, and for the kinds with a low-bit plane (plane_words given) plane, mq and sq.  None where not asked for."""
+    B = shape[0]
+    o = dict.fromkeys(("sym", "plane", "hist", "merr", "mq", "sq"))
+    o.update(ctx=torch.empty(shape, dtype=torch.uint8, device=dev),
+             count=torch.empty(B, RES_CTX, dtype=torch.int32, device=dev),
+             digest=torch.empty(B, dtype=torch.int64, device=dev))
+    if with_x:
+        o.update(sym=torch.empty(shape, dtype=torch.int16, device=dev),
+                 hist=torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev),
+                 merr=torch.empty(B, dtype=torch.int32, device=dev))
+        if plane_words is not None:
+            o.update(plane=torch.empty(B, plane_words, dtype=torch.int64, device=dev),
+                     mq=torch.empty(B, dtype=torch.int32, device=dev), sq=torch.empty(B, dtype=torch.int64, device=dev))
+    if _lib.poison():  # what the kernel does not write shows
+        o["ctx"].fill_(0xEE)
+        for k in ("count", "digest", "hist", "merr", "mq", "sq", "plane"):
+            if o[k] is not None:
+                o[k].fill_(-1)
+        if with_x:
+            o["sym"].fill_(-0x1112)
+    return o
+
+
+def _front_result(o: Dict) -> Dict:
+    """A front wrapper's result from its buffers: the counts as int64."""
+    out = {"ctx": o["ctx"], "ctx_count": o["count"].to(torch.int64), "digest": o["digest"]}
+    if o["sym"] is not None:
+        out.update(sym=o["sym"], hist=o["hist"].to(torch.int64), max_err=o["merr"].to(torch.int64))
+        if o["plane"] is not None:
+            out.update(plane=o["plane"], max_abs_q=o["mq"].to(torch.int64), sum_abs_q=o["sq"])
+    return out
+
+
+def _apply_out(shape, deep: bool, dev) -> torch.Tensor:
+    """An apply wrapper's default `out`: uint8, or uint16 words (made as int16, which fill_ takes), poison filled."""
+    out = torch.empty(tuple(shape), dtype=torch.int16 if deep else torch.uint8, device=dev)
+    if _lib.poison():
+        out.fill_(-1 if deep else 0xFF)
+    return out.view(torch.uint16) if deep else out
+
+
+def _apply_buffers(dev, B: int, ref, sq_shape):
+    """(sq, merr, status) of an apply launch: the error sums go with ref, the status is one word per image."""
+    sq = merr = None
+    if ref is not None:
+        sq = torch.full(sq_shape, -1, dtype=torch.int64, device=dev)
+        merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    return sq, merr, torch.full((B,), -1, dtype=torch.int32, device=dev)
+
+
+def _apply_refusal(what: str, noun: str, status, refs):
+    """After an apply launch: reads the status back and refuses the first image with a symbol outside [-255, 255];
+    `refs` (moved to the device by the caller) stay alive until the stream has read them."""
+    bad = torch.nonzero(status).flatten().cpu().tolist()
+    for t in refs:
+        t.record_stream(torch.cuda.current_stream())
+    if bad:
+        raise ValueError(f"{what}: {noun} {bad[0]} holds a symbol outside [-255, 255]")
+
+
 def residual_front(base, x=None, tau: int = 0, layout: Optional[str] = None, x_layout: Optional[str] = None) -> Dict:
     """The encoder's and the decoder's first pass over the base image (csrc/residual.hip, one launch; DESIGN.md §5
     "Residual coding").  base: uint8 [B,H,W,3] / [B,3,H,W] (or one image), any strides; x: the original, the same
@@ -924,30 +992,13 @@ def residual_front(base, x=None, tau: int = 0, layout: Optional[str] = None, x_l
     base = _in_place(base, layout)
     dev = base.device
     with torch.cuda.device(dev):
-        ctx = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev)
-        count = torch.empty(B, RES_CTX, dtype=torch.int32, device=dev)
-        digest = torch.empty(B, dtype=torch.int64, device=dev)
-        sym = hist = merr = None
         if x is not None:
             x = _in_place(x, x_layout)
-            sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
-            hist = torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev)
-            merr = torch.empty(B, dtype=torch.int32, device=dev)
-        if _lib.poison():  # what the kernel does not write shows
-            ctx.fill_(0xEE)
-            for t in (count, digest, hist, merr):
-                if t is not None:
-                    t.fill_(-1)
-            if sym is not None:
-                sym.fill_(-0x1112)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.call("mlic_image_residual_front_u8", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)), ptr(x),
-                  None if x is None else (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, tau, ptr(ctx), ptr(count),
-                  ptr(digest), ptr(sym), ptr(hist), ptr(merr))
-        out = {"ctx": ctx, "ctx_count": count.to(torch.int64), "digest": digest}
-        if x is not None:
-            out.update(sym=sym, hist=hist.to(torch.int64), max_err=merr.to(torch.int64))
-    return out
+        o = _front_buffers(dev, (B, 3, H, W), x is not None)
+        _lib.call("mlic_image_residual_front_u8", _stream(), _ptr(base), (C.c_int64 * 4)(*_strides(base, layout)), _ptr(x),
+                  None if x is None else (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, tau, _ptr(o["ctx"]),
+                  _ptr(o["count"]), _ptr(o["digest"]), _ptr(o["sym"]), _ptr(o["hist"]), _ptr(o["merr"]))
+        return _front_result(o)
 
 
 def residual_apply(base, sym, tau: int, layout: Optional[str] = None, ref=None, out: Optional[torch.Tensor] = None):
@@ -985,10 +1036,9 @@ def residual_apply(base, sym, tau: int, layout: Optional[str] = None, ref=None, 
             ref = _in_place(ref, layout)
             sq = torch.full((B,), -1, dtype=torch.int64, device=dev)
             merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.call("mlic_image_residual_apply_u8", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
-                  ptr(sym), B, H, W, tau, ptr(out), (C.c_int64 * 4)(*_strides(out, layout)), ptr(ref),
-                  None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)), ptr(sq), ptr(merr))
+        _lib.call("mlic_image_residual_apply_u8", _stream(), _ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
+                  _ptr(sym), B, H, W, tau, _ptr(out), (C.c_int64 * 4)(*_strides(out, layout)), _ptr(ref),
+                  None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)), _ptr(sq), _ptr(merr))
     return out if ref is None else (out, sq, merr.to(torch.int64))
 
 
@@ -1045,23 +1095,49 @@ def is_residual_seg_file(data: bytes) -> bool:
     return bytes(data[:4]) == RESIDUAL_SEG_MAGIC
 
 
+def _write_residual(sfx: str, H, W, vbr, tau, own, digest, m, freq, seg, blobs) -> bytes:
+    """The body of write_container_residual<sfx>: H, W, vbr, tau and `own` (the kind's own integer fields), the
+    digest and the tables, seg = (segment, seg_bytes) of a segmented kind or None, then `blobs`, each behind its
+    length.  Arguments are converted and checked in the order the four functions always had: m, freq, seg_bytes,
+    the shapes, the lengths' range, then the integers.  The library is called twice: for the size, then to write."""
+    what = "write_container_residual" + sfx
+    m = np.ascontiguousarray(m, dtype=np.uint8)
+    freq = np.ascontiguousarray(freq, dtype=np.uint16)
+    if seg is not None:
+        sb = np.ascontiguousarray(np.asarray(seg[1], np.int64).reshape(-1))
+    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
+        raise ValueError(f"{what}: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
+    if seg is not None and (sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF))):
+        raise ValueError(f"{what}: segment lengths must fit 32 bits")
+    args = (H, W, int(bool(vbr)), int(tau), *[int(v) for v in own], int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data,
+            freq.ctypes.data)
+    if seg is not None:
+        sb = sb.astype(np.uint32)
+        args += (int(seg[0]) & 0xFFFFFFFF, sb.size, sb.ctypes.data)
+    for blob in blobs:
+        args += (blob, len(blob))
+    n = C.c_size_t()
+    _lib.call("mlic_container_write_residual" + sfx, *args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(max(1, n.value))
+    _lib.call("mlic_container_write_residual" + sfx, *args, buf, len(buf), C.byref(n))
+    return C.string_at(buf, n.value)
+
+
+def _parse_residual(entry: str, info, data: bytes, n_levels, max_pixels):
+    """The body of the four parse_container_residual* functions: `entry` fills `info`, the kind's info struct."""
+    data = bytes(data)
+    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
+    _lib.call(entry, data, len(data), nl, int(max_pixels), C.byref(info))
+    return info
+
+
 def write_container_residual(H: int, W: int, inner: bytes, res: bytes, tau: int, digest: int, m, freq,
                              vbr: bool = False) -> bytes:
     """The residual file (mlic_container_write_residual): "MLR1", version, flags (bit 0: vbr), tau, n_ctx, H, W, the
     digest of the base image, the 24 tables (m and 2 m + 2 frequencies each, or 0xFF), then `inner`, the image's
     plain or VBR file, unchanged, and `res`, the residual string, each behind its length."""
     inner, res = bytes(inner), bytes(res)
-    m = np.ascontiguousarray(m, dtype=np.uint8)
-    freq = np.ascontiguousarray(freq, dtype=np.uint16)
-    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
-        raise ValueError(f"write_container_residual: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
-    n = C.c_size_t()
-    args = (H, W, int(bool(vbr)), int(tau), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data, freq.ctypes.data, inner,
-            len(inner), res, len(res))
-    _lib.call("mlic_container_write_residual", *args, None, 0, C.byref(n))
-    buf = C.create_string_buffer(max(1, n.value))
-    _lib.call("mlic_container_write_residual", *args, buf, len(buf), C.byref(n))
-    return C.string_at(buf, n.value)
+    return _write_residual("", H, W, vbr, tau, (), digest, m, freq, None, (inner, res))
 
 
 def parse_container_residual(data: bytes, n_levels: Optional[int] = None,
@@ -1069,11 +1145,7 @@ def parse_container_residual(data: bytes, n_levels: Optional[int] = None,
     """The validating parser of a residual file (mlic_container_parse_residual): raises _lib.MlicError on any
     malformed input.  The flags say whether the inner file has a level word; n_levels bounds it (None: any level).
     info.inner is the inner file's ContainerInfo, its offsets relative to data[info.inner_off:]."""
-    data = bytes(data)
-    info = _lib.ContainerResidualInfo()
-    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
-    _lib.call("mlic_container_parse_residual", data, len(data), nl, int(max_pixels), C.byref(info))
-    return info
+    return _parse_residual("mlic_container_parse_residual", _lib.ContainerResidualInfo(), data, n_levels, max_pixels)
 
 
 def _file_tables(data: bytes, s: _lib.ContainerResidualInfo) -> Dict:
@@ -1092,15 +1164,16 @@ def strip_residual(data: bytes, n_levels: Optional[int] = None, max_pixels: int 
     return data[s.inner_off:s.inner_off + s.inner_len]
 
 
+_RESIDUAL_PARSERS = {RESIDUAL_MAGIC: ("mlic_container_parse_residual", _lib.ContainerResidualInfo),
+                     RESIDUAL_SEG_MAGIC: ("mlic_container_parse_residual_seg", _lib.ContainerResidualSegInfo),
+                     b"MLR3": ("mlic_container_parse_residual_deep", _lib.ContainerResidualDeepInfo),
+                     b"MLR4": ("mlic_container_parse_residual_yuv", _lib.ContainerResidualYuvInfo)}
+
+
 def _parse_residual_any(data: bytes, n_levels, max_pixels):
-    """The parse of a residual file of any kind (told apart by the magic)."""
-    if bytes(data[:4]) == b"MLR4":
-        return parse_container_residual_yuv(data, n_levels, max_pixels)
-    if is_residual_deep_file(data):
-        return parse_container_residual_deep(data, n_levels, max_pixels)
-    if is_residual_seg_file(data):
-        return parse_container_residual_seg(data, n_levels, max_pixels)
-    return parse_container_residual(data, n_levels, max_pixels)
+    """The parse of a residual file of any kind (told apart by the magic; "MLR1"'s parser refuses any other)."""
+    entry, info = _RESIDUAL_PARSERS.get(bytes(data[:4]), _RESIDUAL_PARSERS[RESIDUAL_MAGIC])
+    return _parse_residual(entry, info(), data, n_levels, max_pixels)
 
 
 def _peek_residual(data: bytes, n_levels, max_pixels) -> Dict:
@@ -1111,13 +1184,13 @@ def _peek_residual(data: bytes, n_levels, max_pixels) -> Dict:
            "y_len": c.y_len, "z_len": c.z_len, "digest": int(s.digest), "base_bytes": int(s.inner_len),
            "residual_bytes": int(s.res_len), "header_bytes": len(data) - int(s.inner_len) - int(s.res_len),
            "bytes": len(data), "bpp": 8.0 * len(data) / (s.H * s.W)}
-    yuv = bytes(data[:4]) == b"MLR4"
-    if is_residual_seg_file(data) or is_residual_deep_file(data) or yuv:
+    magic = bytes(data[:4])
+    if magic != RESIDUAL_MAGIC:  # every kind but "MLR1" has segments
         out.update(residual_segment=int(s.seg_len), segments=int(s.n_seg))
-    if is_residual_deep_file(data) or yuv:
+    if magic in (b"MLR3", b"MLR4"):  # the low-bit plane
         out.update(depth=int(s.depth), shift=int(s.shift), low_bytes=int(s.lo_len))
         out["header_bytes"] -= int(s.lo_len)
-    if yuv:
+    if magic == b"MLR4":
         out.update(sub=(int(s.sub_x), int(s.sub_y)), matrix={0: "bt601", 1: "bt709", 2: "bt2020"}[int(s.matrix)],
                    full_range=bool(s.full_range), site_x="left" if s.site_x else "centre")
     return out
@@ -1301,21 +1374,7 @@ def write_container_residual_seg(H: int, W: int, inner: bytes, segs: bytes, seg_
     the "MLR1" file, seg_len, n_seg, `inner` behind its length, and behind res_len the n_seg segment byte lengths
     and `segs`, the concatenated segments."""
     inner, segs = bytes(inner), bytes(segs)
-    m = np.ascontiguousarray(m, dtype=np.uint8)
-    freq = np.ascontiguousarray(freq, dtype=np.uint16)
-    sb = np.ascontiguousarray(np.asarray(seg_bytes, np.int64).reshape(-1))
-    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
-        raise ValueError(f"write_container_residual_seg: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
-    if sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF)):
-        raise ValueError("write_container_residual_seg: segment lengths must fit 32 bits")
-    sb = sb.astype(np.uint32)
-    n = C.c_size_t()
-    args = (H, W, int(bool(vbr)), int(tau), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data, freq.ctypes.data,
-            int(segment) & 0xFFFFFFFF, sb.size, sb.ctypes.data, inner, len(inner), segs, len(segs))
-    _lib.call("mlic_container_write_residual_seg", *args, None, 0, C.byref(n))
-    buf = C.create_string_buffer(max(1, n.value))
-    _lib.call("mlic_container_write_residual_seg", *args, buf, len(buf), C.byref(n))
-    return C.string_at(buf, n.value)
+    return _write_residual("_seg", H, W, vbr, tau, (), digest, m, freq, (segment, seg_bytes), (inner, segs))
 
 
 def parse_container_residual_seg(data: bytes, n_levels: Optional[int] = None,
@@ -1323,11 +1382,8 @@ def parse_container_residual_seg(data: bytes, n_levels: Optional[int] = None,
     """The validating parser of a segmented residual file (mlic_container_parse_residual_seg): raises _lib.MlicError
     on any malformed input.  info.index_off: the n_seg big-endian u32 lengths; info.data_off / data_len: the
     segments."""
-    data = bytes(data)
-    info = _lib.ContainerResidualSegInfo()
-    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
-    _lib.call("mlic_container_parse_residual_seg", data, len(data), nl, int(max_pixels), C.byref(info))
-    return info
+    return _parse_residual("mlic_container_parse_residual_seg", _lib.ContainerResidualSegInfo(), data, n_levels,
+                           max_pixels)
 
 
 def _seg_cap_of_hist(hist, t, n_seg: int) -> int:
@@ -1369,42 +1425,170 @@ def _base_x_hat(net, strings, shape, kw, B):
     return x_hat
 
 
+class _ResidualKind(NamedTuple):
+    """What differs between the kinds of residual layer (8-bit RGB, deep RGB, Y'CbCr planes): everything else is in
+    _encode_residual_layer and _decode_residual_layer.  A batch is a tensor [B,H,W,3] or three planes."""
+    entry: str  # the decoder's name in messages
+    noun: str  # "image" or "frame"
+    base_word: str  # "base image" or "base planes"
+    low: bool  # whether the files carry a shift and a low-bit plane
+    front: Callable  # (base, x or None, tau, shift) -> residual_front*'s dictionary
+    stats: Optional[Callable]  # (base, x, tau) -> residual_stats*'s dictionary
+    apply: Callable  # (base, sym, plane, tau, shift, ref, out) -> None, or with ref (sq_err [B...], max_abs_err [B])
+    decode_inner: Callable  # (net, inner files, ref, max_pixels) -> (batch, info): the kind's plain decode
+    size: Callable  # batch -> (H, W, device)
+    crop: Callable  # (batch, slice of the batch, h, w) -> a view; h=None: whole pictures
+    paste: Callable  # (view of one picture, the same picture decoded alone): copies it in
+    canvas: Callable  # (base, zero) -> an output batch like base
+    check_ref: Callable  # (ref, B, H, W, device) -> ref on the device, or ValueError
+    samples: Callable  # (h, w) -> N
+    plane_words: Callable  # (h, w, shift) -> 64-bit words of the low-bit plane
+    check_low: Callable  # (file index, the plane's words, h, w, shift): ValueError if a padding bit is set
+    score: Callable  # (sq_err of one picture, h, w) -> the info fields
+    extra: Callable  # shift -> the info fields a kind adds
+    write: Callable  # (H, W, inner, segs, seg_bytes, segment, tau, shift, low, digest, m, freq, vbr) -> the file
+
+
+def _copy_words(dst: torch.Tensor, src: torch.Tensor):
+    if dst.dtype == torch.uint16:  # copy_ takes int16
+        dst, src = dst.view(torch.int16), src.view(torch.int16)
+    dst.copy_(src)
+
+
+def _like(t: torch.Tensor, zero: bool) -> torch.Tensor:
+    deep = t.dtype == torch.uint16
+    out = (torch.zeros if zero else torch.empty)(tuple(t.shape), dtype=torch.int16 if deep else torch.uint8, device=t.device)
+    return out.view(torch.uint16) if deep else out
+
+
+def _rgb_kind(depth: Optional[int] = None, x_layout: Optional[str] = None) -> _ResidualKind:
+    """The kind of 8-bit RGB images (depth=None: "MLR1", "MLR2") or of deep ones ("MLR3"), base in HWC."""
+    deep = depth is not None
+    word = "uint16" if deep else "uint8"
+
+    def check_ref(ref, B, H, W, dev):
+        if not deep:  # _decode_residual16 has made a batch of it before it split the depths
+            ref, _ = _u8_batch(ref, "hwc", "decode_images ref")
+        if tuple(ref.shape) != (B, H, W, 3):
+            raise ValueError(f"decode_images: ref must be {word} {(B, H, W, 3)}, got {tuple(ref.shape)}")
+        return ref.to(dev)
+
+    def check_low(b, pl, h, w, sh):
+        if sh and w % 64 and (pl.reshape(3 * h, -(-w // 64), sh)[:, -1, :] >> np.uint64(w % 64)).any():
+            raise ValueError(f"decode_images: file {b}: the low-bit plane has bits set beyond column {w} (its "
+                             f"padding bits must be zero)")
+
+    def apply(base, sym, plane, tau, sh, ref, out):
+        if deep:
+            r = residual_apply16(base, sym, plane, depth, tau, sh, "hwc", ref=ref, out=out)
+        else:
+            r = residual_apply(base, sym, tau, "hwc", ref=ref, out=out)
+        return None if ref is None else r[1:]
+
+    def front(base, x, tau, sh):
+        if deep:
+            return residual_front16(base, x, depth, tau, sh, "hwc", x_layout)
+        return residual_front(base, x, tau, "hwc", x_layout)
+
+    def write(H, W, inner, segs, seg_bytes, L, tau, sh, low, digest, m, freq, vbr):
+        if deep:
+            return write_container_residual_deep(H, W, inner, segs, seg_bytes, L, tau, depth, sh, low, digest, m, freq,
+                                                 vbr=vbr)
+        return write_container_residual_seg(H, W, inner, segs, seg_bytes, L, tau, digest, m, freq, vbr=vbr)
+
+    kw = {"depth": depth} if deep else {}
+    peak = (1 << depth) - 1 if deep else 255
+    return _ResidualKind(
+        entry="decode_images", noun="image", base_word="base image", low=deep, front=front,
+        stats=(lambda base, x, tau: residual_stats16(base, x, depth, tau, "hwc", x_layout)) if deep else None, apply=apply,
+        decode_inner=lambda net, inner, ref, max_pixels: decode_images(net, inner, ref=ref, max_pixels=max_pixels, **kw),
+        size=lambda t: (t.size(1), t.size(2), t.device),
+        crop=lambda t, sl, h=None, w=None: t[sl] if h is None else t[sl, :h, :w],
+        paste=_copy_words, canvas=_like, check_ref=check_ref, samples=lambda h, w: 3 * h * w,
+        plane_words=residual_plane_words, check_low=check_low,
+        score=lambda sq, h, w: {"sq_err": int(sq), "psnr": psnr_from_sq_err(int(sq), 3 * h * w, peak)},
+        extra=lambda sh: {"depth": depth, "shift": sh} if deep else {}, write=write)
+
+
+def _residual_shifts(what: str, name: str, kind: _ResidualKind, depth: int, N: int, stats: Dict, shift, B: int):
+    """The shift of every image of a batch from residual_stats*'s figures: by the rule (residual_shift), or the
+    explicit `shift` (the caller's argument `name`), refused if it does not fit an image."""
+    mq, sq = stats["max_abs_q"].cpu().tolist(), stats["sum_abs_q"].cpu().tolist()
+    if shift is None:
+        return [residual_shift(depth, N, mq[b], sq[b]) for b in range(B)]
+    for b in range(B):
+        if not residual_shift_fits(mq[b], shift):
+            raise ValueError(f"{what}: {name}={shift} does not fit {kind.noun} {b} (its largest |q| is {mq[b]}): the "
+                             f"smallest shift that fits is {residual_min_shift(depth, mq[b])}")
+    return [shift] * B
+
+
+def _inner_x_hat(net, inner):
+    """(x_hat, vbr) of the plain or VBR files just written, as a decoder of each file alone will have it."""
+    vbr = hasattr(net, "levels")
+    cs = [parse_container(f, vbr, net.levels if vbr else None) for f in inner]
+    pairs = [_strings(f, c) for f, c in zip(inner, cs)]
+    kw = {"s": [c.level for c in cs]} if vbr else {}
+    x_hat = _base_x_hat(net, [[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), kw, len(inner))
+    return x_hat, vbr
+
+
+def _encode_residual_layer(kind: _ResidualKind, what: str, base, x, H: int, W: int, tau: int, shifts, segment, coder,
+                           inner, vbr: bool):
+    """The residual files of `inner` (the pictures' plain or VBR files) for the originals x over the base pictures
+    `base`, and the info fields they add -> (files, extra).  Runs of pictures with one shift take one front launch
+    each; the bound is checked on the device value; the tables come from the histograms.  segment=L: segmented
+    strings through residual_encode_segments (coder="device": sym and ctx stay on the device, the histograms alone
+    go to the host); segment=None (8-bit RGB only): one serial string per image, coded on the host ("MLR1")."""
+    B = len(inner)
+    N = kind.samples(H, W)
+    files, extra = [None] * B, [None] * B
+    a = 0
+    while a < B:  # runs of pictures with one shift: one front launch each
+        e = a + 1
+        while e < B and shifts[e] == shifts[a]:
+            e += 1
+        s = shifts[a]
+        front = kind.front(kind.crop(base, slice(a, e)), kind.crop(x, slice(a, e)), tau, s)
+        worst = int(front["max_err"].max())  # computed on the device, beside the symbols
+        if worst > tau:
+            raise RuntimeError(f"{what}: the residual layer leaves an error of {worst} > max_error {tau}")
+        hist = front["hist"].cpu().numpy()
+        digest = front["digest"].cpu().tolist()
+        tabs = [residual_tables(hist[j]) for j in range(e - a)]
+        if segment is None:
+            sym = front["sym"].cpu().numpy().reshape(e - a, -1)
+            ctx = front["ctx"].cpu().numpy().reshape(e - a, -1)
+            for j, t in enumerate(tabs):
+                res = entropy.rans_encode(sym[j].astype(np.int32), ctx[j].astype(np.int32), *_coder_tables(t))
+                files[a + j] = write_container_residual(H, W, inner[a + j], res, tau, digest[j], t["m"], t["freq"], vbr=vbr)
+                extra[a + j] = {"max_error": tau, "base_bytes": len(inner[a + j]), "residual_bytes": len(res)}
+            a = e
+            continue
+        n_seg = -(-N // segment)
+        plane = front["plane"].cpu().numpy() if kind.low else None
+        cap = min(max(_seg_cap_of_hist(hist[j], tabs[j], n_seg) for j in range(e - a)), 4 * (N + RES_SEG_SLACK * n_seg))
+        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, segment, coder, cap=cap)
+        for j, (segs, seg_bytes) in enumerate(coded):
+            b, t = a + j, tabs[j]
+            low = plane[j].astype("<i8").tobytes() if kind.low else b""
+            files[b] = kind.write(H, W, inner[b], segs, seg_bytes, segment, tau, s, low, digest[j], t["m"], t["freq"], vbr)
+            extra[b] = {"max_error": tau, **kind.extra(s), "base_bytes": len(inner[b]),
+                        "residual_bytes": len(segs) + 4 * n_seg, **({"low_bytes": len(low)} if kind.low else {}),
+                        "residual_segment": segment, "segments": n_seg}
+        a = e
+    return files, extra
+
+
 def _encode_residual(net, img, layout, files, strings, shape, lv, tau, segment=None, coder="device"):
     """encode_images' second layer: the residual files of `files` (the images' plain or VBR files) and the info.
-    segment=None: one serial string per image, coded on the host ("MLR1").  segment=L: the segmented file ("MLR2");
-    with coder="device" sym and ctx stay on the device, the histograms alone go to the host for the tables, and the
-    kernels code; coder="host" (and a CPU model) takes the host entry.  Both give the same bytes."""
+    segment=None: the serial file ("MLR1"); segment=L: the segmented file ("MLR2").  Both code the same symbols."""
     B = img.size(0)
     H, W = _hw(img, layout)
     kw = {} if lv is None else {"s": list(lv)}
     base = egress_u8(_base_x_hat(net, strings, shape, kw, B), H, W, "hwc")
-    front = residual_front(base, img, tau, "hwc", layout)
-    worst = int(front["max_err"].max())  # computed on the device, beside the symbols
-    if worst > tau:
-        raise RuntimeError(f"encode_images: the residual layer leaves an error of {worst} > max_error {tau}")
-    hist = front["hist"].cpu().numpy()
-    digest = front["digest"].cpu().tolist()
-    out, extra = [], []
-    if segment is not None:
-        n_seg = -(-3 * H * W // segment)
-        tabs = [residual_tables(hist[b]) for b in range(B)]
-        cap = min(max(_seg_cap_of_hist(hist[b], tabs[b], n_seg) for b in range(B)), residual_segment_cap(H, W, segment))
-        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, segment, coder, cap=cap)
-        for b, (segs, seg_bytes) in enumerate(coded):
-            t = tabs[b]
-            out.append(write_container_residual_seg(H, W, files[b], segs, seg_bytes, segment, tau, digest[b], t["m"],
-                                                    t["freq"], vbr=lv is not None))
-            extra.append({"max_error": tau, "base_bytes": len(files[b]), "residual_bytes": len(segs) + 4 * n_seg,
-                          "residual_segment": segment, "segments": n_seg})
-        return out, extra
-    sym = front["sym"].cpu().numpy().reshape(B, -1)
-    ctx = front["ctx"].cpu().numpy().reshape(B, -1)
-    for b in range(B):
-        t = residual_tables(hist[b])
-        res = entropy.rans_encode(sym[b].astype(np.int32), ctx[b].astype(np.int32), *_coder_tables(t))
-        out.append(write_container_residual(H, W, files[b], res, tau, digest[b], t["m"], t["freq"], vbr=lv is not None))
-        extra.append({"max_error": tau, "base_bytes": len(files[b]), "residual_bytes": len(res)})
-    return out, extra
+    return _encode_residual_layer(_rgb_kind(x_layout=layout), "encode_images", base, img, H, W, tau, [0] * B, segment,
+                                  coder, files, lv is not None)
 
 
 def _digest_error(b: int, want: int, got: int, net) -> RuntimeError:
@@ -1417,94 +1601,119 @@ def _digest_error(b: int, want: int, got: int, net) -> RuntimeError:
         f"base image alone with enhance=False")
 
 
-def _decode_residual(net, files, ref, max_pixels, enhance, coder="device"):
-    """decode_images for residual files: the inner files as decode_images decodes them, then the residual layer.
-    "MLR1" files decode their string on the host; "MLR2" files go through residual_decode_segments (coder="device":
-    the kernel, on a GPU model; "host": the host entry), whose int16 output residual_apply reads in place."""
+def _parse_residual_files(entry: str, net, files, max_pixels, check=None):
+    """Every file parsed and its level word checked against the model; check(b, info): the kind's own checks."""
     vbr = hasattr(net, "levels")
-    n_levels = net.levels if vbr else None
-    ss = [_parse_residual_any(f, n_levels, max_pixels) for f in files]
-    seg = [int(s.seg_len) if is_residual_seg_file(f) else 0 for f, s in zip(files, ss)]  # 0: the serial kind
-    for s in ss:
+    ss = [_parse_residual_any(f, net.levels if vbr else None, max_pixels) for f in files]
+    for b, s in enumerate(ss):
         if bool(s.vbr) != vbr:
-            raise ValueError(f"decode_images: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
+            raise ValueError(f"{entry}: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
                              f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+        if check is not None:
+            check(b, s)
+    return ss
+
+
+def _decode_residual_layer(kind: _ResidualKind, net, files, ss, ref, max_pixels, enhance, coder):
+    """The decoder of every kind of residual file, after _parse_residual_files: the inner files through the kind's
+    plain decode, then the residual layer.  Files of one size, tau, shift and segment length go through the kernels
+    as one batch, others one by one.  The base of a file is defined as the decode of that file alone: where the
+    batch's base has another digest (the range guard's fp32 re-run takes a whole lane) the file is decoded alone and
+    that base pasted in; if its digest differs too, no picture is returned (_digest_error).  "MLR1" files decode
+    their string on the host; the others go through residual_decode_segments (coder="device": the kernel, on a GPU
+    model; "host": the host entry), whose int16 output the apply kernel reads in place."""
+    B = len(files)
     inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
-    extra = [{"max_error": int(s.tau), "residual_bytes": int(s.res_len), "base_bytes": int(s.inner_len),
-              "bytes": len(f), "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
-    for e, s, L in zip(extra, ss, seg):
-        if L:
-            e.update(residual_segment=L, segments=int(s.n_seg))
+    keys, extra = [], []
+    for f, s in zip(files, ss):
+        sh, L = int(s.shift) if kind.low else 0, int(getattr(s, "seg_len", 0))  # L = 0: the serial kind
+        keys.append((int(s.tau), sh, L))
+        extra.append({"max_error": int(s.tau), **kind.extra(sh), "residual_bytes": int(s.res_len),
+                      "base_bytes": int(s.inner_len), **({"low_bytes": int(s.lo_len)} if kind.low else {}),
+                      **({"residual_segment": L, "segments": int(s.n_seg)} if L else {}), "bytes": len(f),
+                      "bpp": 8.0 * len(f) / (s.H * s.W)})
     if not enhance:
-        img, info = decode_images(net, inner, ref=ref, max_pixels=max_pixels)
+        img, info = kind.decode_inner(net, inner, ref, max_pixels)
         for d, e in zip(info, extra):
             d.update(e, enhanced=False)
         return img, info
-    base, info = decode_images(net, inner, max_pixels=max_pixels)
-    B, H, W = len(files), base.size(1), base.size(2)
+    base, info = kind.decode_inner(net, inner, None, max_pixels)
+    H, W, dev = kind.size(base)
     if ref is not None:
-        ref, _ = _u8_batch(ref, "hwc", "decode_images ref")
-        if tuple(ref.shape) != (B, H, W, 3):
-            raise ValueError(f"decode_images: ref must be uint8 {(B, H, W, 3)}, got {tuple(ref.shape)}")
-        ref = ref.to(base.device)
+        ref = kind.check_ref(ref, B, H, W, dev)
     same = all((s.H, s.W) == (H, W) for s in ss)
-    one = same and len({(s.tau, L) for s, L in zip(ss, seg)}) == 1  # one size, tau, kind and segment length
+    one = same and len(set(keys)) == 1
     groups = [list(range(B))] if one else [[b] for b in range(B)]
-    img = torch.empty_like(base) if same else torch.zeros_like(base)
+    img = kind.canvas(base, not same)  # files of differing sizes come back in a zeroed canvas
     for g in groups:
-        s0 = ss[g[0]]
-        h, w, tau = s0.H, s0.W, int(s0.tau)
-        view = base[g[0]:g[-1] + 1, :h, :w]
-        front = residual_front(view, None, tau, "hwc")
+        h, w = ss[g[0]].H, ss[g[0]].W
+        tau, sh, L = keys[g[0]]
+        sl = slice(g[0], g[-1] + 1)
+        view = kind.crop(base, sl, h, w)
+        front = kind.front(view, None, tau, 0)
         digest = front["digest"].cpu().tolist()
         for j, b in enumerate(g):
             if (digest[j] & 0xFFFFFFFFFFFFFFFF) == ss[b].digest:
                 continue
-            # the batch's base image may differ from the file's own (the range guard's fp32 re-run takes a whole
-            # lane): the base is defined as the decode of the file alone
-            alone, _ = decode_images(net, [inner[b]], max_pixels=max_pixels)
-            again = int(residual_front(alone, None, tau, "hwc")["digest"].cpu()[0])
+            alone, _ = kind.decode_inner(net, [inner[b]], None, max_pixels)
+            again = int(kind.front(alone, None, tau, 0)["digest"].cpu()[0])
             if (again & 0xFFFFFFFFFFFFFFFF) != ss[b].digest:
                 raise _digest_error(b, int(ss[b].digest), again, net)
-            base[b:b + 1, :h, :w] = alone
+            kind.paste(kind.crop(base, slice(b, b + 1), h, w), alone)
             front = None
         if front is None:
-            front = residual_front(view, None, tau, "hwc")
+            front = kind.front(view, None, tau, 0)
         count = front["ctx_count"].cpu().numpy()
         tabs = [_file_tables(files[b], ss[b]) for b in g]
+        planes = []
         for j, b in enumerate(g):
             missing = [k for k in range(RES_CTX) if count[j, k] > 0 and tabs[j]["m"][k] == RES_ABSENT]
             if missing:
-                raise ValueError(f"decode_images: file {b}: contexts {missing} occur in the base image but the file "
-                                 f"has no table for them")
-        if seg[g[0]]:  # segments: no symbol and no context crosses to the host on the device path
+                raise ValueError(f"{kind.entry}: file {b}: contexts {missing} occur in the {kind.base_word} but the "
+                                 f"file has no table for them")
+            if kind.low:
+                pl = np.frombuffer(files[b], "<u8", kind.plane_words(h, w, sh), ss[b].lo_off)
+                kind.check_low(b, pl, h, w, sh)
+                planes.append(pl.view(np.int64))
+        if L:  # segments: no symbol and no context crosses to the host on the device path
             try:
                 sym_d = residual_decode_segments(
                     [files[b][ss[b].data_off:ss[b].data_off + ss[b].data_len] for b in g],
-                    [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g],
-                    front["ctx"], tabs, seg[g[0]], coder)
+                    [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g], front["ctx"], tabs, L, coder)
             except ResidualSegmentError as e:
-                raise ValueError(f"decode_images: file {g[e.image]}: segment {e.segment} of the residual string is "
+                raise ValueError(f"{kind.entry}: file {g[e.image]}: segment {e.segment} of the residual string is "
                                  f"corrupt: {e.reason}") from None
         else:
             ctx = front["ctx"].cpu().numpy().reshape(len(g), -1)
-            sym = np.empty((len(g), 3 * h * w), np.int16)
+            sym = np.empty(ctx.shape, np.int16)
             for j, b in enumerate(g):
                 res = files[b][ss[b].res_off:ss[b].res_off + ss[b].res_len]
                 q = entropy.rans_decode(res, ctx[j].astype(np.int32), *_coder_tables(tabs[j]))
                 if q.size and (q.min() < -255 or q.max() > 255):
-                    raise ValueError(f"decode_images: file {b}: the residual string holds a symbol outside [-255, 255]")
+                    raise ValueError(f"{kind.entry}: file {b}: the residual string holds a symbol outside [-255, 255]")
                 sym[j] = q
-            sym_d = torch.from_numpy(sym.reshape(len(g), 3, h, w)).to(base.device)
-        out = img[g[0]:g[-1] + 1, :h, :w]
-        r = residual_apply(view, sym_d, tau, "hwc", ref=None if ref is None else ref[g[0]:g[-1] + 1, :h, :w], out=out)
+            sym_d = torch.from_numpy(sym.reshape(tuple(front["ctx"].shape))).to(dev)
+        plane_d = torch.from_numpy(np.stack(planes).reshape(len(g), -1).copy()).to(dev) if kind.low else None
+        try:
+            r = kind.apply(view, sym_d, plane_d, tau, sh, None if ref is None else kind.crop(ref, sl, h, w),
+                           kind.crop(img, sl, h, w))
+        except ValueError as e:
+            if not kind.low:  # only the kinds with a status word refuse a symbol here, and name the files
+                raise
+            raise ValueError(f"{kind.entry}: files {g[0]}..{g[-1]}: {e}") from None
         if ref is not None:
-            sq, me = r[1].cpu().tolist(), r[2].cpu().tolist()
+            sq, me = r[0].cpu().tolist(), r[1].cpu().tolist()
             for j, b in enumerate(g):
-                extra[b].update(sq_err=int(sq[j]), psnr=psnr_from_sq_err(int(sq[j]), 3 * h * w), max_abs_err=int(me[j]))
+                extra[b].update(kind.score(sq[j], h, w), max_abs_err=int(me[j]))
     for d, e in zip(info, extra):
         d.update(e)
     return img, info
+
+
+def _decode_residual(net, files, ref, max_pixels, enhance, coder="device"):
+    """decode_images for "MLR1" and "MLR2" files."""
+    ss = _parse_residual_files("decode_images", net, files, max_pixels)
+    return _decode_residual_layer(_rgb_kind(), net, files, ss, ref, max_pixels, enhance, coder)
 
 
 # ---- residual coding of 9..16-bit samples (csrc/residual16.h, csrc/residual16.hip; DESIGN.md §5 "Deep samples")
@@ -1652,34 +1861,14 @@ def residual_front16(base, x=None, depth: int = 16, tau: int = 0, shift: int = 0
     base = _u16_in_place(base, layout)
     dev = base.device
     with torch.cuda.device(dev):
-        ctx = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev)
-        count = torch.empty(B, RES_CTX, dtype=torch.int32, device=dev)
-        digest = torch.empty(B, dtype=torch.int64, device=dev)
-        sym = plane = hist = merr = mq = sq = None
         if x is not None:
             x = _u16_in_place(x, x_layout)
-            sym = torch.empty(B, 3, H, W, dtype=torch.int16, device=dev)
-            plane = torch.empty(B, residual_plane_words(H, W, shift), dtype=torch.int64, device=dev)
-            hist = torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev)
-            merr = torch.empty(B, dtype=torch.int32, device=dev)
-            mq = torch.empty(B, dtype=torch.int32, device=dev)
-            sq = torch.empty(B, dtype=torch.int64, device=dev)
-        if _lib.poison():  # what the kernel does not write shows
-            ctx.fill_(0xEE)
-            for t in (count, digest, hist, merr, mq, sq, plane):
-                if t is not None:
-                    t.fill_(-1)
-            if sym is not None:
-                sym.fill_(-0x1112)
-        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.call("mlic_image_residual_front_u16", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)), ptr(x),
-                  None if x is None else (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, depth, tau, shift, ptr(ctx),
-                  ptr(count), ptr(digest), ptr(sym), ptr(plane), ptr(hist), ptr(merr), ptr(mq), ptr(sq))
-        out = {"ctx": ctx, "ctx_count": count.to(torch.int64), "digest": digest}
-        if x is not None:
-            out.update(sym=sym, plane=plane, hist=hist.to(torch.int64), max_err=merr.to(torch.int64),
-                       max_abs_q=mq.to(torch.int64), sum_abs_q=sq)
-    return out
+        o = _front_buffers(dev, (B, 3, H, W), x is not None, residual_plane_words(H, W, shift))
+        _lib.call("mlic_image_residual_front_u16", _stream(), _ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
+                  _ptr(x), None if x is None else (C.c_int64 * 4)(*_strides(x, x_layout)), B, H, W, depth, tau, shift,
+                  _ptr(o["ctx"]), _ptr(o["count"]), _ptr(o["digest"]), _ptr(o["sym"]), _ptr(o["plane"]), _ptr(o["hist"]),
+                  _ptr(o["merr"]), _ptr(o["mq"]), _ptr(o["sq"]))
+        return _front_result(o)
 
 
 def residual_stats16(base, x, depth: int, tau: int = 0, layout: Optional[str] = None,
@@ -1762,28 +1951,17 @@ def residual_apply16(base, sym, plane, depth: int, tau: int, shift: int, layout:
     dev = base.device
     with torch.cuda.device(dev):
         if out is None:
-            out = torch.empty(tuple(base.shape), dtype=torch.int16, device=dev)
-            if _lib.poison():
-                out.fill_(-1)
-            out = out.view(torch.uint16)
+            out = _apply_out(base.shape, True, dev)
         elif 0 in _strides(out, layout)[2:]:
             raise ValueError(f"{what}: out has a zero column or channel stride")
-        sq = merr = None
         if ref is not None:
             ref = _u16_in_place(ref, layout)
-            sq = torch.full((B,), -1, dtype=torch.int64, device=dev)
-            merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        status = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.call("mlic_image_residual_apply_u16", _stream(), ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
-                  ptr(sym), ptr(plane), B, H, W, depth, tau, shift, ptr(out), (C.c_int64 * 4)(*_strides(out, layout)),
-                  ptr(ref), None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)), ptr(sq), ptr(merr),
-                  ptr(status))
-        bad = torch.nonzero(status).flatten().cpu().tolist()
-        if ref is not None:
-            ref.record_stream(torch.cuda.current_stream())
-    if bad:
-        raise ValueError(f"{what}: image {bad[0]} holds a symbol outside [-255, 255]")
+        sq, merr, status = _apply_buffers(dev, B, ref, (B,))
+        _lib.call("mlic_image_residual_apply_u16", _stream(), _ptr(base), (C.c_int64 * 4)(*_strides(base, layout)),
+                  _ptr(sym), _ptr(plane), B, H, W, depth, tau, shift, _ptr(out), (C.c_int64 * 4)(*_strides(out, layout)),
+                  _ptr(ref), None if ref is None else (C.c_int64 * 4)(*_strides(ref, layout)), _ptr(sq), _ptr(merr),
+                  _ptr(status))
+        _apply_refusal(what, "image", status, () if ref is None else (ref,))
     return out if ref is None else (out, sq, merr.to(torch.int64))
 
 
@@ -1793,33 +1971,16 @@ def write_container_residual_deep(H: int, W: int, inner: bytes, segs: bytes, seg
     file, depth and shift, seg_len, n_seg, `inner`, the index and `segs`, and behind lo_len the low-bit plane `low`
     (8 * 3 H ceil(W / 64) shift bytes, little-endian 64-bit words)."""
     inner, segs, low = bytes(inner), bytes(segs), bytes(low)
-    m = np.ascontiguousarray(m, dtype=np.uint8)
-    freq = np.ascontiguousarray(freq, dtype=np.uint16)
-    sb = np.ascontiguousarray(np.asarray(seg_bytes, np.int64).reshape(-1))
-    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
-        raise ValueError(f"write_container_residual_deep: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
-    if sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF)):
-        raise ValueError("write_container_residual_deep: segment lengths must fit 32 bits")
-    sb = sb.astype(np.uint32)
-    n = C.c_size_t()
-    args = (H, W, int(bool(vbr)), int(tau), int(depth), int(shift), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data,
-            freq.ctypes.data, int(segment) & 0xFFFFFFFF, sb.size, sb.ctypes.data, inner, len(inner), segs, len(segs),
-            low, len(low))
-    _lib.call("mlic_container_write_residual_deep", *args, None, 0, C.byref(n))
-    buf = C.create_string_buffer(max(1, n.value))
-    _lib.call("mlic_container_write_residual_deep", *args, buf, len(buf), C.byref(n))
-    return C.string_at(buf, n.value)
+    return _write_residual("_deep", H, W, vbr, tau, (depth, shift), digest, m, freq, (segment, seg_bytes),
+                           (inner, segs, low))
 
 
 def parse_container_residual_deep(data: bytes, n_levels: Optional[int] = None,
                                   max_pixels: int = MAX_PIXELS) -> _lib.ContainerResidualDeepInfo:
     """The validating parser of a deep residual file (mlic_container_parse_residual_deep): raises _lib.MlicError on any
     malformed input.  The fields of the "MLR2" parse, and depth, shift, lo_off / lo_len (the low-bit plane)."""
-    data = bytes(data)
-    info = _lib.ContainerResidualDeepInfo()
-    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
-    _lib.call("mlic_container_parse_residual_deep", data, len(data), nl, int(max_pixels), C.byref(info))
-    return info
+    return _parse_residual("mlic_container_parse_residual_deep", _lib.ContainerResidualDeepInfo(), data, n_levels,
+                           max_pixels)
 
 
 @torch.no_grad()
@@ -1843,67 +2004,27 @@ def encode_residual16(net, imgs_u16, depth: int, max_error: int = 0, level=None,
         shift = _check_shift(shift, depth, what)
     img, layout = _u16_batch(imgs_u16, layout, what)
     inner, info = encode_images(net, img, level=level, layout=layout, depth=depth, return_info=True)
-    vbr = hasattr(net, "levels")
-    cs = [parse_container(f, vbr, net.levels if vbr else None) for f in inner]
-    pairs = [_strings(f, c) for f, c in zip(inner, cs)]
     B = img.size(0)
     H, W = _hw(img, layout)
-    kw = {"s": [c.level for c in cs]} if vbr else {}
-    x_hat = _base_x_hat(net, [[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), kw, B)
+    x_hat, vbr = _inner_x_hat(net, inner)
     base = egress_u16(x_hat.float(), H, W, depth, "hwc")
     img = img.to(base.device)
-    stats = residual_stats16(base, img, depth, tau, "hwc", layout)
-    mq, sq = stats["max_abs_q"].cpu().tolist(), stats["sum_abs_q"].cpu().tolist()
-    if shift is None:
-        shifts = [residual_shift(depth, 3 * H * W, mq[b], sq[b]) for b in range(B)]
-    else:
-        for b in range(B):
-            if not residual_shift_fits(mq[b], shift):
-                raise ValueError(f"{what}: shift={shift} does not fit image {b} (its largest |q| is {mq[b]}): the "
-                                 f"smallest shift that fits is {residual_min_shift(depth, mq[b])}")
-        shifts = [shift] * B
-    n_seg = -(-3 * H * W // L)
-    files = [None] * B
-    a = 0
-    while a < B:  # runs of images with one shift: one front launch each
-        e = a + 1
-        while e < B and shifts[e] == shifts[a]:
-            e += 1
-        s = shifts[a]
-        front = residual_front16(base[a:e], img[a:e], depth, tau, s, "hwc", layout)
-        worst = int(front["max_err"].max())  # computed on the device, beside the symbols
-        if worst > tau:
-            raise RuntimeError(f"{what}: the residual layer leaves an error of {worst} > max_error {tau}")
-        hist = front["hist"].cpu().numpy()
-        digest = front["digest"].cpu().tolist()
-        plane = front["plane"].cpu().numpy()
-        tabs = [residual_tables(hist[j]) for j in range(e - a)]
-        cap = min(max(_seg_cap_of_hist(hist[j], tabs[j], n_seg) for j in range(e - a)), residual_segment_cap(H, W, L))
-        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, L, coder, cap=cap)
-        for j, (segs, seg_bytes) in enumerate(coded):
-            b, t = a + j, tabs[j]
-            low = plane[j].astype("<i8").tobytes()
-            files[b] = write_container_residual_deep(H, W, inner[b], segs, seg_bytes, L, tau, depth, s, low, digest[j],
-                                                     t["m"], t["freq"], vbr=vbr)
-            info[b].update(bytes=len(files[b]), bpp=8.0 * len(files[b]) / (H * W), max_error=tau, depth=depth, shift=s,
-                           base_bytes=len(inner[b]), residual_bytes=len(segs) + 4 * n_seg, low_bytes=len(low),
-                           residual_segment=L, segments=n_seg)
-        a = e
+    kind = _rgb_kind(depth, layout)
+    shifts = _residual_shifts(what, "shift", kind, depth, 3 * H * W, kind.stats(base, img, tau), shift, B)
+    files, extra = _encode_residual_layer(kind, what, base, img, H, W, tau, shifts, L, coder, inner, vbr)
+    for d, f, e in zip(info, files, extra):
+        d.update(e, bytes=len(f), bpp=8.0 * len(f) / (H * W))
     return (files, info) if return_info else files
 
 
 def _decode_residual16(net, files, ref, max_pixels, enhance, coder, depth):
     """decode_images for "MLR3" files: the inner files decoded at the file's depth, then the deep residual layer."""
-    vbr = hasattr(net, "levels")
-    n_levels = net.levels if vbr else None
-    ss = [parse_container_residual_deep(f, n_levels, max_pixels) for f in files]
-    B = len(files)
-    for b, s in enumerate(ss):
-        if bool(s.vbr) != vbr:
-            raise ValueError(f"decode_images: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
-                             f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+    def check(b, s):
         if depth is not None and depth != s.depth:
             raise ValueError(f"decode_images: depth={depth}, but file {b} (MLR3) holds samples of depth {s.depth}")
+
+    ss = _parse_residual_files("decode_images", net, files, max_pixels, check)
+    B = len(files)
     if ref is not None:
         ref, _ = _u16_batch(ref, "hwc", "decode_images ref")
     depths = sorted({int(s.depth) for s in ss})
@@ -1923,79 +2044,7 @@ def _decode_residual16(net, files, ref, max_pixels, enhance, coder, depth):
                 img[b, :h, :w].copy_(im[j, :h, :w].view(torch.int16))
                 info[b] = inf[j]
         return img.view(torch.uint16), info
-    d = depths[0]
-    inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
-    extra = [{"max_error": int(s.tau), "depth": d, "shift": int(s.shift), "residual_bytes": int(s.res_len),
-              "base_bytes": int(s.inner_len), "low_bytes": int(s.lo_len), "residual_segment": int(s.seg_len),
-              "segments": int(s.n_seg), "bytes": len(f), "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
-    if not enhance:
-        img, info = decode_images(net, inner, ref=ref, max_pixels=max_pixels, depth=d)
-        for di, e in zip(info, extra):
-            di.update(e, enhanced=False)
-        return img, info
-    base, info = decode_images(net, inner, max_pixels=max_pixels, depth=d)
-    H, W = base.size(1), base.size(2)
-    if ref is not None:
-        if tuple(ref.shape) != (B, H, W, 3):
-            raise ValueError(f"decode_images: ref must be uint16 {(B, H, W, 3)}, got {tuple(ref.shape)}")
-        ref = ref.to(base.device)
-    same = all((s.H, s.W) == (H, W) for s in ss)
-    one = same and len({(s.tau, s.shift, s.seg_len) for s in ss}) == 1
-    groups = [list(range(B))] if one else [[b] for b in range(B)]
-    img = (torch.empty if same else torch.zeros)(B, H, W, 3, dtype=torch.int16, device=base.device).view(torch.uint16)
-    for g in groups:
-        s0 = ss[g[0]]
-        h, w, tau, sh, L = s0.H, s0.W, int(s0.tau), int(s0.shift), int(s0.seg_len)
-        view = base[g[0]:g[-1] + 1, :h, :w]
-        front = residual_front16(view, None, d, tau, 0, "hwc")
-        digest = front["digest"].cpu().tolist()
-        for j, b in enumerate(g):
-            if (digest[j] & 0xFFFFFFFFFFFFFFFF) == ss[b].digest:
-                continue
-            # the base is defined as the decode of the file alone (the range guard's fp32 re-run takes a whole lane)
-            alone, _ = decode_images(net, [inner[b]], max_pixels=max_pixels, depth=d)
-            again = int(residual_front16(alone, None, d, tau, 0, "hwc")["digest"].cpu()[0])
-            if (again & 0xFFFFFFFFFFFFFFFF) != ss[b].digest:
-                raise _digest_error(b, int(ss[b].digest), again, net)
-            base[b:b + 1, :h, :w].view(torch.int16).copy_(alone.view(torch.int16))
-            front = None
-        if front is None:
-            front = residual_front16(view, None, d, tau, 0, "hwc")
-        count = front["ctx_count"].cpu().numpy()
-        tabs = [_file_tables(files[b], ss[b]) for b in g]
-        planes = []
-        for j, b in enumerate(g):
-            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and tabs[j]["m"][k] == RES_ABSENT]
-            if missing:
-                raise ValueError(f"decode_images: file {b}: contexts {missing} occur in the base image but the file "
-                                 f"has no table for them")
-            pl = np.frombuffer(files[b], "<u8", residual_plane_words(h, w, sh), ss[b].lo_off)
-            if sh and w % 64 and (pl.reshape(3 * h, -(-w // 64), sh)[:, -1, :] >> np.uint64(w % 64)).any():
-                raise ValueError(f"decode_images: file {b}: the low-bit plane has bits set beyond column {w} (its "
-                                 f"padding bits must be zero)")
-            planes.append(pl.view(np.int64))
-        try:
-            sym_d = residual_decode_segments(
-                [files[b][ss[b].data_off:ss[b].data_off + ss[b].data_len] for b in g],
-                [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g], front["ctx"], tabs, L, coder)
-        except ResidualSegmentError as e:
-            raise ValueError(f"decode_images: file {g[e.image]}: segment {e.segment} of the residual string is "
-                             f"corrupt: {e.reason}") from None
-        plane_d = torch.from_numpy(np.stack(planes).reshape(len(g), -1).copy()).to(base.device)
-        out = img[g[0]:g[-1] + 1, :h, :w]
-        try:
-            r = residual_apply16(view, sym_d, plane_d, d, tau, sh, "hwc",
-                                 ref=None if ref is None else ref[g[0]:g[-1] + 1, :h, :w], out=out)
-        except ValueError as e:
-            raise ValueError(f"decode_images: files {g[0]}..{g[-1]}: {e}") from None
-        if ref is not None:
-            sq, me = r[1].cpu().tolist(), r[2].cpu().tolist()
-            for j, b in enumerate(g):
-                extra[b].update(sq_err=int(sq[j]), psnr=psnr_from_sq_err(int(sq[j]), 3 * h * w, (1 << d) - 1),
-                                max_abs_err=int(me[j]))
-    for di, e in zip(info, extra):
-        di.update(e)
-    return img, info
+    return _decode_residual_layer(_rgb_kind(depths[0]), net, files, ss, ref, max_pixels, enhance, coder)
 
 
 # ---------------------------------------------------------------------------------------------- ROI
@@ -3873,7 +3922,6 @@ def decode_yuv(net, files: Sequence[bytes], fmt: YuvFormat, ref=None, max_pixels
 
 # ---- residual coding of Y'CbCr frames (csrc/residual_yuv.h, csrc/residual_yuv.hip; DESIGN.md §5 "Y'CbCr frames")
 RESIDUAL_YUV_MAGIC = b"MLR4"
-_residual_shift_rule = residual_shift  # encode_residual_yuv has a parameter of that name
 
 
 def is_residual_yuv_file(data: bytes) -> bool:
@@ -4051,36 +4099,15 @@ def residual_front_yuv(base, x=None, fmt: Optional[YuvFormat] = None, tau: int =
     base = _planes_in_place(base, fmt)
     dev = base[0].device
     with torch.cuda.device(dev):
-        ctx = torch.empty(B, N, dtype=torch.uint8, device=dev)
-        count = torch.empty(B, RES_CTX, dtype=torch.int32, device=dev)
-        digest = torch.empty(B, dtype=torch.int64, device=dev)
-        sym = plane = hist = merr = mq = sq = None
         if x is not None:
             x = _planes_in_place(x, fmt)
-            sym = torch.empty(B, N, dtype=torch.int16, device=dev)
-            plane = torch.empty(B, residual_yuv_plane_words(H, W, fmt.sub, shift), dtype=torch.int64, device=dev)
-            hist = torch.empty(B, RES_CTX, RES_BINS, dtype=torch.int32, device=dev)
-            merr = torch.empty(B, dtype=torch.int32, device=dev)
-            mq = torch.empty(B, dtype=torch.int32, device=dev)
-            sq = torch.empty(B, dtype=torch.int64, device=dev)
-        if _lib.poison():  # what the kernel does not write shows
-            ctx.fill_(0xEE)
-            for t in (count, digest, hist, merr, mq, sq, plane):
-                if t is not None:
-                    t.fill_(-1)
-            if sym is not None:
-                sym.fill_(-0x1112)
-        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        o = _front_buffers(dev, (B, N), x is not None, residual_yuv_plane_words(H, W, fmt.sub, shift))
         name, deep = _yuv_entry("front", fmt)
         d = fmt.desc()
         _lib.call(name, _stream(), *_plane_args(*base), *([None] * 6 if x is None else _plane_args(*x)), C.byref(d),
-                  *deep, B, H, W, tau, shift, ptr(ctx), ptr(count), ptr(digest), ptr(sym), ptr(plane), ptr(hist),
-                  ptr(merr), ptr(mq), ptr(sq))
-        out = {"ctx": ctx, "ctx_count": count.to(torch.int64), "digest": digest}
-        if x is not None:
-            out.update(sym=sym, plane=plane, hist=hist.to(torch.int64), max_err=merr.to(torch.int64),
-                       max_abs_q=mq.to(torch.int64), sum_abs_q=sq)
-    return out
+                  *deep, B, H, W, tau, shift, _ptr(o["ctx"]), _ptr(o["count"]), _ptr(o["digest"]), _ptr(o["sym"]),
+                  _ptr(o["plane"]), _ptr(o["hist"]), _ptr(o["merr"]), _ptr(o["mq"]), _ptr(o["sq"]))
+        return _front_result(o)
 
 
 def residual_stats_yuv(base, x, fmt: YuvFormat, tau: int = 0) -> Dict:
@@ -4176,35 +4203,18 @@ def residual_apply_yuv(base, sym, plane, fmt: YuvFormat, tau: int, shift: int, r
     sym, plane = sym.contiguous(), plane.contiguous()
     with torch.cuda.device(dev):
         if out is None:
-            if fmt.depth == 8:
-                out = tuple(torch.empty(s, dtype=torch.uint8, device=dev) for s in shapes)
-            else:
-                out = tuple(torch.empty(s, dtype=torch.int16, device=dev) for s in shapes)
-            if _lib.poison():
-                for t in out:
-                    t.fill_(0xFF if fmt.depth == 8 else -1)
-            if fmt.depth > 8:
-                out = tuple(t.view(torch.uint16) for t in out)
+            out = tuple(_apply_out(s, fmt.depth > 8, dev) for s in shapes)
         elif any(t.stride(2) == 0 for t in out):
             raise ValueError(f"{what}: an out plane has a zero column stride")
-        sq = merr = None
         if ref is not None:
             ref = _planes_in_place(ref, fmt)
-            sq = torch.full((B, 3), -1, dtype=torch.int64, device=dev)
-            merr = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        status = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+        sq, merr, status = _apply_buffers(dev, B, ref, (B, 3))
         name, deep = _yuv_entry("apply", fmt)
         d = fmt.desc()
-        _lib.call(name, _stream(), *_plane_args(*base), ptr(sym), ptr(plane), C.byref(d), *deep, B, H, W, tau, shift,
-                  *_plane_args(*out), *([None] * 6 if ref is None else _plane_args(*ref)), ptr(sq), ptr(merr),
-                  ptr(status))
-        bad = torch.nonzero(status).flatten().cpu().tolist()
-        if ref is not None:
-            for t in ref:
-                t.record_stream(torch.cuda.current_stream())
-    if bad:
-        raise ValueError(f"{what}: frame {bad[0]} holds a symbol outside [-255, 255]")
+        _lib.call(name, _stream(), *_plane_args(*base), _ptr(sym), _ptr(plane), C.byref(d), *deep, B, H, W, tau, shift,
+                  *_plane_args(*out), *([None] * 6 if ref is None else _plane_args(*ref)), _ptr(sq), _ptr(merr),
+                  _ptr(status))
+        _apply_refusal(what, "frame", status, () if ref is None else ref)
     return out if ref is None else out + (sq, merr.to(torch.int64))
 
 
@@ -4216,34 +4226,16 @@ def write_container_residual_yuv(H: int, W: int, inner: bytes, segs: bytes, seg_
     words are MSB-aligned is not written: the file holds samples."""
     inner, segs, low = bytes(inner), bytes(segs), bytes(low)
     fmt = _check_fmt(fmt, "write_container_residual_yuv")
-    m = np.ascontiguousarray(m, dtype=np.uint8)
-    freq = np.ascontiguousarray(freq, dtype=np.uint16)
-    sb = np.ascontiguousarray(np.asarray(seg_bytes, np.int64).reshape(-1))
-    if m.shape != (RES_CTX,) or freq.shape != (RES_CTX, RES_BINS):
-        raise ValueError(f"write_container_residual_yuv: m [{RES_CTX}] and freq [{RES_CTX}, {RES_BINS}] expected")
-    if sb.size > 0xFFFFFFFF or (sb.size and (sb.min() < 0 or sb.max() > 0xFFFFFFFF)):
-        raise ValueError("write_container_residual_yuv: segment lengths must fit 32 bits")
-    sb = sb.astype(np.uint32)
-    n = C.c_size_t()
-    args = (H, W, int(bool(vbr)), int(tau), fmt.depth, int(shift), fmt.sub[0], fmt.sub[1], _YUV_MATRIX[fmt.matrix][0],
-            int(fmt.full_range), int(fmt.site_x == "left"), int(digest) & 0xFFFFFFFFFFFFFFFF, m.ctypes.data,
-            freq.ctypes.data, int(segment) & 0xFFFFFFFF, sb.size, sb.ctypes.data, inner, len(inner), segs, len(segs),
-            low, len(low))
-    _lib.call("mlic_container_write_residual_yuv", *args, None, 0, C.byref(n))
-    buf = C.create_string_buffer(max(1, n.value))
-    _lib.call("mlic_container_write_residual_yuv", *args, buf, len(buf), C.byref(n))
-    return C.string_at(buf, n.value)
+    own = (fmt.depth, shift, fmt.sub[0], fmt.sub[1], _YUV_MATRIX[fmt.matrix][0], fmt.full_range, fmt.site_x == "left")
+    return _write_residual("_yuv", H, W, vbr, tau, own, digest, m, freq, (segment, seg_bytes), (inner, segs, low))
 
 
 def parse_container_residual_yuv(data: bytes, n_levels: Optional[int] = None,
                                  max_pixels: int = MAX_PIXELS) -> _lib.ContainerResidualYuvInfo:
     """The validating parser of a Y'CbCr residual file (mlic_container_parse_residual_yuv): raises _lib.MlicError on
     any malformed input.  The fields of the "MLR3" parse, and sub_x, sub_y, matrix, full_range, site_x (1: left)."""
-    data = bytes(data)
-    info = _lib.ContainerResidualYuvInfo()
-    nl = _NO_LEVEL_LIMIT if n_levels is None else int(n_levels)
-    _lib.call("mlic_container_parse_residual_yuv", data, len(data), nl, int(max_pixels), C.byref(info))
-    return info
+    return _parse_residual("mlic_container_parse_residual_yuv", _lib.ContainerResidualYuvInfo(), data, n_levels,
+                           max_pixels)
 
 
 _YUV_MATRIX_NAME = {v[0]: k for k, v in _YUV_MATRIX.items()}
@@ -4264,6 +4256,54 @@ def residual_yuv_format(data: bytes, msb: bool = False, n_levels: Optional[int] 
     """The YuvFormat an "MLR4" file was written with; msb (the alignment of uint16 words) is the caller's."""
     f = _file_fmt_fields(parse_container_residual_yuv(data, n_levels, max_pixels))
     return YuvFormat(f["sub"], f["matrix"], f["full_range"], f["site_x"], f["depth"], bool(msb) and f["depth"] > 8)
+
+
+def _yuv_kind(fmt: YuvFormat) -> _ResidualKind:
+    """The kind of Y'CbCr frames ("MLR4"): a batch is the three planes, all frames of one size."""
+    def check_ref(ref, B, H, W, dev):
+        ref = _yuv_planes(*ref, fmt, "decode_yuv ref")
+        if tuple(ref[0].shape) != (B, H, W):
+            raise ValueError(f"decode_yuv: ref must be a frame batch of {(B, H, W)}, got {tuple(ref[0].shape)}")
+        return tuple(t.to(dev) for t in ref)
+
+    geoms = {}  # a call's frames share one size: its geometry is worked out once
+
+    def geom_of(h, w):
+        if (h, w) not in geoms:
+            geoms[h, w] = residual_yuv_geom(h, w, fmt.sub)
+        return geoms[h, w]
+
+    def check_low(b, pl, h, w, sh):
+        geom = geom_of(h, w)
+        for p in range(3):
+            wp, G, a = geom["w"][p], geom["G"][p], geom["rowbase"][p] * sh
+            if sh and wp % 64 and (pl[a:a + geom["h"][p] * G * sh].reshape(geom["h"][p], G, sh)[:, -1, :]
+                                   >> np.uint64(wp % 64)).any():
+                raise ValueError(f"decode_yuv: file {b}: the low-bit plane has bits set beyond column {wp} of plane "
+                                 f"{p} (its padding bits must be zero)")
+
+    def apply(base, sym, plane, tau, sh, ref, out):
+        r = residual_apply_yuv(base, sym, plane, fmt, tau, sh, ref=ref, out=out)
+        return None if ref is None else r[3:]
+
+    def paste(dst, alone):
+        for t, v in zip(dst, alone):
+            _copy_words(t, v)
+
+    return _ResidualKind(
+        entry="decode_yuv", noun="frame", base_word="base planes", low=True,
+        front=lambda base, x, tau, sh: residual_front_yuv(base, x, fmt, tau, sh),
+        stats=lambda base, x, tau: residual_stats_yuv(base, x, fmt, tau), apply=apply,
+        decode_inner=lambda net, inner, ref, max_pixels: decode_yuv(net, inner, fmt, ref=ref, max_pixels=max_pixels),
+        size=lambda planes: (planes[0].size(1), planes[0].size(2), planes[0].device),
+        crop=lambda planes, sl, h=None, w=None: tuple(t[sl] for t in planes),
+        paste=paste, canvas=lambda base, zero: tuple(_like(t, zero) for t in base), check_ref=check_ref,
+        samples=lambda h, w: geom_of(h, w)["N"],
+        plane_words=lambda h, w, sh: geom_of(h, w)["groups"] * sh, check_low=check_low,
+        score=lambda sq, h, w: psnr_yuv_from_sq_err(sq, h, w, fmt),
+        extra=lambda sh: {"depth": fmt.depth, "shift": sh, "sub": fmt.sub},
+        write=lambda H, W, inner, segs, sb, L, tau, sh, low, digest, m, freq, vbr: write_container_residual_yuv(
+            H, W, inner, segs, sb, L, tau, fmt, sh, low, digest, m, freq, vbr=vbr))
 
 
 @torch.no_grad()
@@ -4298,70 +4338,27 @@ def encode_residual_yuv(net, y, cb, cr, fmt: YuvFormat, max_error: int = 0, leve
         shift = _check_shift_yuv(shift, depth, what)
     y, cb, cr = _yuv_planes(y, cb, cr, fmt, what)
     inner, info = encode_yuv(net, y, cb, cr, fmt, level=level, return_info=True)
-    vbr = hasattr(net, "levels")
-    cs = [parse_container(f, vbr, net.levels if vbr else None) for f in inner]
-    pairs = [_strings(f, c) for f, c in zip(inner, cs)]
     B, H, W = y.shape
-    kw = {"s": [c.level for c in cs]} if vbr else {}
-    x_hat = _base_x_hat(net, [[p[0] for p in pairs], [p[1] for p in pairs]], (cs[0].hz, cs[0].wz), kw, B)
+    x_hat, vbr = _inner_x_hat(net, inner)
     base = egress_yuv(x_hat.float(), H, W, fmt)
-    dev = base[0].device
-    x = tuple(t.to(dev) for t in (y, cb, cr))
-    N = residual_yuv_geom(H, W, fmt.sub)["N"]
+    x = tuple(t.to(base[0].device) for t in (y, cb, cr))
+    kind = _yuv_kind(fmt)
     if depth == 8:
         shifts = [0] * B
     else:
-        stats = residual_stats_yuv(base, x, fmt, tau)
-        mq, sq = stats["max_abs_q"].cpu().tolist(), stats["sum_abs_q"].cpu().tolist()
-        if shift is None:
-            shifts = [_residual_shift_rule(depth, N, mq[b], sq[b]) for b in range(B)]
-        else:
-            for b in range(B):
-                if not residual_shift_fits(mq[b], shift):
-                    raise ValueError(f"{what}: residual_shift={shift} does not fit frame {b} (its largest |q| is "
-                                     f"{mq[b]}): the smallest shift that fits is {residual_min_shift(depth, mq[b])}")
-            shifts = [shift] * B
-    n_seg = -(-N // L)
-    files = [None] * B
-    a = 0
-    while a < B:  # runs of frames with one shift: one front launch each
-        e = a + 1
-        while e < B and shifts[e] == shifts[a]:
-            e += 1
-        s = shifts[a]
-        front = residual_front_yuv(tuple(t[a:e] for t in base), tuple(t[a:e] for t in x), fmt, tau, s)
-        worst = int(front["max_err"].max())  # computed on the device, beside the symbols
-        if worst > tau:
-            raise RuntimeError(f"{what}: the residual layer leaves an error of {worst} > max_error {tau}")
-        hist = front["hist"].cpu().numpy()
-        digest = front["digest"].cpu().tolist()
-        plane = front["plane"].cpu().numpy()
-        tabs = [residual_tables(hist[j]) for j in range(e - a)]
-        cap = min(max(_seg_cap_of_hist(hist[j], tabs[j], n_seg) for j in range(e - a)), 4 * (N + RES_SEG_SLACK * n_seg))
-        coded = residual_encode_segments(front["sym"], front["ctx"], tabs, L, coder, cap=cap)
-        for j, (segs, seg_bytes) in enumerate(coded):
-            b, t = a + j, tabs[j]
-            low = plane[j].astype("<i8").tobytes()
-            files[b] = write_container_residual_yuv(H, W, inner[b], segs, seg_bytes, L, tau, fmt, s, low, digest[j],
-                                                    t["m"], t["freq"], vbr=vbr)
-            info[b].update(bytes=len(files[b]), bpp=8.0 * len(files[b]) / (H * W), max_error=tau, depth=depth, shift=s,
-                           sub=fmt.sub, base_bytes=len(inner[b]), residual_bytes=len(segs) + 4 * n_seg,
-                           low_bytes=len(low), residual_segment=L, segments=n_seg)
-        a = e
+        shifts = _residual_shifts(what, "residual_shift", kind, depth, kind.samples(H, W), kind.stats(base, x, tau),
+                                  shift, B)
+    files, extra = _encode_residual_layer(kind, what, base, x, H, W, tau, shifts, L, coder, inner, vbr)
+    for d, f, e in zip(info, files, extra):
+        d.update(e, bytes=len(f), bpp=8.0 * len(f) / (H * W))
     return (files, info) if return_info else files
 
 
 def _decode_residual_yuv(net, files, fmt: YuvFormat, ref, max_pixels, enhance, coder):
     """decode_yuv for "MLR4" files: the inner files decoded to base planes, then the residual layer."""
-    vbr = hasattr(net, "levels")
-    n_levels = net.levels if vbr else None
-    ss = [parse_container_residual_yuv(f, n_levels, max_pixels) for f in files]
-    B = len(files)
     want = _fmt_fields(fmt)
-    for b, s in enumerate(ss):
-        if bool(s.vbr) != vbr:
-            raise ValueError(f"decode_yuv: the residual file's inner file {'carries a' if s.vbr else 'has no'} "
-                             f"level word, the model is {'variable' if vbr else 'fixed'}-rate")
+
+    def check(b, s):
         got = _file_fmt_fields(s)
         for k in ("depth", "sub", "matrix", "full_range", "site_x"):
             if k == "site_x" and got["sub"][0] == 1:
@@ -4369,89 +4366,11 @@ def _decode_residual_yuv(net, files, fmt: YuvFormat, ref, max_pixels, enhance, c
             if got[k] != want[k]:
                 raise ValueError(f"decode_yuv: file {b} (MLR4) was written with {k}={got[k]!r}, fmt has "
                                  f"{k}={want[k]!r}: the residual applies to the encoder's base planes only")
+
+    ss = _parse_residual_files("decode_yuv", net, files, max_pixels, check)
     if len({(s.H, s.W) for s in ss}) != 1:
         raise ValueError(f"decode_yuv: the files must share one size, got {sorted({(s.H, s.W) for s in ss})}")
-    H, W = ss[0].H, ss[0].W
-    inner = [f[s.inner_off:s.inner_off + s.inner_len] for f, s in zip(files, ss)]
-    extra = [{"max_error": int(s.tau), "depth": int(s.depth), "shift": int(s.shift), "sub": fmt.sub,
-              "residual_bytes": int(s.res_len), "base_bytes": int(s.inner_len), "low_bytes": int(s.lo_len),
-              "residual_segment": int(s.seg_len), "segments": int(s.n_seg), "bytes": len(f),
-              "bpp": 8.0 * len(f) / (s.H * s.W)} for f, s in zip(files, ss)]
-    if not enhance:
-        planes, info = decode_yuv(net, inner, fmt, ref=ref, max_pixels=max_pixels)
-        for di, e in zip(info, extra):
-            di.update(e, enhanced=False)
-        return planes, info
-    base, info = decode_yuv(net, inner, fmt, max_pixels=max_pixels)
-    geom = residual_yuv_geom(H, W, fmt.sub)
-    if ref is not None:
-        ref = _yuv_planes(*ref, fmt, "decode_yuv ref")
-        if tuple(ref[0].shape) != (B, H, W):
-            raise ValueError(f"decode_yuv: ref must be a frame batch of {(B, H, W)}, got {tuple(ref[0].shape)}")
-        ref = tuple(t.to(base[0].device) for t in ref)
-    one = len({(s.tau, s.shift, s.seg_len) for s in ss}) == 1
-    groups = [list(range(B))] if one else [[b] for b in range(B)]
-    out = tuple(torch.empty(tuple(t.shape), dtype=torch.uint8 if fmt.depth == 8 else torch.int16, device=t.device)
-                for t in base)
-    if fmt.depth > 8:
-        out = tuple(t.view(torch.uint16) for t in out)
-    for g in groups:
-        s0 = ss[g[0]]
-        tau, sh, L = int(s0.tau), int(s0.shift), int(s0.seg_len)
-        sl = slice(g[0], g[-1] + 1)
-        view = tuple(t[sl] for t in base)
-        front = residual_front_yuv(view, None, fmt, tau, 0)
-        digest = front["digest"].cpu().tolist()
-        for j, b in enumerate(g):
-            if (digest[j] & 0xFFFFFFFFFFFFFFFF) == ss[b].digest:
-                continue
-            # the base is defined as the decode of the file alone (the range guard's fp32 re-run takes a whole lane)
-            alone, _ = decode_yuv(net, [inner[b]], fmt, max_pixels=max_pixels)
-            again = int(residual_front_yuv(alone, None, fmt, tau, 0)["digest"].cpu()[0])
-            if (again & 0xFFFFFFFFFFFFFFFF) != ss[b].digest:
-                raise _digest_error(b, int(ss[b].digest), again, net)
-            for t, v in zip(base, alone):
-                (t[b:b + 1] if fmt.depth == 8 else t[b:b + 1].view(torch.int16)).copy_(
-                    v if fmt.depth == 8 else v.view(torch.int16))
-            front = None
-        if front is None:
-            front = residual_front_yuv(view, None, fmt, tau, 0)
-        count = front["ctx_count"].cpu().numpy()
-        tabs = [_file_tables(files[b], ss[b]) for b in g]
-        planes = []
-        for j, b in enumerate(g):
-            missing = [k for k in range(RES_CTX) if count[j, k] > 0 and tabs[j]["m"][k] == RES_ABSENT]
-            if missing:
-                raise ValueError(f"decode_yuv: file {b}: contexts {missing} occur in the base planes but the file has "
-                                 f"no table for them")
-            pl = np.frombuffer(files[b], "<u8", geom["groups"] * sh, ss[b].lo_off)
-            for p in range(3):
-                w, G, a = geom["w"][p], geom["G"][p], geom["rowbase"][p] * sh
-                if sh and w % 64 and (pl[a:a + geom["h"][p] * G * sh].reshape(geom["h"][p], G, sh)[:, -1, :]
-                                      >> np.uint64(w % 64)).any():
-                    raise ValueError(f"decode_yuv: file {b}: the low-bit plane has bits set beyond column {w} of plane "
-                                     f"{p} (its padding bits must be zero)")
-            planes.append(pl.view(np.int64))
-        try:
-            sym_d = residual_decode_segments(
-                [files[b][ss[b].data_off:ss[b].data_off + ss[b].data_len] for b in g],
-                [np.frombuffer(files[b], ">u4", ss[b].n_seg, ss[b].index_off) for b in g], front["ctx"], tabs, L, coder)
-        except ResidualSegmentError as e:
-            raise ValueError(f"decode_yuv: file {g[e.image]}: segment {e.segment} of the residual string is corrupt: "
-                             f"{e.reason}") from None
-        plane_d = torch.from_numpy(np.stack(planes).reshape(len(g), -1).copy()).to(base[0].device)
-        try:
-            r = residual_apply_yuv(view, sym_d, plane_d, fmt, tau, sh,
-                                   ref=None if ref is None else tuple(t[sl] for t in ref), out=tuple(t[sl] for t in out))
-        except ValueError as e:
-            raise ValueError(f"decode_yuv: files {g[0]}..{g[-1]}: {e}") from None
-        if ref is not None:
-            sq, me = r[3].cpu().tolist(), r[4].cpu().tolist()
-            for j, b in enumerate(g):
-                extra[b].update(psnr_yuv_from_sq_err(sq[j], H, W, fmt), max_abs_err=int(me[j]))
-    for di, e in zip(info, extra):
-        di.update(e)
-    return out, info
+    return _decode_residual_layer(_yuv_kind(fmt), net, files, ss, ref, max_pixels, enhance, coder)
 
 
 def psnr_from_sq_err(sq_err: int, n: int, peak: int = 255) -> float:

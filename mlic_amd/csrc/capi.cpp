@@ -1865,31 +1865,39 @@ int mlic_container_write_residual_seg(uint32_t H, uint32_t W, int vbr, int tau, 
   });
 }
 
+extern "C++" {  // a template cannot have C linkage
+// the fields every segmented residual file has, into its ABI struct (the "MLR2", "MLR3" or "MLR4" one)
+template <typename Abi>
+static void seg_to_abi(const ResidualSegInfo& s, Abi* info) {
+  info->H = s.H;
+  info->W = s.W;
+  info->tau = (int32_t)s.tau;
+  info->vbr = s.vbr ? 1 : 0;
+  info->digest = s.digest;
+  for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
+    info->m[k] = s.m[k];
+    info->freq_off[k] = s.freq_off[k];
+  }
+  info->seg_len = s.seg_len;
+  info->n_seg = s.n_seg;
+  info->inner_off = s.inner_off;
+  info->inner_len = s.inner_len;
+  info->res_off = s.res_off;
+  info->res_len = s.res_len;
+  info->index_off = s.index_off;
+  info->data_off = s.data_off;
+  info->data_len = s.data_len;
+  to_abi(s.inner, &info->inner);
+}
+}  // extern "C++"
+
 int mlic_container_parse_residual_seg(const uint8_t* data, size_t n, int n_levels, uint64_t max_pixels,
                                       mlic_container_residual_seg_info* info) {
   return guard([&] {
     MLIC_CHECK(info != nullptr, "container_parse_residual_seg: null info");
     ResidualSegInfo s;
     container_ok(container_parse_residual_seg(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &s));
-    info->H = s.H;
-    info->W = s.W;
-    info->tau = (int32_t)s.tau;
-    info->vbr = s.vbr ? 1 : 0;
-    info->digest = s.digest;
-    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
-      info->m[k] = s.m[k];
-      info->freq_off[k] = s.freq_off[k];
-    }
-    info->seg_len = s.seg_len;
-    info->n_seg = s.n_seg;
-    info->inner_off = s.inner_off;
-    info->inner_len = s.inner_len;
-    info->res_off = s.res_off;
-    info->res_len = s.res_len;
-    info->index_off = s.index_off;
-    info->data_off = s.data_off;
-    info->data_len = s.data_len;
-    to_abi(s.inner, &info->inner);
+    seg_to_abi(s, info);
   });
 }
 
@@ -1954,30 +1962,11 @@ int mlic_container_parse_residual_deep(const uint8_t* data, size_t n, int n_leve
     MLIC_CHECK(info != nullptr, "container_parse_residual_deep: null info");
     ResidualDeepInfo d;
     container_ok(container_parse_residual_deep(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &d));
-    const ResidualSegInfo& s = d.seg;
-    info->H = s.H;
-    info->W = s.W;
-    info->tau = (int32_t)s.tau;
-    info->vbr = s.vbr ? 1 : 0;
-    info->digest = s.digest;
-    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
-      info->m[k] = s.m[k];
-      info->freq_off[k] = s.freq_off[k];
-    }
-    info->seg_len = s.seg_len;
-    info->n_seg = s.n_seg;
-    info->inner_off = s.inner_off;
-    info->inner_len = s.inner_len;
-    info->res_off = s.res_off;
-    info->res_len = s.res_len;
-    info->index_off = s.index_off;
-    info->data_off = s.data_off;
-    info->data_len = s.data_len;
+    seg_to_abi(d.seg, info);
     info->depth = (int32_t)d.depth;
     info->shift = (int32_t)d.shift;
     info->lo_off = d.lo_off;
     info->lo_len = d.lo_len;
-    to_abi(s.inner, &info->inner);
   });
 }
 
@@ -2430,25 +2419,7 @@ int mlic_container_parse_residual_yuv(const uint8_t* data, size_t n, int n_level
     MLIC_CHECK(info != nullptr, "container_parse_residual_yuv: null info");
     ResidualYuvInfo y;
     container_ok(container_parse_residual_yuv(data, n, (uint32_t)std::max(n_levels, 0), max_pixels, &y));
-    const ResidualSegInfo& s = y.deep.seg;
-    info->H = s.H;
-    info->W = s.W;
-    info->tau = (int32_t)s.tau;
-    info->vbr = s.vbr ? 1 : 0;
-    info->digest = s.digest;
-    for (uint32_t k = 0; k < RESIDUAL_CTX; ++k) {
-      info->m[k] = s.m[k];
-      info->freq_off[k] = s.freq_off[k];
-    }
-    info->seg_len = s.seg_len;
-    info->n_seg = s.n_seg;
-    info->inner_off = s.inner_off;
-    info->inner_len = s.inner_len;
-    info->res_off = s.res_off;
-    info->res_len = s.res_len;
-    info->index_off = s.index_off;
-    info->data_off = s.data_off;
-    info->data_len = s.data_len;
+    seg_to_abi(y.deep.seg, info);
     info->depth = (int32_t)y.deep.depth;
     info->shift = (int32_t)y.deep.shift;
     info->lo_off = y.deep.lo_off;
@@ -2458,7 +2429,6 @@ int mlic_container_parse_residual_yuv(const uint8_t* data, size_t n, int n_level
     info->matrix = (int32_t)y.matrix;
     info->full_range = y.full_range ? 1 : 0;
     info->site_x = y.site_left ? 1 : 0;
-    to_abi(s.inner, &info->inner);
   });
 }
 

@@ -20,12 +20,12 @@
 #include "image_stage.h"
 #include "kernels.h"
 #include "residual.h"
+#include "residual_dev.h"
 
 namespace mlic {
 
 namespace {
 
-constexpr int R_TW = 256;                      // pixels of a row segment
 constexpr int R_SEG = (R_TW + 2 + 3 + 3) / 4;  // dwords of a (R_TW + 2)-byte plane segment at any alignment
 constexpr int R_ROW = 3 * R_SEG;               // one staged row: three plane segments, or 3 (R_TW + 2) + 3 HWC bytes
 constexpr int RF_ROWS = 8, RF_GROUPS = 8;      // front: rows per group, groups per block
@@ -33,10 +33,6 @@ constexpr int RA_ROWS = 4, RA_REF_GROUPS = 16; // apply: a row per wave; with re
 enum { R_GENERAL = 0, R_HWC = 1, R_CHW = 2 };
 static_assert(RF_ROWS * RF_GROUPS <= 255, "a thread's packed class counts are 8 bits each");
 static_assert(3 * (R_TW + 2) + 3 <= 4 * R_ROW, "an HWC row fits the staged row");
-
-struct RStride {
-  int64_t img, row, col, ch;
-};
 
 int r_path(const int64_t* s) { return (s[2] == 3 && s[3] == 1) ? R_HWC : s[2] == 1 ? R_CHW : R_GENERAL; }
 
@@ -67,17 +63,6 @@ __device__ inline void seg_out(int path, uint8_t* __restrict__ p, int64_t ch, in
   } else {  // R_CHW: the general form writes straight to memory
     for (int c = 0; c < 3; ++c) stage_out(p + c * ch, n, r + c * R_SEG, lane);
   }
-}
-
-__device__ inline unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ inline unsigned int wave_max32(unsigned int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned int)__shfl_down(v, off, 64));
-  return v;
 }
 
 template <bool HAS_X>
@@ -208,9 +193,9 @@ __global__ __launch_bounds__(256) void residual_front_kernel(
   }
   __syncthreads();
   if (tid == 0) {
-    atomicAdd(digest + img, (redD[0] + redD[1] + redD[2] + redD[3]) * RES_DIGEST_K);
+    atomicAdd(digest + img, sum4(redD) * RES_DIGEST_K);
     if (HAS_X) {
-      const unsigned int m = max(max(redM[0], redM[1]), max(redM[2], redM[3]));
+      const unsigned int m = max4(redM);
       if (m) atomicMax(max_err + img, m);
     }
   }
@@ -303,23 +288,13 @@ __global__ __launch_bounds__(256) void residual_apply_kernel(const uint8_t* __re
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      const unsigned long long tot = redS[0] + redS[1] + redS[2] + redS[3];
-      const unsigned int m = max(max(redM[0], redM[1]), max(redM[2], redM[3]));
+      const unsigned long long tot = sum4(redS);
+      const unsigned int m = max4(redM);
       if (tot) atomicAdd(sq_err + img, tot);
       if (m) atomicMax(max_err + img, m);
     }
   }
 }
-
-unsigned r_blocks(int B, int H, int W, int block_rows, int* tx, int* ty, const char* what) {
-  *tx = (W + R_TW - 1) / R_TW;
-  *ty = (H + block_rows - 1) / block_rows;
-  const int64_t blocks = (int64_t)B * *tx * *ty;
-  if (blocks > 0x7fffffffLL) throw Error(std::string("mlic: ") + what + ": batch too large for one launch");
-  return (unsigned)blocks;
-}
-
-bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 }  // namespace
 
@@ -332,11 +307,7 @@ void image_residual_front_u8(const uint8_t* base, const int64_t* b, const uint8_
   MLIC_CHECK(H >= 1 && W >= 1, "image_residual_front_u8: H and W must be positive");
   MLIC_CHECK(tau >= 0 && tau <= RES_MAX_TAU, "image_residual_front_u8: tau must be in 0..127");
   MLIC_CHECK(b[2] != 0 && b[3] != 0, "image_residual_front_u8: zero column or channel stride (base)");
-  MLIC_CHECK(ctx != nullptr, "image_residual_front_u8: null ctx");
-  MLIC_CHECK(ctx_count != nullptr, "image_residual_front_u8: null ctx_count");
-  MLIC_CHECK(digest != nullptr, "image_residual_front_u8: null digest");
-  MLIC_CHECK(aligned(ctx_count, 4) && aligned(digest, 8),
-             "image_residual_front_u8: ctx_count must be 4-byte and digest 8-byte aligned");
+  check_front_out("image_residual_front_u8", ctx, ctx_count, digest);
   if (x != nullptr) {
     MLIC_CHECK(xs != nullptr, "image_residual_front_u8: x needs strides");
     MLIC_CHECK(xs[2] != 0 && xs[3] != 0, "image_residual_front_u8: zero column or channel stride (x)");
@@ -383,14 +354,10 @@ void image_residual_apply_u8(const uint8_t* base, const int64_t* b, const int16_
   MLIC_CHECK(b[2] != 0 && b[3] != 0, "image_residual_apply_u8: zero column or channel stride (base)");
   MLIC_CHECK(o[2] != 0 && o[3] != 0, "image_residual_apply_u8: zero column or channel stride (out)");
   MLIC_CHECK(aligned(sym, 2), "image_residual_apply_u8: sym must be 2-byte aligned");
-  MLIC_CHECK(ref == nullptr || sq_err != nullptr, "image_residual_apply_u8: ref without sq_err");
-  MLIC_CHECK(ref == nullptr || max_err != nullptr, "image_residual_apply_u8: ref without max_err");
-  MLIC_CHECK(ref != nullptr || (sq_err == nullptr && max_err == nullptr),
-             "image_residual_apply_u8: sq_err and max_err go with ref");
+  check_apply_scores("image_residual_apply_u8", ref != nullptr, sq_err, max_err);
   MLIC_CHECK(ref == nullptr || (r != nullptr && r[2] != 0 && r[3] != 0),
              "image_residual_apply_u8: ref needs strides with nonzero column and channel stride");
-  MLIC_CHECK(aligned(sq_err, 8) && aligned(max_err, 4),
-             "image_residual_apply_u8: sq_err must be 8-byte and max_err 4-byte aligned");
+  check_apply_scores_aligned("image_residual_apply_u8", sq_err, max_err);
   int tx, ty;
   const unsigned blocks =
       r_blocks(B, H, W, (ref ? RA_REF_GROUPS : 1) * RA_ROWS, &tx, &ty, "image_residual_apply_u8");

@@ -21,25 +21,20 @@
 #include "image_stage.h"
 #include "kernels.h"
 #include "residual16.h"
+#include "residual_dev.h"
 
 namespace mlic {
 
 namespace {
 
-constexpr int R_TW = 256;                            // pixels of a row segment
 constexpr int R_SEG = (2 * (R_TW + 2) + 3 + 3) / 4;  // dwords of a (R_TW + 2)-word plane segment at any alignment
 constexpr int R_ROW = 3 * R_SEG;                     // one staged row: three plane segments, or the HWC words
 constexpr int RF_ROWS = 8, RF_GROUPS = 8;            // front: rows per group, groups per block
 constexpr int RA_ROWS = 4, RA_REF_GROUPS = 16;       // apply: a row per wave; with ref a block walks 16 groups
 enum { R_GENERAL = 0, R_HWC = 1, R_CHW = 2 };
-enum { F_CTX = 0, F_STATS = 1, F_FULL = 2 };  // front: without x; statistics only; everything
 static_assert(RF_ROWS * RF_GROUPS <= 255, "a thread's packed class counts are 8 bits each");
 static_assert(6 * (R_TW + 2) + 3 <= 4 * R_ROW, "an HWC row fits the staged row");
 static_assert(R_TW % 64 == 0, "a wave is one 64-column group of the low-bit plane");
-
-struct RStride {
-  int64_t img, row, col, ch;
-};
 
 int r_path(const int64_t* s) { return (s[2] == 3 && s[3] == 1) ? R_HWC : s[2] == 1 ? R_CHW : R_GENERAL; }
 
@@ -73,29 +68,6 @@ __device__ inline void seg_out(int path, uint16_t* __restrict__ p, int64_t ch, i
     for (int c = 0; c < 3; ++c) stage_out(reinterpret_cast<uint8_t*>(p + c * ch), 2 * n, r + c * R_SEG, lane);
   }
 }
-
-__device__ inline unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ inline unsigned int wave_max32(unsigned int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned int)__shfl_down(v, off, 64));
-  return v;
-}
-
-struct FrontOut {
-  uint8_t* ctx;
-  unsigned int* ctx_count;
-  unsigned long long* digest;
-  int16_t* sym;
-  unsigned long long* plane;
-  unsigned int* hist;
-  unsigned int* max_err;
-  unsigned int* max_abs_q;
-  unsigned long long* sum_abs_q;
-};
 
 template <int MODE>
 __global__ __launch_bounds__(256) void residual_front_u16_kernel(const uint16_t* __restrict__ base, RStride bs,
@@ -260,15 +232,15 @@ __global__ __launch_bounds__(256) void residual_front_u16_kernel(const uint16_t*
   }
   __syncthreads();
   if (tid == 0) {
-    if (CTX) atomicAdd(o.digest + img, (redD[0] + redD[1] + redD[2] + redD[3]) * RES_DIGEST_K);
+    if (CTX) atomicAdd(o.digest + img, sum4(redD) * RES_DIGEST_K);
     if (HAS_X) {
-      const unsigned int mq = max(max(redQ[0], redQ[1]), max(redQ[2], redQ[3]));
-      const unsigned long long sq = redS[0] + redS[1] + redS[2] + redS[3];
+      const unsigned int mq = max4(redQ);
+      const unsigned long long sq = sum4(redS);
       if (mq) atomicMax(o.max_abs_q + img, mq);
       if (sq) atomicAdd(o.sum_abs_q + img, sq);
     }
     if (FULL) {
-      const unsigned int m = max(max(redM[0], redM[1]), max(redM[2], redM[3]));
+      const unsigned int m = max4(redM);
       if (m) atomicMax(o.max_err + img, m);
     }
   }
@@ -382,23 +354,13 @@ __global__ __launch_bounds__(256) void residual_apply_u16_kernel(
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      const unsigned long long tot = redS[0] + redS[1] + redS[2] + redS[3];
-      const unsigned int m = max(max(redM[0], redM[1]), max(redM[2], redM[3]));
+      const unsigned long long tot = sum4(redS);
+      const unsigned int m = max4(redM);
       if (tot) atomicAdd(sq_err + img, tot);
       if (m) atomicMax(max_err + img, m);
     }
   }
 }
-
-unsigned r_blocks(int B, int H, int W, int block_rows, int* tx, int* ty, const char* what) {
-  *tx = (W + R_TW - 1) / R_TW;
-  *ty = (H + block_rows - 1) / block_rows;
-  const int64_t blocks = (int64_t)B * *tx * *ty;
-  if (blocks > 0x7fffffffLL) throw Error(std::string("mlic: ") + what + ": batch too large for one launch");
-  return (unsigned)blocks;
-}
-
-bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 void front_common(const char* what, const uint16_t* base, const int64_t* b, int B, int H, int W, int depth, int tau) {
   const std::string w(what);
@@ -419,28 +381,19 @@ void image_residual_front_u16(const uint16_t* base, const int64_t* b, const uint
                               uint64_t* digest, int16_t* sym, uint64_t* lo_plane, uint32_t* hist, uint32_t* max_err,
                               uint32_t* max_abs_q, uint64_t* sum_abs_q, hipStream_t st) {
   front_common("image_residual_front_u16", base, b, B, H, W, depth, tau);
-  MLIC_CHECK(ctx != nullptr, "image_residual_front_u16: null ctx");
-  MLIC_CHECK(ctx_count != nullptr, "image_residual_front_u16: null ctx_count");
-  MLIC_CHECK(digest != nullptr, "image_residual_front_u16: null digest");
-  MLIC_CHECK(aligned(ctx_count, 4) && aligned(digest, 8),
-             "image_residual_front_u16: ctx_count must be 4-byte and digest 8-byte aligned");
+  const std::string w("image_residual_front_u16");
+  check_front_out(w, ctx, ctx_count, digest);
   if (x != nullptr) {
     MLIC_CHECK(xs != nullptr, "image_residual_front_u16: x needs strides");
     MLIC_CHECK(xs[2] != 0 && xs[3] != 0, "image_residual_front_u16: zero column or channel stride (x)");
     MLIC_CHECK(aligned(x, 2), "image_residual_front_u16: x must be 2-byte aligned");
     MLIC_CHECK(shift >= 0 && shift <= residual16_max_shift(depth),
                "image_residual_front_u16: shift must be in 0..depth - 7");
-    MLIC_CHECK(sym != nullptr && hist != nullptr && max_err != nullptr && max_abs_q != nullptr && sum_abs_q != nullptr,
-               "image_residual_front_u16: with x, sym, hist, max_err, max_abs_q and sum_abs_q are all needed");
+    check_front_x_needed(w, sym, hist, max_err, max_abs_q, sum_abs_q);
     MLIC_CHECK((lo_plane != nullptr) == (shift > 0), "image_residual_front_u16: lo_plane goes with a shift above 0");
-    MLIC_CHECK(aligned(sym, 2) && aligned(hist, 4) && aligned(max_err, 4) && aligned(max_abs_q, 4) &&
-                   aligned(sum_abs_q, 8) && aligned(lo_plane, 8),
-               "image_residual_front_u16: sym must be 2-byte, hist, max_err and max_abs_q 4-byte, sum_abs_q and "
-               "lo_plane 8-byte aligned");
+    check_front_x_aligned(w, sym, lo_plane, hist, max_err, max_abs_q, sum_abs_q);
   } else {
-    MLIC_CHECK(sym == nullptr && lo_plane == nullptr && hist == nullptr && max_err == nullptr &&
-                   max_abs_q == nullptr && sum_abs_q == nullptr,
-               "image_residual_front_u16: sym, lo_plane, hist, max_err, max_abs_q and sum_abs_q go with x");
+    check_front_without_x(w, sym, lo_plane, hist, max_err, max_abs_q, sum_abs_q);
   }
   int tx, ty;
   const unsigned blocks = r_blocks(B, H, W, RF_ROWS * RF_GROUPS, &tx, &ty, "image_residual_front_u16");
@@ -503,10 +456,7 @@ void image_residual_apply_u16(const uint16_t* base, const int64_t* b, const int1
   MLIC_CHECK(o[2] != 0 && o[3] != 0, "image_residual_apply_u16: zero column or channel stride (out)");
   MLIC_CHECK(aligned(sym, 2) && aligned(out, 2) && aligned(lo_plane, 8) && aligned(status, 4),
              "image_residual_apply_u16: sym and out must be 2-byte, lo_plane 8-byte and status 4-byte aligned");
-  MLIC_CHECK(ref == nullptr || sq_err != nullptr, "image_residual_apply_u16: ref without sq_err");
-  MLIC_CHECK(ref == nullptr || max_err != nullptr, "image_residual_apply_u16: ref without max_err");
-  MLIC_CHECK(ref != nullptr || (sq_err == nullptr && max_err == nullptr),
-             "image_residual_apply_u16: sq_err and max_err go with ref");
+  check_apply_scores("image_residual_apply_u16", ref != nullptr, sq_err, max_err);
   MLIC_CHECK(ref == nullptr || (r != nullptr && r[2] != 0 && r[3] != 0),
              "image_residual_apply_u16: ref needs strides with nonzero column and channel stride");
   MLIC_CHECK(aligned(ref, 2) && aligned(sq_err, 8) && aligned(max_err, 4),

@@ -22,17 +22,17 @@
 // Lanes beyond the plane take part with lo = 0, which is the plane's zero padding.
 #include "image_stage.h"
 #include "kernels.h"
+#include "residual_dev.h"
 #include "residual_yuv.h"
 
 namespace mlic {
 
 namespace {
 
-constexpr int P_TW = 256;                       // columns of a row segment
+constexpr int P_TW = R_TW;                      // columns of a row segment
 constexpr int PF_ROWS = 8, PF_GROUPS = 8;       // front: rows per group, groups per block
 constexpr int PA_ROWS = 4, PA_REF_GROUPS = 16;  // apply: a row per wave; with ref a block walks 16 groups
 enum { P_GENERAL = 0, P_DENSE = 1, P_PAIR = 2 };
-enum { F_CTX = 0, F_STATS = 1, F_FULL = 2 };  // front: without x; statistics only; everything
 static_assert(PF_ROWS * PF_GROUPS <= 255, "a thread's packed class counts are 8 bits each");
 static_assert(P_TW % 64 == 0, "a wave is one 64-column group of the low-bit plane");
 
@@ -89,29 +89,6 @@ template <typename WORD>
 __device__ inline int word_at(const uint8_t* row, int byte) {
   return *reinterpret_cast<const WORD*>(row + byte);
 }
-
-__device__ inline unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ inline unsigned int wave_max32(unsigned int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned int)__shfl_down(v, off, 64));
-  return v;
-}
-
-struct FrontOut {
-  uint8_t* ctx;
-  unsigned int* ctx_count;
-  unsigned long long* digest;
-  int16_t* sym;
-  unsigned long long* plane;
-  unsigned int* hist;
-  unsigned int* max_err;
-  unsigned int* max_abs_q;
-  unsigned long long* sum_abs_q;
-};
 
 // what a block works on: frame, plane and the plane's sizes and places in the frame's canonical order
 struct BlockAt {
@@ -254,7 +231,7 @@ __global__ __launch_bounds__(256) void residual_front_planes_kernel(PlaneSet<con
                   run = 1;
                 }
               }
-              if (shift) {  // every lane of the wave is here: one ballot per bit of lo
+              if (shift) {  // every lane of the wave is here
                 unsigned long long mine = 0;
                 for (int j = 0; j < shift; ++j) {
                   const unsigned long long b = __ballot((lo >> j) & 1);
@@ -295,15 +272,15 @@ __global__ __launch_bounds__(256) void residual_front_planes_kernel(PlaneSet<con
   }
   __syncthreads();
   if (tid == 0) {
-    if (CTX) atomicAdd(o.digest + img, (redD[0] + redD[1] + redD[2] + redD[3]) * RES_DIGEST_K);
+    if (CTX) atomicAdd(o.digest + img, sum4(redD) * RES_DIGEST_K);
     if (HAS_X) {
-      const unsigned int mq = max(max(redQ[0], redQ[1]), max(redQ[2], redQ[3]));
-      const unsigned long long sq = redS[0] + redS[1] + redS[2] + redS[3];
+      const unsigned int mq = max4(redQ);
+      const unsigned long long sq = sum4(redS);
       if (mq) atomicMax(o.max_abs_q + img, mq);
       if (sq) atomicAdd(o.sum_abs_q + img, sq);
     }
     if (FULL) {
-      const unsigned int m = max(max(redM[0], redM[1]), max(redM[2], redM[3]));
+      const unsigned int m = max4(redM);
       if (m) atomicMax(o.max_err + img, m);
     }
   }
@@ -416,15 +393,13 @@ __global__ __launch_bounds__(256) void residual_apply_planes_kernel(
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      const unsigned long long tot = redS[0] + redS[1] + redS[2] + redS[3];
-      const unsigned int m = max(max(redM[0], redM[1]), max(redM[2], redM[3]));
+      const unsigned long long tot = sum4(redS);
+      const unsigned int m = max4(redM);
       if (tot) atomicAdd(sq_err + img * 3 + p, tot);
       if (m) atomicMax(max_err + img, m);
     }
   }
 }
-
-bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 PGeom p_geom(const std::string& w, int B, int H, int W, const YuvDesc* d, int block_rows, unsigned* blocks) {
   const ResYuvGeom g = residual_yuv_geom(H, W, d->sub_x, d->sub_y);
@@ -535,23 +510,15 @@ void image_residual_front_planes(const char* who, int word_bytes, const void* co
                                  uint32_t* max_abs_q, uint64_t* sum_abs_q, hipStream_t st) {
   const std::string w(who);
   common_check(w, word_bytes, base, base_strides, desc, depth, msb, B, H, W, tau);
-  MLIC_CHECK(ctx != nullptr, w + ": null ctx");
-  MLIC_CHECK(ctx_count != nullptr, w + ": null ctx_count");
-  MLIC_CHECK(digest != nullptr, w + ": null digest");
-  MLIC_CHECK(aligned(ctx_count, 4) && aligned(digest, 8), w + ": ctx_count must be 4-byte and digest 8-byte aligned");
+  check_front_out(w, ctx, ctx_count, digest);
   const bool has_x = x[0] != nullptr || x[1] != nullptr || x[2] != nullptr;
   if (has_x) {
     planes_check(w, word_bytes, "x", x, x_strides);
     shift_check(w, depth, shift, lo_plane);
-    MLIC_CHECK(sym != nullptr && hist != nullptr && max_err != nullptr && max_abs_q != nullptr && sum_abs_q != nullptr,
-               w + ": with x, sym, hist, max_err, max_abs_q and sum_abs_q are all needed");
-    MLIC_CHECK(aligned(sym, 2) && aligned(hist, 4) && aligned(max_err, 4) && aligned(max_abs_q, 4) &&
-                   aligned(sum_abs_q, 8) && aligned(lo_plane, 8),
-               w + ": sym must be 2-byte, hist, max_err and max_abs_q 4-byte, sum_abs_q and lo_plane 8-byte aligned");
+    check_front_x_needed(w, sym, hist, max_err, max_abs_q, sum_abs_q);
+    check_front_x_aligned(w, sym, lo_plane, hist, max_err, max_abs_q, sum_abs_q);
   } else {
-    MLIC_CHECK(sym == nullptr && lo_plane == nullptr && hist == nullptr && max_err == nullptr &&
-                   max_abs_q == nullptr && sum_abs_q == nullptr,
-               w + ": sym, lo_plane, hist, max_err, max_abs_q and sum_abs_q go with x");
+    check_front_without_x(w, sym, lo_plane, hist, max_err, max_abs_q, sum_abs_q);
   }
   unsigned blocks;
   const PGeom g = p_geom(w, B, H, W, desc, PF_ROWS * PF_GROUPS, &blocks);
@@ -631,14 +598,9 @@ void image_residual_apply_planes(const char* who, int word_bytes, const void* co
   MLIC_CHECK(aligned(sym, 2) && aligned(lo_plane, 8) && aligned(status, 4),
              w + ": sym must be 2-byte, lo_plane 8-byte and status 4-byte aligned");
   const bool has_ref = ref[0] != nullptr || ref[1] != nullptr || ref[2] != nullptr;
-  if (has_ref) {
-    planes_check(w, word_bytes, "ref", ref, ref_strides);
-    MLIC_CHECK(sq_err != nullptr, w + ": ref without sq_err");
-    MLIC_CHECK(max_err != nullptr, w + ": ref without max_err");
-    MLIC_CHECK(aligned(sq_err, 8) && aligned(max_err, 4), w + ": sq_err must be 8-byte and max_err 4-byte aligned");
-  } else {
-    MLIC_CHECK(sq_err == nullptr && max_err == nullptr, w + ": sq_err and max_err go with ref");
-  }
+  if (has_ref) planes_check(w, word_bytes, "ref", ref, ref_strides);
+  check_apply_scores(w, has_ref, sq_err, max_err);
+  check_apply_scores_aligned(w, sq_err, max_err);
   unsigned blocks;
   const PGeom g = p_geom(w, B, H, W, desc, (has_ref ? PA_REF_GROUPS : 1) * PA_ROWS, &blocks);
   HIP_OK(hipMemsetAsync(status, 0, sizeof(uint32_t) * (size_t)B, st));

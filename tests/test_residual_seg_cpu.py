@@ -441,6 +441,58 @@ def test_cpu_path_end_to_end(vbr, tau):
     assert torch.equal(both[0], both[1]) and "segments" not in binfo[0] and binfo[1]["segments"] == n_seg
 
 
+class BatchDriftNet(StubNet):
+    """StubNet whose decompress of two or more images returns image 1 perturbed, while a single image comes back
+    exact: the batch's base then differs from the file's own, as after the range guard's fp32 re-run of a lane."""
+
+    def decompress(self, strings, shape, s=None, **kw):
+        out = super().decompress(strings, shape, s=s, **kw)
+        if len(strings[0]) >= 2:
+            x = out["x_hat"][1]
+            out["x_hat"][1] = torch.where(x > 0.5, x - 0.03, x + 0.03)  # about 8 of 255: no sample stays as it was
+        return out
+
+
+def _same(a, b):
+    if torch.is_tensor(a):
+        return a.dtype == b.dtype and torch.equal(a.view(torch.int16) if a.dtype == torch.uint16 else a,
+                                                  b.view(torch.int16) if b.dtype == torch.uint16 else b)
+    return len(a) == len(b) and all(_same(u, v) for u, v in zip(a, b))
+
+
+def test_a_batch_whose_base_drifts_is_repaired_by_the_decode_alone():
+    """The successful branch of the decoder's retry, for the three kinds of picture through the one driver: the
+    digest of the batch's base differs from the file's, the file decoded alone has the file's digest, that base is
+    pasted in, and the call returns exactly what decoding each file alone returns."""
+    imgs, clean, drift = _images(2), StubNet(), BatchDriftNet()
+    deep = (imgs.to(torch.int32) * 4 + 1).to(torch.uint16)  # 10-bit samples
+    fmt = codec.YuvFormat((2, 2), "bt709", False, "left", 8)
+    planes = codec.egress_yuv(imgs.permute(0, 3, 1, 2).float() / 255, 64, 64, fmt)
+    cases = {
+        b"MLR2": (codec.encode_images(clean, imgs, max_error=1, residual_segment=256), imgs,
+                  lambda net, files, **kw: codec.decode_images(net, files, **kw)),
+        b"MLR3": (codec.encode_residual16(clean, deep, 10, max_error=1, residual_segment=256, shift=1), deep,
+                  lambda net, files, **kw: codec.decode_images(net, files, **kw)),
+        b"MLR4": (codec.encode_residual_yuv(clean, *planes, fmt, max_error=1, residual_segment=256), planes,
+                  lambda net, files, **kw: codec.decode_yuv(net, files, fmt, **kw))}
+    for magic, (files, orig, decode) in cases.items():
+        assert len(files) == 2 and all(f[:4] == magic for f in files)
+        plain = [codec.strip_residual(f) for f in files]
+        own = [decode(clean, [f])[0] for f in plain]  # each file's own base
+        batch = decode(drift, plain)[0]
+        pick = (lambda t, b: t[b:b + 1]) if torch.is_tensor(batch) else (lambda t, b: tuple(p[b:b + 1] for p in t))
+        assert _same(pick(batch, 0), own[0]) and not _same(pick(batch, 1), own[1])  # the drift is real
+        alone = [decode(clean, [f], ref=pick(orig, b)) for b, f in enumerate(files)]
+        drift.calls.clear()
+        out, info = decode(drift, files, ref=orig)
+        # the batch, then file 1 alone (file 0's digest agreed)
+        assert [c for c in drift.calls if c[0] == "decompress"] == [("decompress", 2), ("decompress", 1)]
+        for b in range(2):
+            assert _same(pick(out, b), alone[b][0])
+            assert info[b] == alone[b][1][0] and info[b]["max_abs_err"] <= 1
+        assert _same(decode(drift, files)[0], out)
+
+
 def test_without_a_segment_the_file_is_the_serial_one_byte_for_byte():
     """encode_images(max_error=) without residual_segment= still writes the "MLR1" file: here it is rebuilt by hand
     from the base picture, residual_front's symbols, entropy.rans_encode and write_container_residual."""
